@@ -14,11 +14,17 @@ A "step" = one decode of the rank's whole batch through the C ABI (pack -> BP ke
 plus, when a process group exists, the single gather of decoded rows (bit-packed on the device) + flags onto rank 0
 (RCCL over xGMI).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]        # N > 1: spawns its N ranks itself (torch.distributed.run)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   # N > 1: spawns its N ranks itself
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-After the headline, at N = 1, the two on-chip BASELINE configs (and schedule = serial_relative on the same two codes: `schedule_configs`) are timed as well (`secondary`): configs[2] (rotated
-surface code d = 21, min-sum 30, B = 262 144) and configs[4] (BB [[144,12,12]] product-sum 50 + OSD-0, B = 8 192).
+A plain run sets up, runs W warm-up steps, times K steps, writes the last step's outputs when --dump-outputs is given
+(`dump_outputs`), and prints the line: `value` = syndromes/s over the K steps, `ms_per_step` = milliseconds of one timed step.
+
+--full adds everything the headline does not need, after the timed steps: the roofline (HIP-event kernel times, the device-side
+shader clock, the box's copy rate), the CPU baseline and parity gate (N = 1), per-rank parity (N > 1), the host-I/O leg, and, at
+N = 1, the two on-chip BASELINE configs (and schedule = serial_relative on the same two codes: `schedule_configs`) timed as well
+(`secondary`): configs[2] (rotated surface code d = 21, min-sum 30, B = 262 144) and configs[4] (BB [[144,12,12]] product-sum 50
++ OSD-0, B = 8 192).
 """
 from __future__ import annotations
 
@@ -157,8 +163,12 @@ def parse_args():
     ap.add_argument("--max-iter", type=int, default=50)
     ap.add_argument("--n", type=int, default=10000)
     ap.add_argument("--waves", type=int, default=0, help="waves per workgroup (0 = library default)")
-    ap.add_argument("--cpu-sample", type=int, default=-1, help="syndromes for the CPU baseline and parity gate at N = 1 (-1 = 1024, 0 = skip)")
-    ap.add_argument("--rank-parity", type=int, default=128, help="rows of EVERY rank's shard checked against the CPU checker when N > 1 (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline does not need (roofline, CPU baseline, "
+                    "parity, host I/O, secondary configs); off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the last step's outputs as "
+                    "DIR/<name>.npy (float32 / float64, at most 64 MB: a fixed, seeded sample of the rows)")
+    ap.add_argument("--cpu-sample", type=int, default=-1, help="--full: syndromes for the CPU baseline and parity gate at N = 1 (-1 = 1024, 0 = skip)")
+    ap.add_argument("--rank-parity", type=int, default=128, help="--full: rows of EVERY rank's shard checked against the CPU checker when N > 1 (0 = skip)")
     ap.add_argument("--math", default="libm_exact", choices=["libm_exact", "fast"], help="device tanh/log (include/ldpc_hip.h)")
     ap.add_argument("--bp-method", default="product_sum", choices=["product_sum", "minimum_sum"],
                     help="product_sum is the BASELINE workload; minimum_sum (alpha 0.625) is a diagnostic memory-only run")
@@ -166,13 +176,16 @@ def parse_args():
     ap.add_argument("--ring", type=int, default=1, help="LDS-DMA ring: 0 = register-prefetch variant, 1 = default depth, 2/3 = depth (diagnostic)")
     ap.add_argument("--no-llr", action="store_true", help="skip the LLR output (not the BASELINE workload)")
     ap.add_argument("--repack", type=int, default=-1, help="first-pass iterations of the repacked schedule (-1 = steered by the previous decode, 0 = off; diagnostic)")
-    ap.add_argument("--secondary", type=int, default=1, help="1: also time configs[2] and configs[4] (N = 1 only); 0: skip")
-    ap.add_argument("--host-io", type=int, default=1, help="1: also time the same batch through BpDecoder.decode_batch with pageable NumPy in / out (N = 1 only); 0: skip")
+    ap.add_argument("--secondary", type=int, default=1, help="--full: 1: also time configs[2] and configs[4] (N = 1 only); 0: skip")
+    ap.add_argument("--host-io", type=int, default=1, help="--full: 1: also time the same batch through BpDecoder.decode_batch with pageable NumPy in / out (N = 1 only); 0: skip")
     ap.add_argument("--dry-ranks", action="store_true", help="launcher self-test: every rank joins a gloo group, rank 0 prints the ranks it saw; no GPU work")
     ap.add_argument("--force-launch", action="store_true", help="go through torch.distributed.run even for --gpus 1 (exercises the N > 1 code path on one GPU)")
     ap.add_argument("--share-gpu", action="store_true", help="diagnostic for a one-GPU box: the N ranks all use cuda:0 and form a gloo group (RCCL refuses two ranks on "
                     "one device), collectives carry host tensors -- exercises the N > 1 bookkeeping on hardware; the rate means nothing")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -584,6 +597,30 @@ def early_exit_point(eng, h, dev, B, args, out, alpha, p=0.05):
                           "iteration histogram, the live lanes' message state is compacted into dense tiles once mid-decode (DESIGN.md section 4)"}
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, dec, llr, it, cv, rows_max=256) -> None:
+    """--dump-outputs: what the last timed step handed its caller (this rank's shard; at N = 1 the whole batch), as .npy files of
+    at most DUMP_BYTES in all.  `iterations` and `converge` hold every syndrome; `decoding` and `log_prob_ratios` the rows of
+    `rows`, a fixed, seeded sample of the batch.  Every array is float32 or float64; each value is exact in it."""
+    import torch
+    B, n = dec.shape
+    whole = 8 * B <= DUMP_BYTES // 4  # iterations + converge as float32: every syndrome up to 2 M of them
+    per_row = 8 + 4 * n + (8 * n if llr is not None else 0) + (0 if whole else 8)
+    k = min(B, rows_max, (DUMP_BYTES - (8 * B if whole else 0)) // per_row)
+    rows = np.sort(np.random.default_rng(2024).choice(B, size=k, replace=False))
+    idx = torch.from_numpy(rows).to(dec.device)
+    per_syndrome = slice(None) if whole else idx
+    arrays = {"rows": rows.astype(np.float64), "decoding": dec[idx].cpu().numpy().astype(np.float32),
+              "iterations": it[per_syndrome].cpu().numpy().astype(np.float32), "converge": cv[per_syndrome].cpu().numpy().astype(np.float32)}
+    if llr is not None:
+        arrays["log_prob_ratios"] = llr[idx].cpu().numpy().astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main() -> None:
     args = parse_args()
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.force_launch):
@@ -717,9 +754,10 @@ def run(args, real_stdout, stage) -> None:
     if grouped:
         dist.barrier()
     stage[0] = "timed steps"
-    probe0 = eng.clock_probe()  # (waits for the stream: outside the timed region)
-    sclk = SclkSampler(local_rank)
-    sclk.__enter__()
+    if args.full:
+        probe0 = eng.clock_probe()  # (waits for the stream: outside the timed region)
+        sclk = SclkSampler(local_rank)
+        sclk.__enter__()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         step(True)
@@ -727,22 +765,26 @@ def run(args, real_stdout, stage) -> None:
     if grouped:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    sclk.__exit__()
-    clock_run = eng.clock_ghz(probe0, eng.clock_probe())  # shader clock of the persistent kernel's workgroups over the timed steps
-    # box normaliser (outside the timed steps): a bare copy of the same message segments between the handle's two message arrays --
-    # what THIS box gives, right after the timed steps (same thermal state), to any kernel that moves these bytes once
-    copy_gbps = None
-    try:
-        copy_runs = [eng.copy_probe(min((B + 63) // 64, 1024), eng.nnz, passes=2)[1] for _ in range(3)]
-        copy_gbps = float(np.median(copy_runs))
-    except Exception as exc:  # an older library build (LDPC_HIP_LIB A/B runs) has no probe
-        print(f"[bench] copy probe unavailable: {exc}", file=sys.stderr)
+    if args.dump_outputs and rank == 0:
+        stage[0] = "dump outputs"
+        dump_outputs(args.dump_outputs, dec, llr, it, cv)
+    clock_run = copy_gbps = None
+    if args.full:
+        sclk.__exit__()
+        clock_run = eng.clock_ghz(probe0, eng.clock_probe())  # shader clock of the persistent kernel's workgroups over the timed steps
+        # box normaliser (outside the timed steps): a bare copy of the same message segments between the handle's two message arrays --
+        # what THIS box gives, right after the timed steps (same thermal state), to any kernel that moves these bytes once
+        try:
+            copy_runs = [eng.copy_probe(min((B + 63) // 64, 1024), eng.nnz, passes=2)[1] for _ in range(3)]
+            copy_gbps = float(np.median(copy_runs))
+        except Exception as exc:  # an older library build (LDPC_HIP_LIB A/B runs) has no probe
+            print(f"[bench] copy probe unavailable: {exc}", file=sys.stderr)
     if grouped:
         t = torch.tensor([elapsed], dtype=torch.float64, device=coll)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
-    stage[0] = "parity + report"
+    stage[0] = "parity + report" if args.full else "report"
     iters = it.cpu().numpy()
     conv = cv.cpu().numpy().astype(bool)
     k_ms = float(np.mean(kernel_ms))
@@ -751,7 +793,7 @@ def run(args, real_stdout, stage) -> None:
     # ---- every rank: parity of a sample of ITS shard against the CPU checker; per-rank timings to rank 0 -------------
     rank_ok = 1
     rank_rows = 0
-    if grouped and args.rank_parity > 0:
+    if grouped and args.full and args.rank_parity > 0:
         from oracle import cpu_bench, llr_close  # checker only
         rank_rows = min(B, args.rank_parity)
         rows = np.sort(np.random.default_rng(777 + rank).choice(B, size=rank_rows, replace=False))
@@ -766,58 +808,13 @@ def run(args, real_stdout, stage) -> None:
             ok = bool(torch.equal(own, dec)) and bool(torch.equal(gathered["conv"][:B].to(dev), cv)) and bool(torch.equal(gathered["iters"][:B].to(dev), it))
         rank_ok = int(bool(ok))
     per_rank = None
-    if grouped:
+    if grouped and args.full:
         mine = torch.tensor([k_ms, g_ms, float(rank_ok), float(iters.mean())], dtype=torch.float64, device=coll)
         allr = [torch.empty_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
         per_rank = [[float(v) for v in t_.cpu()] for t_ in allr]
 
     if rank == 0:
-        alg = algorithmic_bytes(iters, m, n, nnz)
-        pers_ms = float(np.mean([p_[0] for p_ in phase_ms]))
-        spread_ms = float(np.mean([p_[1] for p_ in phase_ms]))
-        achieved = alg / (k_ms * 1e-3) / 1e9
-        # HBM bytes per launch and the VALU / clock picture from the committed PMC run of this same workload
-        # (profiles/hbm_traffic.json, profiles/valu_clock.json: tools/profile_bench.sh + tools/prof_parse.py); null when
-        # absent or measured on another workload
-        traffic, second = None, None
-        same = world == 1 and method_id == 0
-
-        def committed(name):
-            try:
-                t_ = json.load(open(os.path.join(ROOT, "profiles", name)))
-                if t_.get("batch_per_gpu") == B and t_.get("p") == args.p and t_.get("max_iter") == args.max_iter and t_.get("n") == n \
-                        and t_.get("math", "libm_exact") == args.math:
-                    return t_
-            except Exception:
-                pass
-            return None
-        build_tag = kernel_sources_sha16()
-        profile_tag = None
-        if same:
-            tj = committed("hbm_traffic.json")
-            traffic = tj["hbm_bytes_per_launch"] if tj else None
-            profile_tag = (tj or {}).get("kernel_sources_sha16")
-            vj = committed("valu_clock.json")
-            if vj and vj.get("valu_insts_per_edge_iteration") and clock_run:
-                # VALU issue: instructions per edge-iteration (PMC profile of this workload; belongs to this build when the fingerprints
-                # match) x this run's edge-iterations, against the issue turns of 1024 SIMDs at THIS run's clock over THIS run's kernel time
-                per = float(vj["valu_insts_per_edge_iteration"])
-                wave_insts = float(iters.astype(np.float64).sum()) * nnz * per / 64.0
-                turns = SIMDS * clock_run * 1e9 * k_ms * 1e-3
-                f64_per = float(vj.get("fp64_arith_insts_per_edge_iteration") or 0.0)
-                second = {"kind": "fp64_valu", "issue_frac": wave_insts * 4.0 / turns,
-                          # the same count with FP64 arithmetic at 4 cycles and everything else (selects, moves, compares, integer work) at 2: a LOWER
-                          # bound of the occupancy; the hardware's own figure of the profiled run is valu_busy_frac_in_profile
-                          "issue_frac_fp64_at_4_others_at_2": (wave_insts * (f64_per / per) * 4.0 + wave_insts * (1.0 - f64_per / per) * 2.0) / turns if f64_per else None,
-                          "valu_busy_frac_in_profile": vj.get("valu_busy_frac"),
-                          "clock_ghz_this_run": clock_run, "sclk_sysfs_ghz": sclk.ghz(), "insts_per_edge_iter": per, "fp64_arith_insts_per_edge_iter": f64_per or None,
-                          "issue_frac_in_profile": vj.get("valu_issue_frac"), "clock_ghz_in_profile": vj.get("clock_ghz"),
-                          "source": "instructions per edge-iteration: profiles/valu_clock.json (SQ_INSTS_VALU of this workload); clock: shader cycles / "
-                                    "constant-rate ticks summed over the persistent kernel's workgroups during the timed steps (ldpc_hip_bp_clock_probe); "
-                                    "kernel time: HIP events of this run"}
-            elif clock_run:
-                second = {"kind": "fp64_valu", "issue_frac": None, "clock_ghz_this_run": clock_run, "sclk_sysfs_ghz": sclk.ghz()}
         res = {
             "metric": "syndromes_per_sec_batched_bp50_product_sum_ldpc36_n10k" if method_id == 0 else "syndromes_per_sec_DIAGNOSTIC_min_sum",
             "value": total * args.steps / elapsed,
@@ -835,7 +832,62 @@ def run(args, real_stdout, stage) -> None:
                 "parallelism": f"batch-sharded x{world}, one gather of bit-packed decoded rows + flags onto rank 0" if grouped else "single GPU, no process group",
                 "device_math": args.math, "mean_iterations": float(iters.mean()), "converged_fraction": float(conv.mean()),
             },
-            "roofline": {
+        }
+        if grouped:
+            res["rccl"] = {"ranks": dist.get_world_size(), "backend": dist.get_backend(),
+                           "version": ".".join(str(v) for v in torch.cuda.nccl.version()),
+                           "devices": [torch.cuda.get_device_name(local_rank)], "launcher": "torch.distributed.run"}
+            if args.share_gpu:
+                res["rccl"]["note"] = "--share-gpu diagnostic: every rank on cuda:0, gloo group, collectives on host tensors; the rate means nothing"
+            res["gather"] = {"ms": g_ms, "bytes_to_rank0": (world - 1) * B * ((n + 7) // 8 + 5),
+                             "rows_on_rank0": int(gathered["dec_b8"].shape[0]) if gathered.get("dec_b8") is not None else 0}
+        if args.full:
+            alg = algorithmic_bytes(iters, m, n, nnz)
+            pers_ms = float(np.mean([p_[0] for p_ in phase_ms]))
+            spread_ms = float(np.mean([p_[1] for p_ in phase_ms]))
+            achieved = alg / (k_ms * 1e-3) / 1e9
+            # HBM bytes per launch and the VALU / clock picture from the committed PMC run of this same workload
+            # (profiles/hbm_traffic.json, profiles/valu_clock.json: tools/profile_bench.sh + tools/prof_parse.py); null when
+            # absent or measured on another workload
+            traffic, second = None, None
+            same = world == 1 and method_id == 0
+
+            def committed(name):
+                try:
+                    t_ = json.load(open(os.path.join(ROOT, "profiles", name)))
+                    if t_.get("batch_per_gpu") == B and t_.get("p") == args.p and t_.get("max_iter") == args.max_iter and t_.get("n") == n \
+                            and t_.get("math", "libm_exact") == args.math:
+                        return t_
+                except Exception:
+                    pass
+                return None
+            build_tag = kernel_sources_sha16()
+            profile_tag = None
+            if same:
+                tj = committed("hbm_traffic.json")
+                traffic = tj["hbm_bytes_per_launch"] if tj else None
+                profile_tag = (tj or {}).get("kernel_sources_sha16")
+                vj = committed("valu_clock.json")
+                if vj and vj.get("valu_insts_per_edge_iteration") and clock_run:
+                    # VALU issue: instructions per edge-iteration (PMC profile of this workload; belongs to this build when the fingerprints
+                    # match) x this run's edge-iterations, against the issue turns of 1024 SIMDs at THIS run's clock over THIS run's kernel time
+                    per = float(vj["valu_insts_per_edge_iteration"])
+                    wave_insts = float(iters.astype(np.float64).sum()) * nnz * per / 64.0
+                    turns = SIMDS * clock_run * 1e9 * k_ms * 1e-3
+                    f64_per = float(vj.get("fp64_arith_insts_per_edge_iteration") or 0.0)
+                    second = {"kind": "fp64_valu", "issue_frac": wave_insts * 4.0 / turns,
+                              # the same count with FP64 arithmetic at 4 cycles and everything else (selects, moves, compares, integer work) at 2: a LOWER
+                              # bound of the occupancy; the hardware's own figure of the profiled run is valu_busy_frac_in_profile
+                              "issue_frac_fp64_at_4_others_at_2": (wave_insts * (f64_per / per) * 4.0 + wave_insts * (1.0 - f64_per / per) * 2.0) / turns if f64_per else None,
+                              "valu_busy_frac_in_profile": vj.get("valu_busy_frac"),
+                              "clock_ghz_this_run": clock_run, "sclk_sysfs_ghz": sclk.ghz(), "insts_per_edge_iter": per, "fp64_arith_insts_per_edge_iter": f64_per or None,
+                              "issue_frac_in_profile": vj.get("valu_issue_frac"), "clock_ghz_in_profile": vj.get("clock_ghz"),
+                              "source": "instructions per edge-iteration: profiles/valu_clock.json (SQ_INSTS_VALU of this workload); clock: shader cycles / "
+                                        "constant-rate ticks summed over the persistent kernel's workgroups during the timed steps (ldpc_hip_bp_clock_probe); "
+                                        "kernel time: HIP events of this run"}
+                elif clock_run:
+                    second = {"kind": "fp64_valu", "issue_frac": None, "clock_ghz_this_run": clock_run, "sclk_sysfs_ghz": sclk.ghz()}
+            res["roofline"] = {
                 "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
                 "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
                 "kernel": "bp_decode_kernel (persistent, one workgroup per 64-syndrome tile) + bp_spread_* per-pass launches for the last tiles",
@@ -855,80 +907,71 @@ def run(args, real_stdout, stage) -> None:
                         "bp_decode_kernel average and kernel_ms_per_pass with the sum of the bp_spread_* kernels); traffic = PMC "
                         "counters of the same kernels from the committed profile run (profiles/); second_bound = that profile's instruction count per "
                         "edge-iteration with THIS run's clock (clock_ghz_this_run: device cycle / tick counters), iterations and kernel time",
-            },
-        }
-        if grouped:
-            res["rccl"] = {"ranks": dist.get_world_size(), "backend": dist.get_backend(),
-                           "version": ".".join(str(v) for v in torch.cuda.nccl.version()),
-                           "devices": [torch.cuda.get_device_name(local_rank)], "launcher": "torch.distributed.run"}
-            if args.share_gpu:
-                res["rccl"]["note"] = "--share-gpu diagnostic: every rank on cuda:0, gloo group, collectives on host tensors; the rate means nothing"
-
-            res["per_rank"] = {"kernel_ms": [r[0] for r in per_rank], "gather_ms": [r[1] for r in per_rank],
-                               "mean_iterations": [r[3] for r in per_rank],
-                               "parity_ok": [bool(r[2]) for r in per_rank], "parity_rows_per_rank": rank_rows,
-                               "parity_all_ranks": bool(all(r[2] for r in per_rank)),
-                               "parity_note": "every rank: decisions, iterations, converge flags bit-exact and LLR <= 1e-5 vs the CPU checker on "
-                                              "random rows of its own shard; rank 0 also checks that its rows came back unchanged through the gather"}
-            res["gather"] = {"ms": g_ms, "bytes_to_rank0": (world - 1) * B * ((n + 7) // 8 + 5),
-                             "rows_on_rank0": int(gathered["dec_b8"].shape[0]) if gathered.get("dec_b8") is not None else 0}
-            if not res["per_rank"]["parity_all_ranks"]:
-                res["parity_failed"] = True
-        # ---- CPU baseline + parity gate on a bounded sample of THIS batch (rank 0, N = 1 only) ----
-        if world == 1 and args.cpu_sample != 0:
-            from oracle import llr_close  # checker only
-            from ldpc_amd.noise_models import generate_bsc_batch
-            sample = args.cpu_sample if args.cpu_sample > 0 else min(B, 1024)
-            # the device shot generator against its host twin on the first rows ...
-            head = min(B, 64)
-            err = generate_bsc_batch(n, args.p, 7, 0, head)
-            s_head = np.asarray((h.astype(np.int32) @ err.T.astype(np.int32)).T % 2, dtype=np.uint8)
-            assert np.array_equal(s_head, synd[:head].cpu().numpy()), "device shot generator differs from its host twin"
-            # ... and the decoder against the CPU reference on a random subset of the timed batch
-            rows = np.sort(np.random.default_rng(12345).choice(B, size=sample, replace=False))
-            rows_t = torch.from_numpy(rows).to(dev)
-            cpu, (cd, cl, ci, cc) = cpu_baseline(h, args.p, args.max_iter, args.bp_method, alpha, synd[rows_t].cpu().numpy())
-            gd = dec[rows_t].cpu().numpy()
-            ok = bool(np.array_equal(gd, cd) and np.array_equal(iters[rows], ci) and np.array_equal(conv[rows], cc))
-            if llr is not None:
-                ok = ok and llr_close(llr[rows_t].cpu().numpy(), cl, rtol=1e-5)
-            cpu["parity_vs_gpu"] = {"syndromes": int(sample), "subset": "random rows of the timed batch (seed 12345)",
-                                    "hard_decisions_iters_converge_exact_llr_1e-5": ok}
-            res["cpu_baseline"] = cpu
-            if not ok:
-                res["parity_failed"] = True
-        else:
-            res["cpu_baseline"] = "N = 1 only" if world > 1 else None  # (None: --cpu-sample 0 asked for no CPU leg)
-            if world > 1:
-                res["roofline"]["traffic_note"] = "PMC traffic is collected at N = 1 only (profiles/hbm_traffic.json)"
-        if world == 1 and not grouped and args.host_io and method_id == 0:
-            stage[0] = "host_io"
-            try:
-                res["host_io"] = host_io_leg(h, args, alpha, synd, dec, it, res["value"])
-                if not res["host_io"].get("equal_to_device_resident_outputs", False):
+            }
+            if grouped:
+                res["per_rank"] = {"kernel_ms": [r[0] for r in per_rank], "gather_ms": [r[1] for r in per_rank],
+                                   "mean_iterations": [r[3] for r in per_rank],
+                                   "parity_ok": [bool(r[2]) for r in per_rank], "parity_rows_per_rank": rank_rows,
+                                   "parity_all_ranks": bool(all(r[2] for r in per_rank)),
+                                   "parity_note": "every rank: decisions, iterations, converge flags bit-exact and LLR <= 1e-5 vs the CPU checker on "
+                                                  "random rows of its own shard; rank 0 also checks that its rows came back unchanged through the gather"}
+                if not res["per_rank"]["parity_all_ranks"]:
                     res["parity_failed"] = True
-            except Exception as exc:  # the headline line must not be lost to this leg
-                res["host_io"] = {"error": repr(exc)[:300]}
-        if world == 1 and args.secondary and method_id == 0:
-            early = None
-            try:  # the headline code at its early-exit operating point (p = 0.05), same engine, same buffers
-                early = early_exit_point(eng, h, dev, B, args, (dec, llr, it, cv), alpha)
-            except Exception as exc:
-                early = {"key": "c2_p050", "error": repr(exc)[:300]}
-            eng.close()
-            del synd, dec, llr, out
-            torch.cuda.empty_cache()
-            try:
-                res["secondary"] = [early] + secondary_configs(dev, max(5, args.steps))  # (millisecond calls: a median of at least five)
-                res["secondary"] += schedule_configs(dev, args.steps)
-                res["secondary"].append(serial_headline_config(dev, args.steps))
-                res["secondary"].append(serial_headline_config(dev, 2, "ldpc48"))
-                res["secondary"].append(serial_headline_config(dev, 2, "irregular"))
-                res["secondary"].append(irregular_config(dev, args.steps))
-                if not all(e.get("parity_vs_oracle", False) for e in res["secondary"]):
+            # ---- CPU baseline + parity gate on a bounded sample of THIS batch (rank 0, N = 1 only) ----
+            if world == 1 and args.cpu_sample != 0:
+                from oracle import llr_close  # checker only
+                from ldpc_amd.noise_models import generate_bsc_batch
+                sample = args.cpu_sample if args.cpu_sample > 0 else min(B, 1024)
+                # the device shot generator against its host twin on the first rows ...
+                head = min(B, 64)
+                err = generate_bsc_batch(n, args.p, 7, 0, head)
+                s_head = np.asarray((h.astype(np.int32) @ err.T.astype(np.int32)).T % 2, dtype=np.uint8)
+                assert np.array_equal(s_head, synd[:head].cpu().numpy()), "device shot generator differs from its host twin"
+                # ... and the decoder against the CPU reference on a random subset of the timed batch
+                rows = np.sort(np.random.default_rng(12345).choice(B, size=sample, replace=False))
+                rows_t = torch.from_numpy(rows).to(dev)
+                cpu, (cd, cl, ci, cc) = cpu_baseline(h, args.p, args.max_iter, args.bp_method, alpha, synd[rows_t].cpu().numpy())
+                gd = dec[rows_t].cpu().numpy()
+                ok = bool(np.array_equal(gd, cd) and np.array_equal(iters[rows], ci) and np.array_equal(conv[rows], cc))
+                if llr is not None:
+                    ok = ok and llr_close(llr[rows_t].cpu().numpy(), cl, rtol=1e-5)
+                cpu["parity_vs_gpu"] = {"syndromes": int(sample), "subset": "random rows of the timed batch (seed 12345)",
+                                        "hard_decisions_iters_converge_exact_llr_1e-5": ok}
+                res["cpu_baseline"] = cpu
+                if not ok:
                     res["parity_failed"] = True
-            except Exception as exc:  # the headline line must not be lost to a secondary config
-                res["secondary"] = {"error": repr(exc)[:300]}
+            else:
+                res["cpu_baseline"] = "N = 1 only" if world > 1 else None  # (None: --cpu-sample 0 asked for no CPU leg)
+                if world > 1:
+                    res["roofline"]["traffic_note"] = "PMC traffic is collected at N = 1 only (profiles/hbm_traffic.json)"
+            if world == 1 and not grouped and args.host_io and method_id == 0:
+                stage[0] = "host_io"
+                try:
+                    res["host_io"] = host_io_leg(h, args, alpha, synd, dec, it, res["value"])
+                    if not res["host_io"].get("equal_to_device_resident_outputs", False):
+                        res["parity_failed"] = True
+                except Exception as exc:  # the headline line must not be lost to this leg
+                    res["host_io"] = {"error": repr(exc)[:300]}
+            if world == 1 and args.secondary and method_id == 0:
+                early = None
+                try:  # the headline code at its early-exit operating point (p = 0.05), same engine, same buffers
+                    early = early_exit_point(eng, h, dev, B, args, (dec, llr, it, cv), alpha)
+                except Exception as exc:
+                    early = {"key": "c2_p050", "error": repr(exc)[:300]}
+                eng.close()
+                del synd, dec, llr, out
+                torch.cuda.empty_cache()
+                try:
+                    res["secondary"] = [early] + secondary_configs(dev, max(5, args.steps))  # (millisecond calls: a median of at least five)
+                    res["secondary"] += schedule_configs(dev, args.steps)
+                    res["secondary"].append(serial_headline_config(dev, args.steps))
+                    res["secondary"].append(serial_headline_config(dev, 2, "ldpc48"))
+                    res["secondary"].append(serial_headline_config(dev, 2, "irregular"))
+                    res["secondary"].append(irregular_config(dev, args.steps))
+                    if not all(e.get("parity_vs_oracle", False) for e in res["secondary"]):
+                        res["parity_failed"] = True
+                except Exception as exc:  # the headline line must not be lost to a secondary config
+                    res["secondary"] = {"error": repr(exc)[:300]}
         print(json.dumps(res), file=real_stdout, flush=True)
     if grouped:
         dist.barrier()

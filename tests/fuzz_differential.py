@@ -6,7 +6,7 @@ outside the image included since round 3), against the CPU checker bit for bit. 
 End of round 2: 3 242 cases over two seeds, no mismatch (gpurun, 7 minutes).  Round 3: the kernel-shape choices are handle switches
 (ldpc_hip_bp_set_debug_switch), mode 6 (the lane = edge kernels) joins wherever it applies, sizes 48 .. 1300."""
 import sys, os, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # the repository root
 import numpy as np, scipy.sparse as sp
 import oracle
 from ldpc_amd.engine import HipBpEngine

@@ -7,7 +7,7 @@ and through the per-lane kernel, plus the fixed-order serial schedule and the ra
 left behind, every row against the CPU checker (oracle/, pinned to the reference and to the host's std::sort).
     python tests/fuzz_schedules.py <seconds> <seed>"""
 import sys, os, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # the repository root
 import numpy as np, scipy.sparse as sp
 import oracle
 from ldpc_amd.engine import HipBpEngine

@@ -7,7 +7,7 @@ kernel from the start) to tens of tiles, random pass lengths, ring depths, wavef
 (oracle/: decode_serial_batch, bp.hpp:451-545), and every variant against the first bit for bit over ALL rows.
       python tests/fuzz_serial_stream.py <seconds> <seed>"""
 import sys, os, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # the repository root
 import numpy as np
 import oracle
 from ldpc_amd.engine import HipBpEngine

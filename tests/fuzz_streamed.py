@@ -7,7 +7,7 @@ entries, columns of 2 .. 8: per-pass kernels from the start by default for produ
 its variable-degree LDS ring with queues of 8 .. 20 units) -- decisions, iteration counts, flags and LOG-RATIO BITS of
 every row against the CPU checker.      python tests/fuzz_streamed.py <seconds> <seed>"""
 import sys, os, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))  # the repository root
 import numpy as np, scipy.sparse as sp
 import oracle
 from ldpc_amd.engine import HipBpEngine

@@ -107,3 +107,35 @@ def test_eight_ranks_as_the_driver_launches_them():
     assert r2.returncode == 0, r2.stderr[-2000:]
     got2 = json.loads([ln for ln in r2.stdout.splitlines() if ln.startswith("{")][-1])
     assert got2["world"] == 8 and len({d["pid"] for d in got2["dry_ranks"]}) == 8
+
+
+def test_dumped_outputs_are_float_and_within_the_budget(tmp_path):
+    """--dump-outputs: every syndrome's iterations and flags, a seeded sample of the (B, n) rows, float32 / float64, <= 64 MB."""
+    import numpy as np
+    import torch
+    import bench
+    B, n = 8192, 1000
+    g = torch.Generator().manual_seed(5)
+    dec = torch.randint(0, 2, (B, n), dtype=torch.uint8, generator=g)
+    llr = torch.randn((B, n), dtype=torch.float64, generator=g)
+    it = torch.randint(1, 51, (B,), dtype=torch.int32, generator=g)
+    cv = torch.randint(0, 2, (B,), dtype=torch.uint8, generator=g)
+    for out in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(str(out), dec, llr, it, cv)
+    got = {f.stem: np.load(f) for f in (tmp_path / "a").glob("*.npy")}
+    assert set(got) == {"rows", "decoding", "log_prob_ratios", "iterations", "converge"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    rows = got["rows"].astype(np.int64)
+    assert len(rows) == 256 and np.array_equal(rows, np.unique(rows))
+    assert np.array_equal(got["decoding"], dec[rows].numpy().astype(np.float32))
+    assert np.array_equal(got["log_prob_ratios"], llr[rows].numpy())
+    assert np.array_equal(got["iterations"], it.numpy().astype(np.float32)) and np.array_equal(got["converge"], cv.numpy().astype(np.float32))
+    assert all(np.array_equal(np.load(tmp_path / "b" / (k + ".npy")), v) for k, v in got.items())  # the same rows every time
+    # rows so long and a batch so large that the budget binds: fewer rows, and per-syndrome arrays sampled on the same rows
+    B, n = 1 << 22, 100000
+    bench.dump_outputs(str(tmp_path / "c"), torch.zeros((1, n), dtype=torch.uint8).expand(B, n), torch.zeros((1, n), dtype=torch.float64).expand(B, n),
+                       torch.zeros(B, dtype=torch.int32), torch.zeros(B, dtype=torch.uint8))
+    files = list((tmp_path / "c").glob("*.npy"))
+    assert sum(f.stat().st_size for f in files) <= bench.DUMP_BYTES
+    k = len(np.load(tmp_path / "c" / "rows.npy"))
+    assert 0 < k < 256 and np.load(tmp_path / "c" / "iterations.npy").shape == (k,) and np.load(tmp_path / "c" / "decoding.npy").shape == (k, n)

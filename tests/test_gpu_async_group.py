@@ -132,7 +132,7 @@ def _bench(args, timeout=900):
 def test_bench_under_a_process_group_of_one():
     """`python bench.py --gpus 1 --force-launch`: torch.distributed.run, init_process_group('nccl'), HipBpEngine under the
     group, gather_rows(eng.pack_b8(dec)) + flags, per-rank parity -- the N > 1 code path on the one GPU this box has."""
-    got = _bench(["--gpus", "1", "--force-launch", "--batch-per-gpu", "4096", "--steps", "2", "--warmup", "1", "--cpu-sample", "0",
+    got = _bench(["--gpus", "1", "--force-launch", "--full", "--batch-per-gpu", "4096", "--steps", "2", "--warmup", "1", "--cpu-sample", "0",
                   "--rank-parity", "48", "--secondary", "0"])
     assert got["n_gpus"] == 1 and got["rccl"]["ranks"] == 1 and got["rccl"]["backend"] == "nccl"
     assert got["per_rank"]["parity_all_ranks"] is True and got["per_rank"]["parity_rows_per_rank"] == 48
@@ -188,7 +188,7 @@ def test_bench_with_two_ranks_on_the_one_gpu():
     """`python bench.py --gpus 2 --share-gpu`: the N > 1 bookkeeping of the bench on hardware -- two shards of the shot stream, barrier,
     max over ranks, gather onto rank 0, per-rank parity and timings -- with both ranks on cuda:0 under a gloo group (a diagnostic: RCCL
     refuses two ranks on one device, and the rate of two processes sharing a GPU means nothing)."""
-    got = _bench(["--gpus", "2", "--share-gpu", "--batch-per-gpu", "4096", "--steps", "2", "--warmup", "1", "--rank-parity", "48"])
+    got = _bench(["--gpus", "2", "--share-gpu", "--full", "--batch-per-gpu", "4096", "--steps", "2", "--warmup", "1", "--rank-parity", "48"])
     assert got["n_gpus"] == 2 and got["rccl"]["ranks"] == 2 and got["rccl"]["backend"] == "gloo"
     assert got["config"]["global_batch"] == 8192 and got["gather"]["rows_on_rank0"] == 8192
     assert got["per_rank"]["parity_ok"] == [True, True] and got["per_rank"]["parity_all_ranks"] is True

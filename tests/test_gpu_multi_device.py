@@ -178,7 +178,7 @@ def test_two_ranks_over_rccl_when_two_gpus_are_visible():
     if torch.cuda.device_count() < 2:
         pytest.skip("one GPU visible")
     from test_gpu_async_group import _bench
-    got = _bench(["--gpus", "2", "--batch-per-gpu", "16384", "--steps", "2", "--warmup", "1", "--rank-parity", "64",
+    got = _bench(["--gpus", "2", "--full", "--batch-per-gpu", "16384", "--steps", "2", "--warmup", "1", "--rank-parity", "64",
                   "--secondary", "0", "--cpu-sample", "0", "--host-io", "0"], timeout=1500)
     assert got["n_gpus"] == 2 and got["rccl"]["ranks"] == 2 and got["rccl"]["backend"] == "nccl"
     assert got["config"]["batch_per_gpu"] == 16384 and got["config"]["global_batch"] == 32768

@@ -9,6 +9,6 @@ echo "# $(date -u +%FT%TZ) $(python -c 'import torch;print(torch.cuda.get_device
 for rep in $(seq 1 ${REPS:-3}); do
 for v in "$@"; do
   if [ "$v" = "base" ]; then unset LDPC_HIP_LIB; else export LDPC_HIP_LIB=$PWD/ldpc_amd/lib/variants/$v.so; fi
-  python bench.py --cpu-sample 0 --secondary 0 --host-io 0 --steps 2 --warmup 1 $ARGS 2>/dev/null | python -c "
+  python bench.py --full --cpu-sample 0 --secondary 0 --host-io 0 --steps 2 --warmup 1 $ARGS 2>/dev/null | python -c "
 import json,sys;d=json.loads(sys.stdin.read());r=d['roofline'];c=r.get('copy_GBps_this_run');print('rep$rep', '$v', round(d['value']), round(r['frac'],4), 'kernel_ms', round(r['kernel_ms'],1), 'persistent', round(r['kernel_ms_persistent'],1), 'copy', round(c) if c else None, 'frac_of_copy', round(r['frac_of_copy'],3) if c else None)"
 done; done
