@@ -129,13 +129,13 @@ int ldpc_hip_bp_set_stream(ldpc_hip_bp *h, void *hip_stream);
  * `for shot: decoder.decode(shot)` -- is served by a RESIDENT workgroup (bp_wave_ps_kernel's team form; csrc/host_onchip.h): the kernel
  * that decoded the last syndrome is still there, tables in LDS, polling a request word in the block; the call writes its syndrome,
  * bumps the word and spins on the served word -- no launch, no completion (BB144: 31 -> 22 us a call, hamming(5): 60 -> 50 us;
- * profiles/r5_single_decode_latency.txt).  The workgroup leaves by itself 100 us after its last request ("RESIDENT_LINGER_US"), at
+ * profiles/r5_single_decode_latency.txt).  The workgroup leaves by itself 100 us after its last request, at
  * once when the handle's parameters or priors change or the handle is destroyed; "RESIDENT" 0 = a launch per call.  A large batch (>= 64 MiB of data in at least three chunks, everything in host memory, BP
  * alone, rows independent of one another: the parallel and the fixed-order serial schedule) is cut into chunks of whole tiles --
  * <= 16 384 rows, ~256 MiB of results -- that move through PINNED double buffers on two copy streams: while the kernels decode
  * chunk c, chunk c + 1 is on its way in, chunk c - 1 on its way out, and the calling thread copies chunk c - 2 from the pinned
  * buffer into the caller's (pageable) arrays; with log-ratios the last quarter of the batch goes in chunks that halve down to 4 096 rows
- * (the last chunk's results cross PCIe with nothing left to overlap them: "HOST_TAPER" 0 = uniform chunks).  Results are those of one undivided call.  Debug switches "NO_HOST_PIPELINE",
+ * (the last chunk's results cross PCIe with nothing left to overlap them).  Results are those of one undivided call.  Debug switches "NO_HOST_PIPELINE",
  * "HOST_CHUNK_ROWS" (tests, measurements).  Measured (bench.py `host_io`): 0.93 of the device-resident rate without LLRs.
  */
 int ldpc_hip_bp_decode_batch(ldpc_hip_bp *h, const uint8_t *syndromes, int64_t batch,
@@ -380,18 +380,15 @@ int ldpc_hip_bp_set_handoff(ldpc_hip_bp *h, int32_t threshold_tiles);
  * are streamed).  Results are identical. */
 int ldpc_hip_bp_set_small_code_kernel(ldpc_hip_bp *h, int32_t mode);
 /* Measurement / test switches: kernel-shape choices that never change a result (profiles/README.md lists them: "PS_TEAM",
- * "OSD_UNBLOCKED", "OSD_PLANES", "TEAM_WAVES", "EDGE_STATIC_PCT", "EDGE_CHUNK", ...; for schedule = serial_relative: "REL_LDS" 0 = the
+ * "OSD_UNBLOCKED", "OSD_PLANES", "EDGE_STATIC_PCT", "EDGE_CHUNK", ...; for schedule = serial_relative: "REL_LDS" 0 = the
  * per-lane kernel with the state in HBM, 16 / 64 = lanes per syndrome of the on-chip kernel; "REL_LEVELS" 0 = sweep bit by bit instead of
  * level by level; "REL_SCRATCH_IN_L" 0 = scratch apart from the posterior array; "REL_PROF" 1 = print the kernel's cycle shares per phase
  * to stderr; for the streamed serial schedule: "SER_WAVES" / "SER_RING" wavefronts per tile and ring depth, "SER_LANE_MAX" rows at or below
- * which what a pass left finishes a workgroup per syndrome (0 = never), "SER_LANE_THREADS"; "NO_SPREAD_COMPACT" 1 = per-pass rounds never
- * compact their list of tiles; "VAR_RING" 1 = the streamed kernel's variable-degree LDS ring wherever it applies (rows <= 16, columns <= 8
- * entries), "VAR_RING_UNITS" its KiB of LDS per wavefront (8 .. 40, default 11); "SPREAD_NODES" / "SPREAD_NODES2" rows per wavefront of the
- * per-pass kernels from the start / after a hand-off; "SER_VAR" 0 = the streamed serial schedule's item form (any degree profile) never, 1 = also
+ * which what a pass left finishes a workgroup per syndrome (0 = never), "SER_LANE_THREADS"; "VAR_RING" 1 = the streamed kernel's variable-degree LDS ring wherever it applies (rows <= 16, columns <= 8
+ * entries), "VAR_RING_UNITS" its KiB of LDS per wavefront (8 .. 40, default 11); "SPREAD_NODES" rows per wavefront of the
+ * per-pass kernels from the start; "SER_VAR" 0 = the streamed serial schedule's item form (any degree profile) never, 1 = also
  * on (6,3)-regular matrices, "SER_VAR_UNITS" its KiB of LDS per wavefront (default 8); "REL_EXT" 0 / 1 = serial_relative's on-chip kernel never / always with the messages and
- * per-entry records in global memory (default: where the all-in-LDS form leaves fewer than four wavefronts per compute unit); "REL_FIRST_ONCE" 0 = every syndrome re-enacts the first
- * iteration's sort itself instead of taking the call's (rel_first_order_kernel); "REPACK2" 1 .. 3 = the two-pass streamed decode compacts a second time, after that many
- * iterations of its second pass, 4 = where the iteration histogram suggests it (default: never -- measured no gain); "OSD_COLLECT_AFTER" 1 = BP + OSD lists the
+ * per-entry records in global memory (default: where the all-in-LDS form leaves fewer than four wavefronts per compute unit); "OSD_COLLECT_AFTER" 1 = BP + OSD lists the
  * rows BP left unconverged in a launch of its own after the BP kernel instead of inside the on-chip BP kernels; "OSD_NO_FLAT" 1 = OSD-0 on small matrices without the column permutation (osd0_reg_kernel instead of osd0_flat_kernel); "EDGE_CLAMP" 1 = the lane = edge min-sum kernel always
  * with its clamp to DBL_MAX (default: left out where it provably never bites)).  A handle reads the environment variables LDPC_HIP_<NAME> ONCE, when it is
  * created; afterwards only this call changes a switch (value < 0: back to "not set").  Unknown names are an error. */

@@ -181,11 +181,11 @@ static int decode_batch_pipelined(ldpc_hip_bp *h, const uint8_t *synd, int64_t b
     if (llr && !llr_direct) advise_huge_pages(llr, (size_t)batch * n * 8);
     // The chunks: `rows` each -- but with log-ratios the LAST chunk's results (90 KB a row on the n = 10 000 code: 1.5 GB for 16 384 rows, ~30 ms
     // of PCIe) cross after its kernels with nothing left to overlap them, so the last quarter of the batch goes in chunks that halve down
-    // to 4 096 rows: what is left exposed is a quarter of that.  (LDPC_HIP_HOST_TAPER=0: uniform chunks; measurement.)
+    // to 4 096 rows: what is left exposed is a quarter of that.
     std::vector<int64_t> chunk_start, chunk_rows;
     {
         int64_t at = 0;
-        const bool taper = llr && h->sw("HOST_TAPER") != 0 && rows >= 8192 && batch >= 3 * rows;
+        const bool taper = llr && rows >= 8192 && batch >= 3 * rows;
         while (at < batch) {
             int64_t r = rows;
             const int64_t left = batch - at;
@@ -309,7 +309,7 @@ static int decode_batch_staged(ldpc_hip_bp *h, int osd, const uint8_t *synd, int
     // and their completion cost more than the kernels.  The kernels work in a host-mapped block instead.
     auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const size_t o_dec = up16(B * m), o_llr = o_dec + up16(B * n), o_it = o_llr + up16(B * n * 8), o_cv = o_it + up16(B * 4), pin_need = o_cv + up16(B);
-    if (h_synd && h_dec && (!llr || h_llr) && (!iters || h_it) && (!conv || h_cv) && pin_need <= ldpc_hip_bp::PIN_MAIL && !h->on("NO_PINNED_PATH")) {
+    if (h_synd && h_dec && (!llr || h_llr) && (!iters || h_it) && (!conv || h_cv) && pin_need <= ldpc_hip_bp::PIN_MAIL) {
         if (!h->pin_host) {
             if (hipHostMalloc((void **)&h->pin_host, ldpc_hip_bp::PIN_BYTES, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
                 hipHostGetDevicePointer((void **)&h->pin_dev, h->pin_host, 0) != hipSuccess) {

@@ -122,7 +122,6 @@ static WavePlan plan_wave(const ldpc_hip_bp *h, bool forced, bool want_llr, int6
     const bool team = h->small_mode == 5 || (h->small_mode != 4 && (w < 6 || 2 * p.np > 3 * 64 * u || batch <= 256 * (int64_t)w));
     if (team) {
         int tw = (p.np + 64 * u - 1) / (64 * u);
-        if (h->sw("TEAM_WAVES") >= 1) tw = h->sw("TEAM_WAVES");  // (measurements)
         if (tw < 2) tw = 2;
         if (tw > 16) tw = 16;
         p.team = true;
@@ -130,11 +129,11 @@ static WavePlan plan_wave(const ldpc_hip_bp *h, bool forced, bool want_llr, int6
         p.kern = p.kern_team;
         if (ms) {  // the LDS copy of the priors, 8 (np + 2) bytes: worth reading them from memory where that fits another workgroup
             const size_t lean_shared = wave_lds_shared(p.mp, p.np, p.dr, p.dc, false, false);
-            if (lds / (lean_shared + p.per_wave) > lds / (p.shared + p.per_wave) && !h->on("TEAM_PRIOR_LDS")) { p.shared = lean_shared; p.prior_global = true; }
+            if (lds / (lean_shared + p.per_wave) > lds / (p.shared + p.per_wave)) { p.shared = lean_shared; p.prior_global = true; }
         }
         // (the kernel's ~100 VGPRs allow 16 wavefronts per CU: two teams of eight beat one of thirteen -- 768 x 1600: 4.0 vs 4.8 ms)
         p.groups_per_cu = (int)(lds / (p.shared + p.per_wave));
-        if (p.groups_per_cu >= 2 && p.waves > 8 && h->sw("TEAM_WAVES") < 1) p.waves = 8;
+        if (p.groups_per_cu >= 2 && p.waves > 8) p.waves = 8;
         if (p.groups_per_cu * p.waves > 16) p.groups_per_cu = 16 / p.waves;
         if (p.groups_per_cu < 1) p.groups_per_cu = 1;
         return p;
@@ -614,8 +613,8 @@ int decode_onchip(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
 // cost ~15 us of such a call and the kernel's table set-up ~10 us more (profiles/r4_single_decode_latency.txt) -- so the workgroup that
 // decoded one syndrome STAYS (bp_wave_ps_kernel<., ., ., TEAM>, WavePsArgs::mail): the next call writes its syndrome into the handle's
 // host-mapped block, bumps the request word, and spins on the served word; the workgroup polls the request word over PCIe, decodes with
-// the tables it already has in LDS, writes the results into the block and bumps the served word.  It leaves after `linger` (100 us,
-// LDPC_HIP_RESIDENT_LINGER_US) without a request -- it cannot outlive a caller by more than that, and a torch.cuda.synchronize() behind a
+// the tables it already has in LDS, writes the results into the block and bumps the served word.  It leaves after `linger` (100 us)
+// without a request -- it cannot outlive a caller by more than that, and a torch.cuda.synchronize() behind a
 // decode() waits that long at most -- or at once when told to (resident_retire: parameters or priors changed, handle destroyed).
 // The block's layout for one syndrome is decode_batch_staged's (host_decode_abi.h); the syndrome is already in it.
 void resident_retire(ldpc_hip_bp *h) {
@@ -673,7 +672,7 @@ int decode_onchip_resident(ldpc_hip_bp *h, bool want_llr, bool *took) {
         for (int i = 0; i < h->m; ++i) a.min_rdeg = std::min(a.min_rdeg, h->h_row_ptr[(size_t)i + 1] - h->h_row_ptr[(size_t)i]);
         a.mail = reinterpret_cast<unsigned *>(h->pin_dev + ldpc_hip_bp::PIN_MAIL);
         a.served0 = __atomic_load_n(mail + 1, __ATOMIC_ACQUIRE);
-        const int linger_us = h->sw("RESIDENT_LINGER_US") > 0 ? h->sw("RESIDENT_LINGER_US") : 100;
+        const int linger_us = 100;
         a.linger_ticks = (unsigned)linger_us * 100u;  // (the constant-rate counter runs at 100 MHz)
         const size_t dyn = p.shared + p.per_wave;
         if (dyn > 48u * 1024u) HIPCHK(hipFuncSetAttribute((const void *)p.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));

@@ -232,7 +232,6 @@ int bposd_device(ldpc_hip_bp *h, int osd_method, int osd_order, const uint8_t *s
         if (A.slot_stride < 1) A.slot_stride = 1;
         int per_cu = (int)((160u * 1024u) / (lds + 1024));  // (+ the kernel's static LDS)
         if (per_cu > 4) per_cu = 4;
-        if (h->sw("OSD_PER_CU") >= 1 && h->sw("OSD_PER_CU") < per_cu) per_cu = h->sw("OSD_PER_CU");  // (measurements)
         if (per_cu < 1) per_cu = 1;
         int64_t slots = 256 * (int64_t)per_cu;
         if (slots > batch) slots = batch;
@@ -268,7 +267,7 @@ int bposd_device(ldpc_hip_bp *h, int osd_method, int osd_order, const uint8_t *s
     // that keeps exactly those rows (osd_exact_kernel.h); the same OSD kernels then run once more over these rows.  No host round trip:
     // both launches size themselves from device-side counters and cost a few microseconds when there is nothing to do.
     const bool rank_known = (double)a.m * a.m * a.words < 4e9;
-    if (rank_known && a.n - osd_k(h) < a.m && a.m <= 8192 && !h->on("OSD_NO_EXACT")) {
+    if (rank_known && a.n - osd_k(h) < a.m && a.m <= 8192) {
         // Footprint (documented in ldpc_hip.h): at most 64 workgroups' working copies, capped at 256 MiB, plus one corrected syndrome and
         // one list entry per row of the batch.  If the device cannot spare that, the second pass is skipped -- the first-pass solutions
         // stand and the affected rows keep status 2 -- rather than failing a decode whose outputs are already complete.

@@ -125,7 +125,7 @@ void ldpc_hip_bp_destroy(ldpc_hip_bp *h) {
     if (h->res.ended) (void)hipEventDestroy(h->res.ended);
     if (h->res.stream) (void)hipStreamDestroy(h->res.stream);
     (void)hipStreamSynchronize(h->stream);
-    for (DeviceBuf *b : {&h->flood_lane_scratch, &h->flood_list2, &h->flood_pos, &h->ser_pos_tab, &h->ser_pos_e0, &h->ser_rows[0], &h->ser_rows[1], &h->ser_synd2}) b->release();
+    for (DeviceBuf *b : {&h->ser_pos_tab, &h->ser_pos_e0, &h->ser_rows[0], &h->ser_rows[1], &h->ser_synd2}) b->release();
     for (DeviceBuf *b : {&h->msgA, &h->msgC, &h->par, &h->nzm, &h->invalid, &h->dec, &h->dcur, &h->llr_t,
                          &h->st_synd, &h->st_dec, &h->st_llr, &h->st_iters, &h->st_conv, &h->st_misc, &h->osd_llr, &h->osd_conv, &h->osd_packed, &h->osd_ell, &h->osd_scratch, &h->sp_hist, &h->sp_iters, &h->osd_list, &h->osd_counters, &h->osd_status, &h->osd_fix_synd, &h->osd_fix_list, &h->osd_fix_counters, &h->osd_fix_scratch, &h->rel_ord, &h->rel_dbit, &h->rl_edge, &h->rl_chk, &h->rl_cdeg, &h->rl_last, &h->sched_orders, &h->sched_order0, &h->sched_lvl_bits, &h->sched_lvl_ptr, &h->lvl_ptr, &h->lvl_bits, &h->rp_synd, &h->rp_dec, &h->rp_llr, &h->rp_iters, &h->rp_conv, &h->counter, &h->w_rdeg, &h->w_cdeg, &h->w_col, &h->w_apos, &h->w_prior, &h->d_edge0, &h->var_row_items, &h->var_pair_items, &h->e_partner, &h->e_kind, &h->e_scol, &h->e_prior, &h->wp_rdeg, &h->wp_col, &h->wp_epos,
                          &h->soft_S, &h->soft_in, &h->soft_out, &h->b8_in, &h->b8_out, &h->b8_synd, &h->b8_dec, &h->obs_row_ptr, &h->obs_col_idx,

@@ -125,12 +125,10 @@ int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
     const bool per_pass_first = h->handoff < 0 && h->bp_method == LDPC_HIP_PRODUCT_SUM && kern.ring_depth == 0 && !kern.var_ring &&
                                 h->max_row_deg <= 16 && h->max_col_deg <= 8 && h->max_iter <= 128;
     const int handoff = h->handoff < 0 ? (per_pass_first ? INT32_MAX : 256) : h->handoff;
-    if (!h->cont_extend) {
-        h->accumulated_ms = 0.f;
-        h->accumulated_persistent_ms = 0.f;
-        h->timed = false;
-        h->timed_mid = false;
-    }
+    h->accumulated_ms = 0.f;
+    h->accumulated_persistent_ms = 0.f;
+    h->timed = false;
+    h->timed_mid = false;
     hipStream_t st = h->stream;
     // second pass of a compacted decode: its rows are known to the device only -- `batch` is the most there can be, the kernels read the
     // real count (cont_rows_dev) and reach the caller's rows through cont_row_map; the grids of the tile-looping kernels follow an estimate
@@ -160,7 +158,7 @@ int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
         a.llr0 = h->d_llr0;
         a.A = (double *)h->msgA.p; a.C = (double *)h->msgC.p;
         if (h->cont_A) { a.A = h->cont_A; a.C = h->cont_C; a.it_start = h->cont_it_start; a.rows_dev = rows_dev; a.row_map = row_map; }
-        a.keep_state = (h->keep_state || h->on("KEEP_LAST_MESSAGES")) ? 1 : 0;
+        a.keep_state = h->keep_state ? 1 : 0;
         a.par = (const uint64_t *)h->par.p; a.nzm = (const uint64_t *)h->nzm.p;
         a.invalid = (const uint64_t *)h->invalid.p;
         a.dec = (uint64_t *)h->dec.p;
@@ -197,7 +195,7 @@ int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
         const size_t dyn_lds = lds_per_wave * (size_t)waves;
         if (dyn_lds > 48u * 1024u)
             HIPCHK(hipFuncSetAttribute((const void *)kern.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn_lds));
-        if (h->timed && !h->cont_extend) {  // fold the previous chunk's time before the events are re-recorded
+        if (h->timed) {  // fold the previous chunk's time before the events are re-recorded
             float prev = 0.f;
             HIPCHK(hipEventSynchronize(h->ev1));
             HIPCHK(hipEventElapsedTime(&prev, h->ev0, h->ev1));
@@ -207,15 +205,13 @@ int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
                 h->accumulated_persistent_ms += prev;
             }
         }
-        if (!h->cont_extend) {  // (a third pass: the second pass's interval goes on -- its ev0 and ev_mid stay, ev1 is recorded again at the end)
-            h->timed_mid = false;
-            HIPCHK(hipEventRecord(h->ev0, st));
-        }
+        h->timed_mid = false;
+        HIPCHK(hipEventRecord(h->ev0, st));
         if (h->cont_A) {
             // the listed rows' message state after the first pass, lane by lane, into dense tiles (inside this pass's timed region)
             const int epw = 16;
             const dim3 gg((unsigned)((h->nnz + 4 * epw - 1) / (4 * epw)), loop_tiles);
-            hipLaunchKernelGGL(gather_lane_state_kernel, gg, dim3(256), 0, st, (const double *)h->cont_C, h->cont_src_map ? h->cont_src_map : row_map, (int64_t)0, h->nnz, epw, h->cont_A, rows_dev);
+            hipLaunchKernelGGL(gather_lane_state_kernel, gg, dim3(256), 0, st, (const double *)h->cont_C, row_map, (int64_t)0, h->nnz, epw, h->cont_A, rows_dev);
             HIPCHK(hipGetLastError());
         }
         SpreadArgs sa = {};
@@ -254,16 +250,14 @@ int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
             }
             hipLaunchKernelGGL(kern.fn, dim3((unsigned)tiles), dim3((unsigned)(waves * LDPC_WAVE)), (unsigned)dyn_lds, st, a);
             HIPCHK(hipGetLastError());
-            if (!h->cont_extend) {
-                HIPCHK(hipEventRecord(h->ev_mid, st));
-                h->timed_mid = true;
-            }
+            HIPCHK(hipEventRecord(h->ev_mid, st));
+            h->timed_mid = true;
             if (handoff > 0 && h->max_iter > 1) {
                 // the persistent kernel parks at most `handoff` tiles (it starts parking when that many are unfinished);
                 // how many it did park stays on the device
                 grid_tiles = (unsigned)(tiles < handoff ? tiles : handoff);
                 sa.n_tiles = -1;
-                sa.nodes = h->sw("SPREAD_NODES2") > 0 ? h->sw("SPREAD_NODES2") : 4;  // (4, 8 and 16 measure the same on the headline's last 256 tiles)
+                sa.nodes = 4;  // (4, 8 and 16 measure the same on the headline's last 256 tiles)
             }
         }
         if (grid_tiles > 0) {
@@ -287,7 +281,7 @@ int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
             // workgroups for the list's first 32 slots + 8 rows of the looping form for whatever lies beyond (normally nothing), instead of
             // `grid_tiles` rows that leave at once at ~50 us a launch.  Not elsewhere: when most tiles keep going (the headline's last 256
             // tiles run to iteration 50, a chunk of the pipelined host path likewise) the row-per-tile grid is what runs them fastest.
-            const bool may_compact = rows_dev != nullptr && h->cont_late_rows >= 0 && h->cont_late_rows <= 24 && grid_tiles > 40 && !h->on("NO_SPREAD_COMPACT");
+            const bool may_compact = rows_dev != nullptr && h->cont_late_rows >= 0 && h->cont_late_rows <= 24 && grid_tiles > 40;
             bool compacted = false;
             for (int round = 0; round < rounds; ++round) {
                 if (*flag == sa.seq) break;  // a look, not a wait
@@ -321,20 +315,6 @@ int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
         HIPCHK(hipEventRecord(h->ev1, st));
         h->timed = true;
         HIPCHK(hipGetLastError());
-        if (h->on("DEBUG_HANDOFF")) {  // diagnostic only: waits for the device and reports what the persistent kernel parked
-            unsigned c[4] = {0, 0, 0, 0};
-            HIPCHK(hipStreamSynchronize(st));
-            HIPCHK(hipMemcpy(c, h->counter.p, 16, hipMemcpyDeviceToHost));
-            const TileState *ts = nullptr; (void)ts;
-            std::vector<TileState> states((size_t)tiles);
-            HIPCHK(hipMemcpy(states.data(), h->tile_state.p, sizeof(TileState) * (size_t)tiles, hipMemcpyDeviceToHost));
-            std::vector<int32_t> list((size_t)tiles);
-            HIPCHK(hipMemcpy(list.data(), h->handoff_list.p, sizeof(int32_t) * (size_t)tiles, hipMemcpyDeviceToHost));
-            long sum_it0 = 0; int min_it0 = 1 << 30, max_it0 = 0;
-            for (unsigned q = 0; q < c[1] && q < (unsigned)tiles; ++q) { const int it0 = states[(size_t)list[q]].it0; sum_it0 += it0; if (it0 < min_it0) min_it0 = it0; if (it0 > max_it0) max_it0 = it0; }
-            fprintf(stderr, "[ldpc_hip] tiles %lld: finished by the persistent kernel %u, parked %u (iterations done when parked: min %d mean %.1f max %d), live afterwards %u\n",
-                    (long long)tiles, c[0], c[1], c[1] ? min_it0 : 0, c[1] ? (double)sum_it0 / c[1] : 0.0, max_it0, c[2]);
-        }
 
         if (h->n > 0) {
             dim3 g((unsigned)((h->n + 255) / 256), loop_tiles);
@@ -368,7 +348,6 @@ int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
 static int stream_first_pass_length(ldpc_hip_bp *h, double *live_after, double gather_cost = 0.25) {
     *live_after = 0.5;
     h->cont_late_rows = -1;
-    for (int R = 0; R <= 3; ++R) h->cont_alive[R] = -1;
     if (h->repack_iters > 0) return h->repack_iters < h->max_iter ? h->repack_iters : 0;
     // The previous decode's histogram, IF its copy has landed -- a look, never a wait (the *_async entry points must not block): a
     // caller that queues decodes back to back is steered by the last histogram that did land
@@ -415,12 +394,6 @@ static int stream_first_pass_length(ldpc_hip_bp *h, double *live_after, double g
         double late = h->hist_landed[0];
         for (int j = best_k + 9; j < 256; ++j) late += h->hist_landed[j];
         h->cont_late_rows = (int64_t)late;
-        h->cont_alive_total = (int64_t)total;  // ... and those still running after best_k + R iterations, R = 0 .. 3 (where the lane kernel takes over)
-        for (int R = 0; R <= 3; ++R) {
-            double alive = h->hist_landed[0];
-            for (int j = best_k + R + 1; j < 256; ++j) alive += h->hist_landed[j];
-            h->cont_alive[R] = (int64_t)alive;
-        }
     }
     return best < 0.97 * plain ? best_k : 0;
 }
@@ -445,19 +418,6 @@ __global__ void repack_rows_kernel(const unsigned *__restrict__ counters, unsign
     const unsigned c = counters[0];
     rows_dev[0] = c;
     rows_dev[1] = (c + LDPC_WAVE - 1) / LDPC_WAVE;
-}
-
-// pos[list[r]] = r for the listed rows: where a row of the caller's arrays sits in the second pass's compacted tiles
-__global__ void __launch_bounds__(256) row_positions_kernel(const int32_t *__restrict__ list, const unsigned *__restrict__ count_dev, int32_t *__restrict__ pos) {
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < (int64_t)count_dev[0]) pos[list[r]] = (int32_t)r;
-}
-
-// out[i] = pos[list[i]] for the listed rows
-__global__ void __launch_bounds__(256) compose_positions_kernel(const int32_t *__restrict__ list, const unsigned *__restrict__ count_dev, const int32_t *__restrict__ pos,
-                                                                int32_t *__restrict__ out) {
-    const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r < (int64_t)count_dev[0]) out[r] = pos[list[r]];
 }
 
 // Nothing here waits for the device: the second pass is queued at once, sized for the most rows there can be (all of them), and
@@ -501,8 +461,8 @@ static int decode_stream_repacked(ldpc_hip_bp *h, const uint8_t *synd, int64_t b
         return stream_leave_histogram(h, iters, conv, batch);
     }
     if ((rc = h->osd_list.ensure(B * sizeof(int32_t)))) return rc;
-    if ((rc = h->osd_counters.ensure(8 * sizeof(unsigned)))) return rc;
-    HIPCHK(hipMemsetAsync(h->osd_counters.p, 0, 8 * sizeof(unsigned), h->stream));
+    if ((rc = h->osd_counters.ensure(4 * sizeof(unsigned)))) return rc;  // {count, next, rows, tiles}
+    HIPCHK(hipMemsetAsync(h->osd_counters.p, 0, 4 * sizeof(unsigned), h->stream));
     hipLaunchKernelGGL(osd_collect_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, h->stream, conv, batch,
                        (int32_t *)h->osd_list.p, (unsigned *)h->osd_counters.p);
     hipLaunchKernelGGL(repack_rows_kernel, dim3(1), dim3(1), 0, h->stream, (const unsigned *)h->osd_counters.p, (unsigned *)h->osd_counters.p + 2);
@@ -513,81 +473,6 @@ static int decode_stream_repacked(ldpc_hip_bp *h, const uint8_t *synd, int64_t b
     std::swap(h->ev_mid, h->evp_mid);
     h->timed_prev = h->timed;
     h->timed_prev_mid = h->timed_mid;
-    // What is left after the first pass -- or after a few more rounds in compacted tiles -- CAN finish a workgroup per syndrome
-    // (bp_flood_lane_kernel.h) instead of in tiles that keep moving 64 lanes for the one or two still alive in each: lane_after = the rounds
-    // in tiles before that (0: none; -1: tiles to the end).  Measured on the headline code at p = 0.05 (round 5, same box, 64 .. 1024 workgroups,
-    // after 0 .. 3 rounds): 108.8 - 111.2 ms against 109.4 ms for tiles to the end -- no gain: a row's two message arrays are 480 KB of 8-byte
-    // gathers that only stay in L2 for a few dozen rows at a time, and 11 000 rows straight after the first pass cost 10 ms MORE than their
-    // tiles.  So it is not chosen automatically; "FLOOD_LANES" 1 = straight after the first pass, 2 .. 4 = after 1 .. 3 rounds in tiles
-    // (tests keep the path honest: it gives the tiles' bits).  The serial schedule's lane kernel (bp_serial_stream_kernel.h) is another
-    // matter: there a tile-iteration is a chain of ~35 level barriers on one compute unit, here it is spread over the chip by the per-pass rounds.
-    int lane_after = -1;
-    {
-        const int fl = h->sw("FLOOD_LANES");
-        const bool fits = h->n <= 60000 && h->m <= 60000 && h->m > 0;  // (a byte per bit and per check in LDS; nodes heavier than the register bounds stream through memory)
-        if (fits && fl != 0) {
-            if (fl >= 1) lane_after = fl - 1 < full - k1 ? fl - 1 : -1;
-        }
-    }
-    auto launch_lanes = [&](int it_start, const double *tiles, const int32_t *pos, const int32_t *rows, const unsigned *count_dev, bool own_interval) -> int {
-        const int64_t groups = h->sw("FLOOD_LANE_GROUPS") > 0 ? h->sw("FLOOD_LANE_GROUPS") : 1024;
-        if ((rc = h->flood_lane_scratch.ensure(2 * sizeof(double) * (size_t)h->nnz * (size_t)groups))) return rc;
-        FloodLaneArgs fa = {};
-        fa.m = h->m; fa.n = h->n; fa.nnz = h->nnz; fa.max_iter = full; fa.it_start = it_start;
-        fa.ms_scaling_factor = h->ms_scaling_factor;
-        fa.row_ptr = h->d_row_ptr; fa.col_idx = h->d_col_idx; fa.col_ptr = h->d_col_ptr; fa.csc_edge = h->d_csc_edge;
-        fa.llr0 = h->d_llr0;
-        fa.A_tiles = tiles;
-        fa.pos = pos;
-        fa.rows = rows;
-        fa.count_dev = count_dev;
-        fa.A = (double *)h->flood_lane_scratch.p;
-        fa.C = fa.A + (size_t)h->nnz * (size_t)groups;
-        fa.synd = synd; fa.decoding = decoding; fa.llr = llr; fa.iters = iters; fa.conv = conv;
-        void (*kern)(const FloodLaneArgs);
-        const bool wide = h->max_row_deg > 8 || h->max_col_deg > 4;
-#define LDPC_PICK_FLOOD_LANE(M, F) (wide ? bp_flood_lane_kernel<M, F, 16, 8> : bp_flood_lane_kernel<M, F, 8, 4>)
-        if (h->bp_method == LDPC_HIP_MINIMUM_SUM) kern = LDPC_PICK_FLOOD_LANE(LDPC_HIP_MINIMUM_SUM, 0);
-        else if (h->math_mode == LDPC_HIP_MATH_FAST) kern = LDPC_PICK_FLOOD_LANE(LDPC_HIP_PRODUCT_SUM, 1);
-        else kern = LDPC_PICK_FLOOD_LANE(LDPC_HIP_PRODUCT_SUM, 0);
-#undef LDPC_PICK_FLOOD_LANE
-        const size_t dyn = (((size_t)h->n + 15) & ~(size_t)15) + (((size_t)h->m + 15) & ~(size_t)15);
-        if (dyn > 48u * 1024u) HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-        if (own_interval) {
-            h->accumulated_ms = 0.f;
-            h->accumulated_persistent_ms = 0.f;
-            h->timed_mid = false;
-            HIPCHK(hipEventRecord(h->ev0, h->stream));
-        }
-        hipLaunchKernelGGL(kern, dim3((unsigned)groups), dim3(512), (unsigned)dyn, h->stream, fa);
-        HIPCHK(hipEventRecord(h->ev1, h->stream));  // (behind a second pass: its interval now ends here)
-        h->timed = true;
-        HIPCHK(hipGetLastError());
-        return LDPC_HIP_OK;
-    };
-    if (lane_after == 0) {
-        if ((rc = launch_lanes(k1, (const double *)h->msgA.p, nullptr, (const int32_t *)h->osd_list.p, (const unsigned *)h->osd_counters.p, true))) return rc;
-        return stream_leave_histogram(h, iters, conv, batch);
-    }
-    // A SECOND COMPACTION (round 6).  Where the histogram says that a few iterations into the second pass most of ITS rows are done too -- the
-    // headline code at p = 0.05: 17 % of the batch go on after iteration 7, 1.9 % after iteration 8 -- the rows that are left sit in every one of
-    // the second pass's tiles, which keep moving 64 lanes' messages for them.  So the second pass stops after k2 iterations (keeping its
-    // messages), the rows still decoding are listed again, their lane state is gathered once more -- out of the second pass's tiles, into the
-    // array that was its check_to_bit scratch -- and a third pass finishes them in a tenth of the tiles.  Same machinery, same bits, still
-    // nothing waits for the device.  MEASURED (profiles/r6_second_compaction_ab.txt, same box, interleaved): 111.5 - 113.4 ms with it against
-    // 112.0 - 112.5 ms without on the headline code at p = 0.05, 146.5 - 148.0 against 146.1 - 146.7 on the irregular code at p = 0.06 -- the gather
-    // and the extra launches cost what the thinner rounds save -- so it is NOT chosen by default: "REPACK2" 1 .. 3 = always, after that many
-    // iterations of the second pass; 4 = where the histogram expects at most a fifth of the second pass's rows (but more than the late rounds'
-    // list compaction is for) to be left after 1 .. 3 iterations.  The tests keep the path honest: it gives the plain decode's bits.
-    int k2 = 0;
-    if (lane_after < 0 && h->sw("REPACK2") > 0) {
-        if (h->sw("REPACK2") <= 3) k2 = h->sw("REPACK2");
-        else if (h->cont_alive[0] > 0)
-            for (int R = 1; R <= 3 && !k2; ++R)
-                if (h->cont_alive[R] >= 0 && h->cont_alive[R] * 5 <= h->cont_alive[0] && h->cont_alive[R] * (double)batch / (double)(h->cont_alive_total > 0 ? h->cont_alive_total : 1) > 256.0) k2 = R;
-        if (k1 + k2 + 2 > full) k2 = 0;  // (nothing worth a gather is left to do)
-    }
-    const int64_t alive2 = k2 > 0 && h->cont_alive[k2] >= 0 && h->cont_alive_total > 0 ? (int64_t)((double)h->cont_alive[k2] * (double)batch / (double)h->cont_alive_total) : -1;
     h->cont_A = (double *)h->msgC.p;   // compacted bit_to_check state (gathered inside decode_device)
     h->cont_C = (double *)h->msgA.p;   // the gather's source, then the second pass's check_to_bit array
     h->cont_it_start = k1;
@@ -595,57 +480,11 @@ static int decode_stream_repacked(ldpc_hip_bp *h, const uint8_t *synd, int64_t b
     h->cont_rows_dev = (const unsigned *)h->osd_counters.p + 2;
     // grids of the tile-looping kernels: the rows the histogram expects + a margin (they loop, so any count is handled)
     h->cont_grid_tiles = (int64_t)(live * 1.25 * (double)tiles1) + 8;
-    if (lane_after > 0) { h->max_iter = k1 + lane_after; h->keep_state = true; }  // (lanes follow: these rounds leave their messages behind)
-    else if (k2 > 0) { h->max_iter = k1 + k2; h->keep_state = true; }             // (a third pass follows)
     rc = decode_device(h, synd, batch, decoding, llr, iters, conv, false);
-    h->keep_state = false;
-    h->max_iter = full;
     h->cont_A = h->cont_C = nullptr;
     h->cont_it_start = 0;
     h->cont_row_map = nullptr;
     h->cont_rows_dev = nullptr;
     if (rc) return rc;
-    if (k2 > 0 && lane_after <= 0) {
-        // what the second pass left: the rows of the whole batch whose flag is still down (only its rows can be), where each sat in its tiles,
-        // {rows, tiles} of the third pass on the device
-        if ((rc = h->flood_list2.ensure(B * sizeof(int32_t))) || (rc = h->flood_pos.ensure(B * sizeof(int32_t))) || (rc = h->flood_src.ensure(B * sizeof(int32_t)))) return rc;
-        unsigned *count2 = (unsigned *)h->osd_counters.p + 4;
-        HIPCHK(hipMemsetAsync(count2, 0, 4 * sizeof(unsigned), h->stream));
-        const dim3 gb((unsigned)((batch + 255) / 256));
-        hipLaunchKernelGGL(osd_collect_kernel, gb, dim3(256), 0, h->stream, conv, batch, (int32_t *)h->flood_list2.p, count2);
-        hipLaunchKernelGGL(row_positions_kernel, gb, dim3(256), 0, h->stream, (const int32_t *)h->osd_list.p, (const unsigned *)h->osd_counters.p, (int32_t *)h->flood_pos.p);
-        hipLaunchKernelGGL(compose_positions_kernel, gb, dim3(256), 0, h->stream, (const int32_t *)h->flood_list2.p, (const unsigned *)count2, (const int32_t *)h->flood_pos.p,
-                           (int32_t *)h->flood_src.p);
-        hipLaunchKernelGGL(repack_rows_kernel, dim3(1), dim3(1), 0, h->stream, (const unsigned *)count2, count2 + 2);
-        HIPCHK(hipGetLastError());
-        h->cont_A = (double *)h->msgA.p;   // gathered out of the second pass's bit_to_check array ...
-        h->cont_C = (double *)h->msgC.p;   // ... which then serves as the third pass's check_to_bit array
-        h->cont_it_start = k1 + k2;
-        h->cont_row_map = (const int32_t *)h->flood_list2.p;
-        h->cont_src_map = (const int32_t *)h->flood_src.p;
-        h->cont_rows_dev = (const unsigned *)count2 + 2;
-        h->cont_grid_tiles = (alive2 >= 0 ? (int64_t)((double)alive2 * 1.5 / LDPC_WAVE) : tiles1 / 8) + 8;
-        h->cont_late_rows = -1;
-        h->cont_extend = true;
-        rc = decode_device(h, synd, batch, decoding, llr, iters, conv, false);
-        h->cont_extend = false;
-        h->cont_A = h->cont_C = nullptr;
-        h->cont_it_start = 0;
-        h->cont_row_map = h->cont_src_map = nullptr;
-        h->cont_rows_dev = nullptr;
-        if (rc) return rc;
-    }
-    if (lane_after > 0) {
-        // what those rounds left: the rows of the whole batch whose flag is still down (only rows of the second pass can be), where each sat in
-        // the second pass's tiles (the inverse of its row list), and the lane kernel on them from the second pass's bit->check array
-        if ((rc = h->flood_list2.ensure(B * sizeof(int32_t))) || (rc = h->flood_pos.ensure(B * sizeof(int32_t)))) return rc;
-        unsigned *count2 = (unsigned *)h->osd_counters.p + 4;
-        HIPCHK(hipMemsetAsync(count2, 0, 2 * sizeof(unsigned), h->stream));
-        hipLaunchKernelGGL(osd_collect_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, h->stream, conv, batch, (int32_t *)h->flood_list2.p, count2);
-        hipLaunchKernelGGL(row_positions_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, h->stream, (const int32_t *)h->osd_list.p,
-                           (const unsigned *)h->osd_counters.p, (int32_t *)h->flood_pos.p);
-        HIPCHK(hipGetLastError());
-        if ((rc = launch_lanes(k1 + lane_after, (const double *)h->msgC.p, (const int32_t *)h->flood_pos.p, (const int32_t *)h->flood_list2.p, count2, false))) return rc;
-    }
     return stream_leave_histogram(h, iters, conv, batch);
 }

@@ -333,9 +333,8 @@ def test_streamed_parallel_schedule_repacks_from_the_previous_histogram(oracle_b
 
 
 
-@pytest.mark.parametrize("flood_lanes", [0, 1, 2, 4])
 @pytest.mark.parametrize("method,alpha", [(0, 1.0), (1, 0.0)])
-def test_lane_compaction_carries_the_decode_on_at_any_cut(method, alpha, flood_lanes, oracle_built):
+def test_lane_compaction_carries_the_decode_on_at_any_cut(method, alpha, oracle_built):
     """The streamed two-pass decode (ldpc_hip_bp_set_repack(k)): k iterations for all, then the unconverged rows' message state is
     compacted lane by lane into dense tiles and iterations k + 1 ... follow on those.  Any cut must give the arrays of the plain
     run -- including a cut after which nothing is left, one that leaves almost everything, the last possible one, the adaptive
@@ -348,8 +347,6 @@ def test_lane_compaction_carries_the_decode_on_at_any_cut(method, alpha, flood_l
     max_iter = 14
     eng = HipBpEngine(h.indptr, h.indices, n, np.full(n, 0.04), max_iter, method, alpha)
     eng.set_small_code_kernel(0)
-    # 1: what the first pass leaves finishes a workgroup per syndrome (bp_flood_lane_kernel) instead of in tiles; 2 / 4: after one / three rounds in compacted tiles
-    eng.set_debug_switch("FLOOD_LANES", flood_lanes)
     s = torch.cat([eng.gen_bsc_syndromes(5, 0.03, shot0=0, shots=33000, device="cuda:0"),
                    eng.gen_bsc_syndromes(6, 0.09, shot0=0, shots=900, device="cuda:0")])
     s = s[torch.randperm(len(s), generator=torch.Generator().manual_seed(2)).to(s.device)].contiguous()
@@ -375,9 +372,9 @@ def test_lane_compaction_carries_the_decode_on_at_any_cut(method, alpha, flood_l
 
 
 @pytest.mark.parametrize("code", ["ldpc36_n1200", "irregular", "hamming_heavy"])
-def test_rows_a_first_pass_leaves_finish_a_workgroup_per_syndrome(code, oracle_built):
-    """bp_flood_lane_kernel on regular, irregular (rows and columns heavier than the register bounds included) and product-sum / min-sum
-    decodes, forced after first passes of several lengths: the arrays of the plain run, bit for bit, and the checker's on a sample."""
+def test_two_pass_decode_on_heavy_rows_and_larger_codes(code, oracle_built):
+    """The streamed two-pass decode on regular, irregular (rows and columns heavier than the register bounds included) and product-sum /
+    min-sum decodes, forced after first passes of several lengths: the arrays of the plain run, bit for bit, and the checker's on a sample."""
     import torch
     from ldpc_amd import codes
     from ldpc_amd.engine import HipBpEngine
@@ -395,12 +392,11 @@ def test_rows_a_first_pass_leaves_finish_a_workgroup_per_syndrome(code, oracle_b
         s[5, 0] = 2
         eng.set_repack(0)
         plain = [t.cpu().numpy() for t in eng.decode_batch(s)]
-        for k, fl in ((1, 1), (3, 1), (max_iter - 1, 1), (2, 2), (3, 3), (1, 4)):
-            eng.set_debug_switch("FLOOD_LANES", fl)
+        for k in (1, 2, 3, max_iter - 1):
             eng.set_repack(k)
             got = [t.cpu().numpy() for t in eng.decode_batch(s)]
             for a, b in zip(plain, got):
-                assert bits_equal(a, b) if a.dtype == np.float64 else np.array_equal(a, b), (code, method, k, fl)
+                assert bits_equal(a, b) if a.dtype == np.float64 else np.array_equal(a, b), (code, method, k)
             lean = eng.decode_batch(s, want_llr=False)
             assert lean[1] is None and np.array_equal(lean[0].cpu().numpy(), plain[0]) and np.array_equal(lean[2].cpu().numpy(), plain[2])
         rows = np.r_[0:40, np.flatnonzero(~plain[3].astype(bool))[:24]]

@@ -1,7 +1,7 @@
-"""The second compaction of the streamed two-pass decode (csrc/host_stream.h: decode_stream_repacked, round 6): first pass k1 iterations, the
-rows still decoding compacted lane by lane into dense tiles, k2 more iterations, the rows STILL decoding compacted once more, a third pass to the
-end -- against the plain decode (no pass structure at all), the two-pass decode, and the CPU checker: every row bit for bit, regular (ring
-variant) and irregular (per-pass kernels) codes, both methods, with and without log-ratios, a hopeless row, a partial last tile."""
+"""The streamed two-pass decode (csrc/host_stream.h: decode_stream_repacked): first pass k1 iterations, the rows still decoding compacted
+lane by lane into dense tiles, a second pass to the end -- against the plain decode (no pass structure at all) and the CPU checker: every row
+bit for bit, regular (ring variant) and irregular (per-pass kernels) codes, both methods, with and without log-ratios, a hopeless row, a
+partial last tile."""
 import numpy as np
 import pytest
 
@@ -13,7 +13,7 @@ def _decode(eng, s, **kw):
 
 
 @pytest.mark.parametrize("code,method,alpha,p,max_iter", [("ldpc36", 0, 1.0, 0.055, 30), ("ldpc36", 1, 0.8, 0.05, 40), ("irregular", 0, 1.0, 0.035, 24), ("ldpc48", 1, 0.0, 0.04, 30)])
-def test_second_compaction_gives_the_plain_decodes_bits(code, method, alpha, p, max_iter, oracle_built):
+def test_two_pass_decode_gives_the_plain_decodes_bits(code, method, alpha, p, max_iter, oracle_built):
     from golden_util import bits_equal
     from ldpc_amd import codes
     from ldpc_amd.engine import HipBpEngine
@@ -34,17 +34,14 @@ def test_second_compaction_gives_the_plain_decodes_bits(code, method, alpha, p, 
     assert np.array_equal(ref[0][rows], want[0]) and np.array_equal(ref[2][rows], want[2]) and np.array_equal(ref[3][rows].astype(bool), want[3].astype(bool))
     assert bits_equal(ref[1][rows], want[1])
     for k1 in (2, 3, 5):
-        for k2 in (0, 1, 2, 3, 4):
-            eng.set_repack(k1)
-            eng.set_debug_switch("REPACK2", k2)
-            for want_llr in (True, False):
-                got = _decode(eng, s, want_llr=want_llr)
-                tag = (code, method, k1, k2, want_llr)
-                assert np.array_equal(got[0], ref[0]) and np.array_equal(got[2], ref[2]) and np.array_equal(got[3], ref[3]), tag
-                assert got[1] is None if not want_llr else bits_equal(got[1], ref[1]), tag
+        eng.set_repack(k1)
+        for want_llr in (True, False):
+            got = _decode(eng, s, want_llr=want_llr)
+            tag = (code, method, k1, want_llr)
+            assert np.array_equal(got[0], ref[0]) and np.array_equal(got[2], ref[2]) and np.array_equal(got[3], ref[3]), tag
+            assert got[1] is None if not want_llr else bits_equal(got[1], ref[1]), tag
     # steered by the histogram of the previous decode (repack -1): whatever it chooses, the same bits
     eng.set_repack(-1)
-    eng.set_debug_switch("REPACK2", 4)
     for _ in range(3):
         got = _decode(eng, s, want_llr=True)
         assert np.array_equal(got[0], ref[0]) and np.array_equal(got[2], ref[2]) and np.array_equal(got[3], ref[3]) and bits_equal(got[1], ref[1])

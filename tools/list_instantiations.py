@@ -26,7 +26,6 @@ RULES = {  # template -> who selects which instantiation
     "bp_serial_level_kernel": "host_serial.h pick_serial_level: serial schedule, level-parallel",
     "bp_serial_stream_kernel": "host_serial.h decode_serial_streamed / decode_serial_pass: serial schedule on (6,3)-shaped matrices with >= 32 bits a level: <METHOD, MATH, 6, 3, RING 1 (default) / 2>",
     "bp_serial_lane_kernel": "host_serial.h serial_lane_launch: what a streamed pass leaves (<= 2048 rows), batches of <= 256 rows: a workgroup per syndrome",
-    "bp_flood_lane_kernel": "host_stream.h decode_stream_repacked, on request only (FLOOD_LANES): the rows a first pass of the flooding schedule leaves, a workgroup per syndrome",
     "bp_spread_compact_kernel": "host_stream.h: the list of parked tiles without the final ones, every 8 rounds of a second pass with few expected stragglers",
     "bp_softinfo_kernel": "host_serial.h soft_info_device", "bp_softinfo_level_kernel": "host_serial.h soft_info_device (level-parallel)",
     "bp_serial_relative_kernel": "host_serial.h decode_serial_relative: codes beyond LDS (or LDPC_HIP_REL_LDS=0)",
