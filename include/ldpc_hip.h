@@ -414,6 +414,11 @@ int ldpc_hip_bp_clock_probe(ldpc_hip_bp *h, uint64_t *cycles, uint64_t *ticks, d
  * message arrays are (re)allocated to the probe's size if they are smaller; their contents are scratch between decodes anyway. */
 int ldpc_hip_bp_copy_probe(ldpc_hip_bp *h, int64_t tiles, int32_t segments_per_tile, int32_t passes, float *ms, double *gbytes_per_s);
 
+/* Bytes of device memory the library's grow-only buffers hold right now, over every handle of the process (a test aid; no counterpart in
+ * the reference): workspaces, staging and the tables built on first use -- not the matrix and priors a handle uploads when it is created.
+ * A handle's share is gone once ldpc_hip_bp_destroy returns. */
+int64_t ldpc_hip_debug_device_buf_bytes(void);
+
 /* Page-locked host memory for a caller's result arrays (no counterpart in the reference: its arrays never leave the host).  A host
  * pointer into such a block -- or into memory the caller registered with hipHostRegister -- handed to ldpc_hip_bp_decode_batch as `llr`
  * is written by the device-to-host copies themselves: the pipelined host path (above) skips its pinned staging buffer and the

@@ -37,12 +37,19 @@ static int fail(int code, const char *fmt, ...) {
                         __LINE__);                                                            \
     } while (0)
 
-struct DeviceBuf {  // grow-only device allocation
+inline std::atomic<long long> g_device_buf_bytes{0};  // bytes every live DeviceBuf of the process holds (ldpc_hip_debug_device_buf_bytes)
+
+struct DeviceBuf {  // grow-only device allocation, freed with its owner (on the device that is current then: see ldpc_hip_bp_destroy)
     void *p = nullptr;
     size_t cap = 0;
+    DeviceBuf() = default;
+    DeviceBuf(const DeviceBuf &) = delete;
+    DeviceBuf &operator=(const DeviceBuf &) = delete;
+    DeviceBuf(DeviceBuf &&o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }  // (std::vector<MultiDev>)
+    ~DeviceBuf() { release(); }
     int ensure(size_t bytes) {
         if (bytes <= cap) return 0;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
+        release();
         hipError_t e = hipMalloc(&p, bytes);
         if (e != hipSuccess) {
             p = nullptr;
@@ -50,9 +57,15 @@ struct DeviceBuf {  // grow-only device allocation
                         hipGetErrorString(e));
         }
         cap = bytes;
+        g_device_buf_bytes += (long long)bytes;
         return 0;
     }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
+    void release() {
+        if (p) (void)hipFree(p);
+        g_device_buf_bytes -= (long long)cap;
+        p = nullptr;
+        cap = 0;
+    }
 };
 
 // Measurement / test switches (none changes a result; profiles/README.md lists them).  They live in the handle: seeded ONCE, at
@@ -81,6 +94,7 @@ struct ldpc_hip_bp {
     int32_t ring_depth = 2; // LDS-DMA ring slots per wavefront for regular matrices (0 = register variant)
     int32_t small_mode = -1; // on-chip kernels for small codes: -1 auto, 0 never, 1 whenever one fits, 2 the slot kernel only
     std::vector<int32_t> h_row_ptr, h_col_idx;  // host copy of the CSR arrays
+    std::vector<int32_t> h_col_ptr, h_csc_edge, h_csc_row;  // ... and of the column view: column j's entries at [h_col_ptr[j], h_col_ptr[j + 1]), rows ascending, as CSR edge / row
     int wave_dr = 0, wave_dc = 0;  // template bounds the uploaded SoA position tables of bp_wave_kernel were built for (0: none)
     int wave_ps_dr = 0, wave_ps_dc = 0;  // likewise for bp_wave_ps_kernel
     DeviceBuf wp_rdeg, wp_col, wp_epos;
@@ -130,7 +144,6 @@ struct ldpc_hip_bp {
         int32_t seed_raw = 0;
         std::mt19937 rng_end;                       // generator behind the table's last row (kind 0)
         std::vector<int> row_end;                   // the table's last row
-        std::vector<int32_t> csc_ptr, csc_row;      // the checks of every bit (levels of an order: host_serial.h random_orders_levels)
         std::vector<int32_t> n_levels;              // levels of every row of the ring (0: row not built)
         std::vector<int32_t> expect_state;          // what the handle's order / generator must be for the table to be current
         std::mt19937 expect_rng;
@@ -227,6 +240,16 @@ struct ldpc_hip_bp {
     int32_t obs_k = -1;                                              // rows of the observables matrix (-1: not set)
     int64_t max_chunk_tiles = 0;                                     // 0 = decide from free memory
 };
+
+// (bp_method, math_mode) of the handle as the compile-time pair <METHOD, MATH> the kernels are instantiated for -- min-sum has one
+// arithmetic, product-sum two -- handed to `f` as two std::integral_constant<int, ...>:
+//     kern = with_method_math(h, [&](auto M, auto F) { return pick_serial<M, F>(rows, cols); });
+template <class Fn>
+static auto with_method_math(const ldpc_hip_bp *h, Fn &&f) {
+    if (h->bp_method == LDPC_HIP_MINIMUM_SUM) return f(std::integral_constant<int, LDPC_HIP_MINIMUM_SUM>{}, std::integral_constant<int, 0>{});
+    if (h->math_mode == LDPC_HIP_MATH_FAST) return f(std::integral_constant<int, LDPC_HIP_PRODUCT_SUM>{}, std::integral_constant<int, 1>{});
+    return f(std::integral_constant<int, LDPC_HIP_PRODUCT_SUM>{}, std::integral_constant<int, 0>{});
+}
 
 static int upload_priors(ldpc_hip_bp *h) {
     ++h->priors_version;

@@ -26,10 +26,7 @@ static int decode_small(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint
     a.llr0 = h->d_llr0;
     a.synd = synd; a.decoding = decoding; a.llr = llr; a.iters = iters; a.conv = conv;
     a.next = (unsigned long long *)h->counter.p;
-    void (*kern)(const SmallArgs);
-    if (h->bp_method == LDPC_HIP_MINIMUM_SUM) kern = bp_small_kernel<LDPC_HIP_MINIMUM_SUM, 0>;
-    else if (h->math_mode == LDPC_HIP_MATH_FAST) kern = bp_small_kernel<LDPC_HIP_PRODUCT_SUM, 1>;
-    else kern = bp_small_kernel<LDPC_HIP_PRODUCT_SUM, 0>;
+    void (*kern)(const SmallArgs) = with_method_math(h, [](auto M, auto F) { return &bp_small_kernel<M, F>; });
     const size_t dyn = small_lds_bytes(h, slots);
     if (dyn > 48u * 1024u)
         HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
@@ -79,9 +76,7 @@ static void pick_wave(int max_row, int max_col, WavePlan &p) {
 static WavePlan plan_wave(const ldpc_hip_bp *h, bool forced, bool want_llr, int64_t batch) {
     WavePlan p;
     if (h->m <= 0 || h->n <= 0 || h->nnz <= 0 || h->max_row_deg > 16 || h->max_col_deg > 8) return p;
-    if (h->bp_method == LDPC_HIP_MINIMUM_SUM) pick_wave<LDPC_HIP_MINIMUM_SUM, 0>(h->max_row_deg, h->max_col_deg, p);
-    else if (h->math_mode == LDPC_HIP_MATH_FAST) pick_wave<LDPC_HIP_PRODUCT_SUM, 1>(h->max_row_deg, h->max_col_deg, p);
-    else pick_wave<LDPC_HIP_PRODUCT_SUM, 0>(h->max_row_deg, h->max_col_deg, p);
+    with_method_math(h, [&](auto M, auto F) { pick_wave<M, F>(h->max_row_deg, h->max_col_deg, p); });
     if (!p.kern) return p;
     p.mp = (h->m + 63) / 64 * 64;
     p.np = (h->n + 63) / 64 * 64;
@@ -203,8 +198,9 @@ static WavePsPlan plan_wave_ps(const ldpc_hip_bp *h, bool forced, bool want_llr,
     WavePsPlan p;
     if (h->bp_method != LDPC_HIP_PRODUCT_SUM || h->m <= 0 || h->n <= 0 || h->nnz <= 0 || h->max_row_deg > 32 || h->max_col_deg > 8) return p;
     const bool heavy = h->max_row_deg > 8 || h->max_col_deg > 4;  // the (16, 8) / (32, 8) variants
-    if (h->math_mode == LDPC_HIP_MATH_FAST) pick_wave_ps<1>(h->max_row_deg, h->max_col_deg, p);
-    else pick_wave_ps<0>(h->max_row_deg, h->max_col_deg, p);
+    with_method_math(h, [&](auto M, auto F) {  // (product-sum only: see above)
+        if constexpr (M == LDPC_HIP_PRODUCT_SUM) pick_wave_ps<F>(h->max_row_deg, h->max_col_deg, p);
+    });
     p.np = (h->n + 63) / 64 * 64;
     const size_t rm = (size_t)p.dr * h->m;
     if (rm + 2 >= 65536 || (size_t)p.np + 1 >= 65536) return p;

@@ -2,6 +2,147 @@
 // Part of libldpc_hip.so: included by bp_hip.hip (one translation unit), in the order given there.
 #pragma once
 
+// ---- what the schedules below share -------------------------------------------------------------------------------------------------
+// a kernel that wants more dynamic LDS than the 48 KiB it gets without asking
+template <class Kernel>
+static int set_dynamic_lds(Kernel kern, size_t bytes) {
+    if (bytes > 48u * 1024u) HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return LDPC_HIP_OK;
+}
+
+// One order cut into levels of mutually check-disjoint POSITIONS (see bp_serial_level_kernel).  The order need not be a permutation -- the
+// reference accepts any n bit numbers, and a caller's serial_schedule_order with repeats is shuffled like any other -- so levels belong to
+// positions.  `bits` [n] gets the order level-major (schedule order inside a level), ptr[l] where level l starts (ptr[0 .. n]: zero behind
+// the end of the last level); returns the number of levels.  check_level [m] and level [n] are scratch.
+static int32_t order_levels(const ldpc_hip_bp *h, const int32_t *order, int32_t *bits, int32_t *ptr, std::vector<int32_t> &check_level,
+                            std::vector<int32_t> &level) {
+    const int n = h->n;
+    std::fill(check_level.begin(), check_level.end(), 0);
+    int32_t n_levels = n ? 1 : 0;
+    for (int t = 0; t < n; ++t) {
+        const int j = order[t];
+        int32_t l = 1;
+        for (int q = h->h_col_ptr[(size_t)j]; q < h->h_col_ptr[(size_t)j + 1]; ++q) l = std::max(l, check_level[(size_t)h->h_csc_row[(size_t)q]] + 1);
+        for (int q = h->h_col_ptr[(size_t)j]; q < h->h_col_ptr[(size_t)j + 1]; ++q) check_level[(size_t)h->h_csc_row[(size_t)q]] = l;
+        level[(size_t)t] = l;
+        n_levels = std::max(n_levels, l);
+    }
+    std::fill(ptr, ptr + n + 1, 0);
+    for (int t = 0; t < n; ++t) ptr[level[(size_t)t]]++;  // (count of level l at ptr[l], shifted into starts below)
+    for (int l = 0; l < n_levels; ++l) ptr[l + 1] += ptr[l];
+    std::vector<int32_t> fill(ptr, ptr + n_levels);
+    for (int t = 0; t < n; ++t) bits[(size_t)fill[(size_t)level[(size_t)t] - 1]++] = order[t];
+    return n_levels;
+}
+
+// wavefronts per tile of the level-parallel kernels for a schedule of `per_level` bits per level on average; 0: one wavefront walks the
+// order bit by bit (fewer than two bits per level, unless the level-parallel kernel was asked for)
+static int level_waves_for(const ldpc_hip_bp *h, double per_level) {
+    if (h->serial_kernel != 1 && !(per_level >= 2.0)) return 0;
+    const int waves = (int)(per_level + 0.999);
+    return waves > 8 ? 8 : waves < 1 ? 1 : waves;
+}
+
+// tiles of per_tile bytes that fit into `margin` of the device memory that is free or held already by the buffers they will live in
+static int tiles_that_fit(size_t per_tile, size_t held, double margin, int64_t *fit) {
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    *fit = (int64_t)((size_t)((double)(free_b + held) * margin) / (per_tile ? per_tile : 1));
+    return LDPC_HIP_OK;
+}
+
+// tiles per chunk of a decode that takes its batch in pieces: all of them, up to what the caller allows (ldpc_hip_bp_set_tuning), one launch
+// carries (`cap`) and memory holds.  `unit`: what a tile holds 64 of, for the message
+static int chunk_tiles_that_fit(const ldpc_hip_bp *h, int64_t tiles_total, size_t per_tile, size_t held, double margin, int64_t cap, const char *unit,
+                                int64_t *chunk) {
+    int64_t fit = 0;
+    int rc;
+    if ((rc = tiles_that_fit(per_tile, held, margin, &fit))) return rc;
+    if (fit < 1) return fail(LDPC_HIP_ERR_NOMEM, "not enough device memory for one 64-%s tile", unit);
+    *chunk = tiles_total;
+    if (h->max_chunk_tiles > 0 && *chunk > h->max_chunk_tiles) *chunk = h->max_chunk_tiles;
+    if (*chunk > cap) *chunk = cap;
+    if (*chunk > fit) *chunk = fit;
+    return LDPC_HIP_OK;
+}
+
+struct ChunkRange { int64_t tiles, b0, nb; };  // a chunk's tiles, its first row and its rows
+static ChunkRange chunk_range(int64_t t0, int64_t chunk, int64_t tiles_total, int64_t batch) {
+    ChunkRange c;
+    c.tiles = (tiles_total - t0 < chunk) ? tiles_total - t0 : chunk;
+    c.b0 = t0 * LDPC_WAVE;
+    c.nb = (batch - c.b0 < c.tiles * LDPC_WAVE) ? batch - c.b0 : c.tiles * LDPC_WAVE;
+    return c;
+}
+
+// the kernel time of a decode (ldpc_hip_bp_last_kernel_ms) starts over; prev_too: also what a two-pass decode before it left (evp0 / evp1)
+static void reset_timing(ldpc_hip_bp *h, bool prev_too) {
+    h->accumulated_ms = 0.f;
+    h->accumulated_persistent_ms = 0.f;
+    h->timed = h->timed_mid = false;
+    if (prev_too) h->timed_prev = h->timed_prev_mid = false;
+}
+
+// around a chunk's decode kernel: the chunk before it gives its time to accumulated_ms (its two events are used again)
+static int chunk_timing_begin(ldpc_hip_bp *h) {
+    if (h->timed) {
+        float prev = 0.f;
+        HIPCHK(hipEventSynchronize(h->ev1));
+        HIPCHK(hipEventElapsedTime(&prev, h->ev0, h->ev1));
+        h->accumulated_ms += prev;
+    }
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    return LDPC_HIP_OK;
+}
+static int chunk_timing_end(ldpc_hip_bp *h) {
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    h->timed = true;
+    HIPCHK(hipGetLastError());
+    return LDPC_HIP_OK;
+}
+
+// a chunk's packed decisions (h->dec) and tile-major log-ratios (h->llr_t) into the caller's arrays; nullptr: not wanted, or the kernel wrote them itself
+static int chunk_outputs(ldpc_hip_bp *h, const ChunkRange &c, uint8_t *decoding, double *llr) {
+    if (h->n > 0 && decoding) {
+        dim3 g((unsigned)((h->n + 255) / 256), (unsigned)c.tiles);
+        hipLaunchKernelGGL(unpack_decoding_kernel, g, dim3(256), 0, h->stream, (const uint64_t *)h->dec.p, c.nb, h->n, decoding + c.b0 * h->n);
+    }
+    if (h->n > 0 && llr) {
+        dim3 gt((unsigned)((h->n + LDPC_WAVE - 1) / LDPC_WAVE), (unsigned)c.tiles);
+        hipLaunchKernelGGL(transpose_llr_kernel, gt, dim3(256), 0, h->stream, (const double *)h->llr_t.p, c.nb, h->n, llr + (size_t)c.b0 * h->n);
+    }
+    HIPCHK(hipGetLastError());
+    return LDPC_HIP_OK;
+}
+
+// The rows a pass left unconverged, listed in h->osd_list and counted: the one place a decode in passes waits for the device.
+static int collect_unconverged(ldpc_hip_bp *h, const uint8_t *conv, int64_t rows, int64_t *count) {
+    int rc;
+    if ((rc = h->osd_list.ensure((size_t)rows * sizeof(int32_t))) || (rc = h->osd_counters.ensure(2 * sizeof(unsigned)))) return rc;
+    if (!h->h_counters) HIPCHK(hipHostMalloc((void **)&h->h_counters, 16, hipHostMallocDefault));
+    HIPCHK(hipMemsetAsync(h->osd_counters.p, 0, 2 * sizeof(unsigned), h->stream));
+    hipLaunchKernelGGL(osd_collect_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, h->stream, conv, rows, (int32_t *)h->osd_list.p, (unsigned *)h->osd_counters.p);
+    HIPCHK(hipMemcpyAsync(&h->h_counters[2], h->osd_counters.p, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));  // the size of what is left is needed on the host
+    *count = (int64_t)h->h_counters[2];
+    return LDPC_HIP_OK;
+}
+
+// what a compacted pass left in rp_dec / rp_llr / rp_iters / rp_conv -> rows list[0 .. cnt) of the caller's arrays (nullptr: not this one)
+static int scatter_pass_outputs(ldpc_hip_bp *h, const int32_t *list, int64_t cnt, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv) {
+    const size_t C = (size_t)cnt;
+    hipStream_t st = h->stream;
+    if (decoding && h->n > 0) {
+        hipLaunchKernelGGL(scatter_rows_kernel<uint8_t>, flat_grid(C * (size_t)h->n), dim3(256), 0, st, (const uint8_t *)h->rp_dec.p, list, cnt, h->n, decoding);
+        if (llr) hipLaunchKernelGGL(scatter_rows_kernel<double>, flat_grid(C * (size_t)h->n), dim3(256), 0, st, (const double *)h->rp_llr.p, list, cnt, h->n, llr);
+    }
+    if (iters) hipLaunchKernelGGL(scatter_rows_kernel<int32_t>, flat_grid(C), dim3(256), 0, st, (const int32_t *)h->rp_iters.p, list, cnt, 1, iters);
+    if (conv) hipLaunchKernelGGL(scatter_rows_kernel<uint8_t>, flat_grid(C), dim3(256), 0, st, (const uint8_t *)h->rp_conv.p, list, cnt, 1, conv);
+    HIPCHK(hipGetLastError());
+    return LDPC_HIP_OK;
+}
+
+// ---- the fixed-order serial schedule -----------------------------------------------------------------------------------------------------
 // levels of the serial schedule: see bp_serial_level_kernel
 static int ensure_serial_levels(ldpc_hip_bp *h) {
     if (h->levels_valid) return LDPC_HIP_OK;
@@ -9,27 +150,9 @@ static int ensure_serial_levels(ldpc_hip_bp *h) {
     std::vector<int32_t> order((size_t)n);
     if (h->custom_order) HIPCHK(hipMemcpy(order.data(), h->d_order, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
     else for (int j = 0; j < n; ++j) order[(size_t)j] = j;
-    std::vector<std::vector<int32_t>> checks_of((size_t)n);
-    for (int i = 0; i < m; ++i)
-        for (int e = h->h_row_ptr[(size_t)i]; e < h->h_row_ptr[(size_t)i + 1]; ++e) checks_of[(size_t)h->h_col_idx[(size_t)e]].push_back(i);
-    // (the order need not be a permutation -- the reference accepts any n bit numbers -- so levels belong to POSITIONS)
-    std::vector<int32_t> check_level((size_t)(m ? m : 1), 0), level((size_t)(n ? n : 1), 1);
-    int32_t n_levels = n ? 1 : 0;
-    for (int t = 0; t < n; ++t) {
-        const int j = order[(size_t)t];
-        int32_t l = 1;
-        for (int i : checks_of[(size_t)j]) l = std::max(l, check_level[(size_t)i] + 1);
-        for (int i : checks_of[(size_t)j]) check_level[(size_t)i] = l;
-        level[(size_t)t] = l;
-        n_levels = std::max(n_levels, l);
-    }
-    std::vector<int32_t> ptr((size_t)n_levels + 1, 0), bits((size_t)(n ? n : 1));
-    for (int t = 0; t < n; ++t) ptr[(size_t)level[(size_t)t]]++;
-    for (int l = 0; l < n_levels; ++l) ptr[(size_t)l + 1] += ptr[(size_t)l];
-    {
-        std::vector<int32_t> fill(ptr.begin(), ptr.end() - 1);
-        for (int t = 0; t < n; ++t) bits[(size_t)fill[(size_t)level[(size_t)t] - 1]++] = order[(size_t)t];  // schedule order inside a level
-    }
+    std::vector<int32_t> check_level((size_t)(m ? m : 1)), level((size_t)(n ? n : 1)), ptr((size_t)n + 1), bits((size_t)(n ? n : 1));
+    const int32_t n_levels = order_levels(h, order.data(), bits.data(), ptr.data(), check_level, level);
+    ptr.resize((size_t)n_levels + 1);
     int rc;
     if ((rc = h->lvl_ptr.ensure(sizeof(int32_t) * ((size_t)n_levels + 1))) || (rc = h->lvl_bits.ensure(sizeof(int32_t) * (size_t)(n ? n : 1)))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -68,13 +191,12 @@ static SerialStreamPlan plan_serial_stream(const ldpc_hip_bp *h) {
 }
 
 // wavefronts per tile and units of 1 KiB per wavefront of bp_serial_stream_var_kernel
-static void serial_var_geometry(const ldpc_hip_bp *h, int waves_cap, int &waves, int &units) {
+static void serial_var_geometry(const ldpc_hip_bp *h, int &waves, int &units) {
     units = h->sw("SER_VAR_UNITS") > 0 ? h->sw("SER_VAR_UNITS") : 8;
     if (units < h->max_row_deg / 2) units = h->max_row_deg / 2;  // (an item must fit the queue)
     if (units < 1) units = 1;
     if (units > 32) units = 32;
     waves = h->sw("SER_WAVES") > 0 ? h->sw("SER_WAVES") : 16;
-    if (waves > waves_cap) waves = waves_cap;
     if (waves > 16) waves = 16;
     while (waves > 1 && (size_t)waves * (size_t)units * 1024u > 150u * 1024u) --waves;
 }
@@ -83,18 +205,8 @@ static void serial_var_geometry(const ldpc_hip_bp *h, int waves_cap, int &waves,
 // kernel's level-major list (a position's items never straddle a wavefront)
 static int ensure_serial_var_tables(ldpc_hip_bp *h, int waves) {
     if (h->ser_var_valid && h->ser_var_waves == waves) return LDPC_HIP_OK;
-    const int n = h->n, m = h->m, L = h->n_levels;
-    std::vector<int32_t> col_ptr((size_t)n + 1, 0), col_edge((size_t)(h->nnz ? h->nnz : 1)), row_of((size_t)(h->nnz ? h->nnz : 1));
-    for (int e = 0; e < h->nnz; ++e) col_ptr[(size_t)h->h_col_idx[(size_t)e] + 1]++;
-    for (int j = 0; j < n; ++j) col_ptr[(size_t)j + 1] += col_ptr[(size_t)j];
-    {
-        std::vector<int32_t> fill(col_ptr.begin(), col_ptr.end() - 1);
-        for (int i = 0; i < m; ++i)
-            for (int e = h->h_row_ptr[(size_t)i]; e < h->h_row_ptr[(size_t)i + 1]; ++e) {  // (CSR order: a column's edges come out rows ascending, the order of its linked list)
-                col_edge[(size_t)fill[(size_t)h->h_col_idx[(size_t)e]]++] = e;
-                row_of[(size_t)e] = i;
-            }
-    }
+    const int n = h->n, L = h->n_levels;
+    const std::vector<int32_t> &col_ptr = h->h_col_ptr, &col_edge = h->h_csc_edge, &col_row = h->h_csc_row;  // (a column's entries rows ascending: the order of its linked list)
     // which entries an earlier position of the schedule has written, per item of every position (first iteration; the positions of one level
     // share no row, so "earlier" is "in an earlier level" and the dealing below changes nothing): mask over the row's OTHER entries
     std::vector<int32_t> pos_item0((size_t)n + 1, 0);
@@ -105,7 +217,7 @@ static int ensure_serial_var_tables(ldpc_hip_bp *h, int waves) {
         for (int p = 0; p < n; ++p) {
             const int j = h->h_lvl_bits[(size_t)p], dj = col_ptr[(size_t)j + 1] - col_ptr[(size_t)j];
             for (int k = 0; k < dj; ++k) {
-                const int e = col_edge[(size_t)col_ptr[(size_t)j] + k], i = row_of[(size_t)e], rs = h->h_row_ptr[(size_t)i], d = h->h_row_ptr[(size_t)i + 1] - rs;
+                const int e = col_edge[(size_t)col_ptr[(size_t)j] + k], i = col_row[(size_t)col_ptr[(size_t)j] + k], rs = h->h_row_ptr[(size_t)i], d = h->h_row_ptr[(size_t)i + 1] - rs;
                 int32_t mask = 0;
                 for (int t = 0; t < d - 1; ++t) if (written[(size_t)(rs + t + (t >= e - rs ? 1 : 0))]) mask |= 1 << t;
                 item_mask[(size_t)pos_item0[(size_t)p] + k] = mask;
@@ -115,7 +227,7 @@ static int ensure_serial_var_tables(ldpc_hip_bp *h, int waves) {
     }
     auto record = [&](int32_t *r, int p, int k, bool lane_form) {
         const int j = h->h_lvl_bits[(size_t)p];
-        const int e = col_edge[(size_t)col_ptr[(size_t)j] + k], i = row_of[(size_t)e], rs = h->h_row_ptr[(size_t)i], d = h->h_row_ptr[(size_t)i + 1] - rs;
+        const int e = col_edge[(size_t)col_ptr[(size_t)j] + k], i = col_row[(size_t)col_ptr[(size_t)j] + k], rs = h->h_row_ptr[(size_t)i], d = h->h_row_ptr[(size_t)i + 1] - rs;
         const int dj = col_ptr[(size_t)j + 1] - col_ptr[(size_t)j];
         r[0] = e; r[1] = rs; r[2] = d | ((e - rs) << 8) | (k << 16) | (dj << 24); r[3] = j; r[4] = i; r[5] = lane_form ? 1 : 0;
         r[6] = item_mask[(size_t)pos_item0[(size_t)p] + k]; r[7] = 0;
@@ -135,7 +247,7 @@ static int ensure_serial_var_tables(ldpc_hip_bp *h, int waves) {
                 const int j = h->h_lvl_bits[(size_t)p];
                 int c = 0;
                 for (int q = col_ptr[(size_t)j]; q < col_ptr[(size_t)j + 1]; ++q) {
-                    const int i = row_of[(size_t)col_edge[(size_t)q]];
+                    const int i = col_row[(size_t)q];
                     c += (h->h_row_ptr[(size_t)i + 1] - h->h_row_ptr[(size_t)i] - 1) + 8;
                 }
                 cost.emplace_back(c, p);
@@ -195,9 +307,7 @@ static int serial_var_init_segments(ldpc_hip_bp *h, const double **out) {
     int rc;
     if ((rc = h->ser_var_init.ensure(sizeof(double) * (size_t)h->nnz * LDPC_WAVE))) return rc;
     const dim3 g((unsigned)((h->nnz + 3) / 4));
-    if (h->bp_method == LDPC_HIP_MINIMUM_SUM) hipLaunchKernelGGL((serial_var_init_kernel<LDPC_HIP_MINIMUM_SUM, 0>), g, dim3(256), 0, h->stream, h->d_llr0, h->d_col_idx, h->nnz, (double *)h->ser_var_init.p);
-    else if (h->math_mode == LDPC_HIP_MATH_FAST) hipLaunchKernelGGL((serial_var_init_kernel<LDPC_HIP_PRODUCT_SUM, 1>), g, dim3(256), 0, h->stream, h->d_llr0, h->d_col_idx, h->nnz, (double *)h->ser_var_init.p);
-    else hipLaunchKernelGGL((serial_var_init_kernel<LDPC_HIP_PRODUCT_SUM, 0>), g, dim3(256), 0, h->stream, h->d_llr0, h->d_col_idx, h->nnz, (double *)h->ser_var_init.p);
+    with_method_math(h, [&](auto M, auto F) { hipLaunchKernelGGL((serial_var_init_kernel<M, F>), g, dim3(256), 0, h->stream, h->d_llr0, h->d_col_idx, h->nnz, (double *)h->ser_var_init.p); });
     HIPCHK(hipGetLastError());
     *out = (const double *)h->ser_var_init.p;
     return LDPC_HIP_OK;
@@ -218,11 +328,7 @@ static int ensure_serial_stream_table(ldpc_hip_bp *h, const SerialStreamPlan &sp
     const int n = h->n, dr = sp.dr, dc = sp.dc;
     const int rec = SERIAL_STREAM_REC;
     std::vector<int32_t> tab((size_t)n * (size_t)rec, 0);
-    std::vector<int32_t> col_fill((size_t)n, 0), col_edges((size_t)n * (size_t)dc, 0);
-    for (int e = 0; e < h->nnz; ++e) {  // (CSR order: a column's edges come out rows ascending, the order of its linked list)
-        const int j = h->h_col_idx[(size_t)e];
-        col_edges[(size_t)j * dc + col_fill[(size_t)j]++] = e;
-    }
+    const int32_t *col_edges = h->h_csc_edge.data();  // (every column has dc entries, rows ascending: the order of its linked list)
     std::vector<char> written((size_t)h->nnz, 0);
     for (int p = 0; p < n; ++p) {
         const int j = h->h_lvl_bits[(size_t)p];
@@ -271,177 +377,165 @@ static void (*pick_serial(int max_row, int max_col))(const SerialArgs) {
     return bp_serial_kernel<METHOD, MATH, 4, 8>;  // also the variant that streams heavier nodes (SerialArgs::fast == 0)
 }
 
+// ring slots, wavefronts per tile and dynamic LDS of bp_serial_stream_kernel
+static void serial_stream_geometry(const ldpc_hip_bp *h, const SerialStreamPlan &sp, int waves_cap, int &ring, int &waves, size_t &dyn) {
+    ring = h->sw("SER_RING") >= 2 ? 2 : 1;
+    waves = h->sw("SER_WAVES") > 0 ? h->sw("SER_WAVES") : 16;
+    if (waves > waves_cap) waves = waves_cap;
+    const size_t per_wave = (size_t)(ring * serial_stream_slot_bytes(sp.dr, sp.dc) + LDPC_NEAR_BYTES);
+    while (waves > 1 && (size_t)waves * per_wave > 150u * 1024u) --waves;
+    if (waves > 16) waves = 16;
+    dyn = (size_t)waves * per_wave;
+}
+
+// The streamed kernel of plan `sp` (sp.dr != 0) ready to launch: its tables current on the device, its geometry, its LDS allowed.
+struct SerialStreamLaunch {
+    void (*kern)(const SerialArgs) = nullptr;
+    int waves = 16, ring = 1, units = 0;
+    size_t dyn = 0;
+};
+static int serial_stream_setup(ldpc_hip_bp *h, const SerialStreamPlan &sp, int waves_cap, SerialStreamLaunch &l) {
+    int rc;
+    if (sp.var) {
+        // (one table for every pass of a decode: the streams are cut for a number of wavefronts, so a pass asked to use fewer keeps the table's)
+        serial_var_geometry(h, l.waves, l.units);
+        if ((rc = ensure_serial_var_tables(h, l.waves))) return rc;
+        l.dyn = (size_t)l.waves * (size_t)l.units * 1024u;
+        l.kern = with_method_math(h, [&](auto M, auto F) { return pick_serial_var<M, F>(sp); });
+    } else {
+        if ((rc = ensure_serial_stream_table(h, sp))) return rc;
+        serial_stream_geometry(h, sp, waves_cap, l.ring, l.waves, l.dyn);
+        l.kern = with_method_math(h, [&](auto M, auto F) { return pick_serial_stream<M, F>(l.ring); });
+    }
+    return set_dynamic_lds(l.kern, l.dyn);
+}
+
+// h->d_edge0 <- the edge form of the priors, what the messages start from (serial_edge0_kernel; queued on h->stream)
+static int ensure_edge0(ldpc_hip_bp *h) {
+    int rc;
+    if ((rc = h->d_edge0.ensure(sizeof(double) * (size_t)h->n))) return rc;
+    const dim3 ge((unsigned)((h->n + 255) / 256));
+    with_method_math(h, [&](auto M, auto F) { hipLaunchKernelGGL((serial_edge0_kernel<M, F>), ge, dim3(256), 0, h->stream, h->d_llr0, h->n, (double *)h->d_edge0.p); });
+    HIPCHK(hipGetLastError());
+    return LDPC_HIP_OK;
+}
+
+// The first iteration of bp_serial_stream_kernel reads tables instead of initial messages -- h->d_edge0 and, per position, h->ser_pos_e0 --
+// unless the order skips bits or EXPLICIT_INIT asks for the messages written out.
+static bool first_iteration_from_tables(const ldpc_hip_bp *h) { return h->order_visits_all && !h->on("EXPLICIT_INIT"); }
+static int ensure_first_iteration_tables(ldpc_hip_bp *h, const SerialStreamPlan &sp) {
+    int rc;
+    if ((rc = ensure_edge0(h)) || (rc = h->ser_pos_e0.ensure(sizeof(double) * 16 * (size_t)h->n))) return rc;
+    hipLaunchKernelGGL(serial_pos_e0_kernel, dim3((unsigned)((h->n * 16 + 255) / 256)), dim3(256), 0, h->stream, (const int32_t *)h->ser_pos_tab.p, h->d_col_idx,
+                       (const double *)h->d_edge0.p, h->n, sp.dc * (sp.dr - 1), (double *)h->ser_pos_e0.p);
+    HIPCHK(hipGetLastError());
+    return LDPC_HIP_OK;
+}
+
+// What every kernel of the fixed-order schedule takes from the handle: the matrix, the priors, the levels, the workspace of the tiles in
+// flight.  The caller adds what its form reads beyond that.
+static void fill_serial_args(const ldpc_hip_bp *h, SerialArgs &a, int max_iter, int64_t rows, double *state, bool want_llr, int32_t *iters, uint8_t *conv) {
+    a.m = h->m; a.n = h->n; a.nnz = h->nnz; a.max_iter = max_iter;
+    a.ms_scaling_factor = h->ms_scaling_factor;
+    a.batch = rows;
+    a.row_ptr = h->d_row_ptr; a.col_idx = h->d_col_idx; a.col_ptr = h->d_col_ptr; a.csc_edge = h->d_csc_edge; a.csc_row = h->d_csc_row;
+    a.llr0 = h->d_llr0;
+    a.A = state;
+    a.par = (const uint64_t *)h->par.p; a.invalid = (const uint64_t *)h->invalid.p;
+    a.dec = (uint64_t *)h->dec.p; a.dcur = (uint64_t *)h->dcur.p;
+    a.llr_t = want_llr ? (double *)h->llr_t.p : nullptr;
+    a.iters = iters; a.conv = conv;
+    a.lvl_ptr = (const int32_t *)h->lvl_ptr.p; a.lvl_bits = (const int32_t *)h->lvl_bits.p; a.n_levels = h->n_levels;
+}
+
+// mean bits per level over the rows of the random schedule's ring (random_orders_append, below)
+static double ring_bits_per_level(const ldpc_hip_bp *h) {
+    double sum = 0.0;
+    int cnt = 0;
+    for (int32_t nl : h->rnd.n_levels) if (nl > 0) { sum += (double)nl; ++cnt; }
+    return cnt ? (double)h->n / (sum / cnt) : 0.0;
+}
+
+// One pass of max_iter iterations over the batch, chunk by chunk (batches whose state is not resident at once; resident batches of the
+// streamed forms go through decode_serial_streamed).  orders: the per-iteration orders of the random schedule (random_orders_*, below).
 static int decode_serial_pass(ldpc_hip_bp *h, int max_iter, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr,
                               int32_t *iters, uint8_t *conv, const int32_t *orders = nullptr, int n_orders = 0, int orders_first = 0) {
     const int64_t tiles_total = (batch + LDPC_WAVE - 1) / LDPC_WAVE;
+    const size_t m1 = (size_t)(h->m ? h->m : 1), n1 = (size_t)(h->n ? h->n : 1);
     const size_t per_tile_msg = sizeof(double) * (size_t)(h->nnz ? h->nnz : 1) * LDPC_WAVE;
-    const size_t per_tile_llr = llr ? sizeof(double) * (size_t)(h->n ? h->n : 1) * LDPC_WAVE : 0;
+    const size_t per_tile_llr = llr ? sizeof(double) * n1 * LDPC_WAVE : 0;
     const bool fast = h->max_col_deg <= 4 && h->max_row_deg <= 8;
-    int64_t chunk = tiles_total;
-    if (h->max_chunk_tiles > 0 && chunk > h->max_chunk_tiles) chunk = h->max_chunk_tiles;
-    if (chunk > 32768) chunk = 32768;
-    {
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(hipMemGetInfo(&free_b, &total_b));
-        const size_t have = h->msgA.cap + h->msgC.cap + h->llr_t.cap;
-        const size_t budget = (size_t)((double)(free_b + have) * 0.85);
-        const size_t per_tile = (fast ? 1 : 2) * per_tile_msg + per_tile_llr + 24 * (size_t)(h->m + h->n + 1);
-        int64_t fit = (int64_t)(budget / (per_tile ? per_tile : 1));
-        if (fit < 1) return fail(LDPC_HIP_ERR_NOMEM, "not enough device memory for one 64-syndrome tile");
-        if (chunk > fit) chunk = fit;
-    }
+    int64_t chunk = 0;
     int rc;
+    if ((rc = chunk_tiles_that_fit(h, tiles_total, (fast ? 1 : 2) * per_tile_msg + per_tile_llr + 24 * (size_t)(h->m + h->n + 1),
+                                   h->msgA.cap + h->msgC.cap + h->llr_t.cap, 0.85, 32768, "syndrome", &chunk))) return rc;
     if ((rc = h->msgA.ensure(per_tile_msg * (size_t)chunk))) return rc;
     if ((rc = h->msgC.ensure(fast ? 16 : per_tile_msg * (size_t)chunk))) return rc;
-    if ((rc = h->par.ensure(sizeof(uint64_t) * (size_t)(h->m ? h->m : 1) * (size_t)chunk))) return rc;
-    if ((rc = h->nzm.ensure(sizeof(uint64_t) * (size_t)(h->m ? h->m : 1) * (size_t)chunk))) return rc;
+    if ((rc = h->par.ensure(sizeof(uint64_t) * m1 * (size_t)chunk))) return rc;
+    if ((rc = h->nzm.ensure(sizeof(uint64_t) * m1 * (size_t)chunk))) return rc;
     if ((rc = h->invalid.ensure(sizeof(uint64_t) * (size_t)chunk))) return rc;
-    if ((rc = h->dec.ensure(sizeof(uint64_t) * (size_t)(h->n ? h->n : 1) * (size_t)chunk))) return rc;
-    if ((rc = h->dcur.ensure(sizeof(uint64_t) * (size_t)(h->n ? h->n : 1) * (size_t)chunk))) return rc;
+    if ((rc = h->dec.ensure(sizeof(uint64_t) * n1 * (size_t)chunk))) return rc;
+    if ((rc = h->dcur.ensure(sizeof(uint64_t) * n1 * (size_t)chunk))) return rc;
     if (llr && (rc = h->llr_t.ensure(per_tile_llr * (size_t)chunk))) return rc;
-    void (*kern)(const SerialArgs);
-    // level-parallel variant when the schedule has at least two bits per level on average (or when asked for)
+    // level-parallel variant when the schedule has at least two bits per level on average (or when asked for); a schedule that changes per
+    // iteration: the levels of every row of the ring
     int level_waves = 0;
     const bool orders_levels = orders && h->rnd.valid && h->sched_lvl_bits.p && h->sched_lvl_ptr.p;  // (the ring carries levels: random_orders_append)
     if (h->serial_kernel != 0 && h->n > 0 && (!orders || orders_levels)) {
-        double per_level;
-        if (orders) {  // a schedule that changes per iteration: the levels of every row of the ring
-            double sum = 0.0;
-            int cnt = 0;
-            for (int32_t nl : h->rnd.n_levels) if (nl > 0) { sum += (double)nl; ++cnt; }
-            per_level = cnt ? (double)h->n / (sum / cnt) : 0.0;
-        } else {
-            if ((rc = ensure_serial_levels(h))) return rc;
-            per_level = (double)h->n / (double)(h->n_levels ? h->n_levels : 1);
-        }
-        if (h->serial_kernel == 1 || per_level >= 2.0) {
-            level_waves = (int)(per_level + 0.999);
-            if (level_waves > 8) level_waves = 8;
-            if (level_waves < 1) level_waves = 1;
-        }
+        if (!orders && (rc = ensure_serial_levels(h))) return rc;
+        level_waves = level_waves_for(h, orders ? ring_bits_per_level(h) : (double)h->n / (double)(h->n_levels ? h->n_levels : 1));
     }
-    // the streamed form (bp_serial_stream_kernel.h) where the matrix and the schedule allow it: automatic, or asked for (mode 2).  (Here: batches
-    // whose state is not resident at once, chunk by chunk, one pass each; resident batches go through decode_serial_streamed.)
+    // the streamed form (bp_serial_stream_kernel.h) where the matrix and the schedule allow it: automatic, or asked for (mode 2)
     SerialStreamPlan sp;
-    int ser_ring = 1, ser_waves = 16;
     if (level_waves && !orders && (h->serial_kernel == -1 || h->serial_kernel == 2)) sp = plan_serial_stream(h);
-    int var_units = 0;
-    if (sp.var) {
-        serial_var_geometry(h, 16, ser_waves, var_units);
-        if ((rc = ensure_serial_var_tables(h, ser_waves))) return rc;
-        if (h->bp_method == LDPC_HIP_MINIMUM_SUM) kern = pick_serial_var<LDPC_HIP_MINIMUM_SUM, 0>(sp);
-        else if (h->math_mode == LDPC_HIP_MATH_FAST) kern = pick_serial_var<LDPC_HIP_PRODUCT_SUM, 1>(sp);
-        else kern = pick_serial_var<LDPC_HIP_PRODUCT_SUM, 0>(sp);
-    } else if (sp.dr) {
-        if ((rc = ensure_serial_stream_table(h, sp))) return rc;
-        if (h->sw("SER_RING") > 0) ser_ring = h->sw("SER_RING") >= 2 ? 2 : 1;
-        if (h->sw("SER_WAVES") > 0) ser_waves = h->sw("SER_WAVES");
-        const int slot = serial_stream_slot_bytes(sp.dr, sp.dc);
-        while (ser_waves > 1 && (size_t)ser_waves * (size_t)(ser_ring * slot + LDPC_NEAR_BYTES) > 150u * 1024u) --ser_waves;
-        if (ser_waves > 16) ser_waves = 16;
-        if (h->bp_method == LDPC_HIP_MINIMUM_SUM) kern = pick_serial_stream<LDPC_HIP_MINIMUM_SUM, 0>(ser_ring);
-        else if (h->math_mode == LDPC_HIP_MATH_FAST) kern = pick_serial_stream<LDPC_HIP_PRODUCT_SUM, 1>(ser_ring);
-        else kern = pick_serial_stream<LDPC_HIP_PRODUCT_SUM, 0>(ser_ring);
-    } else if (level_waves) {
-        if (h->bp_method == LDPC_HIP_MINIMUM_SUM) kern = pick_serial_level<LDPC_HIP_MINIMUM_SUM, 0>(h->max_row_deg, h->max_col_deg);
-        else if (h->math_mode == LDPC_HIP_MATH_FAST) kern = pick_serial_level<LDPC_HIP_PRODUCT_SUM, 1>(h->max_row_deg, h->max_col_deg);
-        else kern = pick_serial_level<LDPC_HIP_PRODUCT_SUM, 0>(h->max_row_deg, h->max_col_deg);
-    } else if (h->bp_method == LDPC_HIP_MINIMUM_SUM) kern = pick_serial<LDPC_HIP_MINIMUM_SUM, 0>(h->max_row_deg, h->max_col_deg);
-    else if (h->math_mode == LDPC_HIP_MATH_FAST) kern = pick_serial<LDPC_HIP_PRODUCT_SUM, 1>(h->max_row_deg, h->max_col_deg);
-    else kern = pick_serial<LDPC_HIP_PRODUCT_SUM, 0>(h->max_row_deg, h->max_col_deg);
-    h->accumulated_ms = 0.f;
-    h->accumulated_persistent_ms = 0.f;
-    h->timed = false;
-    h->timed_mid = false;
+    SerialStreamLaunch sl;
+    void (*kern)(const SerialArgs);
+    if (sp.dr) {
+        if ((rc = serial_stream_setup(h, sp, 16, sl))) return rc;
+        kern = sl.kern;
+    } else if (level_waves) kern = with_method_math(h, [&](auto M, auto F) { return pick_serial_level<M, F>(h->max_row_deg, h->max_col_deg); });
+    else kern = with_method_math(h, [&](auto M, auto F) { return pick_serial<M, F>(h->max_row_deg, h->max_col_deg); });
+    const int waves = sp.dr ? sl.waves : level_waves ? level_waves : 1;
+    reset_timing(h, false);
     hipStream_t st = h->stream;
     for (int64_t t0 = 0; t0 < tiles_total; t0 += chunk) {
-        const int64_t tiles = (tiles_total - t0 < chunk) ? tiles_total - t0 : chunk;
-        const int64_t b0 = t0 * LDPC_WAVE;
-        const int64_t nb = (batch - b0 < tiles * LDPC_WAVE) ? batch - b0 : tiles * LDPC_WAVE;
-        HIPCHK(hipMemsetAsync(h->invalid.p, 0, sizeof(uint64_t) * (size_t)tiles, st));
-        HIPCHK(hipMemsetAsync(h->dec.p, 0, sizeof(uint64_t) * (size_t)(h->n ? h->n : 1) * (size_t)tiles, st));
-        HIPCHK(hipMemsetAsync(h->dcur.p, 0, sizeof(uint64_t) * (size_t)(h->n ? h->n : 1) * (size_t)tiles, st));
+        const ChunkRange c = chunk_range(t0, chunk, tiles_total, batch);
+        HIPCHK(hipMemsetAsync(h->invalid.p, 0, sizeof(uint64_t) * (size_t)c.tiles, st));
+        HIPCHK(hipMemsetAsync(h->dec.p, 0, sizeof(uint64_t) * n1 * (size_t)c.tiles, st));
+        HIPCHK(hipMemsetAsync(h->dcur.p, 0, sizeof(uint64_t) * n1 * (size_t)c.tiles, st));
         if (llr && !h->order_visits_all)  // bits the order never visits report 0 (the reference leaves them stale)
-            HIPCHK(hipMemsetAsync(h->llr_t.p, 0, per_tile_llr * (size_t)tiles, st));
+            HIPCHK(hipMemsetAsync(h->llr_t.p, 0, per_tile_llr * (size_t)c.tiles, st));
         if (h->m > 0) {
-            dim3 g((unsigned)((h->m + 255) / 256), (unsigned)tiles);
-            hipLaunchKernelGGL(pack_syndromes_kernel, g, dim3(256), 0, st, synd + b0 * h->m, nb, h->m,
+            dim3 g((unsigned)((h->m + 255) / 256), (unsigned)c.tiles);
+            hipLaunchKernelGGL(pack_syndromes_kernel, g, dim3(256), 0, st, synd + c.b0 * h->m, c.nb, h->m,
                                (uint64_t *)h->par.p, (uint64_t *)h->nzm.p, (uint64_t *)h->invalid.p);
         }
         SerialArgs a = {};
-        a.m = h->m; a.n = h->n; a.nnz = h->nnz; a.max_iter = max_iter; a.fast = fast ? 1 : 0;
-        a.ms_scaling_factor = h->ms_scaling_factor;
-        a.batch = nb;
-        a.row_ptr = h->d_row_ptr; a.col_idx = h->d_col_idx; a.col_ptr = h->d_col_ptr;
-        a.csc_edge = h->d_csc_edge; a.csc_row = h->d_csc_row; a.order = h->custom_order ? h->d_order : nullptr;
-        a.llr0 = h->d_llr0;
-        a.A = (double *)h->msgA.p; a.C = (double *)h->msgC.p;
-        a.par = (const uint64_t *)h->par.p; a.invalid = (const uint64_t *)h->invalid.p;
-        a.dec = (uint64_t *)h->dec.p; a.dcur = (uint64_t *)h->dcur.p;
-        a.llr_t = llr ? (double *)h->llr_t.p : nullptr;
-        a.iters = iters ? iters + b0 : nullptr;
-        a.conv = conv ? conv + b0 : nullptr;
-        if (h->timed) {
-            float prev = 0.f;
-            HIPCHK(hipEventSynchronize(h->ev1));
-            HIPCHK(hipEventElapsedTime(&prev, h->ev0, h->ev1));
-            h->accumulated_ms += prev;
-        }
-        HIPCHK(hipEventRecord(h->ev0, st));
-        a.lvl_ptr = (const int32_t *)h->lvl_ptr.p; a.lvl_bits = (const int32_t *)h->lvl_bits.p; a.n_levels = h->n_levels;
+        fill_serial_args(h, a, max_iter, c.nb, (double *)h->msgA.p, llr != nullptr, iters ? iters + c.b0 : nullptr, conv ? conv + c.b0 : nullptr);
+        a.fast = fast ? 1 : 0;
+        a.C = (double *)h->msgC.p;
+        a.order = h->custom_order ? h->d_order : nullptr;
         a.orders = orders; a.n_orders = n_orders; a.orders_first = orders_first;
         if (orders && level_waves) { a.orders_lvl = (const int32_t *)h->sched_lvl_bits.p; a.orders_lvl_ptr = (const int32_t *)h->sched_lvl_ptr.p; }
+        if ((rc = chunk_timing_begin(h))) return rc;
+        if (sp.dr) a.clk = h->d_clk;
         if (sp.var) {
-            a.var_items = (const int32_t *)h->ser_var_items.p; a.var_wq = (const int32_t *)h->ser_var_wq.p; a.var_units = var_units;
-            a.clk = h->d_clk;
+            a.var_items = (const int32_t *)h->ser_var_items.p; a.var_wq = (const int32_t *)h->ser_var_wq.p; a.var_units = sl.units;
             if ((rc = serial_var_init_segments(h, &a.var_init))) return rc;
-            const size_t dyn = (size_t)ser_waves * (size_t)var_units * 1024u;
-            if (dyn > 48u * 1024u) HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-            hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3((unsigned)(64 * ser_waves)), (unsigned)dyn, st, a);
         } else if (sp.dr) {
             a.pos_tab = (const int32_t *)h->ser_pos_tab.p;
-            a.clk = h->d_clk;
-            if (h->order_visits_all && !h->on("EXPLICIT_INIT")) {  // the first iteration reads this table instead of initial messages
-                if ((rc = h->d_edge0.ensure(sizeof(double) * (size_t)h->n))) return rc;
-                const dim3 ge((unsigned)((h->n + 255) / 256));
-                if (h->bp_method == LDPC_HIP_MINIMUM_SUM) hipLaunchKernelGGL((serial_edge0_kernel<LDPC_HIP_MINIMUM_SUM, 0>), ge, dim3(256), 0, st, h->d_llr0, h->n, (double *)h->d_edge0.p);
-                else if (h->math_mode == LDPC_HIP_MATH_FAST) hipLaunchKernelGGL((serial_edge0_kernel<LDPC_HIP_PRODUCT_SUM, 1>), ge, dim3(256), 0, st, h->d_llr0, h->n, (double *)h->d_edge0.p);
-                else hipLaunchKernelGGL((serial_edge0_kernel<LDPC_HIP_PRODUCT_SUM, 0>), ge, dim3(256), 0, st, h->d_llr0, h->n, (double *)h->d_edge0.p);
+            if (first_iteration_from_tables(h)) {
+                if ((rc = ensure_first_iteration_tables(h, sp))) return rc;
                 a.edge0 = (const double *)h->d_edge0.p;
-                if ((rc = h->ser_pos_e0.ensure(sizeof(double) * 16 * (size_t)h->n))) return rc;
-                hipLaunchKernelGGL(serial_pos_e0_kernel, dim3((unsigned)((h->n * 16 + 255) / 256)), dim3(256), 0, st, (const int32_t *)h->ser_pos_tab.p, h->d_col_idx,
-                                   (const double *)h->d_edge0.p, h->n, sp.dc * (sp.dr - 1), (double *)h->ser_pos_e0.p);
                 a.pos_e0 = (const double *)h->ser_pos_e0.p;
             }
-            const size_t dyn = (size_t)ser_waves * (size_t)(ser_ring * serial_stream_slot_bytes(sp.dr, sp.dc) + LDPC_NEAR_BYTES);
-            if (dyn > 48u * 1024u) HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-            hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3((unsigned)(64 * ser_waves)), (unsigned)dyn, st, a);
-        } else
-        hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3((unsigned)(64 * (level_waves ? level_waves : 1))), 0, st, a);
-        HIPCHK(hipEventRecord(h->ev1, st));
-        h->timed = true;
-        HIPCHK(hipGetLastError());
-        if (h->n > 0) {
-            dim3 g((unsigned)((h->n + 255) / 256), (unsigned)tiles);
-            hipLaunchKernelGGL(unpack_decoding_kernel, g, dim3(256), 0, st, (const uint64_t *)h->dec.p, nb, h->n,
-                               decoding + b0 * h->n);
-            if (llr) {
-                dim3 gt((unsigned)((h->n + LDPC_WAVE - 1) / LDPC_WAVE), (unsigned)tiles);
-                hipLaunchKernelGGL(transpose_llr_kernel, gt, dim3(256), 0, st, (const double *)h->llr_t.p, nb, h->n,
-                                   llr + (size_t)b0 * h->n);
-            }
         }
-        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(kern, dim3((unsigned)c.tiles), dim3((unsigned)(64 * waves)), (unsigned)sl.dyn, st, a);
+        if ((rc = chunk_timing_end(h)) || (rc = chunk_outputs(h, c, decoding, llr))) return rc;
     }
     return LDPC_HIP_OK;
 }
 
-
-// The serial kernel decodes a 64-syndrome tile with one wavefront, which runs until its slowest lane is done: one
-// syndrome that never converges keeps 63 finished ones waiting for max_iter iterations.  Repacking: a first pass with
-// few iterations over everything, then the rows it left unconverged -- packed densely into new tiles -- are decoded
-// again from the start with the full iteration budget (BP is deterministic: restarting gives what continuing would),
-// and their results replace the first pass's.  Work ~ k1 + f * max_iter instead of max_iter (f = unconverged fraction).
 // ---- schedules whose order lives in the decoder object and changes while decoding (bp.hpp:467-483) ------------------------
 // The reference decodes one syndrome at a time and carries serial_schedule_order (and the shuffle generator) from decode to
 // decode.  A batch cannot do that across its rows (where row b starts would depend on how many iterations rows 0 .. b-1
@@ -461,33 +555,8 @@ static void random_orders_shuffle(ldpc_hip_bp *h, int kind, std::vector<int> &v,
     else std::shuffle(v.begin(), v.end(), std::default_random_engine(h->sched_seed_raw));
 }
 
-// One order cut into levels of mutually check-disjoint POSITIONS (as ensure_serial_levels does for the fixed schedule): `bits` gets the
-// order level-major (schedule order inside a level), ptr[0] the number of levels, ptr[1 + l] where level l starts.  Levels belong to
-// positions, so an order with repeated bits (a caller's serial_schedule_order being shuffled) is handled like any other.
-static void random_orders_levels(ldpc_hip_bp *h, const std::vector<int> &order, int32_t *bits, int32_t *ptr, std::vector<int32_t> &check_level,
-                                 std::vector<int32_t> &level) {
-    auto &r = h->rnd;
-    const int n = r.n;
-    std::fill(check_level.begin(), check_level.end(), 0);
-    int32_t n_levels = n ? 1 : 0;
-    for (int t = 0; t < n; ++t) {
-        const int j = order[(size_t)t];
-        int32_t l = 1;
-        for (int q = r.csc_ptr[(size_t)j]; q < r.csc_ptr[(size_t)j + 1]; ++q) l = std::max(l, check_level[(size_t)r.csc_row[(size_t)q]] + 1);
-        for (int q = r.csc_ptr[(size_t)j]; q < r.csc_ptr[(size_t)j + 1]; ++q) check_level[(size_t)r.csc_row[(size_t)q]] = l;
-        level[(size_t)t] = l;
-        n_levels = std::max(n_levels, l);
-    }
-    std::fill(ptr, ptr + n + 2, 0);
-    ptr[0] = n_levels;
-    for (int t = 0; t < n; ++t) ptr[1 + level[(size_t)t]]++;        // (count of level l at ptr[1 + l], shifted into starts below)
-    for (int l = 0; l < n_levels; ++l) ptr[2 + l] += ptr[1 + l];
-    std::vector<int32_t> fill(ptr + 1, ptr + 1 + n_levels);
-    for (int t = 0; t < n; ++t) bits[(size_t)fill[(size_t)level[(size_t)t] - 1]++] = order[(size_t)t];
-}
-
 // rows [pos, pos + count) of the ring <- `count` further rearrangements of r.row_end (host staging in blocks); every row also goes up
-// level-major with its level bounds, for bp_serial_level_kernel / bp_softinfo_level_kernel
+// level-major with its level bounds (order_levels), for bp_serial_level_kernel / bp_softinfo_level_kernel
 static int random_orders_append(ldpc_hip_bp *h, int pos, int count) {
     auto &r = h->rnd;
     const size_t n = (size_t)r.n;
@@ -501,8 +570,9 @@ static int random_orders_append(ldpc_hip_bp *h, int pos, int count) {
             random_orders_shuffle(h, r.kind, r.row_end, r.rng_end);
             std::copy(r.row_end.begin(), r.row_end.end(), stage.begin() + (size_t)q * n);
             if (with_levels) {
-                random_orders_levels(h, r.row_end, stage_bits.data() + (size_t)q * n, stage_ptr.data() + (size_t)q * (n + 2), check_level, level);
-                r.n_levels[(size_t)((pos + done + q) % r.rows)] = stage_ptr[(size_t)q * (n + 2)];
+                int32_t *ptr = stage_ptr.data() + (size_t)q * (n + 2);  // [0]: the number of levels; [1 + l]: where level l starts
+                ptr[0] = order_levels(h, r.row_end.data(), stage_bits.data() + (size_t)q * n, ptr + 1, check_level, level);
+                r.n_levels[(size_t)((pos + done + q) % r.rows)] = ptr[0];
             }
         }
         for (int q = 0; q < now;) {  // (the ring may wrap inside a block)
@@ -537,15 +607,6 @@ static int random_orders_prepare(ldpc_hip_bp *h, int kind) {
     r.valid = false;
     r.kind = kind; r.rows = rows; r.n = n; r.first = 0; r.seed_raw = h->sched_seed_raw;
     r.n_levels.assign((size_t)rows, 0);
-    {   // the checks of every bit, for the levels
-        r.csc_ptr.assign((size_t)n + 1, 0);
-        for (int e = 0; e < h->nnz; ++e) r.csc_ptr[(size_t)h->h_col_idx[(size_t)e] + 1]++;
-        for (int j = 0; j < n; ++j) r.csc_ptr[(size_t)j + 1] += r.csc_ptr[(size_t)j];
-        r.csc_row.assign((size_t)(h->nnz ? h->nnz : 1), 0);
-        std::vector<int32_t> at(r.csc_ptr.begin(), r.csc_ptr.end() - 1);
-        for (int i = 0; i < h->m; ++i)
-            for (int e = h->h_row_ptr[(size_t)i]; e < h->h_row_ptr[(size_t)i + 1]; ++e) r.csc_row[(size_t)at[(size_t)h->h_col_idx[(size_t)e]]++] = i;
-    }
     r.row_end.assign(h->sched_state.begin(), h->sched_state.end());
     r.rng_end = h->sched_rng;
     if ((rc = random_orders_append(h, 0, rows))) return rc;
@@ -654,12 +715,14 @@ static int decode_serial_relative_lds(ldpc_hip_bp *h, const uint8_t *synd, int64
     if (h->rl_dc != dc) {
         std::vector<uint16_t> te((size_t)h->n * dc, 0), tc((size_t)h->n * dc, 0);
         std::vector<uint8_t> cd((size_t)h->n, 0);
-        for (int i = 0; i < h->m; ++i)
-            for (int e = h->h_row_ptr[(size_t)i]; e < h->h_row_ptr[(size_t)i + 1]; ++e) {
-                const int j = h->h_col_idx[(size_t)e], k = cd[(size_t)j]++;
-                te[(size_t)j * dc + k] = (uint16_t)e;   // (rows ascending: the order of the column's linked list, sparse_matrix_base.hpp:423-482)
-                tc[(size_t)j * dc + k] = (uint16_t)i;
+        for (int j = 0; j < h->n; ++j) {
+            const int q0 = h->h_col_ptr[(size_t)j];
+            cd[(size_t)j] = (uint8_t)(h->h_col_ptr[(size_t)j + 1] - q0);
+            for (int k = 0; k < cd[(size_t)j]; ++k) {
+                te[(size_t)j * dc + k] = (uint16_t)h->h_csc_edge[(size_t)q0 + k];  // (rows ascending: the order of the column's linked list, sparse_matrix_base.hpp:423-482)
+                tc[(size_t)j * dc + k] = (uint16_t)h->h_csc_row[(size_t)q0 + k];
             }
+        }
         if ((rc = h->rl_edge.ensure(te.size() * 2)) || (rc = h->rl_chk.ensure(tc.size() * 2)) || (rc = h->rl_cdeg.ensure(cd.size())) ||
             (rc = h->rl_last.ensure((size_t)h->n * sizeof(int32_t)))) return rc;
         HIPCHK(hipStreamSynchronize(h->stream));
@@ -672,19 +735,14 @@ static int decode_serial_relative_lds(ldpc_hip_bp *h, const uint8_t *synd, int64
     hipStream_t st = h->stream;
     HIPCHK(hipStreamSynchronize(st));
     if (ext && !h->rl_rec_valid) {  // the records the kernel otherwise builds in LDS: CSR edge | row start << 16 | row weight << 32 | check << 48 per (bit, entry of its column)
-        std::vector<unsigned long long> rec((size_t)h->n * dc, 0ull);
-        std::vector<uint8_t> cd((size_t)h->n, 0);
-        for (int i = 0; i < h->m; ++i) {
-            const unsigned long long rs = (unsigned long long)h->h_row_ptr[(size_t)i], rd = (unsigned long long)(h->h_row_ptr[(size_t)i + 1] - h->h_row_ptr[(size_t)i]);
-            for (int e = h->h_row_ptr[(size_t)i]; e < h->h_row_ptr[(size_t)i + 1]; ++e) {
-                const int j = h->h_col_idx[(size_t)e], k = cd[(size_t)j]++;
-                rec[(size_t)j * dc + k] = (unsigned long long)e | (rs << 16) | (rd << 32) | ((unsigned long long)i << 48);
-            }
-        }
         // (entries beyond a column's weight: the kernel's words for t_chk = t_edge = 0 -- check 0's row)
-        const unsigned long long pad = m_pad_word(h);
+        std::vector<unsigned long long> rec((size_t)h->n * dc, m_pad_word(h));
         for (int j = 0; j < h->n; ++j)
-            for (int k = cd[(size_t)j]; k < dc; ++k) rec[(size_t)j * dc + k] = pad;
+            for (int q = h->h_col_ptr[(size_t)j]; q < h->h_col_ptr[(size_t)j + 1]; ++q) {
+                const unsigned long long e = (unsigned long long)h->h_csc_edge[(size_t)q], i = (unsigned long long)h->h_csc_row[(size_t)q];
+                const unsigned long long rs = (unsigned long long)h->h_row_ptr[i], rd = (unsigned long long)(h->h_row_ptr[i + 1] - h->h_row_ptr[i]);
+                rec[(size_t)j * dc + (size_t)(q - h->h_col_ptr[(size_t)j])] = e | (rs << 16) | (rd << 32) | (i << 48);
+            }
         if ((rc = h->rl_rec.ensure(rec.size() * 8))) return rc;
         HIPCHK(hipMemcpy(h->rl_rec.p, rec.data(), rec.size() * 8, hipMemcpyHostToDevice));
         h->rl_rec_valid = true;
@@ -712,20 +770,18 @@ static int decode_serial_relative_lds(ldpc_hip_bp *h, const uint8_t *synd, int64
 #define LDPC_PICK_REL_X(M, F) (h->max_row_deg <= 8 ? (dc <= 4 ? bp_relative_lds_kernel<M, F, 8, 64, 4, 1> : bp_relative_lds_kernel<M, F, 8, 64, 8, 1>) \
                                                    : (dc <= 4 ? bp_relative_lds_kernel<M, F, 16, 64, 4, 1> : bp_relative_lds_kernel<M, F, 16, 64, 8, 1>))
 #define LDPC_PICK_REL(M, F) (ext ? LDPC_PICK_REL_X(M, F) : gs == 16 ? LDPC_PICK_REL_G(M, F, 16, 8) : dc <= 2 ? LDPC_PICK_REL_G(M, F, 64, 2) : dc <= 4 ? LDPC_PICK_REL_G(M, F, 64, 4) : LDPC_PICK_REL_G(M, F, 64, 8))
-    if (!ps) kern = LDPC_PICK_REL(LDPC_HIP_MINIMUM_SUM, 0);
-    else if (h->math_mode == LDPC_HIP_MATH_FAST) kern = LDPC_PICK_REL(LDPC_HIP_PRODUCT_SUM, 1);
-    else kern = LDPC_PICK_REL(LDPC_HIP_PRODUCT_SUM, 0);
+    kern = with_method_math(h, [&](auto M, auto F) { return LDPC_PICK_REL(M, F); });
 #undef LDPC_PICK_REL
 #undef LDPC_PICK_REL_X
 #undef LDPC_PICK_REL_G
     const size_t dyn = shared + (size_t)waves * per_wave_f;
-    if (dyn > 48u * 1024u) HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+    if ((rc = set_dynamic_lds(kern, dyn))) return rc;
     {   // the first iteration's sort, once per call (every row starts from the same order with the same keys): bp_relative_lds_kernel.h
         const size_t n1 = (size_t)h->n;
         const size_t pre = n1 * 8 + ((n1 * 2 + 15) & ~(size_t)15) + rel_lds_scratch(h->n, dc, false);
         if (batch > 1 && h->max_iter > 0 && pre <= 150u * 1024u && (int)h->sched_state.size() == h->n) {
             if ((rc = h->rl_first.ensure(n1 * sizeof(int32_t)))) return rc;
-            if (pre > 48u * 1024u) HIPCHK(hipFuncSetAttribute((const void *)rel_first_order_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pre));
+            if ((rc = set_dynamic_lds(rel_first_order_kernel, pre))) return rc;
             hipLaunchKernelGGL(rel_first_order_kernel, dim3(1), dim3(64), (unsigned)pre, st, h->d_llr0, (const int32_t *)h->sched_order0.p, h->n, (int32_t *)h->rl_first.p);
             HIPCHK(hipGetLastError());
             a.first_order = (const int32_t *)h->rl_first.p;
@@ -738,11 +794,7 @@ static int decode_serial_relative_lds(ldpc_hip_bp *h, const uint8_t *synd, int64
         a.A_g = (double *)h->rl_ext_A.p;
         a.rec_g = (const unsigned long long *)h->rl_rec.p;
         if (ps) {  // the edge form of the priors (what the messages start from): a table in global memory here
-            if ((rc = h->d_edge0.ensure(sizeof(double) * (size_t)h->n))) return rc;
-            const dim3 ge((unsigned)((h->n + 255) / 256));
-            if (h->math_mode == LDPC_HIP_MATH_FAST) hipLaunchKernelGGL((serial_edge0_kernel<LDPC_HIP_PRODUCT_SUM, 1>), ge, dim3(256), 0, st, h->d_llr0, h->n, (double *)h->d_edge0.p);
-            else hipLaunchKernelGGL((serial_edge0_kernel<LDPC_HIP_PRODUCT_SUM, 0>), ge, dim3(256), 0, st, h->d_llr0, h->n, (double *)h->d_edge0.p);
-            HIPCHK(hipGetLastError());
+            if ((rc = ensure_edge0(h))) return rc;
             a.pform_g = (const double *)h->d_edge0.p;
         }
     }
@@ -779,19 +831,10 @@ static int decode_serial_relative(ldpc_hip_bp *h, const uint8_t *synd, int64_t b
     const int64_t tiles_total = (batch + LDPC_WAVE - 1) / LDPC_WAVE;
     const size_t n1 = (size_t)(h->n ? h->n : 1), m1 = (size_t)(h->m ? h->m : 1);
     const size_t per_tile_msg = sizeof(double) * (size_t)(h->nnz ? h->nnz : 1) * LDPC_WAVE;
-    int64_t chunk = tiles_total;
-    if (h->max_chunk_tiles > 0 && chunk > h->max_chunk_tiles) chunk = h->max_chunk_tiles;
-    if (chunk > 32768) chunk = 32768;
-    {
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(hipMemGetInfo(&free_b, &total_b));
-        const size_t have = h->msgA.cap + h->msgC.cap + h->llr_t.cap + h->rel_ord.cap + h->rel_dbit.cap;
-        const size_t per_tile = 2 * per_tile_msg + n1 * LDPC_WAVE * (8 + 4 + 1) + 24 * (m1 + n1);
-        int64_t fit = (int64_t)((double)(free_b + have) * 0.85 / (double)per_tile);
-        if (fit < 1) return fail(LDPC_HIP_ERR_NOMEM, "not enough device memory for one 64-syndrome tile");
-        if (chunk > fit) chunk = fit;
-    }
+    int64_t chunk = 0;
     int rc;
+    if ((rc = chunk_tiles_that_fit(h, tiles_total, 2 * per_tile_msg + n1 * LDPC_WAVE * (8 + 4 + 1) + 24 * (m1 + n1),
+                                   h->msgA.cap + h->msgC.cap + h->llr_t.cap + h->rel_ord.cap + h->rel_dbit.cap, 0.85, 32768, "syndrome", &chunk))) return rc;
     if ((rc = h->msgA.ensure(per_tile_msg * (size_t)chunk)) || (rc = h->msgC.ensure(per_tile_msg * (size_t)chunk)) ||
         (rc = h->llr_t.ensure(n1 * LDPC_WAVE * 8 * (size_t)chunk)) || (rc = h->rel_ord.ensure(n1 * LDPC_WAVE * 4 * (size_t)chunk)) ||
         (rc = h->rel_dbit.ensure(n1 * LDPC_WAVE * (size_t)chunk)) || (rc = h->par.ensure(sizeof(uint64_t) * m1 * (size_t)chunk)) ||
@@ -800,55 +843,34 @@ static int decode_serial_relative(ldpc_hip_bp *h, const uint8_t *synd, int64_t b
     hipStream_t st = h->stream;
     HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipMemcpy(h->sched_order0.p, h->sched_state.data(), (size_t)h->n * sizeof(int32_t), hipMemcpyHostToDevice));
-    void (*kern)(const RelArgs);
-    if (h->bp_method == LDPC_HIP_MINIMUM_SUM) kern = bp_serial_relative_kernel<LDPC_HIP_MINIMUM_SUM, 0>;
-    else if (h->math_mode == LDPC_HIP_MATH_FAST) kern = bp_serial_relative_kernel<LDPC_HIP_PRODUCT_SUM, 1>;
-    else kern = bp_serial_relative_kernel<LDPC_HIP_PRODUCT_SUM, 0>;
-    h->accumulated_ms = 0.f;
-    h->accumulated_persistent_ms = 0.f;
-    h->timed = false;
-    h->timed_mid = false;
+    void (*kern)(const RelArgs) = with_method_math(h, [](auto M, auto F) { return &bp_serial_relative_kernel<M, F>; });
+    reset_timing(h, false);
     int64_t last_tiles = 0;
     for (int64_t t0 = 0; t0 < tiles_total; t0 += chunk) {
-        const int64_t tiles = (tiles_total - t0 < chunk) ? tiles_total - t0 : chunk;
-        const int64_t b0 = t0 * LDPC_WAVE;
-        const int64_t nb = (batch - b0 < tiles * LDPC_WAVE) ? batch - b0 : tiles * LDPC_WAVE;
-        HIPCHK(hipMemsetAsync(h->invalid.p, 0, sizeof(uint64_t) * (size_t)tiles, st));
+        const ChunkRange c = chunk_range(t0, chunk, tiles_total, batch);
+        HIPCHK(hipMemsetAsync(h->invalid.p, 0, sizeof(uint64_t) * (size_t)c.tiles, st));
         if (h->m > 0) {
-            dim3 g((unsigned)((h->m + 255) / 256), (unsigned)tiles);
-            hipLaunchKernelGGL(pack_syndromes_kernel, g, dim3(256), 0, st, synd + b0 * h->m, nb, h->m,
+            dim3 g((unsigned)((h->m + 255) / 256), (unsigned)c.tiles);
+            hipLaunchKernelGGL(pack_syndromes_kernel, g, dim3(256), 0, st, synd + c.b0 * h->m, c.nb, h->m,
                                (uint64_t *)h->par.p, (uint64_t *)h->nzm.p, (uint64_t *)h->invalid.p);
         }
         RelArgs a = {};
         a.m = h->m; a.n = h->n; a.nnz = h->nnz; a.max_iter = h->max_iter;
         a.ms_scaling_factor = h->ms_scaling_factor;
-        a.batch = nb;
+        a.batch = c.nb;
         a.row_ptr = h->d_row_ptr; a.col_idx = h->d_col_idx; a.col_ptr = h->d_col_ptr; a.csc_edge = h->d_csc_edge; a.csc_row = h->d_csc_row;
         a.order0 = (const int32_t *)h->sched_order0.p;
         a.llr0 = h->d_llr0;
         a.A = (double *)h->msgA.p; a.C = (double *)h->msgC.p; a.llr_t = (double *)h->llr_t.p;
         a.ord = (int32_t *)h->rel_ord.p; a.dbit = (uint8_t *)h->rel_dbit.p;
         a.par = (const uint64_t *)h->par.p; a.invalid = (const uint64_t *)h->invalid.p;
-        a.decoding = decoding + b0 * h->n;
-        a.iters = iters ? iters + b0 : nullptr;
-        a.conv = conv ? conv + b0 : nullptr;
-        if (h->timed) {
-            float prev = 0.f;
-            HIPCHK(hipEventSynchronize(h->ev1));
-            HIPCHK(hipEventElapsedTime(&prev, h->ev0, h->ev1));
-            h->accumulated_ms += prev;
-        }
-        HIPCHK(hipEventRecord(h->ev0, st));
-        hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3(64), 0, st, a);
-        HIPCHK(hipEventRecord(h->ev1, st));
-        h->timed = true;
-        HIPCHK(hipGetLastError());
-        if (llr && h->n > 0) {
-            dim3 gt((unsigned)((h->n + LDPC_WAVE - 1) / LDPC_WAVE), (unsigned)tiles);
-            hipLaunchKernelGGL(transpose_llr_kernel, gt, dim3(256), 0, st, (const double *)h->llr_t.p, nb, h->n, llr + (size_t)b0 * h->n);
-        }
-        HIPCHK(hipGetLastError());
-        last_tiles = tiles;
+        a.decoding = decoding + c.b0 * h->n;
+        a.iters = iters ? iters + c.b0 : nullptr;
+        a.conv = conv ? conv + c.b0 : nullptr;
+        if ((rc = chunk_timing_begin(h))) return rc;
+        hipLaunchKernelGGL(kern, dim3((unsigned)c.tiles), dim3(64), 0, st, a);
+        if ((rc = chunk_timing_end(h)) || (rc = chunk_outputs(h, c, nullptr, llr))) return rc;  // (the kernel writes the decisions itself)
+        last_tiles = c.tiles;
     }
     // the order the LAST row ended with becomes the object's serial_schedule_order: column (last lane) of the last tile's ord
     if (h->n > 0) {
@@ -867,7 +889,7 @@ static int decode_serial_relative(ldpc_hip_bp *h, const uint8_t *synd, int64_t b
 // workspace; lanes it finished stay finished).
 // row_map (or nullptr): row r of the launch is row row_map[r] of `decoding` / `llr`; `iters` / `conv` are indexed by the launch's own rows.
 static int serial_stream_launch(ldpc_hip_bp *h, const SerialStreamPlan &sp, int it_start, int it_end, bool resume, double *state, const uint8_t *synd,
-                                int64_t rows, const int32_t *row_map, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv, int waves_cap = 16) {
+                                int64_t rows, const int32_t *row_map, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv, int waves_cap) {
     const int64_t tiles = (rows + LDPC_WAVE - 1) / LDPC_WAVE;
     const size_t m1 = (size_t)h->m, n1 = (size_t)h->n;
     hipStream_t st = h->stream;
@@ -884,54 +906,23 @@ static int serial_stream_launch(ldpc_hip_bp *h, const SerialStreamPlan &sp, int 
         hipLaunchKernelGGL(pack_syndromes_kernel, g, dim3(256), 0, st, synd, rows, h->m, (uint64_t *)h->par.p, (uint64_t *)h->nzm.p, (uint64_t *)h->invalid.p,
                            (const int32_t *)nullptr, (const unsigned *)nullptr);
     }
-    int ser_ring = 1, ser_waves = 16, var_units = 0;
-    void (*kern)(const SerialArgs);
-    int slot = 0;
-    if (sp.var) {
-        // (one table for every pass of a decode: the streams are cut for a number of wavefronts, so a pass asked to use fewer keeps the table's)
-        serial_var_geometry(h, 16, ser_waves, var_units);
-        (void)waves_cap;
-        if ((rc = ensure_serial_var_tables(h, ser_waves))) return rc;
-        if (h->bp_method == LDPC_HIP_MINIMUM_SUM) kern = pick_serial_var<LDPC_HIP_MINIMUM_SUM, 0>(sp);
-        else if (h->math_mode == LDPC_HIP_MATH_FAST) kern = pick_serial_var<LDPC_HIP_PRODUCT_SUM, 1>(sp);
-        else kern = pick_serial_var<LDPC_HIP_PRODUCT_SUM, 0>(sp);
-    } else {
-        if (h->sw("SER_RING") > 0) ser_ring = h->sw("SER_RING") >= 2 ? 2 : 1;
-        if (h->sw("SER_WAVES") > 0) ser_waves = h->sw("SER_WAVES");
-        if (ser_waves > waves_cap) ser_waves = waves_cap;
-        slot = serial_stream_slot_bytes(sp.dr, sp.dc);
-        while (ser_waves > 1 && (size_t)ser_waves * (size_t)(ser_ring * slot + LDPC_NEAR_BYTES) > 150u * 1024u) --ser_waves;
-        if (ser_waves > 16) ser_waves = 16;
-        if (h->bp_method == LDPC_HIP_MINIMUM_SUM) kern = pick_serial_stream<LDPC_HIP_MINIMUM_SUM, 0>(ser_ring);
-        else if (h->math_mode == LDPC_HIP_MATH_FAST) kern = pick_serial_stream<LDPC_HIP_PRODUCT_SUM, 1>(ser_ring);
-        else kern = pick_serial_stream<LDPC_HIP_PRODUCT_SUM, 0>(ser_ring);
-    }
+    SerialStreamLaunch sl;
+    if ((rc = serial_stream_setup(h, sp, waves_cap, sl))) return rc;
     SerialArgs a = {};
-    a.m = h->m; a.n = h->n; a.nnz = h->nnz; a.max_iter = it_end; a.fast = 1;
-    a.ms_scaling_factor = h->ms_scaling_factor;
-    a.batch = rows;
-    a.row_ptr = h->d_row_ptr; a.col_idx = h->d_col_idx; a.col_ptr = h->d_col_ptr; a.csc_edge = h->d_csc_edge; a.csc_row = h->d_csc_row;
-    a.llr0 = h->d_llr0;
-    a.A = state;
-    a.par = (const uint64_t *)h->par.p; a.invalid = (const uint64_t *)h->invalid.p;
-    a.dec = (uint64_t *)h->dec.p; a.dcur = (uint64_t *)h->dcur.p;
-    a.llr_t = llr ? (double *)h->llr_t.p : nullptr;
-    a.iters = iters; a.conv = conv;
-    a.lvl_ptr = (const int32_t *)h->lvl_ptr.p; a.lvl_bits = (const int32_t *)h->lvl_bits.p; a.n_levels = h->n_levels;
+    fill_serial_args(h, a, it_end, rows, state, llr != nullptr, iters, conv);
+    a.fast = 1;
     a.pos_tab = (const int32_t *)h->ser_pos_tab.p;
     a.clk = h->d_clk;
     a.it_start = it_start;
     a.resume = resume ? 1 : 0;
     if (sp.var) {
-        a.var_items = (const int32_t *)h->ser_var_items.p; a.var_wq = (const int32_t *)h->ser_var_wq.p; a.var_units = var_units;
+        a.var_items = (const int32_t *)h->ser_var_items.p; a.var_wq = (const int32_t *)h->ser_var_wq.p; a.var_units = sl.units;
         if (it_start == 0 && (rc = serial_var_init_segments(h, &a.var_init))) return rc;
-    } else if (it_start == 0 && h->order_visits_all && !h->on("EXPLICIT_INIT")) {  // the first iteration reads these tables instead of initial messages
+    } else if (it_start == 0 && first_iteration_from_tables(h)) {  // (decode_serial_streamed filled them)
         a.edge0 = (const double *)h->d_edge0.p;
         a.pos_e0 = (const double *)h->ser_pos_e0.p;
     }
-    const size_t dyn = sp.var ? (size_t)ser_waves * (size_t)var_units * 1024u : (size_t)ser_waves * (size_t)(ser_ring * slot + LDPC_NEAR_BYTES);
-    if (dyn > 48u * 1024u) HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-    hipLaunchKernelGGL(kern, dim3((unsigned)tiles), dim3((unsigned)(64 * ser_waves)), (unsigned)dyn, st, a);
+    hipLaunchKernelGGL(sl.kern, dim3((unsigned)tiles), dim3((unsigned)(64 * sl.waves)), (unsigned)sl.dyn, st, a);
     HIPCHK(hipGetLastError());
     {   // (these kernels loop over the tiles beyond their grid)
         const unsigned gy = (unsigned)(tiles < 32768 ? tiles : 32768);
@@ -945,50 +936,42 @@ static int serial_stream_launch(ldpc_hip_bp *h, const SerialStreamPlan &sp, int 
     return LDPC_HIP_OK;
 }
 
-// A handful of rows on bp_serial_lane_kernel (one workgroup per syndrome): iterations it_start + 1 .. max_iter; `state_rows`: [rows][nnz]
+// A handful of rows on bp_serial_lane_kernel / bp_serial_lane_var_kernel (one workgroup per syndrome): iterations it_start + 1 .. max_iter;
+// `state_rows`: [rows][nnz]
+template <class Args>
+static int serial_lane_launch_kernel(ldpc_hip_bp *h, void (*kern)(const Args), Args &a, int it_start, double *state_rows, const uint8_t *synd, int64_t rows,
+                                     uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv) {
+    a.m = h->m; a.n = h->n; a.nnz = h->nnz; a.max_iter = h->max_iter; a.it_start = it_start; a.n_levels = h->n_levels;
+    a.ms_scaling_factor = h->ms_scaling_factor;
+    a.rows = rows;
+    a.col_idx = h->d_col_idx;
+    a.llr0 = h->d_llr0;
+    a.A = state_rows; a.synd = synd; a.decoding = decoding; a.llr = llr; a.iters = iters; a.conv = conv;
+    if (llr && !h->order_visits_all) HIPCHK(hipMemsetAsync(llr, 0, sizeof(double) * (size_t)h->n * (size_t)rows, h->stream));  // bits the order never visits report 0
+    const size_t dyn = ((size_t)h->n + 15) & ~(size_t)15;
+    int rc;
+    if ((rc = set_dynamic_lds(kern, dyn))) return rc;
+    const int threads = h->sw("SER_LANE_THREADS") > 0 ? h->sw("SER_LANE_THREADS") : rows <= 2048 ? 1024 : 512;
+    hipLaunchKernelGGL(kern, dim3((unsigned)rows), dim3((unsigned)threads), (unsigned)dyn, h->stream, a);
+    HIPCHK(hipGetLastError());
+    return LDPC_HIP_OK;
+}
 static int serial_lane_launch(ldpc_hip_bp *h, const SerialStreamPlan &sp, int it_start, double *state_rows, const uint8_t *synd, int64_t rows,
                               uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv) {
     if (sp.var) {
         int waves = 0, units = 0, rc;
-        serial_var_geometry(h, 16, waves, units);
+        serial_var_geometry(h, waves, units);
         if ((rc = ensure_serial_var_tables(h, waves))) return rc;
         SerialLaneVarArgs v = {};
-        v.m = h->m; v.n = h->n; v.nnz = h->nnz; v.max_iter = h->max_iter; v.it_start = it_start; v.n_levels = h->n_levels;
-        v.ms_scaling_factor = h->ms_scaling_factor;
-        v.rows = rows;
-        v.row_ptr = h->d_row_ptr; v.col_idx = h->d_col_idx;
+        v.row_ptr = h->d_row_ptr;
         v.lane_lvl = (const int32_t *)h->ser_var_lane_lvl.p; v.lane_items = (const int32_t *)h->ser_var_lane_items.p;
-        v.llr0 = h->d_llr0;
-        v.A = state_rows; v.synd = synd; v.decoding = decoding; v.llr = llr; v.iters = iters; v.conv = conv;
-        void (*kv)(const SerialLaneVarArgs);
-        if (h->bp_method == LDPC_HIP_MINIMUM_SUM) kv = pick_serial_lane_var<LDPC_HIP_MINIMUM_SUM, 0>(sp);
-        else if (h->math_mode == LDPC_HIP_MATH_FAST) kv = pick_serial_lane_var<LDPC_HIP_PRODUCT_SUM, 1>(sp);
-        else kv = pick_serial_lane_var<LDPC_HIP_PRODUCT_SUM, 0>(sp);
-        if (llr && !h->order_visits_all) HIPCHK(hipMemsetAsync(llr, 0, sizeof(double) * (size_t)h->n * (size_t)rows, h->stream));  // bits the order never visits report 0
-        const size_t dynv = ((size_t)h->n + 15) & ~(size_t)15;
-        if (dynv > 48u * 1024u) HIPCHK(hipFuncSetAttribute((const void *)kv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dynv));
-        hipLaunchKernelGGL(kv, dim3((unsigned)rows), dim3((unsigned)(h->sw("SER_LANE_THREADS") > 0 ? h->sw("SER_LANE_THREADS") : rows <= 2048 ? 1024 : 512)), (unsigned)dynv, h->stream, v);
-        HIPCHK(hipGetLastError());
-        return LDPC_HIP_OK;
+        return serial_lane_launch_kernel(h, with_method_math(h, [&](auto M, auto F) { return pick_serial_lane_var<M, F>(sp); }), v, it_start, state_rows, synd, rows,
+                                         decoding, llr, iters, conv);
     }
     SerialLaneArgs a = {};
-    a.m = h->m; a.n = h->n; a.nnz = h->nnz; a.max_iter = h->max_iter; a.it_start = it_start; a.n_levels = h->n_levels;
-    a.ms_scaling_factor = h->ms_scaling_factor;
-    a.rows = rows;
-    a.col_idx = h->d_col_idx; a.lvl_ptr = (const int32_t *)h->lvl_ptr.p; a.pos_tab = (const int32_t *)h->ser_pos_tab.p;
-    a.llr0 = h->d_llr0;
-    a.A = state_rows; a.synd = synd; a.decoding = decoding; a.llr = llr; a.iters = iters; a.conv = conv;
-    void (*kern)(const SerialLaneArgs);
-    if (h->bp_method == LDPC_HIP_MINIMUM_SUM) kern = bp_serial_lane_kernel<LDPC_HIP_MINIMUM_SUM, 0, 6, 3>;
-    else if (h->math_mode == LDPC_HIP_MATH_FAST) kern = bp_serial_lane_kernel<LDPC_HIP_PRODUCT_SUM, 1, 6, 3>;
-    else kern = bp_serial_lane_kernel<LDPC_HIP_PRODUCT_SUM, 0, 6, 3>;
-    (void)sp;
-    if (llr && !h->order_visits_all) HIPCHK(hipMemsetAsync(llr, 0, sizeof(double) * (size_t)h->n * (size_t)rows, h->stream));  // bits the order never visits report 0
-    const size_t dyn = ((size_t)h->n + 15) & ~(size_t)15;
-    if (dyn > 48u * 1024u) HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-    hipLaunchKernelGGL(kern, dim3((unsigned)rows), dim3((unsigned)(h->sw("SER_LANE_THREADS") > 0 ? h->sw("SER_LANE_THREADS") : rows <= 2048 ? 1024 : 512)), (unsigned)dyn, h->stream, a);
-    HIPCHK(hipGetLastError());
-    return LDPC_HIP_OK;
+    a.lvl_ptr = (const int32_t *)h->lvl_ptr.p; a.pos_tab = (const int32_t *)h->ser_pos_tab.p;
+    return serial_lane_launch_kernel(h, with_method_math(h, [](auto M, auto F) { return &bp_serial_lane_kernel<M, F, 6, 3>; }), a, it_start, state_rows, synd, rows,
+                                     decoding, llr, iters, conv);
 }
 
 // new_list[i] = list[sub[i]]
@@ -1020,21 +1003,15 @@ static int decode_serial_streamed(ldpc_hip_bp *h, const SerialStreamPlan &sp, co
     int rc;
     if (full <= 0) return 0;
     if (!lane_only) {
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(hipMemGetInfo(&free_b, &total_b));
-        const size_t have = h->msgA.cap + h->msgC.cap + h->llr_t.cap;
-        const size_t per_tile = per_tile_msg + (llr ? sizeof(double) * n1 * LDPC_WAVE : 0) + 24 * (m1 + n1 + 1);
-        if ((double)per_tile * (double)tiles_total > (double)(free_b + have) * 0.8 || (h->max_chunk_tiles > 0 && tiles_total > h->max_chunk_tiles)) return 0;
+        int64_t fit = 0;
+        if ((rc = tiles_that_fit(per_tile_msg + (llr ? sizeof(double) * n1 * LDPC_WAVE : 0) + 24 * (m1 + n1 + 1), h->msgA.cap + h->msgC.cap + h->llr_t.cap, 0.8, &fit))) return rc;
+        if (tiles_total > fit || (h->max_chunk_tiles > 0 && tiles_total > h->max_chunk_tiles)) return 0;
     }
     if (!sp.var && (rc = ensure_serial_stream_table(h, sp))) return rc;
     if (!conv) { if ((rc = h->osd_conv.ensure(B))) return rc; conv = (uint8_t *)h->osd_conv.p; }
     if (!iters) { if ((rc = h->sp_iters.ensure(B * 4))) return rc; iters = (int32_t *)h->sp_iters.p; }
-    if (!h->h_counters) HIPCHK(hipHostMalloc((void **)&h->h_counters, 16, hipHostMallocDefault));
     hipStream_t st = h->stream;
-    h->accumulated_ms = 0.f;
-    h->accumulated_persistent_ms = 0.f;
-    h->timed = h->timed_mid = false;
-    h->timed_prev = h->timed_prev_mid = false;
+    reset_timing(h, true);
     HIPCHK(hipEventRecord(h->ev0, st));
     auto finish = [&]() -> int {
         HIPCHK(hipEventRecord(h->ev1, st));
@@ -1046,16 +1023,7 @@ static int decode_serial_streamed(ldpc_hip_bp *h, const SerialStreamPlan &sp, co
         if ((rc = serial_lane_launch(h, sp, 0, (double *)h->msgC.p, synd, batch, decoding, llr, iters, conv))) return rc;
         return finish();
     }
-    if (!sp.var && h->order_visits_all && !h->on("EXPLICIT_INIT")) {  // the tables that stand in for the initial messages (bp_serial_stream_kernel.h)
-        if ((rc = h->d_edge0.ensure(sizeof(double) * n1)) || (rc = h->ser_pos_e0.ensure(sizeof(double) * 16 * n1))) return rc;
-        const dim3 ge((unsigned)((h->n + 255) / 256));
-        if (h->bp_method == LDPC_HIP_MINIMUM_SUM) hipLaunchKernelGGL((serial_edge0_kernel<LDPC_HIP_MINIMUM_SUM, 0>), ge, dim3(256), 0, st, h->d_llr0, h->n, (double *)h->d_edge0.p);
-        else if (h->math_mode == LDPC_HIP_MATH_FAST) hipLaunchKernelGGL((serial_edge0_kernel<LDPC_HIP_PRODUCT_SUM, 1>), ge, dim3(256), 0, st, h->d_llr0, h->n, (double *)h->d_edge0.p);
-        else hipLaunchKernelGGL((serial_edge0_kernel<LDPC_HIP_PRODUCT_SUM, 0>), ge, dim3(256), 0, st, h->d_llr0, h->n, (double *)h->d_edge0.p);
-        hipLaunchKernelGGL(serial_pos_e0_kernel, dim3((unsigned)((h->n * 16 + 255) / 256)), dim3(256), 0, st, (const int32_t *)h->ser_pos_tab.p, h->d_col_idx,
-                           (const double *)h->d_edge0.p, h->n, sp.dc * (sp.dr - 1), (double *)h->ser_pos_e0.p);
-        HIPCHK(hipGetLastError());
-    }
+    if (!sp.var && first_iteration_from_tables(h) && (rc = ensure_first_iteration_tables(h, sp))) return rc;
     if ((rc = h->msgA.ensure(per_tile_msg * (size_t)tiles_total))) return rc;
     DeviceBuf *state = &h->msgA, *other = &h->msgC;
     // the rows of the running pass: the caller's (identity) or a compacted subset -- their syndromes, their numbers in the caller's arrays
@@ -1064,18 +1032,6 @@ static int decode_serial_streamed(ldpc_hip_bp *h, const SerialStreamPlan &sp, co
     const uint8_t *cur_synd = synd;
     int cur = 0;  // which of the two row-list / syndrome buffers describes the running rows
     DeviceBuf *lists[2] = {&h->ser_rows[0], &h->ser_rows[1]}, *synds[2] = {&h->rp_synd, &h->ser_synd2};
-    auto grid = [](size_t items) { return flat_grid(items); };
-    auto scatter_out = [&](const int32_t *rows_list, int64_t cnt, bool big) -> int {  // rp_* -> the caller's arrays
-        const size_t C = (size_t)cnt;
-        if (big) {
-            hipLaunchKernelGGL(scatter_rows_kernel<uint8_t>, grid(C * n1), dim3(256), 0, st, (const uint8_t *)h->rp_dec.p, rows_list, cnt, h->n, decoding);
-            if (llr) hipLaunchKernelGGL(scatter_rows_kernel<double>, grid(C * n1), dim3(256), 0, st, (const double *)h->rp_llr.p, rows_list, cnt, h->n, llr);
-        }
-        hipLaunchKernelGGL(scatter_rows_kernel<int32_t>, grid(C), dim3(256), 0, st, (const int32_t *)h->rp_iters.p, rows_list, cnt, 1, iters);
-        hipLaunchKernelGGL(scatter_rows_kernel<uint8_t>, grid(C), dim3(256), 0, st, (const uint8_t *)h->rp_conv.p, rows_list, cnt, 1, conv);
-        HIPCHK(hipGetLastError());
-        return LDPC_HIP_OK;
-    };
     const int first = h->repack_iters > 0 ? h->repack_iters : 4;
     int it = 0;
     bool resume = false;
@@ -1090,15 +1046,11 @@ static int decode_serial_streamed(ldpc_hip_bp *h, const SerialStreamPlan &sp, co
         uint8_t *o_cv = identity ? conv : (uint8_t *)h->rp_conv.p;
         const int waves_cap = !identity && h->sw("SER_WAVES2") > 0 ? h->sw("SER_WAVES2") : 16;  // (workgroups of 8 for a second pass of 257 .. 512 tiles measured slower than a second round of 16)
         if ((rc = serial_stream_launch(h, sp, it, next, resume, (double *)state->p, cur_synd, R, identity ? nullptr : (const int32_t *)lists[cur]->p, decoding, llr, o_it, o_cv, waves_cap))) return rc;
-        if (!identity && (rc = scatter_out((const int32_t *)lists[cur]->p, R, false))) return rc;
+        if (!identity && (rc = scatter_pass_outputs(h, (const int32_t *)lists[cur]->p, R, nullptr, nullptr, iters, conv))) return rc;  // (decisions and log-ratios went through the row list)
         if (next >= full) break;
         // the rows of this pass that are still decoding: listed (numbers within the pass) and counted
-        if ((rc = h->osd_list.ensure((size_t)R * sizeof(int32_t))) || (rc = h->osd_counters.ensure(2 * sizeof(unsigned)))) return rc;
-        HIPCHK(hipMemsetAsync(h->osd_counters.p, 0, 2 * sizeof(unsigned), st));
-        hipLaunchKernelGGL(osd_collect_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, o_cv, R, (int32_t *)h->osd_list.p, (unsigned *)h->osd_counters.p);
-        HIPCHK(hipMemcpyAsync(&h->h_counters[2], h->osd_counters.p, sizeof(unsigned), hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));  // the size of what is left is needed on the host
-        const int64_t cnt = (int64_t)h->h_counters[2];
+        int64_t cnt = 0;
+        if ((rc = collect_unconverged(h, o_cv, R, &cnt))) return rc;
         if (cnt == 0) break;
         it = next;
         const int32_t *sub = (const int32_t *)h->osd_list.p;
@@ -1111,7 +1063,7 @@ static int decode_serial_streamed(ldpc_hip_bp *h, const SerialStreamPlan &sp, co
         if ((rc = lists[nxt]->ensure(C * sizeof(int32_t))) || (rc = synds[nxt]->ensure(C * m1))) return rc;
         if (identity) HIPCHK(hipMemcpyAsync(lists[nxt]->p, sub, C * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
         else hipLaunchKernelGGL(compose_lists_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, (const int32_t *)lists[cur]->p, sub, cnt, (int32_t *)lists[nxt]->p);
-        hipLaunchKernelGGL(gather_rows_kernel<uint8_t>, grid(C * m1), dim3(256), 0, st, cur_synd, sub, cnt, h->m, (uint8_t *)synds[nxt]->p);
+        hipLaunchKernelGGL(gather_rows_kernel<uint8_t>, flat_grid(C * m1), dim3(256), 0, st, cur_synd, sub, cnt, h->m, (uint8_t *)synds[nxt]->p);
         HIPCHK(hipGetLastError());
         if ((rc = h->rp_iters.ensure(C * 4)) || (rc = h->rp_conv.ensure(C))) return rc;
         // A compute unit holds one 16-wavefront tile: a pass of 267 tiles is a round of 256 and a round of 11 that takes as long.  The rows
@@ -1133,7 +1085,7 @@ static int decode_serial_streamed(ldpc_hip_bp *h, const SerialStreamPlan &sp, co
             HIPCHK(hipGetLastError());
             if ((rc = serial_lane_launch(h, sp, it, rows_state, (const uint8_t *)synds[nxt]->p + (size_t)at * m1, n_lane, (uint8_t *)h->rp_dec.p, llr ? (double *)h->rp_llr.p : nullptr,
                                          (int32_t *)h->rp_iters.p, (uint8_t *)h->rp_conv.p))) return rc;
-            if ((rc = scatter_out((const int32_t *)lists[nxt]->p + at, n_lane, true))) return rc;
+            if ((rc = scatter_pass_outputs(h, (const int32_t *)lists[nxt]->p + at, n_lane, decoding, llr, iters, conv))) return rc;
             if (to_lanes) break;
         }
         // the others' message state, lane by lane, into dense tiles of the other array
@@ -1167,11 +1119,9 @@ int decode_serial(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
             if (took > 0) return LDPC_HIP_OK;
             // The batch's message state is not resident at once (e.g. 1 048 576 rows of the n = 10 000 code: 252 GB): in pieces that are, each
             // decoded in passes by itself -- a piece's stragglers finish a workgroup per syndrome instead of holding their tiles to max_iter.
-            size_t free_b = 0, total_b = 0;
-            HIPCHK(hipMemGetInfo(&free_b, &total_b));
-            const size_t have = h->msgA.cap + h->msgC.cap + h->llr_t.cap;
-            const size_t per_tile = sizeof(double) * (size_t)h->nnz * LDPC_WAVE + (llr ? sizeof(double) * n1 * LDPC_WAVE : 0) + 24 * (m1 + n1 + 1);
-            int64_t fit = (int64_t)((double)(free_b + have) * 0.7 / (double)per_tile);
+            int64_t fit = 0;
+            if ((rc = tiles_that_fit(sizeof(double) * (size_t)h->nnz * LDPC_WAVE + (llr ? sizeof(double) * n1 * LDPC_WAVE : 0) + 24 * (m1 + n1 + 1),
+                                     h->msgA.cap + h->msgC.cap + h->llr_t.cap, 0.7, &fit))) return rc;
             if (h->max_chunk_tiles > 0 && fit > h->max_chunk_tiles) fit = h->max_chunk_tiles;
             if (fit >= 64) {
                 float ms_sum = 0.f;
@@ -1188,21 +1138,18 @@ int decode_serial(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
             }
         }
     }
+    // The serial kernel decodes a 64-syndrome tile with one wavefront, which runs until its slowest lane is done: one
+    // syndrome that never converges keeps 63 finished ones waiting for max_iter iterations.  Repacking: a first pass with
+    // few iterations over everything, then the rows it left unconverged -- packed densely into new tiles -- are decoded
+    // again from the start with the full iteration budget (BP is deterministic: restarting gives what continuing would),
+    // and their results replace the first pass's.  Work ~ k1 + f * max_iter instead of max_iter (f = unconverged fraction).
     int k1 = h->repack_iters < 0 ? h->max_iter / 8 : h->repack_iters;
     if (h->repack_iters < 0 && k1 < 2) k1 = 2;
     if (k1 <= 0 || k1 >= h->max_iter || batch <= 4 * LDPC_WAVE)
         return decode_serial_pass(h, h->max_iter, synd, batch, decoding, llr, iters, conv);
     if (!conv) { if ((rc = h->osd_conv.ensure(B))) return rc; conv = (uint8_t *)h->osd_conv.p; }
-    if (!h->h_counters) HIPCHK(hipHostMalloc((void **)&h->h_counters, 16, hipHostMallocDefault));
-    if ((rc = decode_serial_pass(h, k1, synd, batch, decoding, llr, iters, conv))) return rc;
-    if ((rc = h->osd_list.ensure(B * sizeof(int32_t)))) return rc;
-    if ((rc = h->osd_counters.ensure(2 * sizeof(unsigned)))) return rc;
-    HIPCHK(hipMemsetAsync(h->osd_counters.p, 0, 2 * sizeof(unsigned), h->stream));
-    hipLaunchKernelGGL(osd_collect_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, h->stream, conv, batch,
-                       (int32_t *)h->osd_list.p, (unsigned *)h->osd_counters.p);
-    HIPCHK(hipMemcpyAsync(&h->h_counters[2], h->osd_counters.p, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));  // the size of the second pass is needed on the host
-    const int64_t cnt = (int64_t)h->h_counters[2];
+    int64_t cnt = 0;
+    if ((rc = decode_serial_pass(h, k1, synd, batch, decoding, llr, iters, conv)) || (rc = collect_unconverged(h, conv, batch, &cnt))) return rc;
     if (cnt == 0) return LDPC_HIP_OK;
     float ms1 = 0.f;
     (void)ldpc_hip_bp_last_kernel_ms(h, &ms1);
@@ -1210,21 +1157,13 @@ int decode_serial(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
     if ((rc = h->rp_synd.ensure(C * m1)) || (rc = h->rp_dec.ensure(C * n1)) || (rc = h->rp_iters.ensure(C * 4)) ||
         (rc = h->rp_conv.ensure(C)) || (llr && (rc = h->rp_llr.ensure(C * n1 * 8)))) return rc;
     const int32_t *list = (const int32_t *)h->osd_list.p;
-    auto grid = [](size_t items) { return flat_grid(items); };
     if (h->m > 0)
-        hipLaunchKernelGGL(gather_rows_kernel<uint8_t>, grid(C * h->m), dim3(256), 0, h->stream, synd, list, cnt, h->m, (uint8_t *)h->rp_synd.p);
+        hipLaunchKernelGGL(gather_rows_kernel<uint8_t>, flat_grid(C * h->m), dim3(256), 0, h->stream, synd, list, cnt, h->m, (uint8_t *)h->rp_synd.p);
     HIPCHK(hipGetLastError());
     if ((rc = decode_serial_pass(h, h->max_iter, (const uint8_t *)h->rp_synd.p, cnt, (uint8_t *)h->rp_dec.p,
                                  llr ? (double *)h->rp_llr.p : nullptr, (int32_t *)h->rp_iters.p, (uint8_t *)h->rp_conv.p))) return rc;
     h->accumulated_ms += ms1;  // both passes count as this decode's kernel time
-    if (h->n > 0) {
-        hipLaunchKernelGGL(scatter_rows_kernel<uint8_t>, grid(C * h->n), dim3(256), 0, h->stream, (const uint8_t *)h->rp_dec.p, list, cnt, h->n, decoding);
-        if (llr) hipLaunchKernelGGL(scatter_rows_kernel<double>, grid(C * h->n), dim3(256), 0, h->stream, (const double *)h->rp_llr.p, list, cnt, h->n, llr);
-    }
-    if (iters) hipLaunchKernelGGL(scatter_rows_kernel<int32_t>, grid(C), dim3(256), 0, h->stream, (const int32_t *)h->rp_iters.p, list, cnt, 1, iters);
-    hipLaunchKernelGGL(scatter_rows_kernel<uint8_t>, grid(C), dim3(256), 0, h->stream, (const uint8_t *)h->rp_conv.p, list, cnt, 1, conv);
-    HIPCHK(hipGetLastError());
-    return LDPC_HIP_OK;
+    return scatter_pass_outputs(h, list, cnt, decoding, llr, iters, conv);
 }
 
 // soft_info_decode_serial over a batch (bp_softinfo_kernel).  Device pointers, on h->stream.
@@ -1239,20 +1178,10 @@ int soft_info_device(ldpc_hip_bp *h, const double *soft, int64_t batch, double c
     const size_t lds = sizeof(uint64_t) * (m1 + 32);  // hard-syndrome words + the level kernel's reduction slots
     if (lds > 150u * 1024u)
         return fail(LDPC_HIP_ERR_UNSUPPORTED, "soft-syndrome decoding keeps one hard-syndrome word per check in LDS: m <= 19200");
-    int64_t chunk = tiles_total;
-    if (h->max_chunk_tiles > 0 && chunk > h->max_chunk_tiles) chunk = h->max_chunk_tiles;
-    if (chunk > 32768) chunk = 32768;
-    {
-        size_t free_b = 0, total_b = 0;
-        HIPCHK(hipMemGetInfo(&free_b, &total_b));
-        const size_t have = h->msgA.cap + h->msgC.cap + h->llr_t.cap + h->soft_S.cap;
-        const size_t budget = (size_t)((double)(free_b + have) * 0.85);
-        const size_t per_tile = 2 * per_tile_msg + per_tile_llr + per_tile_soft + 24 * (m1 + n1);
-        int64_t fit = (int64_t)(budget / per_tile);
-        if (fit < 1) return fail(LDPC_HIP_ERR_NOMEM, "not enough device memory for one 64-shot tile");
-        if (chunk > fit) chunk = fit;
-    }
+    int64_t chunk = 0;
     int rc;
+    if ((rc = chunk_tiles_that_fit(h, tiles_total, 2 * per_tile_msg + per_tile_llr + per_tile_soft + 24 * (m1 + n1),
+                                   h->msgA.cap + h->msgC.cap + h->llr_t.cap + h->soft_S.cap, 0.85, 32768, "shot", &chunk))) return rc;
     if ((rc = h->msgA.ensure(per_tile_msg * (size_t)chunk))) return rc;
     if ((rc = h->msgC.ensure(per_tile_msg * (size_t)chunk))) return rc;
     if ((rc = h->soft_S.ensure(per_tile_soft * (size_t)chunk))) return rc;
@@ -1263,12 +1192,7 @@ int soft_info_device(ldpc_hip_bp *h, const double *soft, int64_t batch, double c
     int level_waves = 0;  // level-parallel variant: as for the serial schedule
     if (h->serial_kernel != 0 && h->n > 0) {
         if ((rc = ensure_serial_levels(h))) return rc;
-        const double per_level = (double)h->n / (double)(h->n_levels ? h->n_levels : 1);
-        if (h->serial_kernel == 1 || per_level >= 2.0) {
-            level_waves = (int)(per_level + 0.999);
-            if (level_waves > 8) level_waves = 8;
-            if (level_waves < 1) level_waves = 1;
-        }
+        level_waves = level_waves_for(h, (double)h->n / (double)(h->n_levels ? h->n_levels : 1));
     }
     // random_serial_schedule in this routine (bp.hpp:573-577): at the top of every iteration that still runs the order the
     // object carries is rearranged by std::shuffle with a NEW std::default_random_engine(random_schedule_seed) -- one fixed
@@ -1279,17 +1203,7 @@ int soft_info_device(ldpc_hip_bp *h, const double *soft, int64_t batch, double c
     if (shuffled) {
         if ((rc = random_orders_prepare(h, 1))) return rc;  // (random_orders_*, above)
         level_waves = 0;  // the fixed order's levels do not apply: those of the ring's rows do (random_orders_append)
-        if (h->serial_kernel != 0 && h->rnd.valid) {
-            double sum = 0.0;
-            int cnt = 0;
-            for (int32_t nl : h->rnd.n_levels) if (nl > 0) { sum += (double)nl; ++cnt; }
-            const double per_level = cnt ? (double)h->n / (sum / cnt) : 0.0;
-            if (h->serial_kernel == 1 || per_level >= 2.0) {
-                level_waves = (int)(per_level + 0.999);
-                if (level_waves > 8) level_waves = 8;
-                if (level_waves < 1) level_waves = 1;
-            }
-        }
+        if (h->serial_kernel != 0 && h->rnd.valid) level_waves = level_waves_for(h, ring_bits_per_level(h));
         if (!iters) { if ((rc = h->sp_iters.ensure((size_t)batch * 4))) return rc; iters = (int32_t *)h->sp_iters.p; }
         d_iters_last = iters + (batch - 1);
     }
@@ -1298,29 +1212,22 @@ int soft_info_device(ldpc_hip_bp *h, const double *soft, int64_t batch, double c
     else if (h->max_row_deg <= 6 && h->max_col_deg <= 3) soft_kern = level_waves ? bp_softinfo_level_kernel<3, 6> : bp_softinfo_kernel<3, 6>;
     else if (h->max_row_deg <= 8 && h->max_col_deg <= 4) soft_kern = level_waves ? bp_softinfo_level_kernel<4, 8> : bp_softinfo_kernel<4, 8>;
     else soft_kern = level_waves ? bp_softinfo_level_kernel<0, 0> : bp_softinfo_kernel<0, 0>;
-    if (lds > 48u * 1024u)
-        HIPCHK(hipFuncSetAttribute((const void *)soft_kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    h->timed_prev = h->timed_prev_mid = false;
-    h->accumulated_ms = 0.f;
-    h->accumulated_persistent_ms = 0.f;
-    h->timed = false;
-    h->timed_mid = false;
+    if ((rc = set_dynamic_lds(soft_kern, lds))) return rc;
+    reset_timing(h, true);
     hipStream_t st = h->stream;
     for (int64_t t0 = 0; t0 < tiles_total; t0 += chunk) {
-        const int64_t tiles = (tiles_total - t0 < chunk) ? tiles_total - t0 : chunk;
-        const int64_t b0 = t0 * LDPC_WAVE;
-        const int64_t nb = (batch - b0 < tiles * LDPC_WAVE) ? batch - b0 : tiles * LDPC_WAVE;
-        HIPCHK(hipMemsetAsync(h->dec.p, 0, sizeof(uint64_t) * n1 * (size_t)tiles, st));
-        HIPCHK(hipMemsetAsync(h->dcur.p, 0, sizeof(uint64_t) * n1 * (size_t)tiles, st));
+        const ChunkRange c = chunk_range(t0, chunk, tiles_total, batch);
+        HIPCHK(hipMemsetAsync(h->dec.p, 0, sizeof(uint64_t) * n1 * (size_t)c.tiles, st));
+        HIPCHK(hipMemsetAsync(h->dcur.p, 0, sizeof(uint64_t) * n1 * (size_t)c.tiles, st));
         if (h->m > 0) {
-            dim3 g((unsigned)((h->m + 3) / 4), (unsigned)tiles);
-            hipLaunchKernelGGL(softinfo_prepare_kernel, g, dim3(256), 0, st, soft + (size_t)b0 * h->m, nb, h->m, sigma,
+            dim3 g((unsigned)((h->m + 3) / 4), (unsigned)c.tiles);
+            hipLaunchKernelGGL(softinfo_prepare_kernel, g, dim3(256), 0, st, soft + (size_t)c.b0 * h->m, c.nb, h->m, sigma,
                                (double *)h->soft_S.p, (uint64_t *)h->par.p);
         }
         SoftArgs a = {};
         a.m = h->m; a.n = h->n; a.nnz = h->nnz; a.max_iter = h->max_iter;
         a.ms_scaling_factor = h->ms_scaling_factor; a.cutoff = cutoff;
-        a.batch = nb;
+        a.batch = c.nb;
         a.row_ptr = h->d_row_ptr; a.col_idx = h->d_col_idx; a.col_ptr = h->d_col_ptr;
         a.csc_edge = h->d_csc_edge; a.csc_row = h->d_csc_row; a.order = h->custom_order ? h->d_order : nullptr;
         if (shuffled && h->max_iter > 0) {
@@ -1332,36 +1239,18 @@ int soft_info_device(ldpc_hip_bp *h, const double *soft, int64_t batch, double c
         a.syn = (const uint64_t *)h->par.p;
         a.dec = (uint64_t *)h->dec.p; a.dcur = (uint64_t *)h->dcur.p;
         a.llr_t = llr ? (double *)h->llr_t.p : nullptr;
-        a.iters = iters ? iters + b0 : nullptr;
-        a.conv = conv ? conv + b0 : nullptr;
-        if (h->timed) {
-            float prev = 0.f;
-            HIPCHK(hipEventSynchronize(h->ev1));
-            HIPCHK(hipEventElapsedTime(&prev, h->ev0, h->ev1));
-            h->accumulated_ms += prev;
-        }
-        HIPCHK(hipEventRecord(h->ev0, st));
+        a.iters = iters ? iters + c.b0 : nullptr;
+        a.conv = conv ? conv + c.b0 : nullptr;
         a.lvl_ptr = (const int32_t *)h->lvl_ptr.p; a.lvl_bits = (const int32_t *)h->lvl_bits.p; a.n_levels = h->n_levels;
-        hipLaunchKernelGGL(soft_kern, dim3((unsigned)tiles), dim3((unsigned)(64 * (level_waves ? level_waves : 1))), (unsigned)lds, st, a);
-        HIPCHK(hipEventRecord(h->ev1, st));
-        h->timed = true;
-        HIPCHK(hipGetLastError());
-        if (h->n > 0) {
-            dim3 g((unsigned)((h->n + 255) / 256), (unsigned)tiles);
-            hipLaunchKernelGGL(unpack_decoding_kernel, g, dim3(256), 0, st, (const uint64_t *)h->dec.p, nb, h->n,
-                               decoding + b0 * h->n);
-            if (llr) {
-                dim3 gt((unsigned)((h->n + LDPC_WAVE - 1) / LDPC_WAVE), (unsigned)tiles);
-                hipLaunchKernelGGL(transpose_llr_kernel, gt, dim3(256), 0, st, (const double *)h->llr_t.p, nb, h->n,
-                                   llr + (size_t)b0 * h->n);
-            }
-        }
+        if ((rc = chunk_timing_begin(h))) return rc;
+        hipLaunchKernelGGL(soft_kern, dim3((unsigned)c.tiles), dim3((unsigned)(64 * (level_waves ? level_waves : 1))), (unsigned)lds, st, a);
+        if ((rc = chunk_timing_end(h)) || (rc = chunk_outputs(h, c, decoding, llr))) return rc;
         if (soft_out && h->m > 0) {
-            dim3 gt((unsigned)((h->m + LDPC_WAVE - 1) / LDPC_WAVE), (unsigned)tiles);
-            hipLaunchKernelGGL(transpose_llr_kernel, gt, dim3(256), 0, st, (const double *)h->soft_S.p, nb, h->m,
-                               soft_out + (size_t)b0 * h->m);
+            dim3 gt((unsigned)((h->m + LDPC_WAVE - 1) / LDPC_WAVE), (unsigned)c.tiles);
+            hipLaunchKernelGGL(transpose_llr_kernel, gt, dim3(256), 0, st, (const double *)h->soft_S.p, c.nb, h->m,
+                               soft_out + (size_t)c.b0 * h->m);
+            HIPCHK(hipGetLastError());
         }
-        HIPCHK(hipGetLastError());
     }
     if (shuffled && batch > 0) {  // the order the last row leaves behind
         int32_t last = 0;

@@ -96,6 +96,9 @@ int ldpc_hip_bp_create(const ldpc_hip_bp_desc *d, ldpc_hip_bp **out) {
     for (int j = 0; j < d->n; ++j) h->sched_state[(size_t)j] = j;  // bp.hpp:120-124
     h->h_row_ptr.assign(d->csr_row_ptr, d->csr_row_ptr + d->m + 1);  // kept for tables that are built on first use
     h->h_col_idx.assign(d->csr_col_idx, d->csr_col_idx + d->nnz);
+    h->h_col_ptr = std::move(col_ptr);
+    h->h_csc_edge = std::move(csc_edge);
+    h->h_csc_row = std::move(csc_row);
     hipError_t e = hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreate(&h->ev0);
     if (e == hipSuccess) e = hipEventCreate(&h->ev1);
@@ -125,12 +128,6 @@ void ldpc_hip_bp_destroy(ldpc_hip_bp *h) {
     if (h->res.ended) (void)hipEventDestroy(h->res.ended);
     if (h->res.stream) (void)hipStreamDestroy(h->res.stream);
     (void)hipStreamSynchronize(h->stream);
-    for (DeviceBuf *b : {&h->ser_pos_tab, &h->ser_pos_e0, &h->ser_rows[0], &h->ser_rows[1], &h->ser_synd2}) b->release();
-    for (DeviceBuf *b : {&h->msgA, &h->msgC, &h->par, &h->nzm, &h->invalid, &h->dec, &h->dcur, &h->llr_t,
-                         &h->st_synd, &h->st_dec, &h->st_llr, &h->st_iters, &h->st_conv, &h->st_misc, &h->osd_llr, &h->osd_conv, &h->osd_packed, &h->osd_ell, &h->osd_scratch, &h->sp_hist, &h->sp_iters, &h->osd_list, &h->osd_counters, &h->osd_status, &h->osd_fix_synd, &h->osd_fix_list, &h->osd_fix_counters, &h->osd_fix_scratch, &h->rel_ord, &h->rel_dbit, &h->rl_edge, &h->rl_chk, &h->rl_cdeg, &h->rl_last, &h->sched_orders, &h->sched_order0, &h->sched_lvl_bits, &h->sched_lvl_ptr, &h->lvl_ptr, &h->lvl_bits, &h->rp_synd, &h->rp_dec, &h->rp_llr, &h->rp_iters, &h->rp_conv, &h->counter, &h->w_rdeg, &h->w_cdeg, &h->w_col, &h->w_apos, &h->w_prior, &h->d_edge0, &h->var_row_items, &h->var_pair_items, &h->e_partner, &h->e_kind, &h->e_scol, &h->e_prior, &h->wp_rdeg, &h->wp_col, &h->wp_epos,
-                         &h->soft_S, &h->soft_in, &h->soft_out, &h->b8_in, &h->b8_out, &h->b8_synd, &h->b8_dec, &h->obs_row_ptr, &h->obs_col_idx,
-                         &h->tile_state, &h->handoff_list})
-        b->release();
     if (h->d_row_ptr) (void)hipFree(h->d_row_ptr);
     if (h->d_col_idx) (void)hipFree(h->d_col_idx);
     if (h->d_col_ptr) (void)hipFree(h->d_col_ptr);
@@ -157,13 +154,12 @@ void ldpc_hip_bp_destroy(ldpc_hip_bp *h) {
         if (h->pipe.ev_in[q]) (void)hipEventDestroy(h->pipe.ev_in[q]);
         if (h->pipe.ev_cmp[q]) (void)hipEventDestroy(h->pipe.ev_cmp[q]);
         if (h->pipe.ev_out[q]) (void)hipEventDestroy(h->pipe.ev_out[q]);
-        for (DeviceBuf *b : {&h->pipe.d_in[q], &h->pipe.d_dec[q], &h->pipe.d_llr[q], &h->pipe.d_it[q], &h->pipe.d_cv[q]}) b->release();
     }
     if (h->pipe.s_in) (void)hipStreamDestroy(h->pipe.s_in);
     if (h->pipe.s_out) (void)hipStreamDestroy(h->pipe.s_out);
     if (h->h_hist) (void)hipHostFree(h->h_hist);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
-    delete h;
+    delete h;  // (every DeviceBuf of the handle goes with it, on h->device)
 }
 
 int ldpc_hip_bp_set_channel(ldpc_hip_bp *h, const double *p, int32_t n) {
@@ -325,6 +321,8 @@ int ldpc_hip_bp_last_kernel_ms(ldpc_hip_bp *h, float *ms) {
     }
     return LDPC_HIP_OK;
 }
+
+int64_t ldpc_hip_debug_device_buf_bytes(void) { return (int64_t)g_device_buf_bytes.load(); }
 
 void *ldpc_hip_host_alloc(size_t bytes) {
     void *p = nullptr;

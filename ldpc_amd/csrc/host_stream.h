@@ -6,9 +6,7 @@
 // nt: non-temporal cache policy for the message traffic (tiles that outgrow the 256 MB MALL; see MsgBufT)
 template <bool LOOP>
 static void pick_spread(const ldpc_hip_bp *h, bool nt, spread_kernel_t &kc, spread_kernel_t &kb) {
-    if (h->bp_method == LDPC_HIP_MINIMUM_SUM) pick_spread_m<LDPC_HIP_MINIMUM_SUM, 0, LOOP>(h->max_row_deg, h->max_col_deg, nt, kc, kb);
-    else if (h->math_mode == LDPC_HIP_MATH_FAST) pick_spread_m<LDPC_HIP_PRODUCT_SUM, 1, LOOP>(h->max_row_deg, h->max_col_deg, nt, kc, kb);
-    else pick_spread_m<LDPC_HIP_PRODUCT_SUM, 0, LOOP>(h->max_row_deg, h->max_col_deg, nt, kc, kb);
+    with_method_math(h, [&](auto M, auto F) { pick_spread_m<M, F, LOOP>(h->max_row_deg, h->max_col_deg, nt, kc, kb); });
 }
 
 // Item tables of the variable-degree ring (bp_stream_kernel.h, LDPC_RING_VAR): the check rows, and the pairs of bit columns, in the
@@ -103,10 +101,7 @@ int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
     // Measured on the irregular n = 10 000 code (profiles/r5_irregular_paths.txt): +5 % over the register variant for product-sum, -4 % for
     // min-sum, and below the per-pass kernels for product-sum -- so it is not what runs by default anywhere.
     const bool var_ring = h->m > 0 && h->n > 0 && h->max_row_deg <= 16 && h->max_col_deg <= 8 && h->on("VAR_RING");
-    KernelChoice kern;
-    if (h->bp_method == LDPC_HIP_MINIMUM_SUM) kern = pick_kernel<LDPC_HIP_MINIMUM_SUM, 0>(h->max_row_deg, h->max_col_deg, ring, var_ring);
-    else if (h->math_mode == LDPC_HIP_MATH_FAST) kern = pick_kernel<LDPC_HIP_PRODUCT_SUM, 1>(h->max_row_deg, h->max_col_deg, ring, var_ring);
-    else kern = pick_kernel<LDPC_HIP_PRODUCT_SUM, 0>(h->max_row_deg, h->max_col_deg, ring, var_ring);
+    const KernelChoice kern = with_method_math(h, [&](auto M, auto F) { return pick_kernel<M, F>(h->max_row_deg, h->max_col_deg, ring, var_ring); });
     const int var_units = !kern.var_ring ? 0 : h->sw("VAR_RING_UNITS") >= 8 ? (h->sw("VAR_RING_UNITS") <= 40 ? h->sw("VAR_RING_UNITS") : 40) : 11;
     if (kern.var_ring && (rc = ensure_var_ring_items(h, kern.max_waves))) return rc;
     // Product-sum on a matrix without a fixed-degree ring variant (irregular, or regular of another shape than (6,3) / (8,4), or the ring
@@ -234,18 +229,14 @@ int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
             first_round = 0;
             hipLaunchKernelGGL(bp_spread_state_init_kernel, dim3((grid_tiles + 255) / 256), dim3(256), 0, st, sa);
             const dim3 gi((unsigned)(h->nnz ? (h->nnz + 63) / 64 : 1), grid_tiles);  // (a grid dimension must not be 0: empty matrices)
-            if (a.it_start > 0) { /* the message state is there already */ }
-            else if (h->bp_method == LDPC_HIP_MINIMUM_SUM) hipLaunchKernelGGL((bp_spread_init_kernel<LDPC_HIP_MINIMUM_SUM, 0>), gi, dim3(256), 0, st, sa);
-            else if (h->math_mode == LDPC_HIP_MATH_FAST) hipLaunchKernelGGL((bp_spread_init_kernel<LDPC_HIP_PRODUCT_SUM, 1>), gi, dim3(256), 0, st, sa);
-            else hipLaunchKernelGGL((bp_spread_init_kernel<LDPC_HIP_PRODUCT_SUM, 0>), gi, dim3(256), 0, st, sa);
+            if (a.it_start == 0)  // (else the message state is there already)
+                with_method_math(h, [&](auto M, auto F) { hipLaunchKernelGGL((bp_spread_init_kernel<M, F>), gi, dim3(256), 0, st, sa); });
             HIPCHK(hipGetLastError());
         } else {
             if (kern.ring_depth && h->n > 0 && !h->on("EXPLICIT_INIT")) {  // the first check pass reads this table instead of initial messages
                 if ((rc = h->d_edge0.ensure(sizeof(double) * (size_t)h->n))) return rc;
                 const dim3 ge((unsigned)((h->n + 255) / 256));
-                if (h->bp_method == LDPC_HIP_MINIMUM_SUM) hipLaunchKernelGGL((bp_edge0_kernel<LDPC_HIP_MINIMUM_SUM, 0>), ge, dim3(256), 0, st, h->d_llr0, h->n, (double *)h->d_edge0.p);
-                else if (h->math_mode == LDPC_HIP_MATH_FAST) hipLaunchKernelGGL((bp_edge0_kernel<LDPC_HIP_PRODUCT_SUM, 1>), ge, dim3(256), 0, st, h->d_llr0, h->n, (double *)h->d_edge0.p);
-                else hipLaunchKernelGGL((bp_edge0_kernel<LDPC_HIP_PRODUCT_SUM, 0>), ge, dim3(256), 0, st, h->d_llr0, h->n, (double *)h->d_edge0.p);
+                with_method_math(h, [&](auto M, auto F) { hipLaunchKernelGGL((bp_edge0_kernel<M, F>), ge, dim3(256), 0, st, h->d_llr0, h->n, (double *)h->d_edge0.p); });
                 a.edge0 = (const double *)h->d_edge0.p;
             }
             hipLaunchKernelGGL(kern.fn, dim3((unsigned)tiles), dim3((unsigned)(waves * LDPC_WAVE)), (unsigned)dyn_lds, st, a);

@@ -40,7 +40,7 @@ def main():
     if args.forms == "one":
         forms = forms[1:2]
     if args.forms == "all":
-        forms += [("REL_GLOBAL 0 (all state in LDS)", (("REL_GLOBAL", 0),)), ("REL_GLOBAL 1", (("REL_GLOBAL", 1),)), ("REL_GLOBAL 2", (("REL_GLOBAL", 2),))]
+        forms += [("REL_EXT 0 (all state in LDS, or the per-lane kernel where it does not fit)", (("REL_EXT", 0),)), ("REL_EXT 1 (messages and records in global memory)", (("REL_EXT", 1),))]
     ref = None
     for label, switches in forms:
         eng = HipBpEngine(h.indptr, h.indices, n, np.full(n, args.p), args.max_iter, args.method, args.alpha if args.method else 1.0)

@@ -24,12 +24,16 @@ RULES = {  # template -> who selects which instantiation
     "bp_small_kernel": "host_onchip.h decode_small: small codes no wavefront kernel takes (rows > 32 or columns > 8)",
     "bp_serial_kernel": "host_serial.h pick_serial: serial schedule, one wavefront per tile",
     "bp_serial_level_kernel": "host_serial.h pick_serial_level: serial schedule, level-parallel",
-    "bp_serial_stream_kernel": "host_serial.h decode_serial_streamed / decode_serial_pass: serial schedule on (6,3)-shaped matrices with >= 32 bits a level: <METHOD, MATH, 6, 3, RING 1 (default) / 2>",
+    "bp_serial_stream_kernel": "host_serial.h serial_stream_setup via pick_serial_stream (for decode_serial_streamed / decode_serial_pass): serial schedule on (6,3)-shaped matrices with >= 32 bits a level: <METHOD, MATH, 6, 3, RING 1 (default) / 2>",
+    "bp_serial_stream_var_kernel": "host_serial.h serial_stream_setup via pick_serial_var: the item form of the streamed serial schedule, any other degree profile with rows <= 16 and columns of 1 .. 8 entries (plan_serial_stream; SER_VAR 1: (6,3) too): <METHOD, MATH, DR 8 / 16, DC 4 / 8>",
     "bp_serial_lane_kernel": "host_serial.h serial_lane_launch: what a streamed pass leaves (<= 2048 rows), batches of <= 256 rows: a workgroup per syndrome",
+    "bp_serial_lane_var_kernel": "host_serial.h serial_lane_launch via pick_serial_lane_var: the same for the item form: <METHOD, MATH, DR 8 / 16, DC 4 / 8>",
+    "serial_edge0_kernel": "host_serial.h ensure_edge0: the edge form of the priors (first iteration of bp_serial_stream_kernel; product-sum messages of bp_relative_lds_kernel<..., EXT = 1>)",
+    "serial_var_init_kernel": "host_serial.h serial_var_init_segments: the initial segments of the item form",
     "bp_spread_compact_kernel": "host_stream.h: the list of parked tiles without the final ones, every 8 rounds of a second pass with few expected stragglers",
     "bp_softinfo_kernel": "host_serial.h soft_info_device", "bp_softinfo_level_kernel": "host_serial.h soft_info_device (level-parallel)",
     "bp_serial_relative_kernel": "host_serial.h decode_serial_relative: codes beyond LDS (or LDPC_HIP_REL_LDS=0)",
-    "bp_relative_lds_kernel": "host_serial.h decode_serial_relative_lds: <METHOD, MATH, DRT in 4/8/16, GS, DCT>: GS = 64 lanes per syndrome and the level-by-level sweep (DCT = 2/4/8 lanes per bit >= the heaviest column) when the order is a permutation of the bits; else bit by bit, product-sum with GS = 16 where four syndromes per wavefront fit (DCT 8 unused).  The 1 - 2 spilled VGPRs of the min-sum forms (~30 of the product-sum ones) sit around the call of the out-of-line sort, once per iteration",
+    "bp_relative_lds_kernel": "host_serial.h decode_serial_relative_lds (LDPC_PICK_REL): <METHOD, MATH, DRT in 4/8/16, GS, DCT[, EXT]>: EXT = 1 (<., ., 8 / 16, 64, 4 / 8, 1>: messages and per-entry records in global memory) where the state in LDS would leave fewer than four wavefronts per compute unit, rows > 4 and columns > 2 entries (REL_EXT 0 / 1: never / wherever it is built); else GS = 64 lanes per syndrome and the level-by-level sweep (DCT = 2/4/8 lanes per bit >= the heaviest column) when the order is a permutation of the bits; else bit by bit, product-sum with GS = 16 where four syndromes per wavefront fit (DCT 8 unused).  The 1 - 2 spilled VGPRs of the min-sum forms (~30 of the product-sum ones) sit around the call of the out-of-line sort, once per iteration",
     "osd0_reg_kernel": "host_osd.h: OSD-0, m <= 64/128/256", "osdw_reg_kernel": "host_osd.h: OSD_E / OSD_CS, m <= 256 and n <= 511",
     "osd_big_kernel": "host_osd.h: <HIGHER, MAT_LDS> workgroup per syndrome", "osd0_kernel": "host_osd.h", "osdw_kernel": "host_osd.h",
 }
