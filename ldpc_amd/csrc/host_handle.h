@@ -150,7 +150,7 @@ struct ldpc_hip_bp {
     } rnd;
     int32_t *d_csc_row = nullptr, *d_order = nullptr;
     bool custom_order = false;
-    DeviceBuf counter;
+    DeviceBuf counter;  // counter_bytes(): the BP kernels' work pools, then the counters of BP + OSD (osd_counter_ptr)
     // BP + OSD: where an on-chip BP kernel that can do so lists the rows it leaves unconverged (bposd_device arms it around its decode_device call;
     // `done` says a kernel honoured it -- and then also zeroed the counters, which sit behind the work pools in `counter`)
     struct { int32_t *list; unsigned *count; uint8_t *status; bool armed, done; } osd_hook = {nullptr, nullptr, nullptr, false, false};
@@ -160,7 +160,7 @@ struct ldpc_hip_bp {
     double *d_llr0 = nullptr;
     double *d_osd_wt = nullptr;  // [n] log(1 / p_j), the candidate weights of higher-order OSD
     bool osd_reg = true;  // register-resident elimination for small matrices (ldpc_hip_bp_set_osd_kernel)
-    bool osd_big = false; // OSD-0 through osd0_big_kernel whatever the size (testing)
+    bool osd_big = false; // OSD through osd_big_kernel whatever the size (testing)
     int osd_k_cached = -1;  // n - rank(H), computed on first use
     int32_t osd_method = 1, osd_order = 0;  // ldpc::osd::OsdMethod (osd.hpp:18-23) used by ldpc_hip_bposd_decode_batch
 
@@ -202,12 +202,12 @@ struct ldpc_hip_bp {
         DeviceBuf d_in[NB], d_dec[NB], d_llr[NB], d_it[NB], d_cv[NB];
     } pipe;
     DeviceBuf osd_llr, osd_conv;                                    // BP outputs OSD-0 needs when the caller does not ask for them
-    DeviceBuf osd_scratch;                                          // working copies of H for osd0_big_kernel
+    DeviceBuf osd_scratch;                                          // working copies of H for osd_big_kernel
     DeviceBuf osd_packed;                                           // [m][words] H bit-packed by rows (register OSD kernels)
     DeviceBuf osd_ell;                                              // [m][8] a row's entries as 16-bit column numbers (osd0_flat_kernel)
     DeviceBuf osd_list, osd_counters;                               // rows BP left unconverged + {count, next}
     DeviceBuf osd_status;                                           // [batch] of the last BP + OSD decode: 0 BP converged, 1 OSD solved, 2 s outside image(H)
-    DeviceBuf osd_fix_synd, osd_fix_list, osd_fix_counters, osd_fix_scratch;  // second OSD pass over the rows outside the image (osd_exact_kernel.h)
+    DeviceBuf osd_fix_synd, osd_fix_list, osd_fix_scratch;  // second OSD pass over the rows outside the image (osd_exact_kernel.h)
     int64_t osd_status_rows = 0;
     DeviceBuf rp_synd, rp_dec, rp_llr, rp_iters, rp_conv;           // repacked second pass of the serial schedule
     int32_t serial_kernel = -1;                                     // -1 auto, 0 one wavefront per tile, 1 level-parallel workgroup per tile
@@ -240,6 +240,13 @@ struct ldpc_hip_bp {
     int32_t obs_k = -1;                                              // rows of the observables matrix (-1: not set)
     int64_t max_chunk_tiles = 0;                                     // 0 = decide from free memory
 };
+
+// h->counter: work_pool_bytes() of work counters for the on-chip BP kernels, then OSD_COUNTER_BYTES for BP + OSD -- {listed, next} of the first
+// OSD pass at [0..1], of the second at [8..9] -- so that one fill clears both.  Everybody sizes the buffer with counter_bytes().
+constexpr size_t OSD_COUNTER_BYTES = 64;
+static_assert(OSD_COUNTER_BYTES >= 10 * sizeof(unsigned), "two pairs of OSD counters, the second at [8..9]");
+static size_t counter_bytes() { return work_pool_bytes() + OSD_COUNTER_BYTES; }
+static unsigned *osd_counter_ptr(const ldpc_hip_bp *h) { return (unsigned *)((char *)h->counter.p + work_pool_bytes()); }
 
 // (bp_method, math_mode) of the handle as the compile-time pair <METHOD, MATH> the kernels are instantiated for -- min-sum has one
 // arithmetic, product-sum two -- handed to `f` as two std::integral_constant<int, ...>:

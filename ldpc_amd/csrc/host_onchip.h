@@ -271,11 +271,11 @@ static int decode_wave_ps(ldpc_hip_bp *h, const WavePsPlan &p, const uint8_t *sy
     if ((rc = ensure_wave_ps_tables(h, p))) return rc;
     // (a team per syndrome and no more syndromes than resident teams -- e.g. ONE decode(): static assignment, no work counter to reset)
     const bool static_teams = p.team && batch <= 256 * (int64_t)p.groups_per_cu;
-    if ((rc = h->counter.ensure(work_pool_bytes()))) return rc;
-    // (BP + OSD: the OSD counters sit right behind the work pools -- bposd_device saw to the room -- and share the fill)
-    const bool osd_hook = h->osd_hook.armed && h->osd_hook.count == (unsigned *)((char *)h->counter.p + work_pool_bytes());
-    if (osd_hook && static_teams) HIPCHK(hipMemsetAsync((char *)h->counter.p + work_pool_bytes(), 0, 64, h->stream));
-    if (!static_teams) HIPCHK(hipMemsetAsync(h->counter.p, 0, work_pool_bytes() + (osd_hook ? 64 : 0), h->stream));
+    if ((rc = h->counter.ensure(counter_bytes()))) return rc;
+    // (BP + OSD: the OSD counters sit right behind the work pools and share the fill)
+    const bool osd_hook = h->osd_hook.armed && h->osd_hook.count == osd_counter_ptr(h);
+    if (osd_hook && static_teams) HIPCHK(hipMemsetAsync(osd_counter_ptr(h), 0, OSD_COUNTER_BYTES, h->stream));
+    if (!static_teams) HIPCHK(hipMemsetAsync(h->counter.p, 0, osd_hook ? counter_bytes() : work_pool_bytes(), h->stream));
     WavePsArgs a = {};
     a.pool_per = work_pool_share(batch, 0);
     a.m = h->m; a.n = h->n; a.np = p.np; a.max_iter = h->max_iter;
@@ -323,11 +323,11 @@ static int decode_wave(ldpc_hip_bp *h, const WavePlan &p, const uint8_t *synd, i
     int rc;
     if ((rc = ensure_wave_tables(h, p))) return rc;
     const bool static_teams = p.team && batch <= 256 * (int64_t)p.groups_per_cu;  // (as decode_wave_ps: no work counter for a handful of syndromes)
-    if ((rc = h->counter.ensure(work_pool_bytes()))) return rc;
-    // (BP + OSD: the OSD counters sit right behind the work pools -- bposd_device saw to the room -- and share the fill)
-    const bool osd_hook = h->osd_hook.armed && h->osd_hook.count == (unsigned *)((char *)h->counter.p + work_pool_bytes());
-    if (osd_hook && static_teams) HIPCHK(hipMemsetAsync((char *)h->counter.p + work_pool_bytes(), 0, 64, h->stream));
-    if (!static_teams) HIPCHK(hipMemsetAsync(h->counter.p, 0, work_pool_bytes() + (osd_hook ? 64 : 0), h->stream));
+    if ((rc = h->counter.ensure(counter_bytes()))) return rc;
+    // (BP + OSD: the OSD counters sit right behind the work pools and share the fill)
+    const bool osd_hook = h->osd_hook.armed && h->osd_hook.count == osd_counter_ptr(h);
+    if (osd_hook && static_teams) HIPCHK(hipMemsetAsync(osd_counter_ptr(h), 0, OSD_COUNTER_BYTES, h->stream));
+    if (!static_teams) HIPCHK(hipMemsetAsync(h->counter.p, 0, osd_hook ? counter_bytes() : work_pool_bytes(), h->stream));
     WaveArgs a = {};
     a.pool_per = work_pool_share(batch, 0);
     a.m = h->m; a.n = h->n; a.mp = p.mp; a.np = p.np; a.max_iter = h->max_iter;
@@ -433,7 +433,7 @@ static int ensure_edge_tables(ldpc_hip_bp *h, const EdgePlan &p) {
 template <typename ARGS>
 static int edge_work_split(ldpc_hip_bp *h, int rounds, int64_t batch, int64_t groups, ARGS &a) {
     int rc;
-    if ((rc = h->counter.ensure(work_pool_bytes()))) return rc;
+    if ((rc = h->counter.ensure(counter_bytes()))) return rc;
     HIPCHK(hipMemsetAsync(h->counter.p, 0, work_pool_bytes(), h->stream));
     a.next = (unsigned long long *)h->counter.p;
     a.clk = h->d_clk;

@@ -7,6 +7,8 @@
 #define OSD_PIECE 9  // blocked elimination of osd_big_kernel: planes per table round
 // workgroup barrier that orders LDS traffic only: global loads and stores in flight stay in flight (__syncthreads() waits for them)
 #define OSD_LDS_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
+// (a wavefront's LDS operations execute in order: this only pins the compiler)
+#define OSD_WAVE_LDS_ORDER() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
 #define OSD_BLOCK_ROWS 2048  // blocked elimination: rows the workgroup keeps in registers (eight per thread)
 #define OSD_TRIP 16  // osd_big_kernel: columns per trip when a candidate is weighed
 
@@ -43,7 +45,8 @@ struct OsdArgs {
     const double *llr;     // [batch][n]  BP posteriors
     const uint8_t *conv;   // [batch]     1 = BP converged: row left untouched
     uint8_t *decoding;     // [batch][n]  in: BP decisions, out: OSD solution for unconverged rows
-    int32_t lds_per_wave;  // bytes
+    // one-wavefront kernels: bytes of dynamic LDS per wavefront (the `total` of the kernel's layout); osd_big_kernel: osd_big_ord_off (the same
+    union { int32_t lds_per_wave, big_ord_off; };  // slot: a further argument costs that kernel scalar spills)
     int32_t method, order; // osdw_kernel: 2 = exhaustive (OSD_E), 3 = combination sweep (OSD_CS); order > 0
     int32_t kwords;        // osdw_reg_kernel: ceil((n - rank H) / 64), at least 1
     int32_t rank;          // register kernels: rank of H over GF(2)
@@ -115,33 +118,25 @@ __device__ __forceinline__ bool osd_less(double a, int ia, double b, int ib) {
     return ia < ib;  // stable: ties in ascending index, as glibc's merge-sort qsort leaves them
 }
 
-__global__ void __launch_bounds__(256) osd0_kernel(const OsdArgs a) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char osd_lds[];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int m = a.m, n = a.n, W = a.words;
-    unsigned char *base = osd_lds + (size_t)wave * a.lds_per_wave;
-    volatile uint64_t *mat = reinterpret_cast<volatile uint64_t *>(base);                  // [m][W]
-    volatile double *keys = reinterpret_cast<volatile double *>(base + (size_t)m * W * 8);  // [n]
-    volatile int32_t *order = reinterpret_cast<volatile int32_t *>(base + (size_t)m * W * 8 + (size_t)n * 8);  // [n]
-    volatile int32_t *pivot_col = order + n;                                                // [m]
-    volatile uint8_t *x = reinterpret_cast<volatile uint8_t *>(const_cast<int32_t *>(pivot_col + m));  // [n]
-
-    const int sw = n >> 6;
-    const uint64_t sbit = 1ull << (n & 63);
-    for (int64_t b = osd_first_row(a, OSD_WAVE_WORKER()); b >= 0; b = osd_next_row(a, lane, OSD_WAVE_WORKERS())) {
+// ---- what osd0_kernel and osdw_kernel share.  [H | s] of batch row b into the wavefront's LDS (bit n of a row = its syndrome byte != 0, gf2sparse_linalg.hpp:309)
+__device__ __forceinline__ void osd_lds_load(const OsdArgs &a, int64_t b, int lane, volatile uint64_t *mat, volatile int32_t *pivot_col) {
+    const int m = a.m, W = a.words, sw = a.n >> 6;
+    const uint64_t sbit = 1ull << (a.n & 63);
     for (int i = lane; i < m; i += 64) {
         for (int w = 0; w < W; ++w) mat[(size_t)i * W + w] = 0;
         for (int e = a.row_ptr[i]; e < a.row_ptr[i + 1]; ++e) {
             const int c = a.col_idx[e];
             mat[(size_t)i * W + (c >> 6)] = mat[(size_t)i * W + (c >> 6)] | (1ull << (c & 63));
         }
-        if (a.synd[b * m + i]) mat[(size_t)i * W + sw] = mat[(size_t)i * W + sw] | sbit;  // `if (i)`, gf2sparse_linalg.hpp:309
+        if (a.synd[b * m + i]) mat[(size_t)i * W + sw] = mat[(size_t)i * W + sw] | sbit;
         pivot_col[i] = -1;
     }
-    for (int j = lane; j < n; j += 64) { keys[j] = a.llr[b * n + j]; x[j] = 0; }
+}
+// soft_decision_col_sort (sort.hpp:48-62): order[rank of column i] = i, rank = number of columns that sort before it
+__device__ __forceinline__ void osd_lds_sort(const OsdArgs &a, int64_t b, int lane, volatile double *keys, volatile int32_t *order) {
+    const int n = a.n;
+    for (int j = lane; j < n; j += 64) keys[j] = a.llr[b * n + j];
     __builtin_amdgcn_wave_barrier();
-    // soft_decision_col_sort: rank of column i = number of columns that sort before it
     for (int i = lane; i < n; i += 64) {
         const double ki = keys[i];
         int r = 0;
@@ -149,7 +144,14 @@ __global__ void __launch_bounds__(256) osd0_kernel(const OsdArgs a) {
         order[r] = i;
     }
     __builtin_amdgcn_wave_barrier();
-
+}
+// Greedy Gauss-Jordan elimination over the sorted columns.  FULL = false (OSD-0): stops once the syndrome is in the span of the pivots
+// (gf2sparse_linalg.hpp:373-383).  FULL = true: rref (gf2sparse_linalg.hpp:132-226), and code[c] = the row that carries pivot column c.
+template <bool FULL>
+__device__ __forceinline__ void osd_lds_eliminate(const OsdArgs &a, int lane, volatile uint64_t *mat, const volatile int32_t *order,
+                                                  volatile int32_t *pivot_col, volatile int32_t *code) {
+    const int m = a.m, n = a.n, W = a.words, sw = n >> 6;
+    const uint64_t sbit = 1ull << (n & 63);
     const int max_rank = m < n ? m : n;
     int rank = 0;
     for (int t = 0; t < n && rank < max_rank; ++t) {
@@ -168,23 +170,67 @@ __global__ void __launch_bounds__(256) osd0_kernel(const OsdArgs a) {
         for (int i = lane; i < m; i += 64)
             if (i != p && (mat[(size_t)i * W + cw] & cb))
                 for (int w = 0; w < W; ++w) mat[(size_t)i * W + w] = mat[(size_t)i * W + w] ^ mat[(size_t)p * W + w];
-        if (lane == 0) pivot_col[p] = c;
+        if (lane == 0) { pivot_col[p] = c; if (FULL) code[c] = p; }
         ++rank;
         __builtin_amdgcn_wave_barrier();
-        // stop once the syndrome is in the span of the pivots (gf2sparse_linalg.hpp:373-383)
-        bool pending = false;
-        for (int i0 = 0; i0 < m && !pending; i0 += 64) {
-            const int i = i0 + lane;
-            pending = __ballot(i < m && pivot_col[i] < 0 && (mat[(size_t)i * W + sw] & sbit)) != 0;
+        if (!FULL) {
+            bool pending = false;
+            for (int i0 = 0; i0 < m && !pending; i0 += 64) {
+                const int i = i0 + lane;
+                pending = __ballot(i < m && pivot_col[i] < 0 && (mat[(size_t)i * W + sw] & sbit)) != 0;
+            }
+            if (!pending) break;
         }
-        if (!pending) break;
     }
-    for (int i = lane; i < m; i += 64)
-        if (pivot_col[i] >= 0 && (mat[(size_t)i * W + sw] & sbit)) x[pivot_col[i]] = 1;
-    __builtin_amdgcn_wave_barrier();
-    for (int j = lane; j < n; j += 64) a.decoding[b * n + j] = x[j];
-    __builtin_amdgcn_wave_barrier();
-    }  // next row
+}
+// Across the lanes of a wavefront: the lightest candidate, the earliest of the reference's list among equals.  A lane without a candidate must hold the
+// OSD-0 weight and index -1: candidates only replace that solution if strictly lighter (osd.hpp:177), so it never ties with a lane that has one.
+__device__ __forceinline__ void osd_wave_lightest(double &best_w, long &best_c) {
+    for (int off = 32; off > 0; off >>= 1) {
+        const double ow = __shfl_xor(best_w, off);
+        const long oc = ((long)__shfl_xor((int)(best_c >> 32), off) << 32) | (unsigned)__shfl_xor((int)(best_c & 0xffffffff), off);
+        if (ow < best_w || (ow == best_w && oc < best_c)) { best_w = ow; best_c = oc; }
+    }
+}
+// per-wavefront LDS of osd0_kernel (HIGHER = false) and osdw_kernel: byte offsets of the regions behind mat [m][W] u64, and the size
+struct OsdLdsLayout { size_t T, keys, order, code, npcol, pivot_col, x, total; };
+__host__ __device__ inline OsdLdsLayout osd_lds_layout(int m, int n, int W, bool higher) {
+    OsdLdsLayout L;
+    L.T = (size_t)m * W * 8;                           // osdw_kernel: [m] u64
+    L.keys = L.T + (higher ? (size_t)m * 8 : 0);       // [n] f64  log-ratios; osdw_kernel: later the weights
+    L.order = L.keys + (size_t)n * 8;                  // [n] i32
+    L.code = L.order + (size_t)n * 4;                  // osdw_kernel: [n] i32  pivot column: its row; non-pivot column: -1 - position among the non-pivots
+    L.npcol = L.code + (size_t)n * 4;                  // osdw_kernel: [n] i32  non-pivot columns in sorted order
+    L.pivot_col = higher ? L.npcol + (size_t)n * 4 : L.code;  // [m] i32
+    L.x = L.pivot_col + (size_t)m * 4;                 // osd0_kernel: [n] u8
+    L.total = (L.x + (higher ? 0 : (size_t)n) + 15) & ~(size_t)15;
+    return L;
+}
+__global__ void __launch_bounds__(256) osd0_kernel(const OsdArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char osd_lds[];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int m = a.m, n = a.n, W = a.words;
+    const OsdLdsLayout L = osd_lds_layout(m, n, W, false);
+    unsigned char *base = osd_lds + (size_t)wave * a.lds_per_wave;
+    volatile uint64_t *mat = reinterpret_cast<volatile uint64_t *>(base);
+    volatile double *keys = reinterpret_cast<volatile double *>(base + L.keys);
+    volatile int32_t *order = reinterpret_cast<volatile int32_t *>(base + L.order);
+    volatile int32_t *pivot_col = reinterpret_cast<volatile int32_t *>(base + L.pivot_col);
+    volatile uint8_t *x = reinterpret_cast<volatile uint8_t *>(base + L.x);
+    const int sw = n >> 6;
+    const uint64_t sbit = 1ull << (n & 63);
+    for (int64_t b = osd_first_row(a, OSD_WAVE_WORKER()); b >= 0; b = osd_next_row(a, lane, OSD_WAVE_WORKERS())) {
+        osd_lds_load(a, b, lane, mat, pivot_col);
+        for (int j = lane; j < n; j += 64) x[j] = 0;
+        osd_lds_sort(a, b, lane, keys, order);
+        osd_lds_eliminate<false>(a, lane, mat, order, pivot_col, nullptr);
+        for (int i = lane; i < m; i += 64)
+            if (pivot_col[i] >= 0 && (mat[(size_t)i * W + sw] & sbit)) x[pivot_col[i]] = 1;
+        __builtin_amdgcn_wave_barrier();
+        for (int j = lane; j < n; j += 64) a.decoding[b * n + j] = x[j];
+        __builtin_amdgcn_wave_barrier();
+    }
 }
 
 // ---- register-resident elimination for small matrices ------------------------------------------------------
@@ -206,9 +252,6 @@ __device__ __forceinline__ uint64_t osd_readlane64(uint64_t v, int src_lane) {  
     const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, src_lane);
     const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), src_lane);
     return ((uint64_t)hi << 32) | lo;
-}
-__device__ __forceinline__ double osd_readlane_f64(double v, int src_lane) {
-    return __builtin_bit_cast(double, osd_readlane64(__builtin_bit_cast(uint64_t, v), src_lane));
 }
 // [H | s] of batch row b into registers (bit n of a row = its syndrome byte != 0, gf2sparse_linalg.hpp:309); H comes
 // bit-packed (a.packed), so a row is W independent loads rather than a walk over its CSR entries
@@ -620,14 +663,25 @@ __device__ __forceinline__ void osd_pair_of(long p, int order, int &i, int &j) {
     j = i + 1 + (int)(p - r * (n2 - r) / 2);
 }
 
+// OSD_E candidate c: the number c + 1 (1 .. 2^order - 1, order <= 24), bit j -> j-th non-pivot column, bits >= k dropped (util.hpp:12-38)
+__device__ __forceinline__ uint64_t osd_kmask(int k) { return k >= 64 ? ~0ull : ((1ull << k) - 1ull); }
+__device__ __forceinline__ uint64_t osd_e_mask(long c, uint64_t kmask) { return (uint64_t)(c + 1) & kmask; }
+// OSD_CS pair number p -- pairs (i, j), i < j < order <= 64, i-major (osd.hpp:91-99) -- as a column mask; valid = false: past the reference's candidate string
+__device__ __forceinline__ uint64_t osd_pair_mask(long p, int order, int k, bool &valid) {
+    int i = 0;
+    while (p >= order - 1 - i) { p -= order - 1 - i; ++i; }
+    const int j = i + 1 + (int)p;
+    valid = j < k;
+    return valid ? (1ull << i) | (1ull << j) : 0ull;
+}
+
 __device__ __forceinline__ OsdCandidate osd_candidate(int method, int order, int k, long c) {
     OsdCandidate r;
     r.mask = 0;
     r.single = r.single2 = -1;
     r.valid = true;
-    const uint64_t kmask = k >= 64 ? ~0ull : ((1ull << k) - 1ull);
-    if (method == 2) {  // numbers 1 .. 2^order - 1, bit j -> j-th non-pivot column, bits >= k dropped (util.hpp:12-38)
-        r.mask = (uint64_t)(c + 1) & kmask;
+    if (method == 2) {
+        r.mask = osd_e_mask(c, osd_kmask(k));
     } else if (c < k) {  // weight one, every non-pivot column (osd.hpp:84-89)
         if (c < 64) r.mask = 1ull << c; else r.single = (int32_t)c;
     } else {  // pairs (i, j), i < j < order, i-major (osd.hpp:91-99)
@@ -647,59 +701,21 @@ __global__ void __launch_bounds__(256) osdw_kernel(const OsdArgs a) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int m = a.m, n = a.n, W = a.words;
+    const OsdLdsLayout L = osd_lds_layout(m, n, W, true);
     unsigned char *base = osd_lds + (size_t)wave * a.lds_per_wave;
-    volatile uint64_t *mat = reinterpret_cast<volatile uint64_t *>(base);                         // [m][W]
-    volatile uint64_t *T = mat + (size_t)m * W;                                                   // [m]
-    volatile double *keys = reinterpret_cast<volatile double *>(const_cast<uint64_t *>(T + m));   // [n] log-ratios, later weights
-    volatile int32_t *order = reinterpret_cast<volatile int32_t *>(const_cast<double *>(keys + n));  // [n]
-    volatile int32_t *code = order + n;       // [n] pivot column: its row; non-pivot column: -1 - position among the non-pivots
-    volatile int32_t *npcol = code + n;       // [n] non-pivot columns in sorted order
-    volatile int32_t *pivot_col = npcol + n;  // [m]
-
+    volatile uint64_t *mat = reinterpret_cast<volatile uint64_t *>(base);
+    volatile uint64_t *T = reinterpret_cast<volatile uint64_t *>(base + L.T);
+    volatile double *keys = reinterpret_cast<volatile double *>(base + L.keys);
+    volatile int32_t *order = reinterpret_cast<volatile int32_t *>(base + L.order);
+    volatile int32_t *code = reinterpret_cast<volatile int32_t *>(base + L.code);
+    volatile int32_t *npcol = reinterpret_cast<volatile int32_t *>(base + L.npcol);
+    volatile int32_t *pivot_col = reinterpret_cast<volatile int32_t *>(base + L.pivot_col);
     const int sw = n >> 6;
-    const uint64_t sbit = 1ull << (n & 63);
     for (int64_t b = osd_first_row(a, OSD_WAVE_WORKER()); b >= 0; b = osd_next_row(a, lane, OSD_WAVE_WORKERS())) {
-    for (int i = lane; i < m; i += 64) {
-        for (int w = 0; w < W; ++w) mat[(size_t)i * W + w] = 0;
-        for (int e = a.row_ptr[i]; e < a.row_ptr[i + 1]; ++e) {
-            const int c = a.col_idx[e];
-            mat[(size_t)i * W + (c >> 6)] = mat[(size_t)i * W + (c >> 6)] | (1ull << (c & 63));
-        }
-        if (a.synd[b * m + i]) mat[(size_t)i * W + sw] = mat[(size_t)i * W + sw] | sbit;
-        pivot_col[i] = -1;
-    }
-    for (int j = lane; j < n; j += 64) { keys[j] = a.llr[b * n + j]; code[j] = INT32_MIN; }
-    __builtin_amdgcn_wave_barrier();
-    for (int i = lane; i < n; i += 64) {  // soft_decision_col_sort (sort.hpp:48-62)
-        const double ki = keys[i];
-        int r = 0;
-        for (int j = 0; j < n; ++j) r += osd_less(keys[j], j, ki, i) ? 1 : 0;
-        order[r] = i;
-    }
-    __builtin_amdgcn_wave_barrier();
-
-    // rref over the sorted columns (gf2sparse_linalg.hpp:132-226), rows fully reduced
-    const int max_rank = m < n ? m : n;
-    int rank = 0;
-    for (int t = 0; t < n && rank < max_rank; ++t) {
-        const int c = order[t];
-        const int cw = c >> 6;
-        const uint64_t cb = 1ull << (c & 63);
-        int p = -1;
-        for (int i0 = 0; i0 < m && p < 0; i0 += 64) {
-            const int i = i0 + lane;
-            const bool cand = i < m && pivot_col[i] < 0 && (mat[(size_t)i * W + cw] & cb);
-            const uint64_t mask = __ballot(cand);
-            if (mask) p = i0 + __builtin_ctzll(mask);
-        }
-        if (p < 0) continue;
-        for (int i = lane; i < m; i += 64)
-            if (i != p && (mat[(size_t)i * W + cw] & cb))
-                for (int w = 0; w < W; ++w) mat[(size_t)i * W + w] = mat[(size_t)i * W + w] ^ mat[(size_t)p * W + w];
-        if (lane == 0) { pivot_col[p] = c; code[c] = p; }
-        ++rank;
-        __builtin_amdgcn_wave_barrier();
-    }
+    osd_lds_load(a, b, lane, mat, pivot_col);
+    for (int j = lane; j < n; j += 64) code[j] = INT32_MIN;
+    osd_lds_sort(a, b, lane, keys, order);
+    osd_lds_eliminate<true>(a, lane, mat, order, pivot_col, code);
     // non-pivot columns in sorted order (`cols[rank ..]`, gf2sparse_linalg.hpp:210-224)
     int k = 0;
     for (int t0 = 0; t0 < n; t0 += 64) {
@@ -767,13 +783,7 @@ __global__ void __launch_bounds__(256) osdw_kernel(const OsdArgs a) {
             }
         }
     }
-    // across lanes: lightest, then earliest
-    for (int off = 32; off > 0; off >>= 1) {
-        const double ow = __shfl_xor(best_w, off);
-        const long oc = ((long)__shfl_xor((int)(best_c >> 32), off) << 32) | (unsigned)__shfl_xor((int)(best_c & 0xffffffff), off);
-        const bool mine_set = best_c >= 0, other_set = oc >= 0;
-        if (other_set && (!mine_set || ow < best_w || (ow == best_w && oc < best_c))) { best_w = ow; best_c = oc; }
-    }
+    osd_wave_lightest(best_w, best_c);
     OsdCandidate win = none;
     if (best_c >= 0) win = osd_candidate(a.method, a.order, k, best_c);
     for (int j = lane; j < n; j += 64) a.decoding[b * n + j] = bit_of(win, j) ? 1 : 0;
@@ -806,6 +816,17 @@ __device__ __forceinline__ void osd_gather_step(const OsdRows<R, W> &rows, uint3
     }
 }
 
+// per-wavefront LDS of osdw_reg_kernel: byte offsets of the regions behind rec [n][kwords + 2] u64 = {weight, S, T[kwords]}, and the size
+// (32-bit: n <= 511, kwords <= 8; with 64-bit offsets the kernel's scalar spills change)
+struct OsdwRegLds { int32_t order, colQ, npcol, total; };
+__host__ __device__ inline OsdwRegLds osdw_reg_lds(int n, int kwords) {
+    OsdwRegLds L;
+    L.order = n * (kwords + 2) * 8;  // [n] i32
+    L.colQ = L.order + n * 4;        // [n] i32  -2: unseen, -1: pivot column, q >= 0: the q-th non-pivot column
+    L.npcol = L.colQ + n * 4;        // [64 kwords] i32
+    L.total = (L.npcol + 64 * kwords * 4 + 15) & ~15;
+    return L;
+}
 template <int R, int W>
 __global__ void __launch_bounds__(256) osdw_reg_kernel(const OsdArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char osd_lds[];
@@ -816,11 +837,12 @@ __global__ void __launch_bounds__(256) osdw_reg_kernel(const OsdArgs a) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int n = a.n, KW = a.kwords, RS = a.kwords + 2;  // RS: 64-bit words of a column record
+    const OsdwRegLds L = osdw_reg_lds(n, KW);
     lds_u8 *base = (lds_u8 *)osd_lds + wave * a.lds_per_wave;
-    volatile lds_u64 *rec = (volatile lds_u64 *)base;              // [n][RS]  {weight, S, T[KW]}
-    volatile lds_i32 *order = (volatile lds_i32 *)(rec + (size_t)n * RS);  // [n]
-    volatile lds_i32 *colQ = order + n;                            // [n] -2: unseen, -1: pivot column, q >= 0: the q-th non-pivot column
-    volatile lds_i32 *npcol = colQ + n;                            // [64 KW]
+    volatile lds_u64 *rec = (volatile lds_u64 *)base;
+    volatile lds_i32 *order = (volatile lds_i32 *)(base + L.order);
+    volatile lds_i32 *colQ = (volatile lds_i32 *)(base + L.colQ);
+    volatile lds_i32 *npcol = (volatile lds_i32 *)(base + L.npcol);
     for (int64_t b = osd_first_row(a, OSD_WAVE_WORKER()); b >= 0; b = osd_next_row(a, lane, OSD_WAVE_WORKERS())) {
         OSD_CLK_START();
         OsdRows<R, W> rows;
@@ -923,13 +945,6 @@ __global__ void __launch_bounds__(256) osdw_reg_kernel(const OsdArgs a) {
             }
             return acc;
         };
-        auto pair_mask = [&](long p, bool &valid) -> uint64_t {  // pairs (i, j), i < j < order <= 64, i-major (osd.hpp:91-99)
-            int i = 0;
-            while (p >= a.order - 1 - i) { p -= a.order - 1 - i; ++i; }
-            const int j = i + 1 + (int)p;
-            valid = j < k;  // past the candidate string in the reference
-            return valid ? (1ull << i) | (1ull << j) : 0ull;
-        };
         // osd_order > 64: a pair may sit in any two words of T -- each lane reads the two words of ITS pair (no broadcast any more)
         auto pair_cols = [&](long p, int &i, int &j) -> bool {  // pair number p of the reference's list (i-major, osd.hpp:91-99) -> i < j; false: past the string
             osd_pair_of(p, a.order, i, j);
@@ -948,7 +963,7 @@ __global__ void __launch_bounds__(256) osdw_reg_kernel(const OsdArgs a) {
         };
         double best_w = weigh_mask(0);  // the OSD-0 solution (osd.hpp:131-136)
         long best_c = -1;               // index in the reference's candidate list; -1: the OSD-0 solution
-        const uint64_t kmask = k >= 64 ? ~0ull : ((1ull << k) - 1ull);
+        const uint64_t kmask = osd_kmask(k);
         const long npairs = (long)a.order * (a.order - 1) / 2;
         if (a.method == 3) {
             for (int v = 0; v * 64 < k; ++v) {
@@ -959,7 +974,7 @@ __global__ void __launch_bounds__(256) osdw_reg_kernel(const OsdArgs a) {
                 for (long p0 = 0; p0 < npairs; p0 += 64) {
                     const long pp = p0 + lane;
                     bool valid = false;
-                    const uint64_t mask = pp < npairs ? pair_mask(pp, valid) : 0ull;
+                    const uint64_t mask = pp < npairs ? osd_pair_mask(pp, a.order, k, valid) : 0ull;
                     const double w = weigh_mask(mask);
                     if (valid && w < best_w) { best_w = w; best_c = k + pp; }
                 }
@@ -977,17 +992,12 @@ __global__ void __launch_bounds__(256) osdw_reg_kernel(const OsdArgs a) {
             const long total = (1L << a.order) - 1;
             for (long c0 = 0; c0 < total; c0 += 64) {
                 const long c = c0 + lane;
-                const double w = weigh_mask((uint64_t)(c + 1) & kmask);
+                const double w = weigh_mask(osd_e_mask(c, kmask));
                 if (c < total && w < best_w) { best_w = w; best_c = c; }
             }
         }
         OSD_CLK(5);
-        for (int off = 32; off > 0; off >>= 1) {  // across lanes: lightest, then earliest
-            const double ow = __shfl_xor(best_w, off);
-            const long oc = ((long)__shfl_xor((int)(best_c >> 32), off) << 32) | (unsigned)__shfl_xor((int)(best_c & 0xffffffff), off);
-            const bool mine_set = best_c >= 0, other_set = oc >= 0;
-            if (other_set && (!mine_set || ow < best_w || (ow == best_w && oc < best_c))) { best_w = ow; best_c = oc; }
-        }
+        osd_wave_lightest(best_w, best_c);
         const bool single = a.method == 3 && best_c >= 0 && best_c < k;
         const bool far_pair = a.method == 3 && best_c >= k && a.order > 64;
         uint64_t win = 0;
@@ -995,7 +1005,7 @@ __global__ void __launch_bounds__(256) osdw_reg_kernel(const OsdArgs a) {
         if (far_pair) (void)pair_cols(best_c - k, wq_i, wq_j);
         else if (best_c >= 0 && !single) {
             bool valid;
-            win = a.method == 3 ? pair_mask(best_c - k, valid) : (uint64_t)(best_c + 1) & kmask;
+            win = a.method == 3 ? osd_pair_mask(best_c - k, a.order, k, valid) : osd_e_mask(best_c, kmask);
         }
         for (int j = lane; j < n; j += 64) {
             uint64_t x = rec_r[(size_t)j * RS + 1];
@@ -1022,6 +1032,24 @@ __global__ void __launch_bounds__(256) osdw_reg_kernel(const OsdArgs a) {
 // HIGHER (OSD_E / OSD_CS): no early stop; afterwards the reduced rows are squeezed to the non-pivot columns (T, again
 // plane-major, behind the matrix in the slot: one pass, a parallel bit compress per plane) and the candidates are weighed as in
 // osdw_reg_kernel: lane = candidate, a task of 64 per wavefront, each wavefront with the T plane it needs staged in LDS.
+// Dynamic LDS of osd_big_kernel, byte offsets.  For a whole row: pivcol [m] i16 at 0, hits [m] u16, sy [m + 1] u8, ord [pow2] u16 (16-bit tables: m, n
+// < 32768 -- the host checks --, and the LDS they save is a third resident workgroup).  The room behind them belongs to one phase at a time -- sort: keys
+// [n] u64; fill: sorted positions [n] u16; elimination: look [m] u64, then (blocked) tbl; higher order, afterwards: colinfo [n] i16, npm [hwords][1 + 6]
+// u64, planes [nplanes][m + 1] u64.  Last the working copy [hwords][m] u64 if it fits (MAT_LDS).  ord, room, tbl and the copy travel in the arguments.
+__host__ __device__ inline size_t osd_big_ord_off(int m) { return ((size_t)m * 5 + 1 + 7) & ~(size_t)7; }
+__host__ __device__ inline size_t osd_big_room_off(int m, int pow2) { return (osd_big_ord_off(m) + (size_t)pow2 * 2 + 15) & ~(size_t)15; }
+__host__ __device__ inline size_t osd_big_tbl_off(size_t room, int m) { return room + (size_t)m * 8; }
+__host__ __device__ inline size_t osd_big_npm_off(size_t room, int n) { return (room + 2 * (size_t)n + 7) & ~(size_t)7; }
+__host__ __device__ inline size_t osd_big_npm_words(int hwords) { return 7 * (size_t)hwords; }
+// end of the room's largest tenant = the size without the working copy; nplanes 0: OSD-0
+__host__ __device__ inline size_t osd_big_lds_bytes(int m, int n, int pow2, int hwords, bool blocked, int nplanes) {
+    const size_t room = osd_big_room_off(m, pow2);
+    const size_t sort = room + (size_t)n * 8;
+    const size_t elim = osd_big_tbl_off(room, m) + (blocked ? (size_t)16 * OSD_PIECE * 16 * 8 : 0);
+    const size_t weigh = nplanes ? osd_big_npm_off(room, n) + (osd_big_npm_words(hwords) + ((size_t)m + 1) * (size_t)nplanes) * 8 : 0;
+    const size_t end = sort > elim ? sort : elim;
+    return end > weigh ? end : weigh;
+}
 struct OsdBigArgs {
     OsdArgs o;
     uint64_t *scratch;      // [slots][hwords + kwords][m]
@@ -1030,10 +1058,10 @@ struct OsdBigArgs {
     int32_t pow2;           // bitonic size: smallest power of two >= n
     int32_t max_rank;       // rank of H if the host worked it out, else min(m, n)
     int32_t kwords;         // HIGHER: planes of T the slot has room for (>= ceil((n - rank) / 64))
-    int32_t extra_off;      // byte offset in LDS of the room the phases share: keys [n] u64 | positions [n] u16 | look [m] u64 + table | {colinfo [n] i16, (8-aligned) plane masks and moves [7][hwords] u64, planes [nplanes][m + 1] u64}
-    int32_t mat_off;        // MAT_LDS: byte offset in LDS of the working copy [hwords][m]
-    int32_t nplanes;        // HIGHER: wavefronts that weigh candidates, each with its own staged plane [m + 1] u64 in LDS (4, 2 or 1)
-    int32_t pbuf_off;       // blocked elimination (m <= OSD_BLOCK_ROWS): byte offset in LDS of the combination table (extra_off + 8 m); -1: one pivot per step
+    int32_t extra_off;      // osd_big_room_off
+    int32_t mat_off;        // MAT_LDS: where the working copy starts
+    int32_t nplanes;        // HIGHER: wavefronts that weigh candidates, each with its own staged plane in LDS (4, 2 or 1)
+    int32_t pbuf_off;       // blocked elimination (m <= OSD_BLOCK_ROWS): osd_big_tbl_off; -1: one pivot per step
 };
 
 // ---- blocked elimination: the 64 columns of a look-ahead block, rows in registers ----------------------------------------------
@@ -1048,11 +1076,6 @@ struct OsdBigArgs {
 // from a table of the XOR combinations of every four pivot rows -- and its syndrome bit parity(M_r & S), S_j = syndrome bit
 // of pivot row j at block start.  Same pivots (first unpivoted row with the bit, columns in sorted order), same reduced matrix:
 // tools/proto_blocked_elimination.py checks the algebra against the one-pivot-at-a-time form, the golden fixtures the kernel.
-__device__ __forceinline__ unsigned osd_bit_at(uint64_t x, int j) {  // j uniform: one 32-bit shift instead of a 64-bit one
-    const unsigned h = j < 32 ? (unsigned)x : (unsigned)(x >> 32);
-    return (h >> (j & 31)) & 1u;
-}
-
 template <int MQ>
 __device__ __forceinline__ int osd_block_eliminate(int tid, int m, int ahead, uint64_t *look, const int16_t *pivcol,
                                                 uint16_t *blk_row, uint16_t *blk_col, unsigned long long *xch, int rank, int max_rank) {
@@ -1144,18 +1167,15 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
     const int tid = threadIdx.x, T = blockDim.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int m = a.m, n = a.n, HW = A.hwords, P = A.pow2;
-    // [pivcol, hits, sy | ord] stay; the room after them (extra_off) belongs to one phase at a time: the sort's keys, the fill's
-    // positions, the elimination's look-ahead words and table, the candidates' tables and planes (sized by the host, decode path of bp_hip.hip)
     uint64_t *keys = reinterpret_cast<uint64_t *>(osd_lds + (size_t)A.extra_off);
-    // (16-bit tables: m, n < 32768 here -- the host checks --, and the LDS they save is a third resident workgroup)
-    uint16_t *ord = reinterpret_cast<uint16_t *>(osd_lds + (size_t)a.lds_per_wave);  // lds_per_wave: bytes before `ord`
-    int16_t *pivcol = reinterpret_cast<int16_t *>(osd_lds);            // [m]
-    uint16_t *hits = reinterpret_cast<uint16_t *>(pivcol + m);         // [m]
-    uint8_t *sy = reinterpret_cast<uint8_t *>(hits + m);               // [m + 1]
-    uint64_t *look = reinterpret_cast<uint64_t *>(osd_lds + (size_t)A.extra_off);  // [m] bits of the block's 64 columns, per row
-    int16_t *colinfo = reinterpret_cast<int16_t *>(osd_lds + (size_t)A.extra_off);  // [n] pivot column: its row; q-th non-pivot column: -1 - q
-    uint64_t *npm = reinterpret_cast<uint64_t *>(osd_lds + (((size_t)A.extra_off + 2 * (size_t)n + 7) & ~(size_t)7));  // [HW] non-pivot positions of every plane, then [HW][6] the compress moves
-    uint64_t *planes = npm + 7 * (size_t)HW;  // [4][m + 1] (entry m: the all-zero dummy row)
+    uint16_t *ord = reinterpret_cast<uint16_t *>(osd_lds + (size_t)a.big_ord_off);
+    int16_t *pivcol = reinterpret_cast<int16_t *>(osd_lds);
+    uint16_t *hits = reinterpret_cast<uint16_t *>(pivcol + m);
+    uint8_t *sy = reinterpret_cast<uint8_t *>(hits + m);
+    uint64_t *look = reinterpret_cast<uint64_t *>(osd_lds + (size_t)A.extra_off);  // bits of the block's 64 columns, per row
+    int16_t *colinfo = reinterpret_cast<int16_t *>(osd_lds + (size_t)A.extra_off);  // pivot column: its row; q-th non-pivot column: -1 - q
+    uint64_t *npm = reinterpret_cast<uint64_t *>(osd_lds + osd_big_npm_off((size_t)A.extra_off, n));
+    uint64_t *planes = npm + osd_big_npm_words(HW);
     __shared__ int sh_row, sh_pivot[3], sh_nhits[3], sh_cnt[4], sh_nact;
     __shared__ uint16_t blk_row[64], blk_col[64];
     __shared__ unsigned long long blk_sy;
@@ -1222,9 +1242,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
                     if (!chunked || j >= (P >> 2) || jn >= (P >> 2) || (k == P && j == 1)) {
                         __syncthreads();
                     } else {
-                        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // LDS operations of a wavefront execute in order; this only pins the compiler
-                        __builtin_amdgcn_wave_barrier();
-                        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                        OSD_WAVE_LDS_ORDER();
                     }
                 }
         }
@@ -1233,7 +1251,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
         // copies of a batch's rows live in HBM / MALL, and bytes moved are what this kernel is bound by), and the non-pivot
         // columns come out in candidate order.  Filled from the CSR form: nnz atomic ORs into the zeroed planes.
         {
-            uint16_t *pos = reinterpret_cast<uint16_t *>(osd_lds + (size_t)A.extra_off);  // [n] sorted position of a column (in the keys' room, until the fill is done)
+            uint16_t *pos = reinterpret_cast<uint16_t *>(osd_lds + (size_t)A.extra_off);  // sorted position of a column (in the keys' room, until the fill is done)
             for (int t = tid; t < n; t += T) pos[ord[t]] = (uint16_t)t;
             __threadfence();
             __syncthreads();
@@ -1619,14 +1637,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
             }
             return acc;
         };
-        auto pair_mask = [&](long p, bool &valid) -> uint64_t {  // pairs (i, j), i < j < order <= 64, i-major (osd.hpp:91-99)
-            int i = 0;
-            while (p >= a.order - 1 - i) { p -= a.order - 1 - i; ++i; }
-            const int j = i + 1 + (int)p;
-            valid = j < k;
-            return valid ? (1ull << i) | (1ull << j) : 0ull;
-        };
-        const uint64_t kmask = k >= 64 ? ~0ull : ((1ull << k) - 1ull);
+        const uint64_t kmask = osd_kmask(k);
         const long npairs = (long)a.order * (a.order - 1) / 2;
         // The winner is the lightest candidate, the earliest of the reference's list among equals, the OSD-0 solution before all of
         // them (osd.hpp:131-136, 171-181: a candidate replaces the incumbent only if strictly lighter) -- a lexicographic minimum, so
@@ -1659,9 +1670,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
                     }
                     if (lane == 0) pl[m] = 0;
                     held = want;
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // LDS operations of a wavefront execute in order; this only pins the compiler
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    OSD_WAVE_LDS_ORDER();
                 }
                 if (want < 0) {
                     const long e = task * 64 + lane;
@@ -1669,8 +1678,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
                     uint64_t mask = 0;
                     long idx = -1;
                     if (valid && e >= 1) {
-                        if (a.method == 3) { mask = pair_mask(e - 1, valid); idx = k + e - 1; }
-                        else { mask = (uint64_t)e & kmask; idx = e - 1; }
+                        if (a.method == 3) { mask = osd_pair_mask(e - 1, a.order, k, valid); idx = k + e - 1; }
+                        else { mask = osd_e_mask(e - 1, kmask); idx = e - 1; }
                     }
                     const double w = weigh_mask(pl, mask);
                     if (valid) offer(w, idx);
@@ -1700,9 +1709,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
                                 for (int r = lane; r < m; r += 64) pl[r] = Tm[(int64_t)vi * m + r];
                                 if (lane == 0) pl[m] = 0;
                                 held = -3 - vi;
-                                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                                __builtin_amdgcn_wave_barrier();
-                                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                                OSD_WAVE_LDS_ORDER();
                             }
                             const int e = e0 + lane;
                             const bool valid = e < npb;
@@ -1729,11 +1736,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
         }
         OSD_WG_CLK(5);  // weighing
         // lightest, then earliest: across the lanes of a wavefront, then across the wavefronts
-        for (int off = 32; off > 0; off >>= 1) {
-            const double ow = __shfl_xor(best_w, off);
-            const long oc = ((long)__shfl_xor((int)(best_c >> 32), off) << 32) | (unsigned)__shfl_xor((int)(best_c & 0xffffffff), off);
-            offer(ow, oc);
-        }
+        osd_wave_lightest(best_w, best_c);
         __syncthreads();
         if (lane == 0) { sh_w[wave] = best_w; sh_c[wave] = best_c; }
         __syncthreads();
@@ -1747,7 +1750,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))
             osd_pair_of(best_c - k, a.order, wq_i, wq_j);
         } else if (best_c >= 0 && !single) {
             bool valid;
-            win = a.method == 3 ? pair_mask(best_c - k, valid) : (uint64_t)(best_c + 1) & kmask;
+            win = a.method == 3 ? osd_pair_mask(best_c - k, a.order, k, valid) : osd_e_mask(best_c, kmask);
         }
         const uint64_t *plw = single ? Tm + (int64_t)(best_c >> 6) * m : Tm;
         for (int j = tid; j < n; j += T) {

@@ -34,8 +34,10 @@ RULES = {  # template -> who selects which instantiation
     "bp_softinfo_kernel": "host_serial.h soft_info_device", "bp_softinfo_level_kernel": "host_serial.h soft_info_device (level-parallel)",
     "bp_serial_relative_kernel": "host_serial.h decode_serial_relative: codes beyond LDS (or LDPC_HIP_REL_LDS=0)",
     "bp_relative_lds_kernel": "host_serial.h decode_serial_relative_lds (LDPC_PICK_REL): <METHOD, MATH, DRT in 4/8/16, GS, DCT[, EXT]>: EXT = 1 (<., ., 8 / 16, 64, 4 / 8, 1>: messages and per-entry records in global memory) where the state in LDS would leave fewer than four wavefronts per compute unit, rows > 4 and columns > 2 entries (REL_EXT 0 / 1: never / wherever it is built); else GS = 64 lanes per syndrome and the level-by-level sweep (DCT = 2/4/8 lanes per bit >= the heaviest column) when the order is a permutation of the bits; else bit by bit, product-sum with GS = 16 where four syndromes per wavefront fit (DCT 8 unused).  The 1 - 2 spilled VGPRs of the min-sum forms (~30 of the product-sum ones) sit around the call of the out-of-line sort, once per iteration",
-    "osd0_reg_kernel": "host_osd.h: OSD-0, m <= 64/128/256", "osdw_reg_kernel": "host_osd.h: OSD_E / OSD_CS, m <= 256 and n <= 511",
-    "osd_big_kernel": "host_osd.h: <HIGHER, MAT_LDS> workgroup per syndrome", "osd0_kernel": "host_osd.h", "osdw_kernel": "host_osd.h",
+    "osd0_reg_kernel": "host_osd.h plan_osd: OSD-0, m <= 64/128/256", "osdw_reg_kernel": "host_osd.h plan_osd: OSD_E / OSD_CS, m <= 256 and n <= 511",
+    "osd0_flat_kernel": "host_osd.h plan_osd: OSD-0, m <= 128, n <= 256, rows of up to eight entries: <R, D> = <ceil(m / 64), dwords of n in 2/3/5/8>",
+    "osd_big_kernel": "host_osd.h plan_osd_big: <HIGHER, MAT_LDS> workgroup per syndrome", "osd0_kernel": "host_osd.h plan_osd: OSD-0, [H | s] in a wavefront's LDS",
+    "osdw_kernel": "host_osd.h plan_osd: OSD_E / OSD_CS, [H | s] in a wavefront's LDS",
 }
 
 txt = open(sys.argv[1]).read()
