@@ -171,6 +171,34 @@ int ldpc_hip_bposd0_decode_batch_async(ldpc_hip_bp *h, const uint8_t *syndromes,
                                        uint8_t *converge);
 
 /*
+ * Row priors: every syndrome decoded with its OWN channel probabilities.
+ * replaces: the per-shot loop `dec.update_channel_probs(p[shot]); out[shot] = dec.decode(s[shot])` -- BpDecoderBase.update_channel_probs /
+ * the error_channel setter (src_python/ldpc/bp_decoder/_bp_decoder.pyx:205-233) followed by BpDecoder.decode (pyx:642-695), whose
+ * BpDecoder::initialise_log_domain_bp re-reads channel_probabilities on every decode (src_cpp/bp.hpp:147-157) -- as ONE batch; the
+ * bposd0 forms replace the same loop around BpOsdDecoder.decode with osd_method = OSD_0 (_bposd_decoder.pyx:125-134; osd.hpp:110-117
+ * orders the columns by BP's posteriors and reads no prior).  The reference's own analog memory experiment runs this loop
+ * (monte_carlo_simulation/memory_experiment_v2.py:55-58, 103-113).
+ * channel_probs [batch][n]: row b is what the reference would have been given before decoding syndrome b; log((1 - p) / p) is formed on the
+ * device with a correctly rounded division and the bit-exact twin of the host's log (bp.hpp:150-151), so p = 0, 1, 0.5 give the
+ * reference's +inf, -inf, +0.0 priors.  Outputs as for ldpc_hip_bp_decode_batch / ldpc_hip_bposd0_decode_batch, row for row what that
+ * loop returns.  UNLIKE the loop, the handle's own channel probabilities are untouched: the next plain decode uses them as before.
+ * Host or device pointers as for the syndromes (each pointer on its own); a host array of probabilities is checked (a value outside
+ * [0, 1] or NaN: LDPC_HIP_ERR_INVALID), a device array is the caller's word.  The *_async forms take device pointers only and do not wait.
+ * Parallel schedule only: any serial schedule -> LDPC_HIP_ERR_UNSUPPORTED (ldpc_hip_last_error says so).  Higher-order OSD weighs its
+ * candidates by log(1 / p) (osd.hpp:134) and has no such form.  Kernels: codes that stream run the per-pass kernels from the first
+ * iteration with a per-lane prior; codes an on-chip kernel takes run the slot kernel (csrc/bp_small_kernel.h), each slot holding its
+ * syndrome's priors.  Extra workspace: 512 n bytes per 64-syndrome tile.
+ */
+int ldpc_hip_bp_decode_batch_priors(ldpc_hip_bp *h, const uint8_t *syndromes, int64_t batch, uint8_t *decoding, double *llr,
+                                    int32_t *iterations, uint8_t *converge, const double *channel_probs);
+int ldpc_hip_bp_decode_batch_priors_async(ldpc_hip_bp *h, const uint8_t *syndromes, int64_t batch, uint8_t *decoding, double *llr,
+                                          int32_t *iterations, uint8_t *converge, const double *channel_probs);
+int ldpc_hip_bposd0_decode_batch_priors(ldpc_hip_bp *h, const uint8_t *syndromes, int64_t batch, uint8_t *decoding, double *llr,
+                                        int32_t *iterations, uint8_t *converge, const double *channel_probs);
+int ldpc_hip_bposd0_decode_batch_priors_async(ldpc_hip_bp *h, const uint8_t *syndromes, int64_t batch, uint8_t *decoding, double *llr,
+                                              int32_t *iterations, uint8_t *converge, const double *channel_probs);
+
+/*
  * BP + ordered-statistics decoding of any order: replaces BpOsdDecoder.decode's per-shot path for
  * osd_method OSD_E / OSD_CS as well (ldpc::osd::OsdDecoder::decode, src_cpp/osd.hpp:103-187; candidate strings
  * osd.hpp:75-101).  ldpc_hip_bp_set_osd stores the method and order the BpOsdDecoder setters write

@@ -136,9 +136,29 @@ public:
     // the same into the caller's arrays ([batch][n] decoding, [batch][n] log-ratios or null, [batch] iterations, [batch] converge):
     // what a binding that hands out NumPy arrays wants -- the results cross the PCIe link straight into them (large batches: in
     // pinned, double-buffered chunks that overlap the kernels, ldpc_hip.h)
+    // channel_probs (or null): [batch][n], row b = the probabilities syndrome b is decoded with -- the loop `update_channel_probs(p[b]);
+    // decode(s[b])` (_bp_decoder.pyx:222, 642-695) as one batch; this object's channel_probabilities stay as they are (ldpc_hip.h:
+    // ldpc_hip_bp_decode_batch_priors).  One GPU, parallel schedule, BP or BP + OSD_0.
     bool decode_batch_into(const uint8_t *syndromes, int64_t batch, uint8_t *dec_out, double *llr_out, int32_t *iters_out,
-                           uint8_t *conv_out, bool osd = false) {
+                           uint8_t *conv_out, bool osd = false, const double *channel_probs = nullptr) {
         if (!sync_()) return false;
+        if (channel_probs) {
+            if (mh_ || (osd && osd_method != 1)) {
+                last_status = LDPC_HIP_ERR_UNSUPPORTED;
+                last_error = mh_ ? "per-row channel probabilities are not sharded over several GPUs"
+                                 : "per-row channel probabilities: OSD_E / OSD_CS weigh their candidates by log(1 / p) of the decoder's own priors (osd.hpp:134); OSD_0 only";
+                return false;
+            }
+            last_status = (osd ? ldpc_hip_bposd0_decode_batch_priors : ldpc_hip_bp_decode_batch_priors)(h_, syndromes, batch, dec_out, llr_out, iters_out, conv_out, channel_probs);
+            if (last_status != LDPC_HIP_OK) { last_error = ldpc_hip_last_error(); return false; }
+            osd_status_batch.clear();
+            if (osd) {
+                osd_status_batch.assign((size_t)batch, 0);
+                last_status = ldpc_hip_bposd_get_status(h_, osd_status_batch.data(), batch);
+                if (last_status != LDPC_HIP_OK) { last_error = ldpc_hip_last_error(); return false; }
+            }
+            return true;
+        }
         if (osd) {
             last_status = each_([&](ldpc_hip_bp *h) { return ldpc_hip_bp_set_osd(h, osd_method, osd_order); });
             if (last_status != LDPC_HIP_OK) { last_error = ldpc_hip_last_error(); return false; }

@@ -23,6 +23,7 @@ SYMBOLS = (
     "ldpc_hip_bp_workspace_bytes", "ldpc_hip_bp_set_tuning", "ldpc_hip_bp_set_math", "ldpc_hip_bp_set_ring", "ldpc_hip_bp_set_small_code_kernel", "ldpc_hip_bp_set_handoff", "ldpc_hip_last_error", "ldpc_hip_version",
     "ldpc_hip_bp_set_debug_switch", "ldpc_hip_bp_multi_create", "ldpc_hip_bp_multi_destroy", "ldpc_hip_bp_multi_devices", "ldpc_hip_bp_multi_handle",
     "ldpc_hip_bp_multi_decode_batch", "ldpc_hip_bp_multi_last_kernel_ms", "ldpc_hip_bp_multi_set_staging",
+    "ldpc_hip_bp_decode_batch_priors", "ldpc_hip_bp_decode_batch_priors_async", "ldpc_hip_bposd0_decode_batch_priors", "ldpc_hip_bposd0_decode_batch_priors_async",
 )
 
 
@@ -77,6 +78,9 @@ def load():
     lib.ldpc_hip_bp_decode_batch_async.argtypes = [vp, vp, i64, vp, vp, vp, vp]
     lib.ldpc_hip_bposd0_decode_batch.argtypes = [vp, vp, i64, vp, vp, vp, vp]
     lib.ldpc_hip_bposd0_decode_batch_async.argtypes = [vp, vp, i64, vp, vp, vp, vp]
+    if not os.environ.get("LDPC_HIP_LIB") or hasattr(lib, "ldpc_hip_bp_decode_batch_priors"):  # (an older build under A/B measurement may lack them)
+        for name in ("ldpc_hip_bp_decode_batch_priors", "ldpc_hip_bp_decode_batch_priors_async", "ldpc_hip_bposd0_decode_batch_priors", "ldpc_hip_bposd0_decode_batch_priors_async"):
+            getattr(lib, name).argtypes = [vp, vp, i64, vp, vp, vp, vp, vp]
     lib.ldpc_hip_bp_set_osd.argtypes = [vp, i32, i32]
     lib.ldpc_hip_bposd_get_status.argtypes = [vp, vp, i64]
     lib.ldpc_hip_bp_set_osd_kernel.argtypes = [vp, i32]

@@ -45,6 +45,7 @@ cdef extern from "ldpc_hip.hpp" namespace "ldpc_hip":
         vector[uint8_t]& decode(vector[uint8_t]& syndrome)
         cbool decode_batch(const uint8_t *syndromes, int64_t batch, cbool want_llr, cbool osd0) nogil
         cbool decode_batch_into(const uint8_t *syndromes, int64_t batch, uint8_t *dec, double *llr, int32_t *iters, uint8_t *conv, cbool osd0) nogil
+        cbool decode_batch_into(const uint8_t *syndromes, int64_t batch, uint8_t *dec, double *llr, int32_t *iters, uint8_t *conv, cbool osd0, const double *channel_probs) nogil
 
 
 cdef class CyBpCore:
@@ -144,9 +145,12 @@ cdef class CyBpCore:
             raise RuntimeError(self.bpd.last_error.decode("utf-8", "replace"))
         return np.array(self.bpd.decoding, dtype=np.uint8)
 
-    def decode_batch(self, const uint8_t[:, ::1] syndromes, bint want_llr=True, bint osd0=False, llr_out=None):
-        """``(B, m)`` uint8 -> ``(decoding (B, n), llr (B, n) | None, iterations (B,), converge (B,) bool)``."""
+    def decode_batch(self, const uint8_t[:, ::1] syndromes, bint want_llr=True, bint osd0=False, llr_out=None, channel_probs=None):
+        """``(B, m)`` uint8 -> ``(decoding (B, n), llr (B, n) | None, iterations (B,), converge (B,) bool)``.
+        ``channel_probs``: ``(B, n)`` float64 C-contiguous, row b = the probabilities syndrome b is decoded with (or None)."""
         cdef int64_t b = syndromes.shape[0]
+        cdef const double[:, ::1] probs_view
+        cdef const double *probs_p = NULL
         cdef cbool ok
         cdef cbool c_llr = want_llr, c_osd = osd0
         if syndromes.shape[1] != self.m:
@@ -177,8 +181,16 @@ cdef class CyBpCore:
             if want_llr:
                 llr_view = llr
                 llr_p = &llr_view[0, 0]
+        if channel_probs is not None:
+            if channel_probs.dtype != np.float64 or channel_probs.shape != (b, self.n) or not channel_probs.flags.c_contiguous or self.n == 0:
+                raise ValueError(f"channel_probs must be a C-contiguous float64 array of shape ({b}, {self.n})")
+            probs_view = channel_probs
+            probs_p = &probs_view[0, 0]
         with nogil:
-            ok = self.bpd.decode_batch_into(&syndromes[0, 0], b, dec_p, llr_p, &it_view[0], &cv_view[0], c_osd)
+            if probs_p != NULL:
+                ok = self.bpd.decode_batch_into(&syndromes[0, 0], b, dec_p, llr_p, &it_view[0], &cv_view[0], c_osd, probs_p)
+            else:
+                ok = self.bpd.decode_batch_into(&syndromes[0, 0], b, dec_p, llr_p, &it_view[0], &cv_view[0], c_osd)
         if not ok:
             raise RuntimeError(self.bpd.last_error.decode("utf-8", "replace"))
         self.osd_status = None

@@ -442,13 +442,34 @@ class BpDecoderBase:
         self._cy.ms_scaling_factor = self._ms_scaling_factor
         return self._cy
 
-    def _decode_numpy(self, synd2d, want_llr=True, osd0=False, llr_out=None):
+    def _decode_numpy(self, synd2d, want_llr=True, osd0=False, llr_out=None, channel_probs=None):
         """(B, m) uint8 NumPy -> (decoding, llr, iterations, converge) through the active backend.  ``llr_out``: a (B, n) float64
-        C-contiguous array to receive the log-ratios instead of a new one."""
+        C-contiguous array to receive the log-ratios instead of a new one.  ``channel_probs``: checked (B, n) row priors or None."""
         cy = self._get_cy() if self._schedule == PARALLEL else None  # the schedule setters live on the ctypes engine
+        if cy is not None and channel_probs is not None:
+            return cy.decode_batch(np.ascontiguousarray(synd2d, np.uint8), want_llr, osd0, llr_out, channel_probs)
         if cy is not None:
             return cy.decode_batch(np.ascontiguousarray(synd2d, np.uint8), want_llr, osd0, llr_out)
+        if channel_probs is not None:
+            return self._get_engine().decode_batch(synd2d, want_llr=want_llr, osd0=osd0, llr_out=llr_out, channel_probs=channel_probs)
         return self._get_engine().decode_batch(synd2d, want_llr=want_llr, osd0=osd0, llr_out=llr_out)
+
+    def _row_probs(self, input_vectors, channel_probs, as_syndrome=True):
+        """``channel_probs`` of ``decode_batch``: what cannot be done is refused with its reason, then the array is checked
+        (``HipBpEngine._row_probs``) -- without a GPU: shape, dtype, range and place need none."""
+        from ldpc_amd.engine import HipBpEngine
+        if self._schedule != PARALLEL:
+            raise NotImplementedError(f"channel_probs with schedule='{self.schedule}': the serial schedules decode with the decoder's own "
+                                      "channel probabilities only; per-row probabilities need schedule='parallel'.")
+        if not as_syndrome:
+            raise NotImplementedError("channel_probs with received vectors (input_vector_type='received_vector'): per-row probabilities are "
+                                      "available for syndrome decoding only.")
+        if self._device_ids is not None:
+            raise NotImplementedError("channel_probs with device_ids=[...]: the rows of channel_probs are not sharded over several GPUs; "
+                                      "decode on one GPU.")
+        shim = HipBpEngine.__new__(HipBpEngine)  # (the check reads n only; no handle is made -- __del__ finds none)
+        shim.n = self.n
+        return HipBpEngine._row_probs(shim, input_vectors, channel_probs)
 
     # Whether ``decode_batch`` may overwrite the log-ratio array it handed out last time (same shape).  Off by default: ownership is never
     # inferred (reference counts are an interpreter detail -- CPython 3.14 borrows stack references, other interpreters have none).  A
@@ -578,8 +599,17 @@ class BpDecoder(BpDecoderBase):
         return out.astype(dtype)
 
     # ---- batch (additive) -----------------------------------------------------------------------
-    def decode_batch(self, input_vectors, want_log_prob_ratios: bool = True, *, log_prob_ratios_out=None, reuse_log_prob_ratios=None):
+    def decode_batch(self, input_vectors, want_log_prob_ratios: bool = True, *, log_prob_ratios_out=None, reuse_log_prob_ratios=None,
+                     channel_probs=None):
         """Decode every row of a 2-D array in one launch.
+
+        ``channel_probs``: a ``(B, n)`` float64 array in the same place as ``input_vectors`` (NumPy, or a CUDA tensor on the same GPU).  Row b is
+        then decoded with ``channel_probs[b]``: ``decoding``, ``converge``, ``iter`` and ``log_prob_ratios`` of row b are what the reference
+        returns for ``update_channel_probs(channel_probs[b]); decode(input_vectors[b])`` (pyx:222, 642-695) -- heralded erasures
+        (p = 0.5 on the flagged bits), soft readout, drifting noise.  Probabilities 0, 1 and 0.5 are legal (priors +inf, -inf, +0.0).  Unlike that
+        loop the call leaves this decoder's own ``channel_probs`` / ``error_rate`` UNCHANGED: a following plain ``decode_batch`` uses them.
+        Syndromes and the parallel schedule only; ``ValueError`` for a wrong shape, a value outside [0, 1] or NaN, or arrays in different
+        places; ``NotImplementedError`` for a serial schedule, received vectors and ``device_ids``.
 
         ``log_prob_ratios_out`` (NumPy inputs): a ``(B, n)`` float64 C-contiguous array that receives the log-ratios;
         ``reuse_log_prob_ratios=True`` (or the attribute ``recycle_log_prob_ratios``): the array the previous call handed out as
@@ -605,6 +635,8 @@ class BpDecoder(BpDecoderBase):
             raise ValueError(f"The input_vector must have length {self.m} (for syndrome decoding) or length {self.n} (for received vector decoding). Not length {ln}.")
         self._require_parallel()
         as_syndrome = self._bp_input_type == SYNDROME or (self._bp_input_type == AUTO and ln == self.m)
+        if channel_probs is not None:
+            channel_probs = self._row_probs(input_vectors, channel_probs, as_syndrome)
         eng = self._get_engine()
         if _is_torch(input_vectors):
             import torch
@@ -613,7 +645,8 @@ class BpDecoder(BpDecoderBase):
                                  "are returned as a device tensor (log_prob_ratios_batch).")
             vec = input_vectors
             synd = vec if as_syndrome else eng.mulvec_batch(vec)
-            dec, llr, it, cv = eng.decode_batch(synd, want_llr=want_log_prob_ratios)
+            dec, llr, it, cv = (eng.decode_batch(synd, want_llr=want_log_prob_ratios) if channel_probs is None else
+                                eng.decode_batch(synd, want_llr=want_log_prob_ratios, channel_probs=channel_probs))
             if not as_syndrome:
                 dec ^= vec
             zero = vec.any(dim=1).logical_not()  # all-zero shortcut rows (pyx:679-681); uint8.any() is uint8
@@ -639,7 +672,8 @@ class BpDecoder(BpDecoderBase):
             scan.start()
         try:
             dec, llr, it, cv = self._decode_numpy(synd, want_llr=want_log_prob_ratios,
-                                                  llr_out=self._llr_destination(len(synd), log_prob_ratios_out, reuse_log_prob_ratios) if want_log_prob_ratios else None)
+                                                  llr_out=self._llr_destination(len(synd), log_prob_ratios_out, reuse_log_prob_ratios) if want_log_prob_ratios else None,
+                                                  channel_probs=channel_probs)
         finally:
             if scan is not None:
                 scan.join()
@@ -725,9 +759,12 @@ class SoftInfoBpDecoder(BpDecoderBase):
         self._soft_syndrome = so[0]
         return dec[0].astype(np.uint8)
 
-    def decode_batch(self, soft_info_syndromes):
+    def decode_batch(self, soft_info_syndromes, channel_probs=None):
         """``(B, m)`` analog syndromes in one launch; row b equals ``decode(soft_info_syndromes[b])``.  Afterwards
         ``converge_batch``, ``iter_batch``, ``log_prob_ratios_batch`` and ``soft_syndrome_batch`` describe every row."""
+        if channel_probs is not None:
+            raise NotImplementedError("channel_probs with SoftInfoBpDecoder: soft-syndrome decoding is a serial schedule (bp.hpp:547-660) and "
+                                      "decodes with the decoder's own channel probabilities only.")
         if soft_info_syndromes.ndim != 2 or soft_info_syndromes.shape[1] != self.m:
             raise ValueError(f"The soft syndromes must have shape (batch, {self.m}).")
         from ldpc_amd.engine import _is_torch

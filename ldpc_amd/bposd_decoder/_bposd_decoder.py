@@ -107,18 +107,22 @@ class BpOsdDecoder(BpDecoderBase):
                 f"osd_method={self.osd_method} with osd_order={self._osd_order} is not available on the MI355X path "
                 "(OSD_E up to order 24 = 16.7 million candidates per syndrome; OSD_CS takes any order); there is no CPU fallback.")
 
-    def _decode_osd(self, synd2d, want_llr=True, force_osd0=False):
-        """BP + OSD through the active backend with this decoder's osd_method / osd_order."""
+    def _decode_osd(self, synd2d, want_llr=True, force_osd0=False, channel_probs=None):
+        """BP + OSD through the active backend with this decoder's osd_method / osd_order (``channel_probs``: checked row priors, OSD_0)."""
         method, order = (OSD_0, 0) if force_osd0 else (self._osd_method, self._osd_order)
         cy = self._get_cy() if self._schedule == PARALLEL else None  # the schedule setters live on the ctypes engine
         if cy is not None:
             cy.osd_method, cy.osd_order = method, order
-            out = cy.decode_batch(np.ascontiguousarray(synd2d, np.uint8), want_llr, True)
+            if channel_probs is not None:
+                out = cy.decode_batch(np.ascontiguousarray(synd2d, np.uint8), want_llr, True, None, channel_probs)
+            else:
+                out = cy.decode_batch(np.ascontiguousarray(synd2d, np.uint8), want_llr, True)
             self._last_status = cy.osd_status
             return out
         eng = self._get_engine()
         eng.set_osd(method, order)
-        out = eng.decode_batch(synd2d, want_llr=want_llr, osd=True)
+        out = (eng.decode_batch(synd2d, want_llr=want_llr, osd=True) if channel_probs is None else
+               eng.decode_batch(synd2d, want_llr=want_llr, osd0=True, channel_probs=channel_probs))
         self._last_status = eng.osd_status(len(synd2d)) if hasattr(eng, "osd_status") else None
         return out
 
@@ -155,16 +159,27 @@ class BpOsdDecoder(BpDecoderBase):
             self._osd0_decoding = None  # evaluated on demand (osd0_decoding) when the order is > 0
             self._last_syndrome = np.asarray(synd_row, np.uint8).copy()
 
-    def decode_batch(self, syndromes, want_log_prob_ratios: bool = True):
-        """Every row through BP (+ OSD-0 where BP does not converge) in one call; row b == ``decode(syndromes[b])``."""
+    def decode_batch(self, syndromes, want_log_prob_ratios: bool = True, channel_probs=None):
+        """Every row through BP (+ OSD-0 where BP does not converge) in one call; row b == ``decode(syndromes[b])``.
+
+        ``channel_probs`` (``osd_method`` OSD_0 only): a ``(B, n)`` float64 array in the same place as ``syndromes``; row b is decoded with
+        ``channel_probs[b]`` -- what the reference returns for ``update_channel_probs(channel_probs[b]); decode(syndromes[b])``, the OSD-0
+        decision included (it orders the columns by BP's posteriors).  Unlike that loop the call leaves this decoder's own ``channel_probs`` /
+        ``error_rate`` UNCHANGED.  Refusals as ``BpDecoder.decode_batch``; OSD_E / OSD_CS: ``NotImplementedError``."""
         if syndromes.ndim != 2 or syndromes.shape[1] != self.m:
             raise ValueError(f"The syndrome must have length {self.m}. Not {syndromes.shape[-1]}.")
         self._require_supported()
+        if channel_probs is not None:
+            if self._osd_method != OSD_0:
+                raise NotImplementedError(f"channel_probs with osd_method='{self.osd_method}': OSD_E / OSD_CS weigh their candidates by log(1 / p) of the "
+                                          "decoder's own channel probabilities (osd.hpp:134); per-row probabilities are available with OSD_0 only.")
+            channel_probs = self._row_probs(syndromes, channel_probs)
         from ldpc_amd.engine import _is_torch
         if _is_torch(syndromes):  # device tensors in, device tensors out (nothing crosses PCIe)
             eng = self._get_engine()
             eng.set_osd(self._osd_method, self._osd_order)
-            dec, llr, it, cv = eng.decode_batch(syndromes, want_llr=want_log_prob_ratios, osd=True)
+            dec, llr, it, cv = (eng.decode_batch(syndromes, want_llr=want_log_prob_ratios, osd=True) if channel_probs is None else
+                                eng.decode_batch(syndromes, want_llr=want_log_prob_ratios, osd0=True, channel_probs=channel_probs))
             self.osd_status_batch = eng.osd_status(int(syndromes.shape[0])) if hasattr(eng, "osd_status") else None
             zero = syndromes.any(dim=1).logical_not()
             if bool(zero.any()):
@@ -177,7 +192,7 @@ class BpOsdDecoder(BpDecoderBase):
             return dec
         dtype = syndromes.dtype
         vec = np.ascontiguousarray(np.asarray(syndromes).astype(np.uint8))
-        dec, llr, it, cv = self._decode_osd(vec, want_llr=want_log_prob_ratios)
+        dec, llr, it, cv = self._decode_osd(vec, want_llr=want_log_prob_ratios, channel_probs=channel_probs)
         self.osd_status_batch = self._last_status
         zero = ~vec.any(axis=1)
         dec[zero] = 0

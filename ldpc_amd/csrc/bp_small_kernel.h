@@ -26,15 +26,23 @@ struct SmallArgs {
     int32_t *iters;             // [batch] or nullptr
     uint8_t *conv;              // [batch] or nullptr
     unsigned long long *next;   // device-wide work counter (zeroed before launch)
+    // Row priors (bp_small_kernel<., ., RP>; io_kernels.h: row_priors_kernel): [tiles][n][64] every syndrome's OWN priors -- syndrome b
+    // at lane b % 64 of tile b / 64 -- or nullptr.  A slot copies the priors of the syndrome it holds into its own LDS when it is (re)filled.
+    const double *llr0_t;
 };
 
-template <int METHOD, int MATH>
+// per-slot LDS of bp_small_kernel, bytes: [A nnz f64][C nnz f64][L n f64][hard n u8][sy m u8], 16-byte rounded, then (RP) [P n f64]
+__host__ __device__ inline size_t small_slot_bytes(int m, int n, int nnz, bool rp) {
+    return (((size_t)nnz * 16 + (size_t)n * 8 + (size_t)n + (size_t)m + 15) & ~(size_t)15) + (rp ? (size_t)n * 8 : 0);
+}
+
+template <int METHOD, int MATH, bool RP = false>
 __global__ void __launch_bounds__(256) bp_small_kernel(const SmallArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char sm_lds[];
     const int tid = threadIdx.x, T = blockDim.x;
     const int m = a.m, n = a.n, nnz = a.nnz, S = a.slots;
     // LDS carve-up: [log table 2 KiB][llr0 n][row_ptr m+1][col_idx nnz][col_ptr n+1][csc_edge nnz] then per slot
-    // [A nnz f64][C nnz f64][L n f64][hard n u8][sy m u8]
+    // [A nnz f64][C nnz f64][L n f64][hard n u8][sy m u8] and, RP, [P n f64] = the priors of the syndrome in the slot
     double *log_tab = reinterpret_cast<double *>(sm_lds);
     double *prior = log_tab + 256;
     int32_t *rp = reinterpret_cast<int32_t *>(prior + n);
@@ -43,7 +51,8 @@ __global__ void __launch_bounds__(256) bp_small_kernel(const SmallArgs a) {
     int32_t *ce = cp + (n + 1);
     size_t off = (size_t)(reinterpret_cast<unsigned char *>(ce + nnz) - sm_lds);
     off = (off + 15) & ~(size_t)15;
-    const size_t slot_bytes = ((size_t)nnz * 16 + (size_t)n * 8 + (size_t)n + (size_t)m + 15) & ~(size_t)15;
+    const size_t slot_bytes = small_slot_bytes(m, n, nnz, RP);
+    const size_t slot_prior_off = slot_bytes - (size_t)n * 8;  // (RP)
     __shared__ long long slot_synd[16];  // syndrome index held by the slot, -1 = idle
     __shared__ int slot_iter[16];
     __shared__ int slot_unsat[16];
@@ -66,6 +75,7 @@ __global__ void __launch_bounds__(256) bp_small_kernel(const SmallArgs a) {
 
     const float inv_m = m > 0 ? 1.0f / (float)m : 0.f, inv_n = n > 0 ? 1.0f / (float)n : 0.f, inv_e = nnz > 0 ? 1.0f / (float)nnz : 0.f;
     auto slot_base = [&](int s) { return sm_lds + off + (size_t)s * slot_bytes; };
+    auto slot_prior = [&](int s) { return RP ? reinterpret_cast<const double *>(slot_base(s) + slot_prior_off) : prior; };
     auto split = [](int w, int len, float inv, int &s, int &r) {  // w = s * len + r, exact for w < 2^22
         s = (int)(((float)w + 0.5f) * inv);
         r = w - s * len;
@@ -75,11 +85,21 @@ __global__ void __launch_bounds__(256) bp_small_kernel(const SmallArgs a) {
 
     for (;;) {
         // ---- (re)initialise fresh slots: initialise_log_domain_bp (bp.hpp:147-157) + syndrome bytes ----
+        if (RP) {
+            for (int w = tid; w < S * n; w += T) {
+                int s, j;
+                split(w, n, inv_n, s, j);
+                const long long b = slot_synd[s];
+                if (slot_state[s] == 2 && b >= 0)
+                    reinterpret_cast<double *>(slot_base(s) + slot_prior_off)[j] = a.llr0_t[((size_t)(b >> 6) * (size_t)n + (size_t)j) * LDPC_WAVE + (size_t)(b & 63)];
+            }
+            __syncthreads();
+        }
         for (int w = tid; w < S * nnz; w += T) {
             int s, e;
             split(w, nnz, inv_e, s, e);
             if (slot_state[s] == 2 && slot_synd[s] >= 0)
-                reinterpret_cast<double *>(slot_base(s))[e] = edge_form<METHOD, MATH>(prior[ci[e]]);
+                reinterpret_cast<double *>(slot_base(s))[e] = edge_form<METHOD, MATH>(slot_prior(s)[ci[e]]);
         }
         for (int w = tid; w < S * m; w += T) {
             int s, i;
@@ -151,7 +171,7 @@ __global__ void __launch_bounds__(256) bp_small_kernel(const SmallArgs a) {
             double *L = Cm + nnz;
             uint8_t *hard = reinterpret_cast<uint8_t *>(L + n);
             const int lo = cp[j], hi = cp[j + 1];
-            double temp = prior[j];
+            double temp = slot_prior(s)[j];
             for (int p = lo; p < hi; ++p) { const int e = ce[p]; A[e] = temp; temp += Cm[e]; }
             L[j] = temp;
             hard[j] = temp <= 0 ? 1 : 0;

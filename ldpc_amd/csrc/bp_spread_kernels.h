@@ -16,6 +16,10 @@ struct SpreadArgs {
     unsigned *host_flag;  // host-mapped word: receives `seq` when the last parked tile becomes final (the host stops queueing rounds)
     unsigned seq;
     int32_t slot0;    // the first slot of the list this launch serves (workgroup row y: slot0 + y; the LOOP forms: and every gridDim.y-th after it)
+    // Row priors (the <..., RP> forms; io_kernels.h: row_priors_kernel): [tiles][n][64] log((1 - p) / p) of every lane's OWN channel
+    // probabilities, in the layout of the messages -- the reference's `update_channel_probs(p[shot]); decode(s[shot])` loop
+    // (_bp_decoder.pyx:222) as one batch.  Read where the other forms read bp.llr0[j]; nullptr otherwise.
+    const double *llr0_t;
 };
 
 // Late rounds.  After a few rounds all but a handful of the tiles are final (what is left is what never converges), yet a launch of a row of
@@ -101,7 +105,7 @@ __global__ void __launch_bounds__(256) bp_spread_check_kernel(const SpreadArgs a
     } while (LOOP && (slot += (int)gridDim.y) < spread_count(a));
 }
 
-template <int METHOD, int MATH, int DC, int NT, bool LOOP = false>
+template <int METHOD, int MATH, int DC, int NT, bool LOOP = false, bool RP = false>
 __global__ void __launch_bounds__(256) bp_spread_bit_kernel(const SpreadArgs a) {
     typedef MsgBufT<NT ? 2 : 0> Buf;
     int64_t tile;
@@ -120,13 +124,14 @@ __global__ void __launch_bounds__(256) bp_spread_bit_kernel(const SpreadArgs a) 
     const Buf Ct = make_msgbuf<Buf>(a.bp.C + (size_t)tile * (size_t)nnz * LDPC_WAVE, (unsigned)nnz);
     const bool want_llr = a.bp.llr_t != nullptr;
     const Buf Lt = make_msgbuf<Buf>(want_llr ? a.bp.llr_t + (size_t)tile * (size_t)n * LDPC_WAVE : a.bp.A, want_llr ? (unsigned)n : 0u);
+    const Buf Pt = make_msgbuf<Buf>(RP ? const_cast<double *>(a.llr0_t) + (size_t)tile * (size_t)n * LDPC_WAVE : a.bp.A, RP ? (unsigned)n : 0u);
     const bool last = it == a.bp.max_iter;
     const bool lane_live = !((done >> lane) & 1ull);
     const bool each = st->llr_each[a.round & 1] != 0;  // (as the persistent kernel's llr_each)
     const int j0 = (blockIdx.x * 4 + wave) * a.nodes;
     for (int j = j0; j < j0 + a.nodes && j < n; ++j) {
         const int cs = sload(a.bp.col_ptr + j), d = sload(a.bp.col_ptr + j + 1) - cs;
-        const double prior = sload(a.bp.llr0 + j);
+        const double prior = RP ? Pt.ld(l8, j) : sload(a.bp.llr0 + j);  // (RP: this lane's own prior)
         double llr;
         if (d <= DC) {
             int e[DC];
@@ -201,16 +206,19 @@ __global__ void __launch_bounds__(256) bp_spread_state_init_kernel(const SpreadA
     if (t == 0) a.bp.counters[1] = a.bp.counters[2] = (unsigned)a.n_tiles;  // parked, live
 }
 
-template <int METHOD, int MATH>
+template <int METHOD, int MATH, bool RP = false>
 __global__ void __launch_bounds__(256) bp_spread_init_kernel(const SpreadArgs a) {  // bp.hpp:147-157
     const int64_t tile = blockIdx.y;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int nnz = a.bp.nnz, l8 = lane * 8;
     const MsgBuf At = make_msgbuf(a.bp.A + (size_t)tile * (size_t)nnz * LDPC_WAVE, (unsigned)nnz);
+    const MsgBuf Pt = make_msgbuf(RP ? const_cast<double *>(a.llr0_t) + (size_t)tile * (size_t)a.bp.n * LDPC_WAVE : a.bp.A, RP ? (unsigned)a.bp.n : 0u);
     const int e0 = (blockIdx.x * 4 + wave) * 16;
-    for (int e = e0; e < e0 + 16 && e < nnz; ++e)
-        At.st(l8, e, edge_form<METHOD, MATH>(sload(a.bp.llr0 + sload(a.bp.col_idx + e))));
+    for (int e = e0; e < e0 + 16 && e < nnz; ++e) {
+        const int j = sload(a.bp.col_idx + e);
+        At.st(l8, e, edge_form<METHOD, MATH>(RP ? Pt.ld(l8, j) : sload(a.bp.llr0 + j)));
+    }
 }
 
 // [n] initial edge values for BpArgs::edge0
@@ -224,7 +232,7 @@ __global__ void __launch_bounds__(256) bp_edge0_kernel(const double *llr0, int n
 // (decisions + posterior of THIS iteration), a tile whose lanes are all frozen or that reached max_iter gets its
 // outputs.  64 bits per workgroup; workgroup 0 of a tile also advances its state.  Almost always there is nothing
 // to freeze and every workgroup but the first leaves at once.
-template <bool LOOP = false>
+template <bool LOOP = false, bool RP = false>
 __global__ void __launch_bounds__(256) bp_spread_finish_kernel(const SpreadArgs a) {
     int64_t tile;
     const TileState *cst;
@@ -252,6 +260,7 @@ __global__ void __launch_bounds__(256) bp_spread_finish_kernel(const SpreadArgs 
         const MsgBuf Ct = make_msgbuf(a.bp.C + (size_t)tile * (size_t)nnz * LDPC_WAVE, (unsigned)nnz);
         const bool want_llr = a.bp.llr_t != nullptr;
         const MsgBuf Lt = make_msgbuf(want_llr ? a.bp.llr_t + (size_t)tile * (size_t)n * LDPC_WAVE : a.bp.A, want_llr ? (unsigned)n : 0u);
+        const MsgBuf Pt = make_msgbuf(RP ? const_cast<double *>(a.llr0_t) + (size_t)tile * (size_t)n * LDPC_WAVE : a.bp.A, RP ? (unsigned)n : 0u);
         const int j0 = blockIdx.x * 64 + wave * 16;
         for (int j = j0; j < j0 + 16 && j < n; ++j) {
             if (lane == 0) {
@@ -261,7 +270,7 @@ __global__ void __launch_bounds__(256) bp_spread_finish_kernel(const SpreadArgs 
                 dec[j] = d;
             }
             if (newly && !last && want_llr && !each) {  // (at the last iteration, or under llr_each, the bit pass has stored the posterior already)
-                double temp = a.bp.llr0[j];
+                double temp = RP ? Pt.ld(l8, j) : a.bp.llr0[j];
                 for (int p = a.bp.col_ptr[j]; p < a.bp.col_ptr[j + 1]; ++p) temp += Ct.ld(l8, a.bp.csc_edge[p]);
                 if (mine) Lt.st(l8, j, temp);
             }

@@ -73,9 +73,55 @@ int ldpc_hip_bp_decode_batch_async(ldpc_hip_bp *h, const uint8_t *synd, int64_t 
     return mark_queued(h, decode_device(h, synd, batch, decoding, llr, iters, conv));
 }
 
-// osd: -1 BP only, 0 BP + OSD-0, 1 BP + the handle's osd_method / osd_order
+// osd: -1 BP only, 0 BP + OSD-0, 1 BP + the handle's osd_method / osd_order; probs: row priors [batch][n] (host or device) or NULL
 static int decode_batch_staged(ldpc_hip_bp *h, int osd, const uint8_t *synd, int64_t batch, uint8_t *decoding,
-                               double *llr, int32_t *iters, uint8_t *conv);
+                               double *llr, int32_t *iters, uint8_t *conv, const double *probs = nullptr);
+
+// ---- row priors: every syndrome decoded with its own channel probabilities ---------------------------------------------------------
+// what the handle is set up for that such a decode cannot do (decode_device would refuse the schedule too: this says so before anything is staged)
+static int row_priors_refusal(const ldpc_hip_bp *h) {
+    if (h->schedule != 1 || h->random_serial)
+        return fail(LDPC_HIP_ERR_UNSUPPORTED, "per-row channel probabilities: the serial schedules read the handle's priors only (parallel schedule required)");
+    return LDPC_HIP_OK;
+}
+
+int ldpc_hip_bp_decode_batch_priors(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr,
+                                    int32_t *iters, uint8_t *conv, const double *channel_probs) {
+    if (h && batch > 0 && !channel_probs) return fail(LDPC_HIP_ERR_INVALID, "channel_probs must not be NULL");
+    return decode_batch_staged(h, -1, synd, batch, decoding, llr, iters, conv, channel_probs);
+}
+
+int ldpc_hip_bposd0_decode_batch_priors(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr,
+                                        int32_t *iters, uint8_t *conv, const double *channel_probs) {
+    if (h && batch > 0 && !channel_probs) return fail(LDPC_HIP_ERR_INVALID, "channel_probs must not be NULL");
+    return decode_batch_staged(h, 0, synd, batch, decoding, llr, iters, conv, channel_probs);
+}
+
+static int decode_priors_async(ldpc_hip_bp *h, bool osd0, const uint8_t *synd, const double *channel_probs, int64_t batch, uint8_t *decoding,
+                               double *llr, int32_t *iters, uint8_t *conv) {
+    if (!h) return fail(LDPC_HIP_ERR_INVALID, "null handle");
+    if (batch < 0) return fail(LDPC_HIP_ERR_INVALID, "negative batch");
+    if (batch == 0) return LDPC_HIP_OK;
+    if (!synd || !decoding || !channel_probs) return fail(LDPC_HIP_ERR_INVALID, "syndromes, channel_probs and decoding must not be NULL");
+    if (batch > (1ll << 40)) return fail(LDPC_HIP_ERR_INVALID, "batch too large");
+    int rc;
+    if ((rc = row_priors_refusal(h))) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    h->row_probs = channel_probs;
+    rc = osd0 ? bposd_device(h, 1, 0, synd, batch, decoding, llr, iters, conv) : decode_device(h, synd, batch, decoding, llr, iters, conv);
+    h->row_probs = nullptr;
+    return mark_queued(h, rc);
+}
+
+int ldpc_hip_bp_decode_batch_priors_async(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr,
+                                          int32_t *iters, uint8_t *conv, const double *channel_probs) {
+    return decode_priors_async(h, false, synd, channel_probs, batch, decoding, llr, iters, conv);
+}
+
+int ldpc_hip_bposd0_decode_batch_priors_async(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr,
+                                              int32_t *iters, uint8_t *conv, const double *channel_probs) {
+    return decode_priors_async(h, true, synd, channel_probs, batch, decoding, llr, iters, conv);
+}
 
 int ldpc_hip_bp_decode_batch(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding,
                              double *llr, int32_t *iters, uint8_t *conv) {
@@ -289,11 +335,12 @@ static int decode_batch_pipelined(ldpc_hip_bp *h, const uint8_t *synd, int64_t b
 }
 
 static int decode_batch_staged(ldpc_hip_bp *h, int osd, const uint8_t *synd, int64_t batch, uint8_t *decoding,
-                               double *llr, int32_t *iters, uint8_t *conv) {
+                               double *llr, int32_t *iters, uint8_t *conv, const double *probs) {
     if (!h) return fail(LDPC_HIP_ERR_INVALID, "null handle");
     if (batch < 0) return fail(LDPC_HIP_ERR_INVALID, "negative batch");
     if (batch == 0) return LDPC_HIP_OK;
     if (!synd || !decoding) return fail(LDPC_HIP_ERR_INVALID, "syndromes and decoding must not be NULL");
+    if (probs) { const int refused = row_priors_refusal(h); if (refused) return refused; }
     HIPCHK(hipSetDevice(h->device));
     const size_t B = (size_t)batch, m = (size_t)h->m, n = (size_t)h->n;
     const uint8_t *d_synd = synd;
@@ -309,7 +356,8 @@ static int decode_batch_staged(ldpc_hip_bp *h, int osd, const uint8_t *synd, int
     // and their completion cost more than the kernels.  The kernels work in a host-mapped block instead.
     auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const size_t o_dec = up16(B * m), o_llr = o_dec + up16(B * n), o_it = o_llr + up16(B * n * 8), o_cv = o_it + up16(B * 4), pin_need = o_cv + up16(B);
-    if (h_synd && h_dec && (!llr || h_llr) && (!iters || h_it) && (!conv || h_cv) && pin_need <= ldpc_hip_bp::PIN_MAIL) {
+    // (row priors take the one-shot path below: their probabilities are staged like the syndromes)
+    if (!probs && h_synd && h_dec && (!llr || h_llr) && (!iters || h_it) && (!conv || h_cv) && pin_need <= ldpc_hip_bp::PIN_MAIL) {
         if (!h->pin_host) {
             if (hipHostMalloc((void **)&h->pin_host, ldpc_hip_bp::PIN_BYTES, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
                 hipHostGetDevicePointer((void **)&h->pin_dev, h->pin_host, 0) != hipSuccess) {
@@ -351,7 +399,7 @@ static int decode_batch_staged(ldpc_hip_bp *h, int osd, const uint8_t *synd, int
         }
     }
     // everything on the host, BP only, rows independent of one another, and enough of them for several chunks: pipelined
-    if (h_synd && h_dec && (!llr || h_llr) && (!iters || h_it) && (!conv || h_cv) && osd < 0 && !h->random_serial && h->schedule != 2 &&
+    if (!probs && h_synd && h_dec && (!llr || h_llr) && (!iters || h_it) && (!conv || h_cv) && osd < 0 && !h->random_serial && h->schedule != 2 &&
         !h->on("NO_HOST_PIPELINE")) {
         // chunk: ~256 MiB of staged results, between 1 024 and 16 384 rows (whole tiles), or what LDPC_HIP_HOST_CHUNK_ROWS says; log-ratios
         // that go straight into page-locked memory of the caller's (decode_batch_pipelined) are not staged and do not count
@@ -376,9 +424,21 @@ static int decode_batch_staged(ldpc_hip_bp *h, int osd, const uint8_t *synd, int
     if (h_llr) { if ((rc = h->st_llr.ensure(B * n * 8 ? B * n * 8 : 1))) return rc; d_llr = (double *)h->st_llr.p; }
     if (h_it) { if ((rc = h->st_iters.ensure(B * 4))) return rc; d_it = (int32_t *)h->st_iters.p; }
     if (h_cv) { if ((rc = h->st_conv.ensure(B))) return rc; d_cv = (uint8_t *)h->st_conv.p; }
+    const double *d_probs = probs;
+    if (probs && !is_device_ptr(probs)) {  // a host array is looked at before it goes over (a device array is the caller's word)
+        for (size_t q = 0; q < B * n; ++q)
+            if (!(probs[q] >= 0.0 && probs[q] <= 1.0))
+                return fail(LDPC_HIP_ERR_INVALID, "channel_probs[%zu][%zu] = %g is not a probability", q / n, q % n, probs[q]);
+        if ((rc = h->st_probs.ensure(B * n * 8 ? B * n * 8 : 1))) return rc;
+        HIPCHK(hipMemcpyAsync(h->st_probs.p, probs, B * n * 8, hipMemcpyHostToDevice, h->stream));
+        d_probs = (const double *)h->st_probs.p;
+    }
 
-    if ((rc = osd >= 0 ? bposd_device(h, osd ? h->osd_method : 1, osd ? h->osd_order : 0, d_synd, batch, d_dec, d_llr, d_it, d_cv)
-                       : decode_device(h, d_synd, batch, d_dec, d_llr, d_it, d_cv))) return rc;
+    h->row_probs = d_probs;
+    rc = osd >= 0 ? bposd_device(h, osd ? h->osd_method : 1, osd ? h->osd_order : 0, d_synd, batch, d_dec, d_llr, d_it, d_cv)
+                  : decode_device(h, d_synd, batch, d_dec, d_llr, d_it, d_cv);
+    h->row_probs = nullptr;
+    if (rc) return rc;
 
     if (h_dec) HIPCHK(hipMemcpyAsync(decoding, d_dec, B * n, hipMemcpyDeviceToHost, h->stream));
     if (h_llr) HIPCHK(hipMemcpyAsync(llr, d_llr, B * n * 8, hipMemcpyDeviceToHost, h->stream));

@@ -239,6 +239,11 @@ struct ldpc_hip_bp {
     DeviceBuf b8_in, b8_out, b8_synd, b8_dec, obs_row_ptr, obs_col_idx;  // bit-packed shot I/O and the observables matrix
     int32_t obs_k = -1;                                              // rows of the observables matrix (-1: not set)
     int64_t max_chunk_tiles = 0;                                     // 0 = decide from free memory
+    // Row priors (ldpc_hip_*_decode_batch_priors): the call's [batch][n] channel probabilities on the device while it runs, nullptr
+    // otherwise -- decode_device and decode_onchip look here, nobody else; the handle's own channel_probs / d_llr0 are not touched.
+    const double *row_probs = nullptr;
+    DeviceBuf rowp_llr;  // their log-ratios in tile layout [tiles of a chunk][n][64] (io_kernels.h: row_priors_kernel)
+    DeviceBuf st_probs;  // staging for a host pointer
 };
 
 // h->counter: work_pool_bytes() of work counters for the on-chip BP kernels, then OSD_COUNTER_BYTES for BP + OSD -- {listed, next} of the first

@@ -4,11 +4,10 @@
 
 
 // LDS bytes of the on-chip kernel for `slots` resident syndromes; 0 if the code is too large for it
-static size_t small_lds_bytes(const ldpc_hip_bp *h, int slots) {
+static size_t small_lds_bytes(const ldpc_hip_bp *h, int slots, bool rp = false) {
     size_t fixed = 256 * 8 + (size_t)h->n * 8 + ((size_t)h->m + 1 + h->nnz + h->n + 1 + h->nnz) * 4;
     fixed = (fixed + 15) & ~(size_t)15;
-    const size_t per_slot = ((size_t)h->nnz * 16 + (size_t)h->n * 9 + (size_t)h->m + 15) & ~(size_t)15;
-    return fixed + per_slot * (size_t)slots;
+    return fixed + small_slot_bytes(h->m, h->n, h->nnz, rp) * (size_t)slots;
 }
 
 // On-chip variant (bp_small_kernel): chosen automatically when four resident syndromes per workgroup still
@@ -26,8 +25,18 @@ static int decode_small(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint
     a.llr0 = h->d_llr0;
     a.synd = synd; a.decoding = decoding; a.llr = llr; a.iters = iters; a.conv = conv;
     a.next = (unsigned long long *)h->counter.p;
-    void (*kern)(const SmallArgs) = with_method_math(h, [](auto M, auto F) { return &bp_small_kernel<M, F>; });
-    const size_t dyn = small_lds_bytes(h, slots);
+    const bool rp = h->row_probs != nullptr;
+    if (rp) {  // every syndrome's own priors, whole batch (a slot reads the lane of the syndrome it holds)
+        const int64_t tiles = (batch + LDPC_WAVE - 1) / LDPC_WAVE;
+        if ((rc = h->rowp_llr.ensure(sizeof(double) * (size_t)h->n * LDPC_WAVE * (size_t)tiles))) return rc;
+        const dim3 gp((unsigned)((h->n + LDPC_WAVE - 1) / LDPC_WAVE), (unsigned)(tiles < 32768 ? tiles : 32768));
+        hipLaunchKernelGGL(row_priors_kernel, gp, dim3(256), 0, h->stream, h->row_probs, batch, h->n, (const double *)h->d_llr0, (double *)h->rowp_llr.p);
+        HIPCHK(hipGetLastError());
+        a.llr0_t = (const double *)h->rowp_llr.p;
+    }
+    void (*kern)(const SmallArgs) = rp ? with_method_math(h, [](auto M, auto F) { return &bp_small_kernel<M, F, true>; })
+                                       : with_method_math(h, [](auto M, auto F) { return &bp_small_kernel<M, F>; });
+    const size_t dyn = small_lds_bytes(h, slots, rp);
     if (dyn > 48u * 1024u)
         HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
     // persistent workgroups: enough to fill the chip, never more than there are syndromes to hand out
@@ -575,30 +584,35 @@ static int decode_edge8(ldpc_hip_bp *h, const Edge8Plan &p, const uint8_t *synd,
 }
 
 // Which on-chip kernel (if any) takes this batch: called by decode_device (host_stream.h) before it falls back to the streamed tiles.
+// Row priors (h->row_probs): a code that one of these kernels takes goes to the SLOT kernel, the one that reads every syndrome's own priors
+// (bp_small_kernel<., ., RP>) -- with as many slots as fit -- and to the per-pass kernels (took = false) if not even one slot fits.
 int decode_onchip(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv, bool *took) {
     *took = false;
+    const bool rp = h->row_probs != nullptr;
     if (h->small_mode != 0 && h->m > 0 && h->n > 0 && h->nnz > 0 && (int64_t)h->nnz * 16 < (1 << 22) && batch < (1ll << 30)) {  // (32-bit syndrome indices in the work pools)
         // small code: keep the messages on chip.  Bounded degrees: one wavefront per syndrome (bp_wave_kernel).
         // Otherwise the slot kernel -- auto: the most resident syndromes (<= 4) per workgroup that still leave
         // four workgroups per CU (<= 39.5 KiB each); forced: whatever fits in 150 KiB
         if (h->small_mode < 2 || h->small_mode == 6) {  // (mode 6: as -1 wherever the lane = edge variants do not apply) product-sum: one lane per entry keeps the lanes busy with transcendentals
             const WavePsPlan pp = plan_wave_ps(h, h->small_mode == 1, llr != nullptr, batch);
-            if (pp.waves) { *took = true; return decode_wave_ps(h, pp, synd, batch, decoding, llr, iters, conv); }
+            if (pp.waves) { *took = true; if (!rp) return decode_wave_ps(h, pp, synd, batch, decoding, llr, iters, conv); }
         }
-        if (h->small_mode == -1 || h->small_mode == 1 || h->small_mode == 6) {  // min-sum on the surface-code family: lane = edge
+        if (!*took && (h->small_mode == -1 || h->small_mode == 1 || h->small_mode == 6)) {  // min-sum on the surface-code family: lane = edge
             const EdgePlan ep = plan_edge(h);
-            if (ep.rounds) { *took = true; return decode_edge(h, ep, synd, batch, decoding, llr, iters, conv); }
+            if (ep.rounds) { *took = true; if (!rp) return decode_edge(h, ep, synd, batch, decoding, llr, iters, conv); }
             const Edge8Plan e8 = plan_edge8(h);  // heavier nodes (rows <= 8, columns <= 4): rows in 8-lane groups
-            if (e8.rounds) { *took = true; return decode_edge8(h, e8, synd, batch, decoding, llr, iters, conv); }
+            if (!*took && e8.rounds) { *took = true; if (!rp) return decode_edge8(h, e8, synd, batch, decoding, llr, iters, conv); }
         }
-        if (h->small_mode != 2) {
+        if (!*took && h->small_mode != 2) {
             const WavePlan wp = plan_wave(h, h->small_mode == 1 || (h->small_mode >= 3 && h->small_mode != 6), llr != nullptr, batch);
-            if (wp.waves) { *took = true; return decode_wave(h, wp, synd, batch, decoding, llr, iters, conv); }
+            if (wp.waves) { *took = true; if (!rp) return decode_wave(h, wp, synd, batch, decoding, llr, iters, conv); }
         }
         int slots = 0;
-        const size_t budget = (h->small_mode == 1 || h->small_mode == 2) ? 150u * 1024u : 39u * 1024u + 512u;
+        // (*took here: row priors, and another on-chip kernel would have taken the code -- whatever fits, as when the slot kernel is forced)
+        const size_t budget = (h->small_mode == 1 || h->small_mode == 2 || *took) ? 150u * 1024u : 39u * 1024u + 512u;
+        *took = false;
         for (int sl = 4; sl >= 1 && !slots; --sl)
-            if (small_lds_bytes(h, sl) <= budget) slots = sl;
+            if (small_lds_bytes(h, sl, rp) <= budget) slots = sl;
         if (slots) { *took = true; return decode_small(h, synd, batch, decoding, llr, iters, conv, slots); }
     }
     return LDPC_HIP_OK;

@@ -276,7 +276,9 @@ int bposd_device(ldpc_hip_bp *h, int osd_method, int osd_order, const uint8_t *s
     if ((rc = h->osd_list.ensure((B ? B : 1) * sizeof(int32_t)))) return rc;
     if ((rc = h->osd_status.ensure(B ? B : 1))) return rc;
     unsigned *const osd_ctr = osd_counter_ptr(h);
-    h->osd_hook = {(int32_t *)h->osd_list.p, osd_ctr, (uint8_t *)h->osd_status.p, !h->on("OSD_COLLECT_AFTER"), false};
+    // (row priors: the kernels that take them have no hand-over of their own -- the rows are collected afterwards, as under OSD_COLLECT_AFTER;
+    //  OSD-0 itself orders the columns by BP's posteriors, which are per row already: it needs no prior)
+    h->osd_hook = {(int32_t *)h->osd_list.p, osd_ctr, (uint8_t *)h->osd_status.p, !h->on("OSD_COLLECT_AFTER") && !h->row_probs, false};
     rc = decode_device(h, synd, batch, decoding, llr, iters, conv);
     h->osd_hook.armed = false;
     if (rc) return rc;

@@ -303,7 +303,7 @@ int64_t ldpc_hip_bp_workspace_bytes(const ldpc_hip_bp *h, int64_t batch) {
     if (!h || batch < 0) return -1;
     const int64_t tiles = (batch + LDPC_WAVE - 1) / LDPC_WAVE;
     return tiles * (2ll * 8 * h->nnz * LDPC_WAVE + 2ll * 8 * h->m + 8 + 8ll * h->n +
-                    8ll * h->n * LDPC_WAVE);
+                    8ll * h->n * LDPC_WAVE /* log-ratios */ + 8ll * h->n * LDPC_WAVE /* row priors (ldpc_hip_*_decode_batch_priors) */);
 }
 
 int ldpc_hip_bp_last_kernel_ms(ldpc_hip_bp *h, float *ms) {

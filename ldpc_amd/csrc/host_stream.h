@@ -8,6 +8,10 @@ template <bool LOOP>
 static void pick_spread(const ldpc_hip_bp *h, bool nt, spread_kernel_t &kc, spread_kernel_t &kb) {
     with_method_math(h, [&](auto M, auto F) { pick_spread_m<M, F, LOOP>(h->max_row_deg, h->max_col_deg, nt, kc, kb); });
 }
+// ... with every lane's own prior (row priors: SpreadArgs::llr0_t; no LOOP forms -- such a decode is never a compacted second pass)
+static void pick_spread_row_priors(const ldpc_hip_bp *h, bool nt, spread_kernel_t &kc, spread_kernel_t &kb) {
+    with_method_math(h, [&](auto M, auto F) { pick_spread_m<M, F, false, true>(h->max_row_deg, h->max_col_deg, nt, kc, kb); });
+}
 
 // Item tables of the variable-degree ring (bp_stream_kernel.h, LDPC_RING_VAR): the check rows, and the pairs of bit columns, in the
 // order the wavefronts take them -- wavefront w of a workgroup of W takes entries w, w + W, w + 2 W, ...  Blocks of W items come
@@ -55,6 +59,11 @@ int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
     const int64_t tiles_total = (batch + LDPC_WAVE - 1) / LDPC_WAVE;
     if (tiles_total == 0) return LDPC_HIP_OK;
     if (!h->cont_A) h->timed_prev = h->timed_prev_mid = false;  // (a second pass keeps the first pass's events: ldpc_hip_bp_last_kernel_ms adds them)
+    // Row priors (ldpc_hip_*_decode_batch_priors): every row is decoded with its own channel probabilities, h->row_probs [batch][n].  Two kernel
+    // families read them: the slot kernel (decode_onchip sends there whatever an on-chip kernel would take) and the per-pass kernels, which
+    // such a decode runs from its first iteration whatever the batch size -- no persistent kernel, no edge0 table, no repacking, no hand-off.
+    const bool rp = h->row_probs != nullptr;
+    if (rp && h->schedule != 1) return fail(LDPC_HIP_ERR_UNSUPPORTED, "per-row channel probabilities: the serial schedules read the handle's priors only (parallel schedule required)");
     if (h->schedule == 0 || h->schedule == 2) return decode_serial(h, synd, batch, decoding, llr, iters, conv);
     {   // small code: the kernels that keep a syndrome's messages on chip (tu_onchip.hip), where one applies
         bool took = false;
@@ -63,7 +72,7 @@ int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
     }
     // streamed tiles: a tile runs until the slowest of its 64 syndromes is done.  Where most syndromes converge early
     // a short first pass + a second pass over the compacted rest does the same work in a fraction of the tile-iterations
-    if (may_repack && h->repack_iters != 0 && h->max_iter >= 8 && tiles_total >= 512 && h->m > 0 && h->n > 0)
+    if (may_repack && !rp && h->repack_iters != 0 && h->max_iter >= 8 && tiles_total >= 512 && h->m > 0 && h->n > 0)
         return decode_stream_repacked(h, synd, batch, decoding, llr, iters, conv);
     const size_t per_tile_msg = sizeof(double) * (size_t)(h->nnz ? h->nnz : 1) * LDPC_WAVE;
     const size_t per_tile_llr = llr ? sizeof(double) * (size_t)(h->n ? h->n : 1) * LDPC_WAVE : 0;
@@ -76,7 +85,7 @@ int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
         HIPCHK(hipMemGetInfo(&free_b, &total_b));
         const size_t have = h->msgA.cap + h->msgC.cap + h->llr_t.cap;
         const size_t budget = (size_t)((double)(free_b + have) * 0.85);
-        const size_t per_tile = 2 * per_tile_msg + per_tile_llr + 16 * (size_t)(h->m + h->n + 1);
+        const size_t per_tile = 2 * per_tile_msg + per_tile_llr + 16 * (size_t)(h->m + h->n + 1) + (rp ? sizeof(double) * (size_t)h->n * LDPC_WAVE : 0);
         int64_t fit = (int64_t)(budget / (per_tile ? per_tile : 1));
         if (fit < 1) return fail(LDPC_HIP_ERR_NOMEM, "not enough device memory for one 64-syndrome tile");
         if (chunk > fit) chunk = fit;
@@ -90,6 +99,7 @@ int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
     if ((rc = h->dec.ensure(sizeof(uint64_t) * (size_t)(h->n ? h->n : 1) * (size_t)chunk))) return rc;
     if ((rc = h->dcur.ensure(sizeof(uint64_t) * (size_t)(h->n ? h->n : 1) * (size_t)chunk))) return rc;
     if (llr && (rc = h->llr_t.ensure(per_tile_llr * (size_t)chunk))) return rc;
+    if (rp && (rc = h->rowp_llr.ensure(sizeof(double) * (size_t)(h->n ? h->n : 1) * LDPC_WAVE * (size_t)chunk))) return rc;  // (per chunk, like the messages)
     h->last_chunk_tiles = chunk;
     if ((rc = h->tile_state.ensure(sizeof(TileState) * (size_t)chunk))) return rc;
     if ((rc = h->handoff_list.ensure(sizeof(int32_t) * (size_t)chunk))) return rc;
@@ -213,11 +223,17 @@ int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
         sa.bp = a;
         sa.host_flag = h->d_flag;
         sa.seq = ++h->flag_seq ? h->flag_seq : ++h->flag_seq;  // never 0 (the word's initial value)
+        if (rp && h->n > 0) {  // this chunk's rows [b0, b0 + nb) of the probabilities -> priors in the layout of its tiles (inside the timed region)
+            const dim3 gp((unsigned)((h->n + LDPC_WAVE - 1) / LDPC_WAVE), (unsigned)tiles);
+            hipLaunchKernelGGL(row_priors_kernel, gp, dim3(256), 0, st, h->row_probs + (size_t)b0 * (size_t)h->n, nb, h->n, (const double *)h->d_llr0, (double *)h->rowp_llr.p);
+            HIPCHK(hipGetLastError());
+            sa.llr0_t = (const double *)h->rowp_llr.p;
+        }
         // per-pass rounds: `grid_tiles` workgroup rows; how many of them have a tile is known to the host only when the
         // batch skips the persistent kernel (sa.n_tiles >= 0), otherwise the kernels read it from counters[1]
         unsigned grid_tiles = 0;
         int first_round = 1;  // a tile parked by the persistent kernel has completed >= 1 iteration
-        if (handoff > 0 && tiles <= handoff && h->max_iter - a.it_start > 1 && !rows_dev) {
+        if (rp || (handoff > 0 && tiles <= handoff && h->max_iter - a.it_start > 1 && !rows_dev)) {
             // so few tiles that they would each sit on one compute unit: per-pass launches from the start
             grid_tiles = (unsigned)tiles;
             sa.n_tiles = (int32_t)tiles;
@@ -229,7 +245,9 @@ int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
             first_round = 0;
             hipLaunchKernelGGL(bp_spread_state_init_kernel, dim3((grid_tiles + 255) / 256), dim3(256), 0, st, sa);
             const dim3 gi((unsigned)(h->nnz ? (h->nnz + 63) / 64 : 1), grid_tiles);  // (a grid dimension must not be 0: empty matrices)
-            if (a.it_start == 0)  // (else the message state is there already)
+            if (rp)
+                with_method_math(h, [&](auto M, auto F) { hipLaunchKernelGGL((bp_spread_init_kernel<M, F, true>), gi, dim3(256), 0, st, sa); });
+            else if (a.it_start == 0)  // (else the message state is there already)
                 with_method_math(h, [&](auto M, auto F) { hipLaunchKernelGGL((bp_spread_init_kernel<M, F>), gi, dim3(256), 0, st, sa); });
             HIPCHK(hipGetLastError());
         } else {
@@ -262,6 +280,8 @@ int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
             const bool nt = (double)grid_tiles * 2.0 * (double)per_tile_msg > 384.0 * 1024.0 * 1024.0;
             pick_spread<false>(h, nt, kc, kb);
             pick_spread<true>(h, nt, kcl, kbl);
+            if (rp) pick_spread_row_priors(h, nt, kc, kb);
+            const auto k_finish = rp ? bp_spread_finish_kernel<false, true> : bp_spread_finish_kernel<false>;
             const unsigned per_wg = 4u * (unsigned)sa.nodes;
             const dim3 gc((unsigned)(h->m ? (h->m + per_wg - 1) / per_wg : 1), grid_tiles), gb((unsigned)(h->n ? (h->n + per_wg - 1) / per_wg : 1), grid_tiles);
             const dim3 gs((unsigned)(h->m ? (h->m + 255) / 256 : 1), grid_tiles), gf((unsigned)(h->n ? (h->n + 63) / 64 : 1), grid_tiles);
@@ -287,7 +307,7 @@ int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
                     hipLaunchKernelGGL(kc, gc, dim3(256), 0, st, sa);
                     hipLaunchKernelGGL(kb, gb, dim3(256), 0, st, sa);
                     hipLaunchKernelGGL(bp_spread_synd_kernel<false>, gs, dim3(256), 0, st, sa);
-                    hipLaunchKernelGGL(bp_spread_finish_kernel<false>, gf, dim3(256), 0, st, sa);
+                    hipLaunchKernelGGL(k_finish, gf, dim3(256), 0, st, sa);
                 } else {
                     SpreadArgs sb = sa;
                     sb.slot0 = 32;

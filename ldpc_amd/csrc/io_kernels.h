@@ -81,6 +81,38 @@ LDPC_IO_KERNEL void __launch_bounds__(256) transpose_llr_kernel(const double *__
     }
 }
 
+// Row priors: channel_probs [batch][n] f64 (row b = the probabilities syndrome b is decoded with) -> llr0_t [tiles][n][64] f64, the
+// layout of the messages, as log((1 - p) / p): the operations of upload_priors (host_handle.h; bp.hpp:150-151) on the device -- an IEEE
+// division and the bit-exact twin of the host's log (bp_math.h) -- so that row b holds what `update_channel_probs(p[b])`
+// (_bp_decoder.pyx:222) would have left in initial_log_prob_ratios.  p = 0, 1, 0.5 give +inf, -inf, +0.0 as there.  Lanes past the end
+// of the batch get the handle's own priors `llr0`.  64 x 64 tiles through LDS; grid (ceil(n / 64), tiles or fewer: the kernel loops).
+LDPC_IO_KERNEL void __launch_bounds__(256) row_priors_kernel(const double *__restrict__ probs, int64_t batch, int n,
+                                                             const double *__restrict__ llr0, double *__restrict__ out) {
+    __shared__ double tilebuf[LDPC_WAVE][LDPC_WAVE + 1];
+    __shared__ __attribute__((aligned(16))) double log_tab[256];
+    log_tab[threadIdx.x] = ldpc_math::k_log_tab[threadIdx.x];
+    __syncthreads();
+    const int j0 = blockIdx.x * LDPC_WAVE;
+    const int lo = threadIdx.x & 63, hi = threadIdx.x >> 6;
+    const bool col = j0 + lo < n;
+    for (int64_t tile = blockIdx.y; tile * LDPC_WAVE < batch; tile += gridDim.y) {
+        for (int r = 0; r < 16; ++r) {
+            const int l = r * 4 + hi;  // (wave-uniform: a wavefront converts 64 columns of one row)
+            const int64_t b = tile * LDPC_WAVE + l;
+            const bool own = b < batch && col;
+            const double p = own ? probs[(size_t)b * n + j0 + lo] : 0.5;
+            const double v = ldpc_math::log_libm((1.0 - p) / p, log_tab);
+            tilebuf[lo][l] = own ? v : col ? llr0[j0 + lo] : 0.0;
+        }
+        __syncthreads();
+        for (int r = 0; r < 16; ++r) {
+            const int jj = r * 4 + hi;
+            if (j0 + jj < n) out[((size_t)tile * n + j0 + jj) * LDPC_WAVE + lo] = tilebuf[jj][lo];
+        }
+        __syncthreads();  // (the buffer is refilled for the next tile)
+    }
+}
+
 // GF2Sparse::mulvec over a batch (gf2sparse.hpp:177-214): one thread per (vector, check)
 LDPC_IO_KERNEL void gf2_mulvec_kernel(const int32_t *__restrict__ row_ptr,
                                   const int32_t *__restrict__ col_idx, int m, int n,

@@ -189,8 +189,36 @@ class HipBpEngine:
         return dc / dt * after[2] / 1e9 if dt > 0 and dc > 0 else None
 
     # -- data path --------------------------------------------------------------------------------
-    def decode_batch(self, syndromes, want_llr=True, out=None, asynchronous=False, osd0=False, osd=False, llr_out=None):
+    def _row_probs(self, syndromes, channel_probs):
+        """``channel_probs`` of ``decode_batch`` as a contiguous ``(B, n)`` float64 array in the same place as ``syndromes``, checked."""
+        b = int(syndromes.shape[0])
+        if _is_torch(syndromes) != _is_torch(channel_probs):
+            raise ValueError("channel_probs must be in the same place as the syndromes: both NumPy arrays or both CUDA tensors")
+        if _is_torch(channel_probs):
+            import torch
+            p = channel_probs
+            if p.dtype != torch.float64 or p.dim() != 2 or tuple(p.shape) != (b, self.n) or not p.is_cuda:
+                raise ValueError(f"channel_probs must be a CUDA float64 tensor of shape ({b}, {self.n})")
+            if p.device != syndromes.device:
+                raise ValueError("channel_probs must be in the same place as the syndromes: both on the same GPU")
+            p = p.contiguous()
+            bad = int(torch.count_nonzero(~((p >= 0) & (p <= 1)))) if p.numel() else 0
+        else:
+            p = np.asarray(channel_probs)
+            if p.ndim != 2 or p.shape != (b, self.n) or p.dtype != np.float64:
+                raise ValueError(f"channel_probs must be a float64 array of shape ({b}, {self.n})")
+            p = np.ascontiguousarray(p)
+            bad = int(np.count_nonzero(~((p >= 0) & (p <= 1))))
+        if bad:
+            raise ValueError(f"channel_probs must be probabilities: {bad} values are outside [0, 1] or NaN")
+        return p
+
+    def decode_batch(self, syndromes, want_llr=True, out=None, asynchronous=False, osd0=False, osd=False, llr_out=None, channel_probs=None):
         """Decode ``(B, m)`` uint8 syndromes.  Returns ``(decoding, llr|None, iterations, converge)``.
+
+        ``channel_probs``: ``(B, n)`` float64, in the same place as the syndromes -- row b is decoded with ``channel_probs[b]`` instead of the
+        handle's probabilities, which stay as they are (``ldpc_hip_bp_decode_batch_priors`` / ``ldpc_hip_bposd0_decode_batch_priors``:
+        BP or ``osd0``, parallel schedule).
 
         ``osd0=True`` runs BP + OSD-0 (``ldpc_hip_bposd0_decode_batch``): ``decoding`` holds the OSD-0 solution for
         rows BP left unconverged; llr / iterations / converge remain BP's.  ``osd=True`` does the same with the
@@ -215,6 +243,16 @@ class HipBpEngine:
                 llr = torch.empty((b, self.n), dtype=torch.float64, device=s.device) if want_llr else None
                 it = torch.empty((b,), dtype=torch.int32, device=s.device)
                 cv = torch.empty((b,), dtype=torch.uint8, device=s.device)
+            if channel_probs is not None:
+                if osd:
+                    raise NotImplementedError("channel_probs: BP or BP + OSD_0 only (osd0=True); OSD_E / OSD_CS weigh their candidates by log(1 / p) "
+                                              "of the handle's own probabilities (osd.hpp:134)")
+                p = self._row_probs(s, channel_probs)
+                fn = getattr(self._lib, ("ldpc_hip_bposd0" if osd0 else "ldpc_hip_bp") + "_decode_batch_priors" + ("_async" if asynchronous else ""))
+                _lib.check(fn(self._h, s.data_ptr(), b, dec.data_ptr(), llr.data_ptr() if llr is not None else None,
+                              it.data_ptr(), cv.data_ptr(), p.data_ptr()))
+                self._row_probs_alive = p  # (an asynchronous call may still read it)
+                return dec, llr, it, cv
             if osd:
                 fn = self._lib.ldpc_hip_bposd_decode_batch_async if asynchronous else self._lib.ldpc_hip_bposd_decode_batch
             elif osd0:
@@ -237,6 +275,15 @@ class HipBpEngine:
             llr = np.empty((b, self.n), np.float64) if want_llr else None
         it = np.empty(b, np.int32)
         cv = np.empty(b, np.uint8)
+        if channel_probs is not None:
+            if osd:
+                raise NotImplementedError("channel_probs: BP or BP + OSD_0 only (osd0=True); OSD_E / OSD_CS weigh their candidates by log(1 / p) "
+                                          "of the handle's own probabilities (osd.hpp:134)")
+            p = self._row_probs(s, channel_probs)
+            fn = self._lib.ldpc_hip_bposd0_decode_batch_priors if osd0 else self._lib.ldpc_hip_bp_decode_batch_priors
+            _lib.check(fn(self._h, s.ctypes.data, b, dec.ctypes.data, llr.ctypes.data if want_llr else None,
+                          it.ctypes.data, cv.ctypes.data, p.ctypes.data))
+            return dec, llr, it, cv.astype(bool)
         fn = (self._lib.ldpc_hip_bposd_decode_batch if osd else
               self._lib.ldpc_hip_bposd0_decode_batch if osd0 else self._lib.ldpc_hip_bp_decode_batch)
         _lib.check(fn(self._h, s.ctypes.data, b, dec.ctypes.data, llr.ctypes.data if want_llr else None,
@@ -485,8 +532,10 @@ class HipBpMultiEngine:
             sub = next((s_ for s_ in self.subs if s_.device == idx), sub)
         return sub.gen_bsc_syndromes(seed, error_rate, shot0, shots, device=device, want_errors=want_errors)
 
-    def decode_batch(self, syndromes, want_llr=True, out=None, osd0=False, osd=False, asynchronous=False, llr_out=None):
+    def decode_batch(self, syndromes, want_llr=True, out=None, osd0=False, osd=False, asynchronous=False, llr_out=None, channel_probs=None):
         """As ``HipBpEngine.decode_batch`` (always synchronous: the call returns when every GPU has delivered its rows)."""
+        if channel_probs is not None:
+            raise NotImplementedError("channel_probs is not sharded over several GPUs (device_ids=[...]): decode on one GPU")
         with_osd = 1 if osd else (0 if osd0 else -1)
         if _is_torch(syndromes):
             import torch

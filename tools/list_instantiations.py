@@ -13,15 +13,17 @@ RULES = {  # template -> who selects which instantiation
                         "(VAR_RING 1).  Since round 5 a product-sum batch WITHOUT a ring variant skips this kernel unless the caller sets a hand-off threshold: it takes "
                         "bp_spread_* from its first iteration (host_stream.h: per_pass_first)",
     "bp_spread_check_kernel": "host_stream.h pick_spread: <METHOD, MATH, DR in 8/16, NT, LOOP> (NT: tiles in flight outgrow the MALL; LOOP: the slots beyond the first 32 of a compacted list)",
-    "bp_spread_bit_kernel": "host_stream.h pick_spread: <METHOD, MATH, DC in 4/8, NT, LOOP>",
-    "bp_spread_init_kernel": "host_stream.h: batches of <= 256 tiles, and product-sum batches without a ring variant (per-pass kernels from the first iteration)",
+    "bp_spread_bit_kernel": "host_stream.h pick_spread: <METHOD, MATH, DC in 4/8, NT, LOOP, RP> (RP: pick_spread_row_priors -- every lane's own prior, decode_batch(..., channel_probs=P))",
+    "bp_spread_init_kernel": "host_stream.h: batches of <= 256 tiles, and product-sum batches without a ring variant (per-pass kernels from the first iteration); <., ., RP = true>: row priors",
+    "bp_spread_finish_kernel": "host_stream.h: <LOOP, RP> (RP: the posterior it recomputes at a convergence event starts from the lane's own prior)",
+    "row_priors_kernel": "host_stream.h decode_device / host_onchip.h decode_small: channel_probs [B][n] -> log-ratios in tile layout (one copy per translation unit: internal linkage)",
     "bp_edge0_kernel": "host_stream.h: initial edge values of the ring variants",
     "bp_wave_kernel": "host_onchip.h plan_wave / pick_wave: <METHOD, MATH, DR, DC, TEAM> for (4,2) (4,4) (6,3) (8,4) (8,8) and, min-sum only, (16,8); TEAM where LDS leaves "
                       "few wavefronts per CU or the batch is small",
     "bp_wave_ps_kernel": "host_onchip.h plan_wave_ps / pick_wave_ps: product-sum, <MATH, DR, DC, TEAM> for (4,2) (4,4) (6,3) (8,4) (16,8) (32,8)",
     "bp_edge_kernel": "host_onchip.h plan_edge: min-sum, rows <= 4, columns <= 2, R = ceil(4 m / 64) rounds (1 .. 16), UNIFORM = one prior for all columns",
     "bp_edge8_kernel": "host_onchip.h plan_edge8: min-sum, rows <= 8, columns <= 4: <R rounds, DC, UNIFORM>",
-    "bp_small_kernel": "host_onchip.h decode_small: small codes no wavefront kernel takes (rows > 32 or columns > 8)",
+    "bp_small_kernel": "host_onchip.h decode_small: small codes no wavefront kernel takes (rows > 32 or columns > 8); <., ., RP = true>: row priors, every code an on-chip kernel would take",
     "bp_serial_kernel": "host_serial.h pick_serial: serial schedule, one wavefront per tile",
     "bp_serial_level_kernel": "host_serial.h pick_serial_level: serial schedule, level-parallel",
     "bp_serial_stream_kernel": "host_serial.h serial_stream_setup via pick_serial_stream (for decode_serial_streamed / decode_serial_pass): serial schedule on (6,3)-shaped matrices with >= 32 bits a level: <METHOD, MATH, 6, 3, RING 1 (default) / 2>",
