@@ -102,15 +102,6 @@ struct ldpc_hip_bp {
     DeviceBuf d_edge0;       // [n] initial edge values of the streamed kernel (BpArgs::edge0)
     DeviceBuf var_row_items, var_pair_items;  // item tables of the variable-degree ring (BpArgs::row_items, pair_items; host_stream.h: ensure_var_ring_items)
     bool var_items_built = false;
-    // continuation of a first pass (decode_stream_repacked): decode_device takes its message state from here and counts on from cont_it_start
-    double *cont_A = nullptr, *cont_C = nullptr;  // its bit_to_check (compacted) / check_to_bit arrays
-    int32_t cont_it_start = 0;
-    const int32_t *cont_row_map = nullptr;        // its rows in the caller's arrays (BpArgs::row_map)
-    const unsigned *cont_rows_dev = nullptr;      // {rows, tiles} on the device (BpArgs::rows_dev)
-    int64_t cont_late_rows = -1;                  // rows the steering histogram expects to be still running 8 iterations into it (-1: unknown)
-    int64_t cont_grid_tiles = 0;                  // grid.y of its tile-looping kernels (an estimate; they loop)
-    bool keep_state = false;       // this decode_device call is a first pass: its last bit pass must leave the messages behind
-    int64_t last_chunk_tiles = 0;  // tiles per chunk of the last streamed decode (== its tile count: the whole batch's state is resident)
     int edge_rounds = 0;     // rounds the uploaded slot tables of bp_edge_kernel were built for (0: none)
     DeviceBuf e_partner, e_kind, e_scol, e_prior;
     int32_t handoff = -1;    // straggler hand-off threshold in tiles: -1 auto (256), 0 off
@@ -234,13 +225,13 @@ struct ldpc_hip_bp {
     unsigned hist_landed[256] = {};  // the last histogram whose copy was SEEN complete (never waited for)
     bool hist_landed_valid = false;
     int32_t hist_landed_max_iter = 0;
-    int32_t repack_iters = -1;                                      // first-pass iterations: -1 auto (max_iter / 8), 0 = no repacking
+    int32_t repack_iters = -1;                                      // first-pass iterations: -1 auto (stream_first_pass_length: the last histogram decides), 0 = no repacking
     DeviceBuf soft_S, soft_in, soft_out;                             // soft-syndrome decoding: scaled analog syndromes, staging
     DeviceBuf b8_in, b8_out, b8_synd, b8_dec, obs_row_ptr, obs_col_idx;  // bit-packed shot I/O and the observables matrix
     int32_t obs_k = -1;                                              // rows of the observables matrix (-1: not set)
     int64_t max_chunk_tiles = 0;                                     // 0 = decide from free memory
     // Row priors (ldpc_hip_*_decode_batch_priors): the call's [batch][n] channel probabilities on the device while it runs, nullptr
-    // otherwise -- decode_device and decode_onchip look here, nobody else; the handle's own channel_probs / d_llr0 are not touched.
+    // otherwise -- decode_device, the streamed decode (host_stream.h: rp) and decode_onchip look here, nobody else; the handle's own channel_probs / d_llr0 are not touched.
     const double *row_probs = nullptr;
     DeviceBuf rowp_llr;  // their log-ratios in tile layout [tiles of a chunk][n][64] (io_kernels.h: row_priors_kernel)
     DeviceBuf st_probs;  // staging for a host pointer
@@ -313,10 +304,76 @@ static bool is_device_ptr(const void *p) {
     return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
 }
 
+// ---- what the chunked decodes of every schedule share (host_serial.h, host_stream.h) ------------------------------------------------------
+// a kernel that wants more dynamic LDS than the 48 KiB it gets without asking
+template <class Kernel>
+static int set_dynamic_lds(Kernel kern, size_t bytes) {
+    if (bytes > 48u * 1024u) HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    return LDPC_HIP_OK;
+}
+
+// tiles of per_tile bytes that fit into `margin` of the device memory that is free or held already by the buffers they will live in
+static int tiles_that_fit(size_t per_tile, size_t held, double margin, int64_t *fit) {
+    size_t free_b = 0, total_b = 0;
+    HIPCHK(hipMemGetInfo(&free_b, &total_b));
+    *fit = (int64_t)((size_t)((double)(free_b + held) * margin) / (per_tile ? per_tile : 1));
+    return LDPC_HIP_OK;
+}
+
+// tiles per chunk of a decode that takes its batch in pieces: all of them, up to what the caller allows (ldpc_hip_bp_set_tuning), one launch
+// carries (`cap`) and memory holds.  `unit`: what a tile holds 64 of, for the message
+static int chunk_tiles_that_fit(const ldpc_hip_bp *h, int64_t tiles_total, size_t per_tile, size_t held, double margin, int64_t cap, const char *unit, int64_t *chunk) {
+    int64_t fit = 0;
+    int rc;
+    if ((rc = tiles_that_fit(per_tile, held, margin, &fit))) return rc;
+    if (fit < 1) return fail(LDPC_HIP_ERR_NOMEM, "not enough device memory for one 64-%s tile", unit);
+    *chunk = tiles_total;
+    if (h->max_chunk_tiles > 0 && *chunk > h->max_chunk_tiles) *chunk = h->max_chunk_tiles;
+    if (*chunk > cap) *chunk = cap;
+    if (*chunk > fit) *chunk = fit;
+    return LDPC_HIP_OK;
+}
+
+struct ChunkRange { int64_t tiles, b0, nb; };  // a chunk's tiles, its first row and its rows
+static ChunkRange chunk_range(int64_t t0, int64_t chunk, int64_t tiles_total, int64_t batch) {
+    ChunkRange c = {(tiles_total - t0 < chunk) ? tiles_total - t0 : chunk, t0 * LDPC_WAVE, 0};
+    c.nb = (batch - c.b0 < c.tiles * LDPC_WAVE) ? batch - c.b0 : c.tiles * LDPC_WAVE;
+    return c;
+}
+
+// the kernel time of a decode (ldpc_hip_bp_last_kernel_ms) starts over; prev_too: also what a two-pass decode before it left (evp0 / evp1)
+static void reset_timing(ldpc_hip_bp *h, bool prev_too) {
+    h->accumulated_ms = h->accumulated_persistent_ms = 0.f;
+    h->timed = h->timed_mid = false;
+    if (prev_too) h->timed_prev = h->timed_prev_mid = false;
+}
+
+// around a chunk's decode kernels: the chunk before it gives its time to accumulated_ms / accumulated_persistent_ms (its events are used again)
+static int chunk_timing_begin(ldpc_hip_bp *h) {
+    if (h->timed) {
+        float prev = 0.f;
+        HIPCHK(hipEventSynchronize(h->ev1));
+        HIPCHK(hipEventElapsedTime(&prev, h->ev0, h->ev1));
+        h->accumulated_ms += prev;
+        if (h->timed_mid) {  // (the streamed decode: its persistent kernel's share, ev0 .. ev_mid)
+            HIPCHK(hipEventElapsedTime(&prev, h->ev0, h->ev_mid));
+            h->accumulated_persistent_ms += prev;
+        }
+    }
+    h->timed_mid = false;
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    return LDPC_HIP_OK;
+}
+static int chunk_timing_end(ldpc_hip_bp *h) {
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    h->timed = true;
+    HIPCHK(hipGetLastError());
+    return LDPC_HIP_OK;
+}
+
 // ---- what the translation units call in each other (device pointers, on h->stream) -------------------------------------------------
 // tu_stream.hip: the dispatch of a batch to a kernel family, and the streamed kernels themselves
-int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv,
-                  bool may_repack = true);
+int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv);
 // tu_onchip.hip: ONE syndrome in the handle's host-mapped block (already copied in) through the resident workgroup; *took = false: not
 // applicable (then the ordinary path).  resident_retire: the resident workgroup leaves now (destroy, or a change it must not outlive)
 int decode_onchip_resident(ldpc_hip_bp *h, bool want_llr, bool *took);

@@ -3,13 +3,6 @@
 #pragma once
 
 // ---- what the schedules below share -------------------------------------------------------------------------------------------------
-// a kernel that wants more dynamic LDS than the 48 KiB it gets without asking
-template <class Kernel>
-static int set_dynamic_lds(Kernel kern, size_t bytes) {
-    if (bytes > 48u * 1024u) HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    return LDPC_HIP_OK;
-}
-
 // One order cut into levels of mutually check-disjoint POSITIONS (see bp_serial_level_kernel).  The order need not be a permutation -- the
 // reference accepts any n bit numbers, and a caller's serial_schedule_order with repeats is shuffled like any other -- so levels belong to
 // positions.  `bits` [n] gets the order level-major (schedule order inside a level), ptr[l] where level l starts (ptr[0 .. n]: zero behind
@@ -41,64 +34,6 @@ static int level_waves_for(const ldpc_hip_bp *h, double per_level) {
     if (h->serial_kernel != 1 && !(per_level >= 2.0)) return 0;
     const int waves = (int)(per_level + 0.999);
     return waves > 8 ? 8 : waves < 1 ? 1 : waves;
-}
-
-// tiles of per_tile bytes that fit into `margin` of the device memory that is free or held already by the buffers they will live in
-static int tiles_that_fit(size_t per_tile, size_t held, double margin, int64_t *fit) {
-    size_t free_b = 0, total_b = 0;
-    HIPCHK(hipMemGetInfo(&free_b, &total_b));
-    *fit = (int64_t)((size_t)((double)(free_b + held) * margin) / (per_tile ? per_tile : 1));
-    return LDPC_HIP_OK;
-}
-
-// tiles per chunk of a decode that takes its batch in pieces: all of them, up to what the caller allows (ldpc_hip_bp_set_tuning), one launch
-// carries (`cap`) and memory holds.  `unit`: what a tile holds 64 of, for the message
-static int chunk_tiles_that_fit(const ldpc_hip_bp *h, int64_t tiles_total, size_t per_tile, size_t held, double margin, int64_t cap, const char *unit,
-                                int64_t *chunk) {
-    int64_t fit = 0;
-    int rc;
-    if ((rc = tiles_that_fit(per_tile, held, margin, &fit))) return rc;
-    if (fit < 1) return fail(LDPC_HIP_ERR_NOMEM, "not enough device memory for one 64-%s tile", unit);
-    *chunk = tiles_total;
-    if (h->max_chunk_tiles > 0 && *chunk > h->max_chunk_tiles) *chunk = h->max_chunk_tiles;
-    if (*chunk > cap) *chunk = cap;
-    if (*chunk > fit) *chunk = fit;
-    return LDPC_HIP_OK;
-}
-
-struct ChunkRange { int64_t tiles, b0, nb; };  // a chunk's tiles, its first row and its rows
-static ChunkRange chunk_range(int64_t t0, int64_t chunk, int64_t tiles_total, int64_t batch) {
-    ChunkRange c;
-    c.tiles = (tiles_total - t0 < chunk) ? tiles_total - t0 : chunk;
-    c.b0 = t0 * LDPC_WAVE;
-    c.nb = (batch - c.b0 < c.tiles * LDPC_WAVE) ? batch - c.b0 : c.tiles * LDPC_WAVE;
-    return c;
-}
-
-// the kernel time of a decode (ldpc_hip_bp_last_kernel_ms) starts over; prev_too: also what a two-pass decode before it left (evp0 / evp1)
-static void reset_timing(ldpc_hip_bp *h, bool prev_too) {
-    h->accumulated_ms = 0.f;
-    h->accumulated_persistent_ms = 0.f;
-    h->timed = h->timed_mid = false;
-    if (prev_too) h->timed_prev = h->timed_prev_mid = false;
-}
-
-// around a chunk's decode kernel: the chunk before it gives its time to accumulated_ms (its two events are used again)
-static int chunk_timing_begin(ldpc_hip_bp *h) {
-    if (h->timed) {
-        float prev = 0.f;
-        HIPCHK(hipEventSynchronize(h->ev1));
-        HIPCHK(hipEventElapsedTime(&prev, h->ev0, h->ev1));
-        h->accumulated_ms += prev;
-    }
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    return LDPC_HIP_OK;
-}
-static int chunk_timing_end(ldpc_hip_bp *h) {
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    HIPCHK(hipGetLastError());
-    return LDPC_HIP_OK;
 }
 
 // a chunk's packed decisions (h->dec) and tile-major log-ratios (h->llr_t) into the caller's arrays; nullptr: not wanted, or the kernel wrote them itself
@@ -469,12 +404,9 @@ static int decode_serial_pass(ldpc_hip_bp *h, int max_iter, const uint8_t *synd,
     int rc;
     if ((rc = chunk_tiles_that_fit(h, tiles_total, (fast ? 1 : 2) * per_tile_msg + per_tile_llr + 24 * (size_t)(h->m + h->n + 1),
                                    h->msgA.cap + h->msgC.cap + h->llr_t.cap, 0.85, 32768, "syndrome", &chunk))) return rc;
-    if ((rc = h->msgA.ensure(per_tile_msg * (size_t)chunk))) return rc;
-    if ((rc = h->msgC.ensure(fast ? 16 : per_tile_msg * (size_t)chunk))) return rc;
-    if ((rc = h->par.ensure(sizeof(uint64_t) * m1 * (size_t)chunk))) return rc;
-    if ((rc = h->nzm.ensure(sizeof(uint64_t) * m1 * (size_t)chunk))) return rc;
-    if ((rc = h->invalid.ensure(sizeof(uint64_t) * (size_t)chunk))) return rc;
-    if ((rc = h->dec.ensure(sizeof(uint64_t) * n1 * (size_t)chunk))) return rc;
+    if ((rc = h->msgA.ensure(per_tile_msg * (size_t)chunk)) || (rc = h->msgC.ensure(fast ? 16 : per_tile_msg * (size_t)chunk))) return rc;
+    if ((rc = h->par.ensure(sizeof(uint64_t) * m1 * (size_t)chunk)) || (rc = h->nzm.ensure(sizeof(uint64_t) * m1 * (size_t)chunk))) return rc;
+    if ((rc = h->invalid.ensure(sizeof(uint64_t) * (size_t)chunk)) || (rc = h->dec.ensure(sizeof(uint64_t) * n1 * (size_t)chunk))) return rc;
     if ((rc = h->dcur.ensure(sizeof(uint64_t) * n1 * (size_t)chunk))) return rc;
     if (llr && (rc = h->llr_t.ensure(per_tile_llr * (size_t)chunk))) return rc;
     // level-parallel variant when the schedule has at least two bits per level on average (or when asked for); a schedule that changes per
@@ -1182,12 +1114,9 @@ int soft_info_device(ldpc_hip_bp *h, const double *soft, int64_t batch, double c
     int rc;
     if ((rc = chunk_tiles_that_fit(h, tiles_total, 2 * per_tile_msg + per_tile_llr + per_tile_soft + 24 * (m1 + n1),
                                    h->msgA.cap + h->msgC.cap + h->llr_t.cap + h->soft_S.cap, 0.85, 32768, "shot", &chunk))) return rc;
-    if ((rc = h->msgA.ensure(per_tile_msg * (size_t)chunk))) return rc;
-    if ((rc = h->msgC.ensure(per_tile_msg * (size_t)chunk))) return rc;
-    if ((rc = h->soft_S.ensure(per_tile_soft * (size_t)chunk))) return rc;
-    if ((rc = h->par.ensure(sizeof(uint64_t) * m1 * (size_t)chunk))) return rc;
-    if ((rc = h->dec.ensure(sizeof(uint64_t) * n1 * (size_t)chunk))) return rc;
-    if ((rc = h->dcur.ensure(sizeof(uint64_t) * n1 * (size_t)chunk))) return rc;
+    if ((rc = h->msgA.ensure(per_tile_msg * (size_t)chunk)) || (rc = h->msgC.ensure(per_tile_msg * (size_t)chunk))) return rc;
+    if ((rc = h->soft_S.ensure(per_tile_soft * (size_t)chunk)) || (rc = h->par.ensure(sizeof(uint64_t) * m1 * (size_t)chunk))) return rc;
+    if ((rc = h->dec.ensure(sizeof(uint64_t) * n1 * (size_t)chunk)) || (rc = h->dcur.ensure(sizeof(uint64_t) * n1 * (size_t)chunk))) return rc;
     if (llr && (rc = h->llr_t.ensure(per_tile_llr * (size_t)chunk))) return rc;
     int level_waves = 0;  // level-parallel variant: as for the serial schedule
     if (h->serial_kernel != 0 && h->n > 0) {

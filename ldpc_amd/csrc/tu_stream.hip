@@ -1,6 +1,6 @@
 // tu_stream.hip -- libldpc_hip.so, translation unit of the streamed kernels: bp_decode_kernel (persistent workgroup per 64-syndrome
-// tile, bp.hpp:192-325) and the chip-wide per-pass kernels bp_spread_*, with their host side (host_stream.h: decode_device, the
-// two-pass decode with lane compaction).  See bp_hip.hip for the design notes and the list of kernel headers.
+// tile, bp.hpp:192-325) and the chip-wide per-pass kernels bp_spread_*, with their host side (host_stream.h: plan_stream / decode_streamed, the
+// dispatch decode_device, the two-pass decode with lane compaction).  See bp_hip.hip for the design notes and the list of kernel headers.
 #include "bp_device_common.h"
 #include "bp_stream_kernel.h"
 #include "bp_spread_kernels.h"

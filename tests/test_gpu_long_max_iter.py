@@ -1,5 +1,5 @@
 """The reference's default ``max_iter = n`` with one hopeless syndrome in a large batch: a product-sum batch on a
-matrix without a fixed-degree ring variant must not queue thousands of full-size, empty per-pass rounds (host_stream.h: per_pass_first is
+matrix without a fixed-degree ring variant must not queue thousands of full-size, empty per-pass rounds (host_stream.h plan_stream: per_pass_first is
 bounded by max_iter; beyond it the persistent kernel's hand-off parks at most 256 tiles).  Results = the CPU checker's, and the decode is
 not slower than the same batch with a short max_iter by more than the hopeless row's own iterations cost."""
 import time

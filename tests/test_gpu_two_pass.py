@@ -1,4 +1,4 @@
-"""The streamed two-pass decode (csrc/host_stream.h: decode_stream_repacked): first pass k1 iterations, the rows still decoding compacted
+"""The streamed two-pass decode (csrc/host_stream.h: decode_stream_repacked, two StreamPass of decode_streamed): first pass k1 iterations, the rows still decoding compacted
 lane by lane into dense tiles, a second pass to the end -- against the plain decode (no pass structure at all) and the CPU checker: every row
 bit for bit, regular (ring variant) and irregular (per-pass kernels) codes, both methods, with and without log-ratios, a hopeless row, a
 partial last tile."""
@@ -45,4 +45,37 @@ def test_two_pass_decode_gives_the_plain_decodes_bits(code, method, alpha, p, ma
     for _ in range(3):
         got = _decode(eng, s, want_llr=True)
         assert np.array_equal(got[0], ref[0]) and np.array_equal(got[2], ref[2]) and np.array_equal(got[3], ref[3]) and bits_equal(got[1], ref[1])
+    eng.close()
+
+
+def test_second_pass_with_compacted_late_rounds_gives_the_plain_decodes_bits(oracle_built):
+    """The late rounds of a second pass (bp_spread_compact_kernel, then 32 + 8 workgroup rows per launch): mild noise, so that the histogram the
+    first steered decode leaves shows a handful of stragglers -- here the three hopeless rows and the few that need 13 iterations or more -- and
+    the second pass of the next ones compacts its list of parked tiles every 8 rounds.  Every steered decode must equal the plain one bit for bit."""
+    from golden_util import bits_equal
+    from ldpc_amd import codes
+    from ldpc_amd.engine import HipBpEngine
+    n, p, max_iter, alpha = 600, 0.03, 40, 0.8
+    h = codes.regular_ldpc_code(n, 3, 6, seed=3)
+    eng = HipBpEngine(h.indptr, h.indices, n, np.full(n, p), max_iter, 1, alpha)
+    eng.set_small_code_kernel(0)
+    B = 33000 + 37                 # 517 tiles, the last one partial
+    s = eng.gen_bsc_syndromes(5, p, shot0=0, shots=B, device="cuda:0")
+    hopeless = [100, 7777, 20011]
+    for r in hopeless:
+        s[r, 3] = 2
+    eng.set_repack(0)
+    ref = _decode(eng, s, want_llr=True)
+    conv = ref[3].astype(bool)
+    print("unconverged rows:", int((~conv).sum()), " mean iterations of the rest:", float(ref[2][conv].mean()))
+    # what makes the late rounds compact (host_stream.h: may_compact): at most 24 rows still running late in the second pass
+    assert 1 <= (~conv).sum() <= 24 and ref[2][conv].mean() < 8
+    rows = np.r_[hopeless, 0:32, B - 32:B]
+    want = oracle_built.BpOracle(h, error_rate=p, max_iter=max_iter, bp_method="minimum_sum", ms_scaling_factor=alpha).decode_batch(s.cpu().numpy()[rows])
+    assert np.array_equal(ref[0][rows], want[0]) and np.array_equal(ref[2][rows], want[2]) and np.array_equal(conv[rows], want[3].astype(bool))
+    assert bits_equal(ref[1][rows], want[1])
+    eng.set_repack(-1)
+    for i in range(3):  # the first leaves a histogram, the next two are steered by one
+        got = _decode(eng, s, want_llr=True)
+        assert np.array_equal(got[0], ref[0]) and np.array_equal(got[2], ref[2]) and np.array_equal(got[3], ref[3]) and bits_equal(got[1], ref[1]), i
     eng.close()
