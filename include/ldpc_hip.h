@@ -357,7 +357,7 @@ int ldpc_hip_bp_last_kernel_ms(ldpc_hip_bp *h, float *ms);
 int ldpc_hip_bp_last_phase_ms(ldpc_hip_bp *h, float *persistent_ms, float *per_pass_ms);
 
 /* Bytes of device workspace a decode of `batch` syndromes needs (message arrays dominate:
- * 2 * 8 * nnz bytes per syndrome). */
+ * 2 * 8 * nnz bytes per syndrome; 2 * 4 * nnz with LDPC_HIP_MSG_F32). */
 int64_t ldpc_hip_bp_workspace_bytes(const ldpc_hip_bp *h, int64_t batch);
 
 /* Tuning knobs (0 = library default): wavefronts per workgroup of the BP kernel (1..16) and the
@@ -417,7 +417,7 @@ int ldpc_hip_bp_set_small_code_kernel(ldpc_hip_bp *h, int32_t mode);
  * per-pass kernels from the start; "SER_VAR" 0 = the streamed serial schedule's item form (any degree profile) never, 1 = also
  * on (6,3)-regular matrices, "SER_VAR_UNITS" its KiB of LDS per wavefront (default 8); "REL_EXT" 0 / 1 = serial_relative's on-chip kernel never / always with the messages and
  * per-entry records in global memory (default: where the all-in-LDS form leaves fewer than four wavefronts per compute unit); "OSD_COLLECT_AFTER" 1 = BP + OSD lists the
- * rows BP left unconverged in a launch of its own after the BP kernel instead of inside the on-chip BP kernels; "OSD_NO_FLAT" 1 = OSD-0 on small matrices without the column permutation (osd0_reg_kernel instead of osd0_flat_kernel); "EDGE_CLAMP" 1 = the lane = edge min-sum kernel always
+ * rows BP left unconverged in a launch of its own after the BP kernel instead of inside the on-chip BP kernels; "OSD_NO_FLAT" 1 = OSD-0 on small matrices without the column permutation (osd0_reg_kernel instead of osd0_flat_kernel); "F32_NT" 0 / 1 = the float32 per-pass kernels with the default / the non-temporal cache policy whatever the batch size (default: non-temporal beyond 384 MiB of messages in flight); "EDGE_CLAMP" 1 = the lane = edge min-sum kernel always
  * with its clamp to DBL_MAX (default: left out where it provably never bites)).  A handle reads the environment variables LDPC_HIP_<NAME> ONCE, when it is
  * created; afterwards only this call changes a switch (value < 0: back to "not set").  Unknown names are an error. */
 int ldpc_hip_bp_set_debug_switch(ldpc_hip_bp *h, const char *name, int32_t value);
@@ -425,6 +425,25 @@ int ldpc_hip_bp_set_debug_switch(ldpc_hip_bp *h, const char *name, int32_t value
 #define LDPC_HIP_MATH_LIBM_EXACT 0
 #define LDPC_HIP_MATH_FAST 1
 int ldpc_hip_bp_set_math(ldpc_hip_bp *h, int32_t math_mode);
+
+/*
+ * Precision of the messages (opt-in; the default is the reference's FP64 arithmetic, bit for bit).
+ *   LDPC_HIP_MSG_F64 (default): every kernel family stores and computes messages in FP64.
+ *   LDPC_HIP_MSG_F32: minimum-sum on the parallel schedule with FP32 messages -- half the message traffic.  The priors are the handle's
+ *       FP64 log((1 - p) / p) rounded once to FP32; every minimum, multiply by alpha (formed in FP64, rounded once) and addition of the
+ *       FP64 kernels is performed as ONE FP32 operation in the same order, no FMA contraction; the posterior is the FP32 sum, the hard
+ *       decision `posterior <= 0`; convergence, early exit and iteration counts as in FP64.  The results are NOT the reference's bits:
+ *       they are those of this FP32 restatement (tests/f32_util.py), bit for bit.  log-ratios keep their type: each is an FP32
+ *       posterior widened exactly.  ldpc_hip_bp_decode_batch[_async], ldpc_hip_bposd0_decode_batch[_async] and
+ *       ldpc_hip_bposd_decode_batch[_async] route BP through the FP32 kernels (OSD runs unchanged on the widened posteriors).
+ *       Refused with LDPC_HIP_ERR_UNSUPPORTED (ldpc_hip_last_error says why) before anything is staged: product-sum, any serial
+ *       schedule, the *_priors entry points, soft-syndrome decoding, and ldpc_hip_bp_multi_decode_batch.
+ * The setter returns LDPC_HIP_ERR_INVALID for any other value; the getter returns the current value, or LDPC_HIP_ERR_INVALID for NULL.
+ */
+#define LDPC_HIP_MSG_F64 0
+#define LDPC_HIP_MSG_F32 1
+int ldpc_hip_bp_set_message_dtype(ldpc_hip_bp *h, int32_t dtype);
+int ldpc_hip_bp_get_message_dtype(const ldpc_hip_bp *h);
 
 /* The shader clock the BP kernels actually ran at (a measurement aid; no counterpart in the reference).  Every workgroup of the
  * long-running BP kernels (bp_decode_kernel, bp_wave_kernel, bp_wave_ps_kernel, bp_edge_kernel, bp_edge8_kernel) adds the shader cycles

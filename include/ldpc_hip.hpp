@@ -35,6 +35,8 @@ public:
     BpSchedule schedule = PARALLEL;            // SERIAL_RELATIVE is refused by the device (LDPC_HIP_ERR_UNSUPPORTED)
     BpInputType bp_input_type = SYNDROME;
     double ms_scaling_factor = 1.0;
+    int message_dtype = LDPC_HIP_MSG_F64;      // LDPC_HIP_MSG_F32: float32 messages (minimum-sum, parallel schedule, one GPU; ldpc_hip.h:
+                                               // ldpc_hip_bp_set_message_dtype) -- results are then not the reference's bits
     std::vector<int> serial_schedule_order;    // empty: 0 .. n-1 (bp.hpp:120-124)
     std::vector<double> soft_syndrome;         // after soft_info_decode_serial (bp.hpp:65, 547-660)
     std::vector<uint8_t> decoding;
@@ -190,6 +192,11 @@ private:
         }
         last_status = each_([&](ldpc_hip_bp *h) { return ldpc_hip_bp_set_params(h, maximum_iterations, (int32_t)bp_method, ms_scaling_factor); });
         if (last_status != LDPC_HIP_OK) { last_error = ldpc_hip_last_error(); return false; }
+        if (message_dtype != synced_dtype_) {
+            last_status = each_([&](ldpc_hip_bp *h) { return ldpc_hip_bp_set_message_dtype(h, (int32_t)message_dtype); });
+            if (last_status != LDPC_HIP_OK) { last_error = ldpc_hip_last_error(); return false; }
+            synced_dtype_ = message_dtype;
+        }
         if ((int)schedule != synced_schedule_ || serial_schedule_order != synced_order_) {
             if (!serial_schedule_order.empty() && (int)serial_schedule_order.size() != bit_count) {
                 fail_(LDPC_HIP_ERR_INVALID, "serial_schedule_order must have n entries");
@@ -217,6 +224,7 @@ private:
     ldpc_hip_bp_multi *mh_ = nullptr;
     std::vector<double> synced_probs_;
     int synced_schedule_ = (int)PARALLEL;
+    int synced_dtype_ = LDPC_HIP_MSG_F64;
     std::vector<int> synced_order_;
 };
 

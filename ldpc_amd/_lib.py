@@ -24,6 +24,7 @@ SYMBOLS = (
     "ldpc_hip_bp_set_debug_switch", "ldpc_hip_bp_multi_create", "ldpc_hip_bp_multi_destroy", "ldpc_hip_bp_multi_devices", "ldpc_hip_bp_multi_handle",
     "ldpc_hip_bp_multi_decode_batch", "ldpc_hip_bp_multi_last_kernel_ms", "ldpc_hip_bp_multi_set_staging",
     "ldpc_hip_bp_decode_batch_priors", "ldpc_hip_bp_decode_batch_priors_async", "ldpc_hip_bposd0_decode_batch_priors", "ldpc_hip_bposd0_decode_batch_priors_async",
+    "ldpc_hip_bp_set_message_dtype", "ldpc_hip_bp_get_message_dtype",
 )
 
 
@@ -112,6 +113,8 @@ def load():
     lib.ldpc_hip_bp_set_tuning.argtypes = [vp, i32, i32]
     lib.ldpc_hip_bp_set_math.argtypes = [vp, i32]
     lib.ldpc_hip_bp_set_ring.argtypes = [vp, i32]
+    lib.ldpc_hip_bp_set_message_dtype.argtypes = [vp, i32]
+    lib.ldpc_hip_bp_get_message_dtype.argtypes = [vp]
     lib.ldpc_hip_bp_set_small_code_kernel.argtypes = [vp, i32]
     lib.ldpc_hip_bp_set_debug_switch.argtypes = [vp, C.c_char_p, i32]
     lib.ldpc_hip_bp_set_handoff.argtypes = [vp, i32]

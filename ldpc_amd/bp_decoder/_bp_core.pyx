@@ -29,6 +29,7 @@ cdef extern from "ldpc_hip.hpp" namespace "ldpc_hip":
         int maximum_iterations
         BpMethod bp_method
         double ms_scaling_factor
+        int message_dtype
         vector[uint8_t] decoding
         vector[double] log_prob_ratios
         int iterations
@@ -103,6 +104,15 @@ cdef class CyBpCore:
     @ms_scaling_factor.setter
     def ms_scaling_factor(self, double value):
         self.bpd.ms_scaling_factor = value
+
+    @property
+    def message_dtype(self):
+        """0 = float64 messages (default), 1 = float32 (``ldpc_hip_bp_set_message_dtype``)."""
+        return self.bpd.message_dtype
+
+    @message_dtype.setter
+    def message_dtype(self, int value):
+        self.bpd.message_dtype = value
 
     @property
     def converge(self):

@@ -141,6 +141,8 @@ class BpDecoderBase:
         # the reference's own binding style); "ctypes": everything through ldpc_amd/engine.py.  Same C ABI underneath.
         self._backend = kwargs.get("_backend", None)
         self._cy = None
+        self._message_dtype = "float64"
+        self._engine_dtype = "float64"  # what the engine's handle is set to (a new handle starts at float64)
 
         self._h = _ingest(pcm)
         self.m, self.n = int(pcm.shape[0]), int(pcm.shape[1])
@@ -382,6 +384,38 @@ class BpDecoderBase:
     def random_serial_schedule(self, value: bool) -> None:
         self._random_serial_schedule = bool(value)  # a C truth value
 
+    # ---- message precision (additive; not a constructor keyword: the signatures are the reference's) ----------
+    @property
+    def message_dtype(self) -> str:
+        """``'float64'`` (default): the reference's arithmetic, bit for bit.  ``'float32'``: minimum-sum on the parallel schedule with FP32
+        messages -- half the message traffic; decisions, flags, iteration counts and log-ratios are those of the FP32 restatement of the
+        algorithm (every operation one FP32 operation, same order), NOT the reference's bits.  ``log_prob_ratios`` stay float64 (each an
+        FP32 posterior widened).  With ``'float32'``, product-sum, the serial schedules, ``channel_probs=``, soft-syndrome decoding and
+        ``device_ids=[...]`` raise ``NotImplementedError`` at decode time."""
+        return self._message_dtype
+
+    @message_dtype.setter
+    def message_dtype(self, value) -> None:
+        names = {"float64": "float64", "float32": "float32"}
+        key = names.get(value) if isinstance(value, str) else ("float64" if value is np.float64 else "float32" if value is np.float32 else None)
+        if key is None:
+            raise ValueError(f"message_dtype must be 'float64', 'float32', np.float64 or np.float32, not {value!r}.")
+        self._message_dtype = key
+
+    def _require_message_dtype(self, what=None):
+        """What ``message_dtype='float32'`` cannot do is refused here, at decode time, with its reason (``what``: the call's own addition)."""
+        if self._message_dtype != "float32":
+            return
+        if what is not None:
+            raise NotImplementedError(f"message_dtype='float32' with {what}; set message_dtype='float64'.")
+        if self._bp_method != MINIMUM_SUM:
+            raise NotImplementedError("message_dtype='float32' with bp_method='product_sum': its tanh / log have no bit-exact float32 form here; "
+                                      "float32 messages are available for bp_method='minimum_sum' only.")
+        if self._schedule != PARALLEL:
+            raise NotImplementedError(f"message_dtype='float32' with schedule='{self.schedule}': float32 messages need schedule='parallel'.")
+        if self._device_ids is not None:
+            raise NotImplementedError("message_dtype='float32' with device_ids=[...]: float32 messages are not sharded over several GPUs; decode on one GPU.")
+
     # ---- device engine --------------------------------------------------------------------------
     def _get_engine(self):
         """Create / refresh the HIP handle lazily so that construction and validation need no GPU."""
@@ -411,6 +445,9 @@ class BpDecoderBase:
                 self._engine.set_schedule({SERIAL: "serial", SERIAL_RELATIVE: "serial_relative"}[self._schedule],
                                           np.asarray(self._serial_schedule_order, np.int32))
             self._engine_sched = sched
+        if self._message_dtype != self._engine_dtype:
+            self._engine.set_message_dtype(self._message_dtype)
+            self._engine_dtype = self._message_dtype
         rnd = (bool(self._random_serial_schedule), self._random_schedule_seed, self._seed_epoch)
         if rnd != getattr(self, "_engine_random", (False, 0, 0)):
             self._engine.set_random_serial(rnd[0], rnd[1])  # re-seeds, as bpd.set_random_schedule_seed does (pyx:553-554)
@@ -440,6 +477,7 @@ class BpDecoderBase:
         self._cy.maximum_iterations = self._max_iter
         self._cy.bp_method = self._bp_method
         self._cy.ms_scaling_factor = self._ms_scaling_factor
+        self._cy.message_dtype = 1 if self._message_dtype == "float32" else 0
         return self._cy
 
     def _decode_numpy(self, synd2d, want_llr=True, osd0=False, llr_out=None, channel_probs=None):
@@ -458,6 +496,7 @@ class BpDecoderBase:
         """``channel_probs`` of ``decode_batch``: what cannot be done is refused with its reason, then the array is checked
         (``HipBpEngine._row_probs``) -- without a GPU: shape, dtype, range and place need none."""
         from ldpc_amd.engine import HipBpEngine
+        self._require_message_dtype("channel_probs: per-row channel probabilities are decoded with float64 messages only")
         if self._schedule != PARALLEL:
             raise NotImplementedError(f"channel_probs with schedule='{self.schedule}': the serial schedules decode with the decoder's own "
                                       "channel probabilities only; per-row probabilities need schedule='parallel'.")
@@ -583,6 +622,7 @@ class BpDecoder(BpDecoderBase):
             self._converge = True
             return np.zeros(self.n, dtype=dtype)
         self._require_parallel()
+        self._require_message_dtype()  # (float32: the one row goes through the batch kernels; the resident single-decode path is float64 only)
         as_syndrome = self._bp_input_type == SYNDROME or (self._bp_input_type == AUTO and ln == self.m)
         if as_syndrome:
             dec, llr, it, cv = self._decode_numpy(vec[None, :])
@@ -634,6 +674,7 @@ class BpDecoder(BpDecoderBase):
         elif self._bp_input_type == AUTO and not (ln == self.m or ln == self.n):
             raise ValueError(f"The input_vector must have length {self.m} (for syndrome decoding) or length {self.n} (for received vector decoding). Not length {ln}.")
         self._require_parallel()
+        self._require_message_dtype()
         as_syndrome = self._bp_input_type == SYNDROME or (self._bp_input_type == AUTO and ln == self.m)
         if channel_probs is not None:
             channel_probs = self._row_probs(input_vectors, channel_probs, as_syndrome)
@@ -744,6 +785,7 @@ class SoftInfoBpDecoder(BpDecoderBase):
         """With random_serial_schedule the routine rearranges the order the object carries at the top of every iteration it runs
         (bp.hpp:573-577: ``shuffle(order, std::default_random_engine(random_schedule_seed))``, a new engine each time); the engine
         does the same draws, every row of a batch from the order at the time of the call, and leaves its last row's order."""
+        self._require_message_dtype("soft-syndrome decoding: it is a serial schedule (bp.hpp:547-660)")
         out = self._get_engine().soft_info_decode_batch(soft2d, self.cutoff, self.sigma)
         self._pull_schedule_state()
         return out

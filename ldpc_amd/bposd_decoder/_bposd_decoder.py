@@ -99,6 +99,7 @@ class BpOsdDecoder(BpDecoderBase):
 
     def _require_supported(self):
         self._require_parallel()
+        self._require_message_dtype()  # (float32: BP in FP32, OSD unchanged on the widened posteriors)
         if self._osd_method == OSD_OFF:
             raise NotImplementedError("osd_method='OSD_OFF': the reference dereferences an unset LU object here (osd.hpp:63, 110); "
                                       "choose OSD_0, OSD_E or OSD_CS.")

@@ -28,9 +28,9 @@
 //
 // Built with: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared
 //
-// Five translation units, compiled side by side and linked into one library (Makefile): this one carries the C ABI (handle, setup,
-// decode entry points, layout kernels); tu_stream.hip, tu_serial.hip, tu_onchip.hip and tu_osd.hip carry one kernel family each
-// together with its host side (host_stream.h, host_serial.h, host_onchip.h, host_osd.h).  What they call in each other is
+// Six translation units, compiled side by side and linked into one library (Makefile): this one carries the C ABI (handle, setup,
+// decode entry points, layout kernels); tu_stream.hip, tu_serial.hip, tu_onchip.hip, tu_osd.hip and tu_f32.hip carry one kernel family each
+// together with its host side (host_stream.h, host_serial.h, host_onchip.h, host_osd.h, host_f32.h).  What they call in each other is
 // declared at the end of host_handle.h.  Device code lives in the kernel headers:
 //   bp_device_common.h   argument blocks, buffer-descriptor message addressing, per-node arithmetic, LDS-DMA helpers
 //   bp_math.h            tanh / log / division: bit-identical twins of the host libm + the fast variants
@@ -41,6 +41,7 @@
 //   bp_edge_kernel.h     bp_edge_kernel                      min-sum, rows <= 4 / columns <= 2 (surface-code family): lane = edge, messages in registers
 //                        (lane = node; for product-sum lane = entry)
 //   bp_serial_kernels.h  bp_serial_kernel, bp_softinfo_kernel   serial schedule, soft-syndrome serial min-sum
+//   bp_f32_kernels.h     bp_f32_*_kernel                    float32 message mode: min-sum, parallel schedule, one launch per pass (host_f32.h)
 //   osd_kernels.h        osd0[_reg]_kernel, osdw[_reg]_kernel, osd_big_kernel   OSD-0 / OSD-E / OSD-CS post-processing
 //   io_kernels.h         pack / unpack / transpose, H v, b8 shot data, synthetic BSC shots
 //   multi_device.h       ldpc_hip_bp_multi_*: a batch sharded over several GPUs inside one process (host code only)

@@ -299,9 +299,24 @@ int ldpc_hip_bp_set_math(ldpc_hip_bp *h, int32_t math_mode) {
     return LDPC_HIP_OK;
 }
 
+int ldpc_hip_bp_set_message_dtype(ldpc_hip_bp *h, int32_t dtype) {
+    if (!h) return fail(LDPC_HIP_ERR_INVALID, "null handle");
+    if (dtype != LDPC_HIP_MSG_F64 && dtype != LDPC_HIP_MSG_F32)
+        return fail(LDPC_HIP_ERR_INVALID, "message dtype must be 0 (LDPC_HIP_MSG_F64) or 1 (LDPC_HIP_MSG_F32)");
+    h->msg_dtype = dtype;
+    return LDPC_HIP_OK;
+}
+
+int ldpc_hip_bp_get_message_dtype(const ldpc_hip_bp *h) {
+    if (!h) return fail(LDPC_HIP_ERR_INVALID, "null handle");
+    return h->msg_dtype;
+}
+
 int64_t ldpc_hip_bp_workspace_bytes(const ldpc_hip_bp *h, int64_t batch) {
     if (!h || batch < 0) return -1;
     const int64_t tiles = (batch + LDPC_WAVE - 1) / LDPC_WAVE;
+    if (h->msg_dtype == LDPC_HIP_MSG_F32)  // FP32 messages and posteriors, no row priors
+        return tiles * (2ll * 4 * h->nnz * LDPC_WAVE + 2ll * 8 * h->m + 8 + 8ll * h->n + 4ll * h->n * LDPC_WAVE /* posteriors */);
     return tiles * (2ll * 8 * h->nnz * LDPC_WAVE + 2ll * 8 * h->m + 8 + 8ll * h->n +
                     8ll * h->n * LDPC_WAVE /* log-ratios */ + 8ll * h->n * LDPC_WAVE /* row priors (ldpc_hip_*_decode_batch_priors) */);
 }

@@ -499,6 +499,7 @@ int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
     h->timed_prev = h->timed_prev_mid = false;  // (what a two-pass decode before this one left)
     // Row priors (ldpc_hip_*_decode_batch_priors): every row is decoded with its own channel probabilities, h->row_probs [batch][n].  Two kernel
     // families read them: the slot kernel (decode_onchip sends there whatever an on-chip kernel would take) and the per-pass kernels (StreamPlan::rp).
+    if (h->msg_dtype == LDPC_HIP_MSG_F32) return decode_f32(h, synd, batch, decoding, llr, iters, conv);  // (never an FP64 kernel: what the mode cannot do is refused there)
     const bool rp = h->row_probs != nullptr;
     if (rp && h->schedule != 1) return fail(LDPC_HIP_ERR_UNSUPPORTED, "per-row channel probabilities: the serial schedules read the handle's priors only (parallel schedule required)");
     if (h->schedule == 0 || h->schedule == 2) return decode_serial(h, synd, batch, decoding, llr, iters, conv);

@@ -223,6 +223,10 @@ extern "C" int ldpc_hip_bp_multi_decode_batch(ldpc_hip_bp_multi *mh, int32_t wit
     if (with_osd < -1 || with_osd > 1) return fail(LDPC_HIP_ERR_INVALID, "with_osd must be -1 (BP only), 0 (BP + OSD-0) or 1 (BP + the handles' OSD method)");
     if (batch == 0) return LDPC_HIP_OK;
     if (!synd || !decoding) return fail(LDPC_HIP_ERR_INVALID, "syndromes and decoding must not be NULL");
+    for (const MultiDev &md : mh->devs) {
+        const int refused = f32_refusal(md.h, "decoding over several GPUs (ldpc_hip_bp_multi) is");
+        if (refused) return refused;
+    }
     // where the caller's arrays live: all in host memory, or all on ONE GPU
     const int pd = pointer_device(synd);
     for (const void *p : {(const void *)decoding, (const void *)llr, (const void *)iters, (const void *)conv})

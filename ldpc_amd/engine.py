@@ -114,6 +114,15 @@ class HipBpEngine:
         code = {"libm_exact": 0, "exact": 0, 0: 0, "fast": 1, 1: 1}[mode]
         _lib.check(self._lib.ldpc_hip_bp_set_math(self._h, code))
 
+    def set_message_dtype(self, dtype):
+        """``'float64'`` (default: the reference's arithmetic, bit for bit) or ``'float32'`` (minimum-sum, parallel schedule: FP32 messages,
+        half the traffic; results are those of the FP32 restatement, not the reference's bits -- ``ldpc_hip_bp_set_message_dtype``)."""
+        code = {"float64": 0, "float32": 1, 0: 0, 1: 1}[dtype]
+        _lib.check(self._lib.ldpc_hip_bp_set_message_dtype(self._h, code))
+
+    def message_dtype(self) -> str:
+        return ("float64", "float32")[int(self._lib.ldpc_hip_bp_get_message_dtype(self._h))]
+
     def set_ring(self, depth):
         """LDS-DMA ring for regular-degree matrices: False/0 = off, True/1 = default depth, 2 or 3 = slots per wave."""
         _lib.check(self._lib.ldpc_hip_bp_set_ring(self._h, int(depth)))
@@ -433,7 +442,7 @@ class HipBpMultiEngine:
     """
 
     _BROADCAST = ("set_debug_switch", "set_channel", "set_params", "set_schedule", "set_random_serial", "set_tuning", "set_math", "set_ring", "set_handoff", "set_osd",
-                  "set_repack", "set_serial_kernel", "set_osd_kernel", "set_small_code_kernel")
+                  "set_repack", "set_serial_kernel", "set_osd_kernel", "set_small_code_kernel", "set_message_dtype")
 
     def __init__(self, row_ptr, col_idx, n, channel_probs, max_iter, bp_method, ms_scaling_factor, device_ids):
         self._lib = _lib.load()

@@ -1,0 +1,125 @@
+#!/usr/bin/env python
+"""float32 message mode against float64: agreement of the results, and speed.
+
+    python tools/bench_f32.py --agreement                 # share of rows whose decisions / converge flags differ between the modes
+    python tools/bench_f32.py --speed                     # syndromes/s of both modes + the copy probe, same process, same box
+    python tools/bench_f32.py --speed --modes float64 --tree <checkout>   # the float64 of another built checkout (the parent commit: A/B on one box)
+
+Configurations: (3,6)-regular n = 10 000, min-sum 50 iterations, at p = 0.05 and 0.09; the irregular n = 10 000 code of
+``bench.py --full`` (speed only); BB144 min-sum 50 + OSD-0 (agreement only).  Syndromes are generated on the device; everything stays
+in HBM.  One JSON line per figure.  Reads nothing but this repository.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+# --tree DIR: take ldpc_amd (and its built library) from another checkout -- it must be on the path before the first import of the package
+_pre = argparse.ArgumentParser(add_help=False)
+_pre.add_argument("--tree", default=None)
+_TREE = os.path.abspath(_pre.parse_known_args()[0].tree or os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, _TREE)
+
+
+def _engine(h, p, max_iter, alpha=0.625):
+    from ldpc_amd.engine import HipBpEngine
+    h = h.tocsr()
+    h.sort_indices()
+    return HipBpEngine(h.indptr, h.indices, h.shape[1], np.full(h.shape[1], p), max_iter, 1, alpha)
+
+
+def _configs(which):
+    from ldpc_amd import codes
+    out = []
+    if "ldpc36" in which:
+        h = codes.regular_ldpc_code(10000, 3, 6, seed=1)
+        out += [("ldpc36_n10000_ms50_p050", h, 0.05, False), ("ldpc36_n10000_ms50_p090", h, 0.09, False)]
+    if "irregular" in which:
+        out += [("irregular_n10000_ms50_p030", codes.irregular_ldpc_code(10000, 5000, seed=1), 0.03, False)]
+    if "bb144" in which:
+        out += [("bb144_ms50_osd0_p050", codes.bivariate_bicycle_hx(), 0.05, True)]
+    return out
+
+
+def agreement(batch):
+    import torch
+    for name, h, p, osd in _configs(("ldpc36", "bb144")):
+        eng = _engine(h, p, 50)
+        if osd:
+            eng.set_osd(1, 0)
+        synd = eng.gen_bsc_syndromes(12345, p, 0, batch, device="cuda")
+        res = {}
+        for mode in ("float64", "float32"):
+            eng.set_message_dtype(mode)
+            dec, _, it, cv = eng.decode_batch(synd, want_llr=False, osd=osd)
+            torch.cuda.synchronize()
+            res[mode] = (dec.clone(), cv.clone(), it.clone())
+        d = (res["float64"][0] != res["float32"][0]).any(dim=1)
+        c = res["float64"][1] != res["float32"][1]
+        i = res["float64"][2] != res["float32"][2]
+        print(json.dumps(dict(kind="agreement", config=name, batch=batch, rows_decisions_differ=int(d.sum()), rows_converge_differ=int(c.sum()),
+                              rows_either_differ=int((d | c).sum()), share_either_differ=float((d | c).sum()) / batch,
+                              rows_iterations_differ=int(i.sum()),
+                              converged_float64=int(res["float64"][1].sum()), converged_float32=int(res["float32"][1].sum()))), flush=True)
+        eng.close()
+
+
+def speed(batch, modes, reps):
+    import torch
+    for name, h, p, _ in _configs(("ldpc36", "irregular")):
+        eng = _engine(h, p, 50)
+        synd = eng.gen_bsc_syndromes(12345, p, 0, batch, device="cuda")
+        tiles = (batch + 63) // 64
+        for mode in modes:
+            if mode != "float64" or hasattr(eng, "set_message_dtype"):  # (a checkout from before the mode has float64 only)
+                eng.set_message_dtype(mode)
+            out = None
+            rates, kms = [], []
+            for r in range(reps + 2):  # two untimed: allocations, and the histogram that steers the two-pass decode
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                out = eng.decode_batch(synd, want_llr=False, out=out)
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+                if r >= 2:
+                    rates.append(batch / dt)
+                    kms.append(eng.last_kernel_ms())
+            it = out[2].cpu().numpy().astype(np.int64)
+            pad = np.zeros(tiles * 64, np.int64)
+            pad[:batch] = it
+            tile_iters = int(pad.reshape(tiles, 64).max(axis=1).sum())
+            esize = 4 if mode == "float32" else 8
+            # what a tile-by-tile flooding decode has to move: 4 message-array passes per tile-iteration (float64: as if nothing were compacted)
+            gbytes = tile_iters * 4 * eng.nnz * 64 * esize / 1e9
+            _, probe = eng.copy_probe(min(tiles, 1024), eng.nnz, 4)
+            print(json.dumps(dict(kind="speed", config=name, mode=mode, tree=os.path.relpath(_TREE), batch=batch,
+                                  syndromes_per_s=[round(x) for x in rates], median_syndromes_per_s=round(float(np.median(rates))),
+                                  kernel_ms=[round(x, 2) for x in kms], tile_iterations=tile_iters, message_gbytes=round(gbytes, 1),
+                                  message_gbytes_per_s=round(gbytes / (float(np.median(kms)) * 1e-3), 1), copy_probe_gbytes_per_s=round(probe, 1),
+                                  fraction_of_copy_probe=round(gbytes / (float(np.median(kms)) * 1e-3) / probe, 3),
+                                  converged=int(out[3].sum()))), flush=True)
+        eng.close()
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--agreement", action="store_true")
+    ap.add_argument("--speed", action="store_true")
+    ap.add_argument("--batch", type=int, default=65536)
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--modes", default="float64,float32")
+    ap.add_argument("--tree", default=None, help="another built checkout to take ldpc_amd from (default: this one)")
+    a = ap.parse_args()
+    if a.agreement:
+        agreement(a.batch)
+    if a.speed:
+        speed(a.batch, a.modes.split(","), a.reps)
+
+
+if __name__ == "__main__":
+    main()
