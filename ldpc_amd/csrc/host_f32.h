@@ -86,7 +86,12 @@ int decode_f32(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *deco
         // Every kernel of a round loops over the listed tiles, so a launch needs only enough workgroup rows to fill the chip: all the
         // tiles while they are few, else what gives ~16 384 workgroups (at least 256 rows).  Once tiles have finished the list is
         // compacted every 4 rounds and the rows beyond it leave at once.
-        auto rows_for = [&](unsigned gx) { const unsigned want = 16384u / gx > 256u ? 16384u / gx : 256u; return tiles < want ? tiles : want; };
+        // (switch F32_GRID_ROWS k > 0: at most k rows for all four kernels -- the tests reach gridDim.y < count at 70 tiles with it)
+        const int grid_rows = h->sw("F32_GRID_ROWS");
+        auto rows_for = [&](unsigned gx) {
+            const unsigned want = grid_rows > 0 ? (unsigned)grid_rows : 16384u / gx > 256u ? 16384u / gx : 256u;
+            return tiles < want ? tiles : want;
+        };
         const unsigned per_wg = 4u * (unsigned)a.nodes;
         const unsigned gcx = (unsigned)(h->m ? (h->m + per_wg - 1) / per_wg : 1), gbx = (unsigned)(h->n ? (h->n + per_wg - 1) / per_wg : 1);
         const unsigned gsx = (unsigned)(h->m ? (h->m + 255) / 256 : 1), gfx = (unsigned)(h->n ? (h->n + 63) / 64 : 1);

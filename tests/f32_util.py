@@ -184,3 +184,82 @@ def expected(key, case, dtype):
     if k not in _EXPECT:
         _EXPECT[k] = min_sum_restatement(case["h"], case["probs"], case["synd"], case["max_iter"], case["alpha"], dtype)
     return _EXPECT[k]
+
+
+# ---- a large batch assembled from rows whose float32 outcome is known: which tile ends at which iteration is chosen ------------------
+def row_end_iterations(want, max_iter):
+    """The iteration at which each row of a restatement result stops occupying its lane: its count, or ``max_iter`` if it never converges."""
+    return np.where(want[3], want[2], max_iter).astype(np.int64)
+
+
+def scheduled_batch(case, want, finish, last_rows, seed):
+    """-> (idx, synd[idx]): a batch of ``len(finish)`` tiles of 64 rows (the last of ``last_rows``) whose tile t is drawn, with a seeded
+    generator, from the rows of ``case`` that take at most ``finish[t]`` iterations in ``want`` (its restatement outputs), at least one of
+    them exactly ``finish[t]`` -- so tile t ends at iteration ``finish[t]``.  ``finish[t] == max_iter`` stands for a tile that holds an
+    unconverged row.  Rows are independent: the expectation is ``tuple(x[idx] for x in want)``."""
+    rng = np.random.default_rng(seed)
+    max_iter = int(case["max_iter"])
+    end, conv = row_end_iterations(want, max_iter), np.asarray(want[3], bool)
+    idx = []
+    for t, f in enumerate(finish):
+        rows = last_rows if t == len(finish) - 1 else 64
+        pool = np.flatnonzero(end <= f)
+        exact = np.flatnonzero(~conv) if f == max_iter else np.flatnonzero(conv & (end == f))
+        assert 1 <= rows <= 64 and len(exact), f"tile {t}: no row of the case ends at iteration {f}"
+        tile = rng.choice(pool, size=rows)
+        tile[rng.integers(rows)] = rng.choice(exact)
+        idx.append(tile)
+    idx = np.concatenate(idx).astype(np.int64)
+    return idx, np.ascontiguousarray(case["synd"][idx])
+
+
+def tile_end_iterations(want, idx, max_iter):
+    """Per tile of 64 rows of ``idx``: the iteration after which the tile is final (the largest of its rows)."""
+    end = row_end_iterations(want, max_iter)[idx]
+    return np.array([int(end[t:t + 64].max()) for t in range(0, len(idx), 64)])
+
+
+# The standard schedule: 70 tiles, the last of 7 rows (B = 4 423).  The sorted end iterations below are dealt out by the fixed
+# permutation t -> (37 t + 8) mod 70, which puts tiles that end early in both 64-slot chunks of the tile list and between tiles that run to
+# the end; tests/test_f32_restatement.py::test_standard_schedule_has_the_properties_the_gpu_tests_rely_on says what that gives.
+_STANDARD_LEVELS = [2, 4, 5, 7, 8, 10, 10, 11, 11, 12, 12] + [16] * 59
+STANDARD_FINISH = tuple(_STANDARD_LEVELS[(37 * t + 8) % 70] for t in range(70))
+STANDARD_LAST_ROWS = 7
+COMPACTION_ROUNDS = (4, 8, 12)  # host_f32.h: round >= 4 && round % 4 == 0, 16 iterations
+
+
+@functools.lru_cache(maxsize=None)
+def standard_schedule(converging_only=False, seed=2024):
+    """-> (case, idx, syndromes, expectation) of the standard schedule on ``irregular_case()``; ``converging_only``: tiles that would hold
+    an unconverged row end with the slowest row that converges instead (iteration 12), so every row of the batch converges."""
+    case = irregular_case()
+    want = expected("irregular600", case, np.float32)
+    finish = STANDARD_FINISH
+    if converging_only:
+        longest = int(want[2][want[3]].max())
+        finish = tuple(min(f, longest) for f in finish)
+    idx, synd = scheduled_batch(case, want, finish, STANDARD_LAST_ROWS, seed)
+    return case, idx, synd, tuple(x[idx] for x in want)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_values_batch(code, alpha, tiles=70, last_rows=6):
+    """-> (case, idx, syndromes, expectation): the 70 rows of ``small_case(code, alpha)`` replicated by index to ``tiles`` tiles, the last
+    of ``last_rows`` rows.  Tiles 1, 4, 7, ... hold only rows that converge (within 2 iterations: they end at once); every other tile
+    walks through all rows of the case -- the syndrome bytes 2 and 3 and the rows that never converge included -- and runs to ``max_iter``.
+    The index strides (37 rows of 70, 1 row of the converging ones) are no multiples of 64, so no tile repeats its neighbour."""
+    case = small_case(code, alpha)
+    want = expected(f"{code}_a{alpha}", case, np.float32)
+    quick = np.flatnonzero(want[3])
+    b = np.arange((tiles - 1) * 64 + last_rows, dtype=np.int64)
+    idx = np.where((b // 64) % 3 == 1, quick[b % len(quick)], (b * 37) % len(case["synd"]))
+    return case, idx, np.ascontiguousarray(case["synd"][idx]), tuple(x[idx] for x in want)
+
+
+@functools.lru_cache(maxsize=None)
+def converging_rows_expected(max_iter):
+    """-> (rows, outputs): the rows of ``irregular_case()`` that converge within its 16 iterations, and the float32 restatement of exactly
+    those rows with another ``max_iter`` (it stops once all have converged, so a huge ``max_iter`` costs nothing)."""
+    case = irregular_case()
+    rows = np.flatnonzero(expected("irregular600", case, np.float32)[3])
+    return rows, min_sum_restatement(case["h"], case["probs"], case["synd"][rows], max_iter, case["alpha"], np.float32)

@@ -59,6 +59,88 @@ def test_edge_syndromes_are_what_the_issue_asks():
         assert not cv[9] and not cv[66], "a syndrome byte > 1 never converges"
 
 
+def _simulated_lists(end):
+    """The device's tile list before each compaction (host_f32.h: rounds 4, 8, 12; bp_f32_compact_kernel keeps a tile whose last round,
+    0-based ``end - 1``, is not before the compaction's) -> [(round, list)], and the list after the last one."""
+    lst, out = list(range(len(end))), []
+    for r in fu.COMPACTION_ROUNDS:
+        out.append((r, lst))
+        lst = [t for t in lst if r <= end[t] - 1]
+    return out, lst
+
+
+def test_standard_schedule_has_the_properties_the_gpu_tests_rely_on():
+    """Derived from the restatement's outputs alone: per-tile end iteration = the largest of its rows, and the list each compaction sees."""
+    case, idx, synd, want = fu.standard_schedule()
+    base = fu.expected("irregular600", case, np.float32)
+    max_iter = case["max_iter"]
+    assert max_iter == 16 and len(idx) == 69 * 64 + 7 == 4423 and synd.shape == (4423, 300)
+    assert all(np.array_equal(w, x[idx]) for w, x in zip(want, base)) and np.array_equal(synd, case["synd"][idx])
+    end = fu.tile_end_iterations(base, idx, max_iter)
+    print(f"standard schedule: tile end iterations {end.tolist()}")
+    assert len(end) == 70 and end.tolist() == list(fu.STANDARD_FINISH), "a tile does not end at the iteration the schedule gives it"
+    row_end = fu.row_end_iterations(want, max_iter)
+    for t in np.flatnonzero(end == max_iter):
+        assert not want[3][64 * t:64 * t + 64].all(), f"tile {t} runs to the end without an unconverged row"
+    for lo, hi in ((1, 4), (5, 8), (9, 12), (13, 16)):
+        assert ((row_end >= lo) & (row_end <= hi)).any(), f"no row ends in iterations {lo} .. {hi}"
+    steps = np.diff(end)
+    assert (steps > 0).any() and (steps < 0).any() and sorted(end) != end.tolist(), "end iterations in order"
+    lists, left = _simulated_lists(end)
+    for r, lst in lists:
+        ended = [end[t] - 1 < r for t in lst]
+        print(f"compaction at round {r}: {len(lst)} tiles listed, {sum(ended)} of them final ({sum(ended[64:])} beyond slot 63)")
+        assert len(lst) > 64, f"round {r}: the list has no second chunk of 64"
+        assert any(ended[:64]), f"round {r}: no final tile among the first 64 slots (nothing moves: kept == s0)"
+        assert not all(ended[64:]), f"round {r}: no running tile beyond slot 63 (kept is never carried into the second chunk)"
+        # a tile that became final before the round just before this compaction stayed listed: the kernels had to skip it
+        assert any(end[t] - 1 < r - 1 for t in lst), f"round {r}: no tile ended between two compactions"
+    assert left and all(end[t] == max_iter for t in left) and len(left) == int((end == max_iter).sum())
+    full = np.flatnonzero(end == max_iter)
+    assert (full < 64).any() and (full >= 64).any(), "tiles that run to the end in one chunk only"
+    assert end[-1] == max_iter and len(idx) % 64 == fu.STANDARD_LAST_ROWS, "the partial tile must run to the end"
+    for t in range(69):
+        rows = min(64, len(idx) - 64 * (t + 1))
+        assert not np.array_equal(idx[64 * t:64 * t + rows], idx[64 * (t + 1):64 * (t + 1) + rows]), f"tiles {t} and {t + 1} hold the same rows"
+        assert not np.array_equal(synd[64 * t:64 * t + rows], synd[64 * (t + 1):64 * (t + 1) + rows])
+    again = fu.scheduled_batch(case, base, fu.STANDARD_FINISH, fu.STANDARD_LAST_ROWS, 2024)
+    assert np.array_equal(again[0], idx), "the builder is not deterministic in its seed"
+
+
+def test_converging_schedule_and_its_restatement_at_a_huge_max_iter():
+    """What the early-stop GPU test decodes: every row converges, the slowest at iteration 12, and 200 000 allowed iterations give those
+    rows exactly what 16 give them."""
+    case, idx, synd, want = fu.standard_schedule(converging_only=True)
+    base = fu.expected("irregular600", case, np.float32)
+    assert want[3].all() and int(want[2].max()) == 12 and len(idx) == 4423
+    end = fu.tile_end_iterations(base, idx, case["max_iter"])
+    assert end.tolist() == [min(f, 12) for f in fu.STANDARD_FINISH]
+    rows, huge = fu.converging_rows_expected(200000)
+    assert set(idx.tolist()) <= set(rows.tolist())
+    assert int(huge[2].max()) == 12 and huge[3].all()
+    for got, x in zip(huge, base):
+        assert np.array_equal(got.view(np.uint64) if got.dtype == np.float64 else got, x[rows].view(np.uint64) if x.dtype == np.float64 else x[rows])
+
+
+def test_edge_value_batches_mix_tiles_that_end_at_once_with_tiles_that_never_do():
+    for code, alpha in (("hamming3", 0.625), ("rep5", 0.0)):
+        case, idx, synd, want = fu.edge_values_batch(code, alpha)
+        base = fu.expected(f"{code}_a{alpha}", case, np.float32)
+        end = fu.tile_end_iterations(base, idx, case["max_iter"])
+        assert len(end) == 70 and len(idx) == 69 * 64 + 6
+        quick = np.arange(70) % 3 == 1
+        assert (end[quick] <= 2).all() and (end[~quick] == case["max_iter"]).all(), end.tolist()
+        assert (synd == 2).any() and (synd == 3).any() and (~synd.any(axis=1)).any() and np.isinf(want[1]).any()
+        lists, _ = _simulated_lists(np.where(end < 4, end, 16))  # (12 iterations: compactions at rounds 4 and 8; nothing ends in between)
+        r, lst = lists[0]
+        assert r == 4 and any(end[t] <= 2 for t in lst[:64]) and any(end[t] > 2 for t in lst[64:])
+        for t in range(69):
+            rows = min(64, len(idx) - 64 * (t + 1))
+            assert not np.array_equal(idx[64 * t:64 * t + rows], idx[64 * (t + 1):64 * (t + 1) + rows]), f"{code}: tiles {t} and {t + 1} hold the same rows"
+        invalid = [bool((synd[64 * t:64 * t + 64] > 1).any()) for t in range(70)]
+        assert not any(np.array(invalid)[quick]) and sum(invalid) >= 20 and any(invalid[64:]), "tiles with a syndrome byte > 1: too few, or none in the second chunk"
+
+
 # ---- the property -----------------------------------------------------------------------------------------------------------------
 def _decoder(cls=None, **kw):
     from ldpc_amd.bp_decoder import BpDecoder

@@ -2,7 +2,15 @@
 restatement's operation order to the oracle at float64): hard decisions, converge flags, iteration counts and the bit patterns of the
 log-ratios, through BpDecoder.decode_batch on host arrays with both backends, CUDA tensors, the engine's synchronous and asynchronous
 entry points, chunked batches, BP + OSD, and back to float64 on the same decoder.  Plus what the C ABI refuses, and that close() frees
-every buffer the mode grew."""
+every buffer the mode grew.
+
+From test_tile_list_loops_and_compaction on: what only large batches reach -- the looping form of the per-round kernels (workgroup rows
+that serve several slots of the tile list: switch F32_GRID_ROWS), bp_f32_compact_kernel beyond its first 64 entries, tiles that are
+final but still listed, 4 and 16 nodes per wavefront, and the host's look at the flag that stops the queueing of rounds -- on batches of
+70 tiles whose tiles end at chosen iterations (f32_util.scheduled_batch; tests/test_f32_restatement.py pins the schedule's properties).
+Every output buffer is poisoned first, so a tile that is dropped shows as missing outputs, not as stale equal ones."""
+import time
+
 import numpy as np
 import pytest
 
@@ -224,3 +232,113 @@ def test_close_frees_every_device_buffer():
     after = held()
     print(f"float32: device buffer bytes before {before}, with the engine {during}, after close {after}")
     assert during > before and after == before, f"{after - before} bytes of device buffers outlive the handle"
+
+
+# ---- 70 tiles: looping kernels, the second chunk of the tile list, the early stop ----------------------------------------------------
+def _poisoned(b, n, want_llr=True):
+    """Output tensors no decode leaves as they are: 0xFF bytes (decisions and flags are 0 / 1, iteration counts positive), NaN."""
+    import torch
+    return (torch.full((b, n), 0xFF, dtype=torch.uint8, device="cuda"),
+            torch.full((b, n), float("nan"), dtype=torch.float64, device="cuda") if want_llr else None,
+            torch.full((b,), -1, dtype=torch.int32, device="cuda"), torch.full((b,), 0xFF, dtype=torch.uint8, device="cuda"))
+
+
+def _decode_poisoned(eng, synd, want, what, want_llr=True):
+    """decode_batch on CUDA tensors (one device chunk unless max_chunk_tiles says otherwise) into poisoned buffers, against ``want``."""
+    import torch
+    assert not np.isnan(want[1]).any() and want[2].min() >= 1, "the poison must differ from every expected value"
+    out = _poisoned(len(synd), want[0].shape[1], want_llr)
+    got = eng.decode_batch(synd, want_llr=want_llr, out=out)
+    torch.cuda.synchronize()
+    assert all(g is o for g, o in zip(got, out))
+    dec, llr, it, cv = (None if x is None else x.cpu().numpy() for x in got)
+    if not want_llr:
+        assert llr is None
+        llr = want[1]
+    assert set(np.unique(cv).tolist()) <= {0, 1}, f"{what}: converge flags that were never written"
+    _same((dec, llr, it, cv), want, what)
+
+
+def _switches(eng, grid_rows=None, nodes=None, nt=None):
+    for name, value in (("F32_GRID_ROWS", grid_rows), ("SPREAD_NODES", nodes), ("F32_NT", nt)):
+        if value is not None:
+            eng.set_debug_switch(name, value)
+
+
+# (grid rows, nodes per wavefront, F32_NT, want_llr): the full product of rows x nodes; F32_NT = 1 and want_llr = False on two of them each
+_LOOP_CASES = [(None, 1, None, True), (None, 4, None, False), (None, 16, 1, True),
+               (1, 1, None, True), (1, 4, None, True), (1, 16, None, True),
+               (3, 1, None, False), (3, 4, 1, True), (3, 16, None, True),
+               (64, 1, None, True), (64, 4, None, True), (64, 16, None, True)]
+
+
+@pytest.mark.parametrize("grid_rows,nodes,nt,want_llr", _LOOP_CASES,
+                         ids=[f"rows{g}-nodes{k}" + ("-nt" if nt else "") + ("" if w else "-nollr") for g, k, nt, w in _LOOP_CASES])
+def test_tile_list_loops_and_compaction(grid_rows, nodes, nt, want_llr):
+    """The standard schedule (70 tiles, B = 4 423; tiles end at iterations 2 ... 12 and 16 in both chunks of the list) with 1, 3 (70 slots
+    leave a remainder) and 64 (only rows 0 ... 5 loop twice) workgroup rows and all 70; 16 nodes per wavefront make 64 per workgroup against
+    m = 300, n = 600, so the last workgroup of each pass is partial."""
+    import torch
+    case, idx, synd, want = fu.standard_schedule()
+    eng = _engine(case)
+    _switches(eng, grid_rows, nodes, nt)
+    _decode_poisoned(eng, torch.as_tensor(synd, device="cuda"), want, f"standard schedule/rows {grid_rows}/nodes {nodes}/nt {nt}", want_llr)
+    eng.close()
+
+
+def test_tile_list_in_several_chunks_and_after_a_larger_batch():
+    """Chunks of 33, 33 and 4 tiles, each with its own list, counters, flag sequence number and compactions; then 3 tiles on the same
+    engine (nothing of the larger decode's list, state or counters may be read), then the 70 again -- that time with 4 workgroup rows."""
+    import torch
+    case, idx, synd, want = fu.standard_schedule()
+    s = torch.as_tensor(synd, device="cuda")
+    eng = _engine(case)
+    eng.set_tuning(max_chunk_tiles=33)
+    _decode_poisoned(eng, s, want, "standard schedule/chunks of 33 tiles")
+    _decode_poisoned(eng, s[:192].contiguous(), tuple(x[:192] for x in want), "its first 3 tiles after the 70")
+    eng.set_debug_switch("F32_GRID_ROWS", 4)
+    _decode_poisoned(eng, s, want, "standard schedule/chunks of 33 tiles again, 4 rows")
+    eng.close()
+
+
+@pytest.mark.parametrize("grid_rows", [None, 2])
+@pytest.mark.parametrize("code,alpha", [("hamming3", 0.625), ("rep5", 0.0)])
+def test_edge_values_across_the_second_list_chunk(code, alpha, grid_rows):
+    """Priors of +-inf and 0, syndrome bytes 2 and 3 and an all-zero row (not short-cut by the engine) in 70 tiles: tiles 1, 4, 7, ... end
+    at once, the others run to max_iter, so the first compaction moves running tiles from the second chunk of the list forward."""
+    import torch
+    case, idx, synd, want = fu.edge_values_batch(code, alpha)
+    eng = _engine(case)
+    _switches(eng, grid_rows)
+    _decode_poisoned(eng, torch.as_tensor(synd, device="cuda"), want, f"{code} a = {alpha} x 70 tiles/rows {grid_rows}")
+    eng.close()
+
+
+def test_large_max_iter_stops_queueing_rounds_f32():
+    """As tests/test_gpu_long_max_iter.py for the FP64 route: the round loop of host_f32.h looks at the host-mapped flag before it queues a
+    round.  The standard schedule on rows that all converge (the slowest at iteration 12) with max_iter = 200 000 gives what 16 give, and
+    its second call costs at most 1.5 s more (that test's margin; without the look the host queues 800 000 launches: several seconds).
+    Measured on one MI355X: 0.0011 s at 16 and 0.0015 s at 200 000; 2.40 s at 200 000 with the look taken out."""
+    import torch
+    case, idx, synd, want16 = fu.standard_schedule(converging_only=True)
+    rows, huge = fu.converging_rows_expected(200000)
+    pos = np.searchsorted(rows, idx)
+    assert np.array_equal(rows[pos], idx)
+    want = tuple(x[pos] for x in huge)
+    assert want[3].all() and int(want[2].max()) == 12
+    assert all(np.array_equal(a, b) for a, b in zip(want[:1] + want[2:], want16[:1] + want16[2:])) and bits_equal(want[1], want16[1])
+    s = torch.as_tensor(synd, device="cuda")
+    timings = {}
+    for max_iter in (16, 200000):
+        eng = _engine(dict(case, max_iter=max_iter))
+        _decode_poisoned(eng, s, want, f"converging schedule/max_iter {max_iter}, first call")
+        out = _poisoned(len(synd), 600)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        eng.decode_batch(s, out=out)
+        torch.cuda.synchronize()
+        timings[max_iter] = time.perf_counter() - t0
+        _same(tuple(x.cpu().numpy() for x in out), want, f"converging schedule/max_iter {max_iter}, second call")
+        eng.close()
+    print(f"float32 early stop: second call {timings[16]:.4f} s at max_iter 16, {timings[200000]:.4f} s at max_iter 200 000")
+    assert timings[200000] < timings[16] + 1.5, timings
