@@ -466,6 +466,15 @@ int ldpc_hip_bp_copy_probe(ldpc_hip_bp *h, int64_t tiles, int32_t segments_per_t
  * A handle's share is gone once ldpc_hip_bp_destroy returns. */
 int64_t ldpc_hip_debug_device_buf_bytes(void);
 
+/* Launch log (a test aid; no counterpart in the reference): which kernel instantiations the library launched, over every handle and thread
+ * of the process.  ldpc_hip_debug_launch_log(1) empties the table and starts recording, (0) stops AND empties it -- read before disabling; off -- the default -- a launch costs one
+ * load of a flag.  ldpc_hip_debug_launch_log_read copies the table as text, one "count<TAB>name" line per instantiation in the spelling
+ * of tools/list_instantiations.py ("bp_edge8_kernel<12, 3, true>"), NUL-terminated and cut to `capacity` bytes, and returns the bytes the
+ * whole text needs (call it with capacity 0 first).  The environment variable LDPC_HIP_LAUNCH_LOG=<file>, read when the library is loaded,
+ * records for the whole process and appends its table to the file at unload (profiles/README.md); the calls here do not disturb it. */
+void ldpc_hip_debug_launch_log(int32_t enable);
+int64_t ldpc_hip_debug_launch_log_read(char *buf, int64_t capacity);
+
 /* Page-locked host memory for a caller's result arrays (no counterpart in the reference: its arrays never leave the host).  A host
  * pointer into such a block -- or into memory the caller registered with hipHostRegister -- handed to ldpc_hip_bp_decode_batch as `llr`
  * is written by the device-to-host copies themselves: the pipelined host path (above) skips its pinned staging buffer and the

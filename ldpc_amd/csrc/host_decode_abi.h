@@ -471,7 +471,7 @@ int ldpc_hip_gf2_mulvec_batch(ldpc_hip_bp *h, const uint8_t *vectors, int64_t ba
     }
     if (h_out) { if ((rc = h->st_synd.ensure(B * m))) return rc; d_out = (uint8_t *)h->st_synd.p; }
     const int64_t total = batch * h->m;
-    hipLaunchKernelGGL(gf2_mulvec_kernel, flat_grid((size_t)(total)), dim3(256), 0, h->stream,
+    LDPC_LAUNCH(gf2_mulvec_kernel, flat_grid((size_t)(total)), dim3(256), 0, h->stream,
                        h->d_row_ptr, h->d_col_idx, h->m, h->n, d_in, batch, d_out);
     HIPCHK(hipGetLastError());
     if (h_out) HIPCHK(hipMemcpyAsync(out, d_out, B * m, hipMemcpyDeviceToHost, h->stream));
@@ -528,7 +528,7 @@ int ldpc_hip_pack_b8(ldpc_hip_bp *h, const uint8_t *bytes, int64_t batch, int32_
     if (!is_device_ptr(bytes) || !is_device_ptr(packed)) return fail(LDPC_HIP_ERR_INVALID, "ldpc_hip_pack_b8 takes device pointers");
     HIPCHK(hipSetDevice(h->device));
     const size_t total = (size_t)batch * (size_t)((bits + 7) / 8);
-    hipLaunchKernelGGL(pack_b8_kernel, flat_grid((size_t)(total)), dim3(256), 0, h->stream, bytes, batch, bits, packed);
+    LDPC_LAUNCH(pack_b8_kernel, flat_grid((size_t)(total)), dim3(256), 0, h->stream, bytes, batch, bits, packed);
     HIPCHK(hipGetLastError());
     return mark_queued(h, LDPC_HIP_OK);
 }
@@ -541,7 +541,7 @@ int ldpc_hip_unpack_b8(ldpc_hip_bp *h, const uint8_t *packed, int64_t batch, int
     if (!is_device_ptr(bytes) || !is_device_ptr(packed)) return fail(LDPC_HIP_ERR_INVALID, "ldpc_hip_unpack_b8 takes device pointers");
     HIPCHK(hipSetDevice(h->device));
     const size_t total = (size_t)batch * (size_t)bits;
-    hipLaunchKernelGGL(unpack_b8_kernel, flat_grid((size_t)(total)), dim3(256), 0, h->stream, packed, batch, bits, bytes);
+    LDPC_LAUNCH(unpack_b8_kernel, flat_grid((size_t)(total)), dim3(256), 0, h->stream, packed, batch, bits, bytes);
     HIPCHK(hipGetLastError());
     return mark_queued(h, LDPC_HIP_OK);
 }
@@ -589,7 +589,7 @@ int ldpc_hip_bp_decode_b8(ldpc_hip_bp *h, const uint8_t *dets_b8, int64_t batch,
     if ((rc = h->b8_synd.ensure(B * m ? B * m : 1))) return rc;
     if ((rc = h->b8_dec.ensure(B * n ? B * n : 1))) return rc;
     uint8_t *d_synd = (uint8_t *)h->b8_synd.p, *d_dec = (uint8_t *)h->b8_dec.p;
-    if (m) hipLaunchKernelGGL(unpack_b8_kernel, flat_grid((size_t)(B * m)), dim3(256), 0, h->stream, d_in, batch, h->m, d_synd);
+    if (m) LDPC_LAUNCH(unpack_b8_kernel, flat_grid((size_t)(B * m)), dim3(256), 0, h->stream, d_in, batch, h->m, d_synd);
     HIPCHK(hipGetLastError());
     const bool h_it = iters && !is_device_ptr(iters), h_cv = conv && !is_device_ptr(conv);
     int32_t *d_it = iters;
@@ -598,7 +598,7 @@ int ldpc_hip_bp_decode_b8(ldpc_hip_bp *h, const uint8_t *dets_b8, int64_t batch,
     if (h_cv) { if ((rc = h->st_conv.ensure(B))) return rc; d_cv = (uint8_t *)h->st_conv.p; }
     if ((rc = with_osd ? bposd_device(h, h->osd_method, h->osd_order, d_synd, batch, d_dec, nullptr, d_it, d_cv)
                        : decode_device(h, d_synd, batch, d_dec, nullptr, d_it, d_cv))) return rc;
-    hipLaunchKernelGGL(zero_shot_shortcut_kernel, flat_grid((size_t)(B)), dim3(256), 0, h->stream, d_in, batch, h->m, h->n,
+    LDPC_LAUNCH(zero_shot_shortcut_kernel, flat_grid((size_t)(B)), dim3(256), 0, h->stream, d_in, batch, h->m, h->n,
                        d_dec, d_it, d_cv);
     size_t off = 0;
     if ((rc = h->b8_out.ensure(B * (kb + nb) ? B * (kb + nb) : 1))) return rc;
@@ -607,10 +607,10 @@ int ldpc_hip_bp_decode_b8(ldpc_hip_bp *h, const uint8_t *dets_b8, int64_t batch,
     if (h_obs) { d_obs = (uint8_t *)h->b8_out.p; off = B * kb; }
     if (h_dec8) d_dec8 = (uint8_t *)h->b8_out.p + off;
     if (obs_b8 && kb)
-        hipLaunchKernelGGL(observables_b8_kernel, flat_grid((size_t)(B * kb)), dim3(256), 0, h->stream,
+        LDPC_LAUNCH(observables_b8_kernel, flat_grid((size_t)(B * kb)), dim3(256), 0, h->stream,
                            (const int32_t *)h->obs_row_ptr.p, (const int32_t *)h->obs_col_idx.p, h->obs_k, h->n, d_dec, batch, d_obs);
     if (decoding_b8 && nb)
-        hipLaunchKernelGGL(pack_b8_kernel, flat_grid((size_t)(B * nb)), dim3(256), 0, h->stream, d_dec, batch, h->n, d_dec8);
+        LDPC_LAUNCH(pack_b8_kernel, flat_grid((size_t)(B * nb)), dim3(256), 0, h->stream, d_dec, batch, h->n, d_dec8);
     HIPCHK(hipGetLastError());
     if (h_obs && kb) HIPCHK(hipMemcpyAsync(obs_b8, d_obs, B * kb, hipMemcpyDeviceToHost, h->stream));
     if (h_dec8 && nb) HIPCHK(hipMemcpyAsync(decoding_b8, d_dec8, B * nb, hipMemcpyDeviceToHost, h->stream));
@@ -635,13 +635,13 @@ int ldpc_hip_gen_bsc_syndromes(ldpc_hip_bp *h, uint64_t seed, uint64_t threshold
     if (h_e) { if ((rc = h->st_misc.ensure(B * n ? B * n : 1))) return rc; d_e = (uint8_t *)h->st_misc.p; }
     if (h->m > 0) {
         const int64_t total = batch * h->m;
-        hipLaunchKernelGGL(gen_bsc_syndromes_kernel, flat_grid((size_t)(total)), dim3(256), 0,
+        LDPC_LAUNCH(gen_bsc_syndromes_kernel, flat_grid((size_t)(total)), dim3(256), 0,
                            h->stream, h->d_row_ptr, h->d_col_idx, h->m, h->n, seed, threshold, shot0,
                            batch, d_s);
     }
     if (errors && h->n > 0) {
         const int64_t total = batch * h->n;
-        hipLaunchKernelGGL(gen_bsc_errors_kernel, flat_grid((size_t)(total)), dim3(256), 0,
+        LDPC_LAUNCH(gen_bsc_errors_kernel, flat_grid((size_t)(total)), dim3(256), 0,
                            h->stream, h->n, seed, threshold, shot0, batch, d_e);
     }
     HIPCHK(hipGetLastError());

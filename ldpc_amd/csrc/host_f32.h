@@ -52,7 +52,7 @@ int decode_f32(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *deco
     if ((rc = h->f32_llr0.ensure(sizeof(float) * n1))) return rc;
     reset_timing(h, false);
     hipStream_t st = h->stream;
-    if (h->n > 0) hipLaunchKernelGGL(bp_f32_priors_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, st, (const double *)h->d_llr0, h->n, (float *)h->f32_llr0.p);
+    if (h->n > 0) LDPC_LAUNCH(bp_f32_priors_kernel, dim3((unsigned)((h->n + 255) / 256)), dim3(256), 0, st, (const double *)h->d_llr0, h->n, (float *)h->f32_llr0.p);
     HIPCHK(hipGetLastError());
     for (int64_t t0 = 0; t0 < tiles_total; t0 += chunk) {
         const ChunkRange c = chunk_range(t0, chunk, tiles_total, batch);
@@ -61,7 +61,7 @@ int decode_f32(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *deco
         HIPCHK(hipMemsetAsync(h->dec.p, 0, sizeof(uint64_t) * n1 * (size_t)c.tiles, st));
         HIPCHK(hipMemsetAsync(h->counter.p, 0, 16, st));
         if (h->m > 0)
-            hipLaunchKernelGGL(pack_syndromes_kernel, dim3((unsigned)((h->m + 255) / 256), tiles), dim3(256), 0, st, synd + c.b0 * h->m, c.nb, h->m,
+            LDPC_LAUNCH(pack_syndromes_kernel, dim3((unsigned)((h->m + 255) / 256), tiles), dim3(256), 0, st, synd + c.b0 * h->m, c.nb, h->m,
                                (uint64_t *)h->par.p, (uint64_t *)h->nzm.p, (uint64_t *)h->invalid.p, (const int32_t *)nullptr, (const unsigned *)nullptr);
         HIPCHK(hipGetLastError());
         F32Args a = {};
@@ -80,8 +80,8 @@ int decode_f32(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *deco
         // rows (columns) per wavefront, as the FP64 per-pass route chooses them (host_stream.h: stream_start_per_pass)
         a.nodes = h->sw("SPREAD_NODES") > 0 ? h->sw("SPREAD_NODES") : tiles <= 8 ? 1 : tiles < 512 ? 4 : 16;
         if ((rc = chunk_timing_begin(h))) return rc;
-        hipLaunchKernelGGL(bp_f32_state_init_kernel, dim3((tiles + 255) / 256), dim3(256), 0, st, a, (int)tiles);
-        hipLaunchKernelGGL(bp_f32_init_kernel, dim3((unsigned)(h->nnz ? (h->nnz + 63) / 64 : 1), tiles), dim3(256), 0, st, a);
+        LDPC_LAUNCH(bp_f32_state_init_kernel, dim3((tiles + 255) / 256), dim3(256), 0, st, a, (int)tiles);
+        LDPC_LAUNCH(bp_f32_init_kernel, dim3((unsigned)(h->nnz ? (h->nnz + 63) / 64 : 1), tiles), dim3(256), 0, st, a);
         HIPCHK(hipGetLastError());
         // Every kernel of a round loops over the listed tiles, so a launch needs only enough workgroup rows to fill the chip: all the
         // tiles while they are few, else what gives ~16 384 workgroups (at least 256 rows).  Once tiles have finished the list is
@@ -103,19 +103,19 @@ int decode_f32(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *deco
         for (int round = 0; round < h->max_iter; ++round) {
             if (*flag == a.seq) break;  // a look, not a wait: the device has reported the last tile final
             a.round = round;
-            if (round >= 4 && round % 4 == 0) hipLaunchKernelGGL(bp_f32_compact_kernel, dim3(1), dim3(64), 0, st, a);
-            hipLaunchKernelGGL(k.check, dim3(gcx, rows_for(gcx)), dim3(256), 0, st, a);
-            hipLaunchKernelGGL(k.bit, dim3(gbx, rows_for(gbx)), dim3(256), 0, st, a);
-            hipLaunchKernelGGL(bp_f32_synd_kernel, dim3(gsx, rows_for(gsx)), dim3(256), 0, st, a);
-            hipLaunchKernelGGL(bp_f32_finish_kernel, dim3(gfx, rows_for(gfx)), dim3(256), 0, st, a);
+            if (round >= 4 && round % 4 == 0) LDPC_LAUNCH(bp_f32_compact_kernel, dim3(1), dim3(64), 0, st, a);
+            LDPC_LAUNCH(k.check, dim3(gcx, rows_for(gcx)), dim3(256), 0, st, a);
+            LDPC_LAUNCH(k.bit, dim3(gbx, rows_for(gbx)), dim3(256), 0, st, a);
+            LDPC_LAUNCH(bp_f32_synd_kernel, dim3(gsx, rows_for(gsx)), dim3(256), 0, st, a);
+            LDPC_LAUNCH(bp_f32_finish_kernel, dim3(gfx, rows_for(gfx)), dim3(256), 0, st, a);
         }
         HIPCHK(hipGetLastError());
         if ((rc = chunk_timing_end(h))) return rc;
         if (h->n > 0) {
-            hipLaunchKernelGGL(unpack_decoding_kernel, dim3((unsigned)((h->n + 255) / 256), tiles), dim3(256), 0, st, (const uint64_t *)h->dec.p, c.nb, h->n,
+            LDPC_LAUNCH(unpack_decoding_kernel, dim3((unsigned)((h->n + 255) / 256), tiles), dim3(256), 0, st, (const uint64_t *)h->dec.p, c.nb, h->n,
                                decoding + c.b0 * h->n, (const int32_t *)nullptr, (const unsigned *)nullptr);
             if (llr)
-                hipLaunchKernelGGL(bp_f32_transpose_llr_kernel, dim3((unsigned)((h->n + LDPC_WAVE - 1) / LDPC_WAVE), tiles), dim3(256), 0, st,
+                LDPC_LAUNCH(bp_f32_transpose_llr_kernel, dim3((unsigned)((h->n + LDPC_WAVE - 1) / LDPC_WAVE), tiles), dim3(256), 0, st,
                                    (const float *)h->llr_t.p, c.nb, h->n, llr + (size_t)c.b0 * h->n);
         }
         HIPCHK(hipGetLastError());

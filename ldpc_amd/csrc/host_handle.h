@@ -9,6 +9,13 @@
 #include <random>
 #include <atomic>
 #include <thread>
+#include <map>
+#include <mutex>
+#include <string>
+#include <unordered_map>
+
+#include <cxxabi.h>
+#include <unistd.h>
 
 #include <sys/mman.h>
 
@@ -38,6 +45,77 @@ static int fail(int code, const char *fmt, ...) {
     } while (0)
 
 inline std::atomic<long long> g_device_buf_bytes{0};  // bytes every live DeviceBuf of the process holds (ldpc_hip_debug_device_buf_bytes)
+
+// Launch log (ldpc_hip_debug_launch_log / ldpc_hip_debug_launch_log_read, LDPC_HIP_LAUNCH_LOG=<file>): which kernel instantiations the process
+// launched, name -> count.  EVERY launch of the library goes through LDPC_LAUNCH / LDPC_LAUNCH_TIMED / LDPC_LAUNCH_PTR below (tests/test_layout.py
+// looks for strays), which hand the launched host-function pointer to launch_log_note when the log is on; off, a launch costs one load of the flag.
+// A pointer's name is resolved once, when it is first recorded: the runtime's name of the kernel (hipKernelNameRefByPtr -- it names every kernel
+// of the library, those with internal linkage in several translation units included), demangled and cut to the spelling of
+// tools/list_instantiations.py -- "bp_edge8_kernel<12, 3, true>"; "?<pointer>" should it ever know none (the tests that read the log then fail).
+inline std::atomic<bool> g_launch_log_on{false};
+struct LaunchLog {
+    std::mutex mu;  // (the host pipeline and multi_device.h launch from several threads)
+    std::unordered_map<const void *, std::string> names;
+    std::map<std::string, long long> counts;  // since ldpc_hip_debug_launch_log(1)
+    std::map<std::string, long long> total;   // of the process, kept only for LDPC_HIP_LAUNCH_LOG=<file>: the calls above do not clear it
+    bool by_call = false;
+    std::string file;                         // empty: no LDPC_HIP_LAUNCH_LOG
+};
+inline LaunchLog &launch_log() {
+    static LaunchLog *const log = new LaunchLog;  // never destroyed: the table is written out while the library unloads (host_setup.h)
+    return *log;
+}
+
+inline std::string launch_log_spelling(const char *mangled) {
+    std::string s = mangled;
+    if (s.size() > 3 && s.compare(s.size() - 3, 3, ".kd") == 0) s.resize(s.size() - 3);
+    int status = -1;
+    char *d = abi::__cxa_demangle(s.c_str(), nullptr, nullptr, &status);
+    if ((status != 0 || !d) && s.find('.') != std::string::npos) {  // (a kernel with internal linkage may carry a ".suffix" of its translation unit)
+        std::free(d);
+        d = abi::__cxa_demangle(s.substr(0, s.find('.')).c_str(), nullptr, nullptr, &status);
+    }
+    if (status == 0 && d) s = d;
+    std::free(d);
+    for (size_t at; (at = s.find("void ")) != std::string::npos;) s.erase(at, 5);
+    if (s.find('(') != std::string::npos) s.resize(s.find('('));
+    while (!s.empty() && s.back() == ' ') s.pop_back();
+    return s;
+}
+
+inline void launch_log_note(const void *host_fn, hipStream_t stream) {
+    LaunchLog &log = launch_log();
+    std::lock_guard<std::mutex> lock(log.mu);
+    auto it = log.names.find(host_fn);
+    if (it == log.names.end()) {
+        const char *ref = hipKernelNameRefByPtr(host_fn, stream);
+        std::string name = ref && *ref ? launch_log_spelling(ref) : std::string();
+        if (name.empty()) {
+            char buf[32];
+            snprintf(buf, sizeof buf, "?%p", host_fn);
+            name = buf;
+        }
+        it = log.names.emplace(host_fn, std::move(name)).first;
+    }
+    if (log.by_call) ++log.counts[it->second];
+    if (!log.file.empty()) ++log.total[it->second];
+}
+
+// `kern`: a kernel's name -- a template-id in its own parentheses, (bp_edge0_kernel<M, F>) -- or a pointer a plan picked
+#define LDPC_LAUNCH(kern, grid, block, dyn, stream, ...)                                                      \
+    do {                                                                                                      \
+        if (g_launch_log_on.load(std::memory_order_relaxed)) launch_log_note((const void *)(kern), (stream)); \
+        hipLaunchKernelGGL(kern, grid, block, dyn, stream, __VA_ARGS__);                                      \
+    } while (0)
+// ... with the timing events on the dispatch itself (hipExtLaunchKernelGGL)
+#define LDPC_LAUNCH_TIMED(kern, grid, block, dyn, stream, ev_start, ev_stop, flags, ...)                      \
+    do {                                                                                                      \
+        if (g_launch_log_on.load(std::memory_order_relaxed)) launch_log_note((const void *)(kern), (stream)); \
+        hipExtLaunchKernelGGL(kern, grid, block, dyn, stream, ev_start, ev_stop, flags, __VA_ARGS__);         \
+    } while (0)
+// ... with the arguments as an array of pointers (hipLaunchKernel); an expression: the launch's hipError_t
+#define LDPC_LAUNCH_PTR(fn, grid, block, params, dyn, stream) \
+    ((g_launch_log_on.load(std::memory_order_relaxed) ? launch_log_note((const void *)(fn), (stream)) : (void)0), hipLaunchKernel((fn), grid, block, params, dyn, stream))
 
 struct DeviceBuf {  // grow-only device allocation, freed with its owner (on the device that is current then: see ldpc_hip_bp_destroy)
     void *p = nullptr;

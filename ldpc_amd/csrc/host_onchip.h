@@ -30,7 +30,7 @@ static int decode_small(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint
         const int64_t tiles = (batch + LDPC_WAVE - 1) / LDPC_WAVE;
         if ((rc = h->rowp_llr.ensure(sizeof(double) * (size_t)h->n * LDPC_WAVE * (size_t)tiles))) return rc;
         const dim3 gp((unsigned)((h->n + LDPC_WAVE - 1) / LDPC_WAVE), (unsigned)(tiles < 32768 ? tiles : 32768));
-        hipLaunchKernelGGL(row_priors_kernel, gp, dim3(256), 0, h->stream, h->row_probs, batch, h->n, (const double *)h->d_llr0, (double *)h->rowp_llr.p);
+        LDPC_LAUNCH(row_priors_kernel, gp, dim3(256), 0, h->stream, h->row_probs, batch, h->n, (const double *)h->d_llr0, (double *)h->rowp_llr.p);
         HIPCHK(hipGetLastError());
         a.llr0_t = (const double *)h->rowp_llr.p;
     }
@@ -45,7 +45,7 @@ static int decode_small(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint
     if (groups > resident) groups = resident;
     h->accumulated_ms = 0.f;
     HIPCHK(hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(kern, dim3((unsigned)groups), dim3(256), (unsigned)dyn, h->stream, a);
+    LDPC_LAUNCH(kern, dim3((unsigned)groups), dim3(256), (unsigned)dyn, h->stream, a);
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     h->timed = true;
     HIPCHK(hipGetLastError());
@@ -308,8 +308,8 @@ static int decode_wave_ps(ldpc_hip_bp *h, const WavePsPlan &p, const uint8_t *sy
     const bool timed = !(h->untimed_call && static_teams);
     // (the timing events ride on the dispatch itself -- hipExtLaunchKernelGGL attaches them to the kernel's own start and completion -- instead of
     // two hipEventRecord around it: those are a barrier packet each on the stream, 5.8 us of a 0.38 ms step, profiles/r6_c5_step_fusion.txt)
-    if (timed) hipExtLaunchKernelGGL(p.kern, dim3((unsigned)groups), dim3((unsigned)(p.waves * 64)), (unsigned)dyn, h->stream, h->ev0, h->ev1, 0, a);
-    else hipLaunchKernelGGL(p.kern, dim3((unsigned)groups), dim3((unsigned)(p.waves * 64)), (unsigned)dyn, h->stream, a);
+    if (timed) LDPC_LAUNCH_TIMED(p.kern, dim3((unsigned)groups), dim3((unsigned)(p.waves * 64)), (unsigned)dyn, h->stream, h->ev0, h->ev1, 0, a);
+    else LDPC_LAUNCH(p.kern, dim3((unsigned)groups), dim3((unsigned)(p.waves * 64)), (unsigned)dyn, h->stream, a);
     h->timed = timed;
     HIPCHK(hipGetLastError());
 #ifdef LDPC_WPS_PROF  // measurement build: print and clear the kernel's cycle sums (tools/wave_ps_phases.py)
@@ -347,7 +347,7 @@ static int decode_wave(ldpc_hip_bp *h, const WavePlan &p, const uint8_t *synd, i
     a.llr0 = h->d_llr0;
     if (p.prior_global) {
         if ((rc = h->w_prior.ensure(sizeof(double) * (size_t)(p.np + 2)))) return rc;
-        hipLaunchKernelGGL(wave_prior_pad_kernel, dim3((unsigned)((p.np + 2 + 255) / 256)), dim3(256), 0, h->stream, h->d_llr0, h->n, p.np, (double *)h->w_prior.p);
+        LDPC_LAUNCH(wave_prior_pad_kernel, dim3((unsigned)((p.np + 2 + 255) / 256)), dim3(256), 0, h->stream, h->d_llr0, h->n, p.np, (double *)h->w_prior.p);
         a.prior_g = (const double *)h->w_prior.p;
     }
     a.synd = synd; a.decoding = decoding; a.llr = llr; a.iters = iters; a.conv = conv;
@@ -366,8 +366,8 @@ static int decode_wave(ldpc_hip_bp *h, const WavePlan &p, const uint8_t *synd, i
     const bool timed = !(h->untimed_call && static_teams);
     // (the timing events ride on the dispatch itself -- hipExtLaunchKernelGGL attaches them to the kernel's own start and completion -- instead of
     // two hipEventRecord around it: those are a barrier packet each on the stream, 5.8 us of a 0.38 ms step, profiles/r6_c5_step_fusion.txt)
-    if (timed) hipExtLaunchKernelGGL(p.kern, dim3((unsigned)groups), dim3((unsigned)(p.waves * 64)), (unsigned)dyn, h->stream, h->ev0, h->ev1, 0, a);
-    else hipLaunchKernelGGL(p.kern, dim3((unsigned)groups), dim3((unsigned)(p.waves * 64)), (unsigned)dyn, h->stream, a);
+    if (timed) LDPC_LAUNCH_TIMED(p.kern, dim3((unsigned)groups), dim3((unsigned)(p.waves * 64)), (unsigned)dyn, h->stream, h->ev0, h->ev1, 0, a);
+    else LDPC_LAUNCH(p.kern, dim3((unsigned)groups), dim3((unsigned)(p.waves * 64)), (unsigned)dyn, h->stream, a);
     h->timed = timed;
     HIPCHK(hipGetLastError());
     return LDPC_HIP_OK;
@@ -463,7 +463,7 @@ static int decode_edge(ldpc_hip_bp *h, const EdgePlan &p, const uint8_t *synd, i
     if ((rc = ensure_edge_tables(h, p))) return rc;
     const int slots = p.rounds * 64;
     // (the priors may have changed since the last call: ldpc_hip_bp_set_channel)
-    hipLaunchKernelGGL(edge_prior_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, h->stream, h->d_llr0, (const int32_t *)h->e_scol.p,
+    LDPC_LAUNCH(edge_prior_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, h->stream, h->d_llr0, (const int32_t *)h->e_scol.p,
                        (const uint8_t *)h->e_kind.p, slots, (double *)h->e_prior.p);
     EdgeArgs a = {};
     a.m = h->m; a.n = h->n; a.max_iter = h->max_iter;
@@ -482,7 +482,7 @@ static int decode_edge(ldpc_hip_bp *h, const EdgePlan &p, const uint8_t *synd, i
     if ((rc = edge_work_split(h, p.rounds, batch, groups, a))) return rc;
     h->accumulated_ms = 0.f;
     HIPCHK(hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(p.kern, dim3((unsigned)groups), dim3(64), (unsigned)dyn, h->stream, a);
+    LDPC_LAUNCH(p.kern, dim3((unsigned)groups), dim3(64), (unsigned)dyn, h->stream, a);
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     h->timed = true;
     HIPCHK(hipGetLastError());
@@ -558,7 +558,7 @@ static int decode_edge8(ldpc_hip_bp *h, const Edge8Plan &p, const uint8_t *synd,
     int rc;
     if ((rc = ensure_edge8_tables(h, p))) return rc;
     const int slots = p.rounds * 64;
-    hipLaunchKernelGGL(edge_prior_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, h->stream, h->d_llr0, (const int32_t *)h->e_scol.p,
+    LDPC_LAUNCH(edge_prior_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, h->stream, h->d_llr0, (const int32_t *)h->e_scol.p,
                        (const uint8_t *)h->e_kind.p, slots, (double *)h->e_prior.p);
     Edge8Args a = {};
     a.m = h->m; a.n = h->n; a.max_iter = h->max_iter;
@@ -576,7 +576,7 @@ static int decode_edge8(ldpc_hip_bp *h, const Edge8Plan &p, const uint8_t *synd,
     if ((rc = edge_work_split(h, p.rounds, batch, groups, a))) return rc;
     h->accumulated_ms = 0.f;
     HIPCHK(hipEventRecord(h->ev0, h->stream));
-    hipLaunchKernelGGL(p.kern, dim3((unsigned)groups), dim3(64), (unsigned)dyn, h->stream, a);
+    LDPC_LAUNCH(p.kern, dim3((unsigned)groups), dim3(64), (unsigned)dyn, h->stream, a);
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     h->timed = true;
     HIPCHK(hipGetLastError());
@@ -688,7 +688,7 @@ int decode_onchip_resident(ldpc_hip_bp *h, bool want_llr, bool *took) {
         if (dyn > 48u * 1024u) HIPCHK(hipFuncSetAttribute((const void *)p.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
         __atomic_store_n(mail + 3, 0u, __ATOMIC_SEQ_CST);
         __atomic_store_n(mail + 2, 1u, __ATOMIC_SEQ_CST);
-        hipLaunchKernelGGL(p.kern, dim3(1), dim3((unsigned)(p.waves * 64)), (unsigned)dyn, r.stream, a);
+        LDPC_LAUNCH(p.kern, dim3(1), dim3((unsigned)(p.waves * 64)), (unsigned)dyn, r.stream, a);
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(r.ended, r.stream));
         std::memcpy(r.key, key, sizeof key);

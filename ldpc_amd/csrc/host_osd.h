@@ -212,7 +212,7 @@ static int launch_osd(ldpc_hip_bp *h, const OsdPlan &P, const OsdArgs &a) {
     OsdBigArgs A = P.big_args;
     A.o = a;
     void *params[] = {P.big ? (void *)&A : (void *)&a};
-    HIPCHK(hipLaunchKernel(P.kernel, dim3((unsigned)P.grid), dim3((unsigned)(P.waves * 64)), params, P.lds, h->stream));
+    HIPCHK(LDPC_LAUNCH_PTR(P.kernel, dim3((unsigned)P.grid), dim3((unsigned)(P.waves * 64)), params, P.lds, h->stream));
     return LDPC_HIP_OK;
 }
 
@@ -248,7 +248,7 @@ static int osd_second_pass(ldpc_hip_bp *h, const OsdPlan &P, const OsdArgs &a) {
     X.hw = (a.n + 63) / 64;
     const size_t xl = osd_exact_lds_bytes(a.m);
     if (xl > 48u * 1024u) HIPCHK(hipFuncSetAttribute((const void *)osd_exact_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)xl));
-    hipLaunchKernelGGL(osd_exact_kernel, dim3((unsigned)slots), dim3(256), (unsigned)xl, h->stream, X);
+    LDPC_LAUNCH(osd_exact_kernel, dim3((unsigned)slots), dim3(256), (unsigned)xl, h->stream, X);
     HIPCHK(hipGetLastError());
     OsdArgs a2 = a;
     a2.synd = X.corrected;
@@ -293,7 +293,7 @@ int bposd_device(ldpc_hip_bp *h, int osd_method, int osd_order, const uint8_t *s
     a.status = P.writes_status ? (uint8_t *)h->osd_status.p : nullptr;
     if (!h->osd_hook.done) {  // list the unconverged rows
         HIPCHK(hipMemsetAsync(osd_ctr, 0, OSD_COUNTER_BYTES, h->stream));
-        hipLaunchKernelGGL(osd_collect_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, h->stream, conv, batch,
+        LDPC_LAUNCH(osd_collect_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, h->stream, conv, batch,
                            (int32_t *)h->osd_list.p, osd_ctr, (uint8_t *)h->osd_status.p);
     }
     h->osd_status_rows = batch;
@@ -301,7 +301,7 @@ int bposd_device(ldpc_hip_bp *h, int osd_method, int osd_order, const uint8_t *s
     if (P.big && h->h_flag) HIPCHK(hipMemcpyAsync(&h->h_flag[8], a.counters, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));  // rows listed: the next call's guide
     if (!P.writes_status) {  // did every OSD output solve its syndrome?  (the array was cleared on the way -- by the BP kernel or by osd_collect_kernel)
         const int64_t blocks = batch < 4096 ? batch : 4096;
-        hipLaunchKernelGGL(osd_status_kernel, dim3((unsigned)(blocks ? blocks : 1)), dim3(256), 0, h->stream, a, (uint8_t *)h->osd_status.p);
+        LDPC_LAUNCH(osd_status_kernel, dim3((unsigned)(blocks ? blocks : 1)), dim3(256), 0, h->stream, a, (uint8_t *)h->osd_status.p);
         HIPCHK(hipGetLastError());
     }
     return osd_second_pass(h, P, a);

@@ -40,11 +40,11 @@ static int level_waves_for(const ldpc_hip_bp *h, double per_level) {
 static int chunk_outputs(ldpc_hip_bp *h, const ChunkRange &c, uint8_t *decoding, double *llr) {
     if (h->n > 0 && decoding) {
         dim3 g((unsigned)((h->n + 255) / 256), (unsigned)c.tiles);
-        hipLaunchKernelGGL(unpack_decoding_kernel, g, dim3(256), 0, h->stream, (const uint64_t *)h->dec.p, c.nb, h->n, decoding + c.b0 * h->n);
+        LDPC_LAUNCH(unpack_decoding_kernel, g, dim3(256), 0, h->stream, (const uint64_t *)h->dec.p, c.nb, h->n, decoding + c.b0 * h->n);
     }
     if (h->n > 0 && llr) {
         dim3 gt((unsigned)((h->n + LDPC_WAVE - 1) / LDPC_WAVE), (unsigned)c.tiles);
-        hipLaunchKernelGGL(transpose_llr_kernel, gt, dim3(256), 0, h->stream, (const double *)h->llr_t.p, c.nb, h->n, llr + (size_t)c.b0 * h->n);
+        LDPC_LAUNCH(transpose_llr_kernel, gt, dim3(256), 0, h->stream, (const double *)h->llr_t.p, c.nb, h->n, llr + (size_t)c.b0 * h->n);
     }
     HIPCHK(hipGetLastError());
     return LDPC_HIP_OK;
@@ -56,7 +56,7 @@ static int collect_unconverged(ldpc_hip_bp *h, const uint8_t *conv, int64_t rows
     if ((rc = h->osd_list.ensure((size_t)rows * sizeof(int32_t))) || (rc = h->osd_counters.ensure(2 * sizeof(unsigned)))) return rc;
     if (!h->h_counters) HIPCHK(hipHostMalloc((void **)&h->h_counters, 16, hipHostMallocDefault));
     HIPCHK(hipMemsetAsync(h->osd_counters.p, 0, 2 * sizeof(unsigned), h->stream));
-    hipLaunchKernelGGL(osd_collect_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, h->stream, conv, rows, (int32_t *)h->osd_list.p, (unsigned *)h->osd_counters.p);
+    LDPC_LAUNCH(osd_collect_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, h->stream, conv, rows, (int32_t *)h->osd_list.p, (unsigned *)h->osd_counters.p);
     HIPCHK(hipMemcpyAsync(&h->h_counters[2], h->osd_counters.p, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));  // the size of what is left is needed on the host
     *count = (int64_t)h->h_counters[2];
@@ -68,11 +68,11 @@ static int scatter_pass_outputs(ldpc_hip_bp *h, const int32_t *list, int64_t cnt
     const size_t C = (size_t)cnt;
     hipStream_t st = h->stream;
     if (decoding && h->n > 0) {
-        hipLaunchKernelGGL(scatter_rows_kernel<uint8_t>, flat_grid(C * (size_t)h->n), dim3(256), 0, st, (const uint8_t *)h->rp_dec.p, list, cnt, h->n, decoding);
-        if (llr) hipLaunchKernelGGL(scatter_rows_kernel<double>, flat_grid(C * (size_t)h->n), dim3(256), 0, st, (const double *)h->rp_llr.p, list, cnt, h->n, llr);
+        LDPC_LAUNCH(scatter_rows_kernel<uint8_t>, flat_grid(C * (size_t)h->n), dim3(256), 0, st, (const uint8_t *)h->rp_dec.p, list, cnt, h->n, decoding);
+        if (llr) LDPC_LAUNCH(scatter_rows_kernel<double>, flat_grid(C * (size_t)h->n), dim3(256), 0, st, (const double *)h->rp_llr.p, list, cnt, h->n, llr);
     }
-    if (iters) hipLaunchKernelGGL(scatter_rows_kernel<int32_t>, flat_grid(C), dim3(256), 0, st, (const int32_t *)h->rp_iters.p, list, cnt, 1, iters);
-    if (conv) hipLaunchKernelGGL(scatter_rows_kernel<uint8_t>, flat_grid(C), dim3(256), 0, st, (const uint8_t *)h->rp_conv.p, list, cnt, 1, conv);
+    if (iters) LDPC_LAUNCH(scatter_rows_kernel<int32_t>, flat_grid(C), dim3(256), 0, st, (const int32_t *)h->rp_iters.p, list, cnt, 1, iters);
+    if (conv) LDPC_LAUNCH(scatter_rows_kernel<uint8_t>, flat_grid(C), dim3(256), 0, st, (const uint8_t *)h->rp_conv.p, list, cnt, 1, conv);
     HIPCHK(hipGetLastError());
     return LDPC_HIP_OK;
 }
@@ -242,7 +242,7 @@ static int serial_var_init_segments(ldpc_hip_bp *h, const double **out) {
     int rc;
     if ((rc = h->ser_var_init.ensure(sizeof(double) * (size_t)h->nnz * LDPC_WAVE))) return rc;
     const dim3 g((unsigned)((h->nnz + 3) / 4));
-    with_method_math(h, [&](auto M, auto F) { hipLaunchKernelGGL((serial_var_init_kernel<M, F>), g, dim3(256), 0, h->stream, h->d_llr0, h->d_col_idx, h->nnz, (double *)h->ser_var_init.p); });
+    with_method_math(h, [&](auto M, auto F) { LDPC_LAUNCH((serial_var_init_kernel<M, F>), g, dim3(256), 0, h->stream, h->d_llr0, h->d_col_idx, h->nnz, (double *)h->ser_var_init.p); });
     HIPCHK(hipGetLastError());
     *out = (const double *)h->ser_var_init.p;
     return LDPC_HIP_OK;
@@ -350,7 +350,7 @@ static int ensure_edge0(ldpc_hip_bp *h) {
     int rc;
     if ((rc = h->d_edge0.ensure(sizeof(double) * (size_t)h->n))) return rc;
     const dim3 ge((unsigned)((h->n + 255) / 256));
-    with_method_math(h, [&](auto M, auto F) { hipLaunchKernelGGL((serial_edge0_kernel<M, F>), ge, dim3(256), 0, h->stream, h->d_llr0, h->n, (double *)h->d_edge0.p); });
+    with_method_math(h, [&](auto M, auto F) { LDPC_LAUNCH((serial_edge0_kernel<M, F>), ge, dim3(256), 0, h->stream, h->d_llr0, h->n, (double *)h->d_edge0.p); });
     HIPCHK(hipGetLastError());
     return LDPC_HIP_OK;
 }
@@ -361,7 +361,7 @@ static bool first_iteration_from_tables(const ldpc_hip_bp *h) { return h->order_
 static int ensure_first_iteration_tables(ldpc_hip_bp *h, const SerialStreamPlan &sp) {
     int rc;
     if ((rc = ensure_edge0(h)) || (rc = h->ser_pos_e0.ensure(sizeof(double) * 16 * (size_t)h->n))) return rc;
-    hipLaunchKernelGGL(serial_pos_e0_kernel, dim3((unsigned)((h->n * 16 + 255) / 256)), dim3(256), 0, h->stream, (const int32_t *)h->ser_pos_tab.p, h->d_col_idx,
+    LDPC_LAUNCH(serial_pos_e0_kernel, dim3((unsigned)((h->n * 16 + 255) / 256)), dim3(256), 0, h->stream, (const int32_t *)h->ser_pos_tab.p, h->d_col_idx,
                        (const double *)h->d_edge0.p, h->n, sp.dc * (sp.dr - 1), (double *)h->ser_pos_e0.p);
     HIPCHK(hipGetLastError());
     return LDPC_HIP_OK;
@@ -439,7 +439,7 @@ static int decode_serial_pass(ldpc_hip_bp *h, int max_iter, const uint8_t *synd,
             HIPCHK(hipMemsetAsync(h->llr_t.p, 0, per_tile_llr * (size_t)c.tiles, st));
         if (h->m > 0) {
             dim3 g((unsigned)((h->m + 255) / 256), (unsigned)c.tiles);
-            hipLaunchKernelGGL(pack_syndromes_kernel, g, dim3(256), 0, st, synd + c.b0 * h->m, c.nb, h->m,
+            LDPC_LAUNCH(pack_syndromes_kernel, g, dim3(256), 0, st, synd + c.b0 * h->m, c.nb, h->m,
                                (uint64_t *)h->par.p, (uint64_t *)h->nzm.p, (uint64_t *)h->invalid.p);
         }
         SerialArgs a = {};
@@ -462,7 +462,7 @@ static int decode_serial_pass(ldpc_hip_bp *h, int max_iter, const uint8_t *synd,
                 a.pos_e0 = (const double *)h->ser_pos_e0.p;
             }
         }
-        hipLaunchKernelGGL(kern, dim3((unsigned)c.tiles), dim3((unsigned)(64 * waves)), (unsigned)sl.dyn, st, a);
+        LDPC_LAUNCH(kern, dim3((unsigned)c.tiles), dim3((unsigned)(64 * waves)), (unsigned)sl.dyn, st, a);
         if ((rc = chunk_timing_end(h)) || (rc = chunk_outputs(h, c, decoding, llr))) return rc;
     }
     return LDPC_HIP_OK;
@@ -714,7 +714,7 @@ static int decode_serial_relative_lds(ldpc_hip_bp *h, const uint8_t *synd, int64
         if (batch > 1 && h->max_iter > 0 && pre <= 150u * 1024u && (int)h->sched_state.size() == h->n) {
             if ((rc = h->rl_first.ensure(n1 * sizeof(int32_t)))) return rc;
             if ((rc = set_dynamic_lds(rel_first_order_kernel, pre))) return rc;
-            hipLaunchKernelGGL(rel_first_order_kernel, dim3(1), dim3(64), (unsigned)pre, st, h->d_llr0, (const int32_t *)h->sched_order0.p, h->n, (int32_t *)h->rl_first.p);
+            LDPC_LAUNCH(rel_first_order_kernel, dim3(1), dim3(64), (unsigned)pre, st, h->d_llr0, (const int32_t *)h->sched_order0.p, h->n, (int32_t *)h->rl_first.p);
             HIPCHK(hipGetLastError());
             a.first_order = (const int32_t *)h->rl_first.p;
         }
@@ -735,7 +735,7 @@ static int decode_serial_relative_lds(ldpc_hip_bp *h, const uint8_t *synd, int64
     h->timed_mid = false;
     h->timed_prev = h->timed_prev_mid = false;
     HIPCHK(hipEventRecord(h->ev0, st));
-    hipLaunchKernelGGL(kern, dim3((unsigned)groups), dim3((unsigned)(waves * 64)), (unsigned)dyn, st, a);
+    LDPC_LAUNCH(kern, dim3((unsigned)groups), dim3((unsigned)(waves * 64)), (unsigned)dyn, st, a);
     HIPCHK(hipEventRecord(h->ev1, st));
     h->timed = true;
     HIPCHK(hipGetLastError());
@@ -783,7 +783,7 @@ static int decode_serial_relative(ldpc_hip_bp *h, const uint8_t *synd, int64_t b
         HIPCHK(hipMemsetAsync(h->invalid.p, 0, sizeof(uint64_t) * (size_t)c.tiles, st));
         if (h->m > 0) {
             dim3 g((unsigned)((h->m + 255) / 256), (unsigned)c.tiles);
-            hipLaunchKernelGGL(pack_syndromes_kernel, g, dim3(256), 0, st, synd + c.b0 * h->m, c.nb, h->m,
+            LDPC_LAUNCH(pack_syndromes_kernel, g, dim3(256), 0, st, synd + c.b0 * h->m, c.nb, h->m,
                                (uint64_t *)h->par.p, (uint64_t *)h->nzm.p, (uint64_t *)h->invalid.p);
         }
         RelArgs a = {};
@@ -800,7 +800,7 @@ static int decode_serial_relative(ldpc_hip_bp *h, const uint8_t *synd, int64_t b
         a.iters = iters ? iters + c.b0 : nullptr;
         a.conv = conv ? conv + c.b0 : nullptr;
         if ((rc = chunk_timing_begin(h))) return rc;
-        hipLaunchKernelGGL(kern, dim3((unsigned)c.tiles), dim3(64), 0, st, a);
+        LDPC_LAUNCH(kern, dim3((unsigned)c.tiles), dim3(64), 0, st, a);
         if ((rc = chunk_timing_end(h)) || (rc = chunk_outputs(h, c, nullptr, llr))) return rc;  // (the kernel writes the decisions itself)
         last_tiles = c.tiles;
     }
@@ -835,7 +835,7 @@ static int serial_stream_launch(ldpc_hip_bp *h, const SerialStreamPlan &sp, int 
         HIPCHK(hipMemsetAsync(h->dcur.p, 0, sizeof(uint64_t) * n1 * (size_t)tiles, st));
         if (llr && !h->order_visits_all) HIPCHK(hipMemsetAsync(h->llr_t.p, 0, sizeof(double) * n1 * LDPC_WAVE * (size_t)tiles, st));  // bits the order never visits report 0
         dim3 g((unsigned)((h->m + 255) / 256), (unsigned)(tiles < 32768 ? tiles : 32768));
-        hipLaunchKernelGGL(pack_syndromes_kernel, g, dim3(256), 0, st, synd, rows, h->m, (uint64_t *)h->par.p, (uint64_t *)h->nzm.p, (uint64_t *)h->invalid.p,
+        LDPC_LAUNCH(pack_syndromes_kernel, g, dim3(256), 0, st, synd, rows, h->m, (uint64_t *)h->par.p, (uint64_t *)h->nzm.p, (uint64_t *)h->invalid.p,
                            (const int32_t *)nullptr, (const unsigned *)nullptr);
     }
     SerialStreamLaunch sl;
@@ -854,14 +854,14 @@ static int serial_stream_launch(ldpc_hip_bp *h, const SerialStreamPlan &sp, int 
         a.edge0 = (const double *)h->d_edge0.p;
         a.pos_e0 = (const double *)h->ser_pos_e0.p;
     }
-    hipLaunchKernelGGL(sl.kern, dim3((unsigned)tiles), dim3((unsigned)(64 * sl.waves)), (unsigned)sl.dyn, st, a);
+    LDPC_LAUNCH(sl.kern, dim3((unsigned)tiles), dim3((unsigned)(64 * sl.waves)), (unsigned)sl.dyn, st, a);
     HIPCHK(hipGetLastError());
     {   // (these kernels loop over the tiles beyond their grid)
         const unsigned gy = (unsigned)(tiles < 32768 ? tiles : 32768);
-        hipLaunchKernelGGL(unpack_decoding_kernel, dim3((unsigned)((h->n + 255) / 256), gy), dim3(256), 0, st, (const uint64_t *)h->dec.p, rows, h->n, decoding, row_map,
+        LDPC_LAUNCH(unpack_decoding_kernel, dim3((unsigned)((h->n + 255) / 256), gy), dim3(256), 0, st, (const uint64_t *)h->dec.p, rows, h->n, decoding, row_map,
                            (const unsigned *)nullptr);
         if (llr)
-            hipLaunchKernelGGL(transpose_llr_kernel, dim3((unsigned)((h->n + LDPC_WAVE - 1) / LDPC_WAVE), gy), dim3(256), 0, st, (const double *)h->llr_t.p, rows, h->n, llr, row_map,
+            LDPC_LAUNCH(transpose_llr_kernel, dim3((unsigned)((h->n + LDPC_WAVE - 1) / LDPC_WAVE), gy), dim3(256), 0, st, (const double *)h->llr_t.p, rows, h->n, llr, row_map,
                                (const unsigned *)nullptr);
     }
     HIPCHK(hipGetLastError());
@@ -884,7 +884,7 @@ static int serial_lane_launch_kernel(ldpc_hip_bp *h, void (*kern)(const Args), A
     int rc;
     if ((rc = set_dynamic_lds(kern, dyn))) return rc;
     const int threads = h->sw("SER_LANE_THREADS") > 0 ? h->sw("SER_LANE_THREADS") : rows <= 2048 ? 1024 : 512;
-    hipLaunchKernelGGL(kern, dim3((unsigned)rows), dim3((unsigned)threads), (unsigned)dyn, h->stream, a);
+    LDPC_LAUNCH(kern, dim3((unsigned)rows), dim3((unsigned)threads), (unsigned)dyn, h->stream, a);
     HIPCHK(hipGetLastError());
     return LDPC_HIP_OK;
 }
@@ -994,8 +994,8 @@ static int decode_serial_streamed(ldpc_hip_bp *h, const SerialStreamPlan &sp, co
         const int nxt = cur ^ 1;
         if ((rc = lists[nxt]->ensure(C * sizeof(int32_t))) || (rc = synds[nxt]->ensure(C * m1))) return rc;
         if (identity) HIPCHK(hipMemcpyAsync(lists[nxt]->p, sub, C * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-        else hipLaunchKernelGGL(compose_lists_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, (const int32_t *)lists[cur]->p, sub, cnt, (int32_t *)lists[nxt]->p);
-        hipLaunchKernelGGL(gather_rows_kernel<uint8_t>, flat_grid(C * m1), dim3(256), 0, st, cur_synd, sub, cnt, h->m, (uint8_t *)synds[nxt]->p);
+        else LDPC_LAUNCH(compose_lists_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, (const int32_t *)lists[cur]->p, sub, cnt, (int32_t *)lists[nxt]->p);
+        LDPC_LAUNCH(gather_rows_kernel<uint8_t>, flat_grid(C * m1), dim3(256), 0, st, cur_synd, sub, cnt, h->m, (uint8_t *)synds[nxt]->p);
         HIPCHK(hipGetLastError());
         if ((rc = h->rp_iters.ensure(C * 4)) || (rc = h->rp_conv.ensure(C))) return rc;
         // A compute unit holds one 16-wavefront tile: a pass of 267 tiles is a round of 256 and a round of 11 that takes as long.  The rows
@@ -1012,7 +1012,7 @@ static int decode_serial_streamed(ldpc_hip_bp *h, const SerialStreamPlan &sp, co
             const int64_t at = cnt - n_lane;  // the last n_lane rows of the list
             double *rows_state = (double *)((char *)other->p + per_tile_msg * (size_t)tiles2);
             if ((rc = h->rp_dec.ensure((size_t)n_lane * n1)) || (llr && (rc = h->rp_llr.ensure((size_t)n_lane * n1 * 8)))) return rc;
-            hipLaunchKernelGGL(serial_rows_from_tiles_kernel, dim3((unsigned)((h->nnz + 1023) / 1024), (unsigned)n_lane), dim3(256), 0, st, (const double *)state->p, sub + at, n_lane,
+            LDPC_LAUNCH(serial_rows_from_tiles_kernel, dim3((unsigned)((h->nnz + 1023) / 1024), (unsigned)n_lane), dim3(256), 0, st, (const double *)state->p, sub + at, n_lane,
                                h->nnz, rows_state);
             HIPCHK(hipGetLastError());
             if ((rc = serial_lane_launch(h, sp, it, rows_state, (const uint8_t *)synds[nxt]->p + (size_t)at * m1, n_lane, (uint8_t *)h->rp_dec.p, llr ? (double *)h->rp_llr.p : nullptr,
@@ -1023,7 +1023,7 @@ static int decode_serial_streamed(ldpc_hip_bp *h, const SerialStreamPlan &sp, co
         // the others' message state, lane by lane, into dense tiles of the other array
         const int epw = 16;
         const dim3 gg((unsigned)((h->nnz + 4 * epw - 1) / (4 * epw)), (unsigned)(tiles2 < 32768 ? tiles2 : 32768));
-        hipLaunchKernelGGL(gather_lane_state_kernel, gg, dim3(256), 0, st, (const double *)state->p, sub, keep, h->nnz, epw, (double *)other->p, (const unsigned *)nullptr);
+        LDPC_LAUNCH(gather_lane_state_kernel, gg, dim3(256), 0, st, (const double *)state->p, sub, keep, h->nnz, epw, (double *)other->p, (const unsigned *)nullptr);
         HIPCHK(hipGetLastError());
         std::swap(state, other);
         cur = nxt;
@@ -1090,7 +1090,7 @@ int decode_serial(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
         (rc = h->rp_conv.ensure(C)) || (llr && (rc = h->rp_llr.ensure(C * n1 * 8)))) return rc;
     const int32_t *list = (const int32_t *)h->osd_list.p;
     if (h->m > 0)
-        hipLaunchKernelGGL(gather_rows_kernel<uint8_t>, flat_grid(C * h->m), dim3(256), 0, h->stream, synd, list, cnt, h->m, (uint8_t *)h->rp_synd.p);
+        LDPC_LAUNCH(gather_rows_kernel<uint8_t>, flat_grid(C * h->m), dim3(256), 0, h->stream, synd, list, cnt, h->m, (uint8_t *)h->rp_synd.p);
     HIPCHK(hipGetLastError());
     if ((rc = decode_serial_pass(h, h->max_iter, (const uint8_t *)h->rp_synd.p, cnt, (uint8_t *)h->rp_dec.p,
                                  llr ? (double *)h->rp_llr.p : nullptr, (int32_t *)h->rp_iters.p, (uint8_t *)h->rp_conv.p))) return rc;
@@ -1150,7 +1150,7 @@ int soft_info_device(ldpc_hip_bp *h, const double *soft, int64_t batch, double c
         HIPCHK(hipMemsetAsync(h->dcur.p, 0, sizeof(uint64_t) * n1 * (size_t)c.tiles, st));
         if (h->m > 0) {
             dim3 g((unsigned)((h->m + 3) / 4), (unsigned)c.tiles);
-            hipLaunchKernelGGL(softinfo_prepare_kernel, g, dim3(256), 0, st, soft + (size_t)c.b0 * h->m, c.nb, h->m, sigma,
+            LDPC_LAUNCH(softinfo_prepare_kernel, g, dim3(256), 0, st, soft + (size_t)c.b0 * h->m, c.nb, h->m, sigma,
                                (double *)h->soft_S.p, (uint64_t *)h->par.p);
         }
         SoftArgs a = {};
@@ -1172,11 +1172,11 @@ int soft_info_device(ldpc_hip_bp *h, const double *soft, int64_t batch, double c
         a.conv = conv ? conv + c.b0 : nullptr;
         a.lvl_ptr = (const int32_t *)h->lvl_ptr.p; a.lvl_bits = (const int32_t *)h->lvl_bits.p; a.n_levels = h->n_levels;
         if ((rc = chunk_timing_begin(h))) return rc;
-        hipLaunchKernelGGL(soft_kern, dim3((unsigned)c.tiles), dim3((unsigned)(64 * (level_waves ? level_waves : 1))), (unsigned)lds, st, a);
+        LDPC_LAUNCH(soft_kern, dim3((unsigned)c.tiles), dim3((unsigned)(64 * (level_waves ? level_waves : 1))), (unsigned)lds, st, a);
         if ((rc = chunk_timing_end(h)) || (rc = chunk_outputs(h, c, decoding, llr))) return rc;
         if (soft_out && h->m > 0) {
             dim3 gt((unsigned)((h->m + LDPC_WAVE - 1) / LDPC_WAVE), (unsigned)c.tiles);
-            hipLaunchKernelGGL(transpose_llr_kernel, gt, dim3(256), 0, st, (const double *)h->soft_S.p, c.nb, h->m,
+            LDPC_LAUNCH(transpose_llr_kernel, gt, dim3(256), 0, st, (const double *)h->soft_S.p, c.nb, h->m,
                                soft_out + (size_t)c.b0 * h->m);
             HIPCHK(hipGetLastError());
         }

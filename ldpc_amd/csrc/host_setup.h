@@ -339,6 +339,53 @@ int ldpc_hip_bp_last_kernel_ms(ldpc_hip_bp *h, float *ms) {
 
 int64_t ldpc_hip_debug_device_buf_bytes(void) { return (int64_t)g_device_buf_bytes.load(); }
 
+void ldpc_hip_debug_launch_log(int32_t enable) {
+    LaunchLog &log = launch_log();
+    std::lock_guard<std::mutex> lock(log.mu);
+    log.counts.clear();
+    log.by_call = enable != 0;
+    g_launch_log_on.store(log.by_call || !log.file.empty());
+}
+
+static std::string launch_log_text(const std::map<std::string, long long> &counts) {
+    std::string text;
+    for (const auto &kv : counts) text += std::to_string(kv.second) + "\t" + kv.first + "\n";
+    return text;
+}
+
+int64_t ldpc_hip_debug_launch_log_read(char *buf, int64_t capacity) {
+    LaunchLog &log = launch_log();
+    std::lock_guard<std::mutex> lock(log.mu);
+    const std::string text = launch_log_text(log.counts);
+    if (buf && capacity > 0) {
+        const size_t k = std::min(text.size(), (size_t)capacity - 1);
+        std::memcpy(buf, text.data(), k);
+        buf[k] = 0;
+    }
+    return (int64_t)text.size() + 1;
+}
+
+// LDPC_HIP_LAUNCH_LOG=<file>, read once when the library is loaded: the log is on for the whole process, and its table is appended to the
+// file when the library is unloaded -- one block per process, headed by the pid; names were resolved at record time, so no HIP call is made here
+__attribute__((constructor)) static void launch_log_from_environment() {
+    const char *e = getenv("LDPC_HIP_LAUNCH_LOG");
+    if (!e || !*e) return;
+    LaunchLog &log = launch_log();
+    std::lock_guard<std::mutex> lock(log.mu);
+    log.file = e;
+    g_launch_log_on.store(true);
+}
+__attribute__((destructor)) static void launch_log_to_file() {
+    LaunchLog &log = launch_log();
+    std::lock_guard<std::mutex> lock(log.mu);
+    if (log.file.empty()) return;
+    const std::string text = "# pid " + std::to_string((long long)getpid()) + "\n" + launch_log_text(log.total);
+    if (FILE *f = fopen(log.file.c_str(), "a")) {  // (one write per process: blocks of concurrent processes do not interleave)
+        fwrite(text.data(), 1, text.size(), f);
+        fclose(f);
+    }
+}
+
 void *ldpc_hip_host_alloc(size_t bytes) {
     void *p = nullptr;
     if (hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault) != hipSuccess) {
@@ -379,10 +426,10 @@ int ldpc_hip_bp_copy_probe(ldpc_hip_bp *h, int64_t tiles, int32_t segments_per_t
     HIPCHK(hipEventCreate(&e0));
     HIPCHK(hipEventCreate(&e1));
     double *a = (double *)h->msgA.p, *c = (double *)h->msgC.p;
-    hipLaunchKernelGGL(segcopy_probe_kernel, dim3((unsigned)tiles), dim3(768), 0, st, a, c, (int)segments_per_tile);  // untimed: page tables, clocks
+    LDPC_LAUNCH(segcopy_probe_kernel, dim3((unsigned)tiles), dim3(768), 0, st, a, c, (int)segments_per_tile);  // untimed: page tables, clocks
     HIPCHK(hipEventRecord(e0, st));
     for (int p = 0; p < passes; ++p) {
-        hipLaunchKernelGGL(segcopy_probe_kernel, dim3((unsigned)tiles), dim3(768), 0, st, (p & 1) ? c : a, (p & 1) ? a : c, (int)segments_per_tile);
+        LDPC_LAUNCH(segcopy_probe_kernel, dim3((unsigned)tiles), dim3(768), 0, st, (p & 1) ? c : a, (p & 1) ? a : c, (int)segments_per_tile);
     }
     HIPCHK(hipEventRecord(e1, st));
     HIPCHK(hipEventSynchronize(e1));

@@ -168,7 +168,7 @@ static int stream_pack(ldpc_hip_bp *h, const StreamPass &pass, const ChunkRange 
     HIPCHK(hipMemsetAsync(h->dec.p, 0, sizeof(uint64_t) * (size_t)(h->n ? h->n : 1) * (size_t)c.tiles, h->stream));
     if (h->m > 0) {
         dim3 g((unsigned)((h->m + 255) / 256), loop_tiles);
-        hipLaunchKernelGGL(pack_syndromes_kernel, g, dim3(256), 0, h->stream, synd + c.b0 * h->m, c.nb, h->m, (uint64_t *)h->par.p, (uint64_t *)h->nzm.p, (uint64_t *)h->invalid.p, pass.row_map, pass.rows_dev);
+        LDPC_LAUNCH(pack_syndromes_kernel, g, dim3(256), 0, h->stream, synd + c.b0 * h->m, c.nb, h->m, (uint64_t *)h->par.p, (uint64_t *)h->nzm.p, (uint64_t *)h->invalid.p, pass.row_map, pass.rows_dev);
     }
     return LDPC_HIP_OK;
 }
@@ -204,12 +204,12 @@ static int stream_start_per_pass(ldpc_hip_bp *h, const StreamPlan &p, int64_t ti
     // LDS, the tile's state) is then paid per 64 rows instead of per 16: 0.563 against 0.535 of HBM on the irregular code's 512
     // tiles, same box (profiles/r5_irregular_paths.txt)
     sa.nodes = h->sw("SPREAD_NODES") > 0 ? h->sw("SPREAD_NODES") : tiles <= 8 ? 1 : tiles < 512 ? 4 : 16;
-    hipLaunchKernelGGL(bp_spread_state_init_kernel, dim3((r.grid_tiles + 255) / 256), dim3(256), 0, h->stream, sa);
+    LDPC_LAUNCH(bp_spread_state_init_kernel, dim3((r.grid_tiles + 255) / 256), dim3(256), 0, h->stream, sa);
     const dim3 gi((unsigned)(h->nnz ? (h->nnz + 63) / 64 : 1), r.grid_tiles);  // (a grid dimension must not be 0: empty matrices)
     if (p.rp)
-        with_method_math(h, [&](auto M, auto F) { hipLaunchKernelGGL((bp_spread_init_kernel<M, F, true>), gi, dim3(256), 0, h->stream, sa); });
+        with_method_math(h, [&](auto M, auto F) { LDPC_LAUNCH((bp_spread_init_kernel<M, F, true>), gi, dim3(256), 0, h->stream, sa); });
     else if (sa.bp.it_start == 0)  // (else the message state is there already)
-        with_method_math(h, [&](auto M, auto F) { hipLaunchKernelGGL((bp_spread_init_kernel<M, F>), gi, dim3(256), 0, h->stream, sa); });
+        with_method_math(h, [&](auto M, auto F) { LDPC_LAUNCH((bp_spread_init_kernel<M, F>), gi, dim3(256), 0, h->stream, sa); });
     HIPCHK(hipGetLastError());
     return LDPC_HIP_OK;
 }
@@ -220,10 +220,10 @@ static int stream_persistent(ldpc_hip_bp *h, const StreamPlan &p, int64_t tiles,
     if (p.kern.ring_depth && h->n > 0 && !h->on("EXPLICIT_INIT")) {  // the first check pass reads this table instead of initial messages
         if ((rc = h->d_edge0.ensure(sizeof(double) * (size_t)h->n))) return rc;
         const dim3 ge((unsigned)((h->n + 255) / 256));
-        with_method_math(h, [&](auto M, auto F) { hipLaunchKernelGGL((bp_edge0_kernel<M, F>), ge, dim3(256), 0, h->stream, h->d_llr0, h->n, (double *)h->d_edge0.p); });
+        with_method_math(h, [&](auto M, auto F) { LDPC_LAUNCH((bp_edge0_kernel<M, F>), ge, dim3(256), 0, h->stream, h->d_llr0, h->n, (double *)h->d_edge0.p); });
         a.edge0 = (const double *)h->d_edge0.p;
     }
-    hipLaunchKernelGGL(p.kern.fn, dim3((unsigned)tiles), dim3((unsigned)(waves * LDPC_WAVE)), (unsigned)(p.lds_per_wave * (size_t)waves), h->stream, a);
+    LDPC_LAUNCH(p.kern.fn, dim3((unsigned)tiles), dim3((unsigned)(waves * LDPC_WAVE)), (unsigned)(p.lds_per_wave * (size_t)waves), h->stream, a);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(h->ev_mid, h->stream));
     h->timed_mid = true;
@@ -265,26 +265,26 @@ static int stream_rounds(ldpc_hip_bp *h, const StreamPlan &p, const StreamPass &
         sa.round = round;
         sa.slot0 = 0;
         if (may_compact && round >= 8 && round % 8 == 0) {
-            hipLaunchKernelGGL(bp_spread_compact_kernel, dim3(1), dim3(64), 0, st, sa);
+            LDPC_LAUNCH(bp_spread_compact_kernel, dim3(1), dim3(64), 0, st, sa);
             sa.n_tiles = -1;  // (the count is the device's from here on: counters[1])
             compacted = true;
         }
         if (!compacted) {
-            hipLaunchKernelGGL(k.check, gc, dim3(256), 0, st, sa);
-            hipLaunchKernelGGL(k.bit, gb, dim3(256), 0, st, sa);
-            hipLaunchKernelGGL(bp_spread_synd_kernel<false>, gs, dim3(256), 0, st, sa);
-            hipLaunchKernelGGL(k.finish, gf, dim3(256), 0, st, sa);
+            LDPC_LAUNCH(k.check, gc, dim3(256), 0, st, sa);
+            LDPC_LAUNCH(k.bit, gb, dim3(256), 0, st, sa);
+            LDPC_LAUNCH(bp_spread_synd_kernel<false>, gs, dim3(256), 0, st, sa);
+            LDPC_LAUNCH(k.finish, gf, dim3(256), 0, st, sa);
         } else {
             SpreadArgs sb = sa;
             sb.slot0 = 32;
-            hipLaunchKernelGGL(k.check, dim3(gc.x, 32), dim3(256), 0, st, sa);
-            hipLaunchKernelGGL(k.check_loop, dim3(gc.x, 8), dim3(256), 0, st, sb);
-            hipLaunchKernelGGL(k.bit, dim3(gb.x, 32), dim3(256), 0, st, sa);
-            hipLaunchKernelGGL(k.bit_loop, dim3(gb.x, 8), dim3(256), 0, st, sb);
-            hipLaunchKernelGGL(bp_spread_synd_kernel<false>, dim3(gs.x, 32), dim3(256), 0, st, sa);
-            hipLaunchKernelGGL(bp_spread_synd_kernel<true>, dim3(gs.x, 8), dim3(256), 0, st, sb);
-            hipLaunchKernelGGL(k.finish, dim3(gf.x, 32), dim3(256), 0, st, sa);
-            hipLaunchKernelGGL(bp_spread_finish_kernel<true>, dim3(gf.x, 8), dim3(256), 0, st, sb);
+            LDPC_LAUNCH(k.check, dim3(gc.x, 32), dim3(256), 0, st, sa);
+            LDPC_LAUNCH(k.check_loop, dim3(gc.x, 8), dim3(256), 0, st, sb);
+            LDPC_LAUNCH(k.bit, dim3(gb.x, 32), dim3(256), 0, st, sa);
+            LDPC_LAUNCH(k.bit_loop, dim3(gb.x, 8), dim3(256), 0, st, sb);
+            LDPC_LAUNCH(bp_spread_synd_kernel<false>, dim3(gs.x, 32), dim3(256), 0, st, sa);
+            LDPC_LAUNCH(bp_spread_synd_kernel<true>, dim3(gs.x, 8), dim3(256), 0, st, sb);
+            LDPC_LAUNCH(k.finish, dim3(gf.x, 32), dim3(256), 0, st, sa);
+            LDPC_LAUNCH(bp_spread_finish_kernel<true>, dim3(gf.x, 8), dim3(256), 0, st, sb);
         }
     }
     HIPCHK(hipGetLastError());
@@ -295,10 +295,10 @@ static int stream_rounds(ldpc_hip_bp *h, const StreamPlan &p, const StreamPass &
 static int stream_outputs(ldpc_hip_bp *h, const StreamPass &pass, const ChunkRange &c, unsigned loop_tiles, uint8_t *decoding, double *llr) {
     if (h->n > 0) {
         dim3 g((unsigned)((h->n + 255) / 256), loop_tiles);
-        hipLaunchKernelGGL(unpack_decoding_kernel, g, dim3(256), 0, h->stream, (const uint64_t *)h->dec.p, c.nb, h->n, decoding + c.b0 * h->n, pass.row_map, pass.rows_dev);
+        LDPC_LAUNCH(unpack_decoding_kernel, g, dim3(256), 0, h->stream, (const uint64_t *)h->dec.p, c.nb, h->n, decoding + c.b0 * h->n, pass.row_map, pass.rows_dev);
         if (llr) {
             dim3 gt((unsigned)((h->n + LDPC_WAVE - 1) / LDPC_WAVE), loop_tiles);
-            hipLaunchKernelGGL(transpose_llr_kernel, gt, dim3(256), 0, h->stream, (const double *)h->llr_t.p, c.nb, h->n, llr + (size_t)c.b0 * h->n, pass.row_map, pass.rows_dev);
+            LDPC_LAUNCH(transpose_llr_kernel, gt, dim3(256), 0, h->stream, (const double *)h->llr_t.p, c.nb, h->n, llr + (size_t)c.b0 * h->n, pass.row_map, pass.rows_dev);
         }
     }
     HIPCHK(hipGetLastError());
@@ -328,7 +328,7 @@ static int decode_streamed(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, u
             // the listed rows' message state after the first pass, lane by lane, into dense tiles (inside this pass's timed region)
             const int epw = 16;
             const dim3 gg((unsigned)((h->nnz + 4 * epw - 1) / (4 * epw)), loop_tiles);
-            hipLaunchKernelGGL(gather_lane_state_kernel, gg, dim3(256), 0, st, (const double *)pass.C, pass.row_map, (int64_t)0, h->nnz, epw, pass.A, pass.rows_dev);
+            LDPC_LAUNCH(gather_lane_state_kernel, gg, dim3(256), 0, st, (const double *)pass.C, pass.row_map, (int64_t)0, h->nnz, epw, pass.A, pass.rows_dev);
             HIPCHK(hipGetLastError());
         }
         SpreadArgs sa = {};
@@ -337,7 +337,7 @@ static int decode_streamed(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, u
         sa.seq = ++h->flag_seq ? h->flag_seq : ++h->flag_seq;  // never 0 (the word's initial value)
         if (p.rp && h->n > 0) {  // this chunk's rows [b0, b0 + nb) of the probabilities -> priors in the layout of its tiles (inside the timed region)
             const dim3 gp((unsigned)((h->n + LDPC_WAVE - 1) / LDPC_WAVE), (unsigned)c.tiles);
-            hipLaunchKernelGGL(row_priors_kernel, gp, dim3(256), 0, st, h->row_probs + (size_t)c.b0 * (size_t)h->n, c.nb, h->n, (const double *)h->d_llr0, (double *)h->rowp_llr.p);
+            LDPC_LAUNCH(row_priors_kernel, gp, dim3(256), 0, st, h->row_probs + (size_t)c.b0 * (size_t)h->n, c.nb, h->n, (const double *)h->d_llr0, (double *)h->rowp_llr.p);
             HIPCHK(hipGetLastError());
             sa.llr0_t = (const double *)h->rowp_llr.p;
         }
@@ -424,7 +424,7 @@ static int stream_leave_histogram(ldpc_hip_bp *h, const int32_t *iters, const ui
     HIPCHK(hipMemsetAsync(h->sp_hist.p, 0, 256 * sizeof(unsigned), h->stream));
     int64_t blocks = (batch + 255) / 256;
     if (blocks > 1024) blocks = 1024;
-    hipLaunchKernelGGL(iteration_histogram_kernel, dim3((unsigned)blocks), dim3(256), 0, h->stream, iters, conv, batch, (unsigned *)h->sp_hist.p);
+    LDPC_LAUNCH(iteration_histogram_kernel, dim3((unsigned)blocks), dim3(256), 0, h->stream, iters, conv, batch, (unsigned *)h->sp_hist.p);
     HIPCHK(hipMemcpyAsync(h->h_hist, h->sp_hist.p, 256 * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipEventRecord(h->ev_hist, h->stream));
     h->hist_pending = true;
@@ -476,9 +476,9 @@ static int decode_stream_repacked(ldpc_hip_bp *h, const uint8_t *synd, int64_t b
     }
     if ((rc = h->osd_list.ensure(B * sizeof(int32_t))) || (rc = h->osd_counters.ensure(4 * sizeof(unsigned)))) return rc;  // {count, next, rows, tiles}
     HIPCHK(hipMemsetAsync(h->osd_counters.p, 0, 4 * sizeof(unsigned), h->stream));
-    hipLaunchKernelGGL(osd_collect_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, h->stream, conv, batch,
+    LDPC_LAUNCH(osd_collect_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, h->stream, conv, batch,
                        (int32_t *)h->osd_list.p, (unsigned *)h->osd_counters.p);
-    hipLaunchKernelGGL(repack_rows_kernel, dim3(1), dim3(1), 0, h->stream, (const unsigned *)h->osd_counters.p, (unsigned *)h->osd_counters.p + 2);
+    LDPC_LAUNCH(repack_rows_kernel, dim3(1), dim3(1), 0, h->stream, (const unsigned *)h->osd_counters.p, (unsigned *)h->osd_counters.p + 2);
     HIPCHK(hipGetLastError());
     // the first pass's events stay readable while the second pass records its own (ldpc_hip_bp_last_kernel_ms adds both; nobody waits here)
     std::swap(h->ev0, h->evp0); std::swap(h->ev1, h->evp1); std::swap(h->ev_mid, h->evp_mid);

@@ -7,6 +7,7 @@ torch CUDA tensors as device pointers (no copy; outputs stay resident in HBM).
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -15,6 +16,26 @@ from ldpc_amd import _lib
 
 PRODUCT_SUM = 0  # ldpc::bp::BpMethod, bp.hpp:23-26
 MINIMUM_SUM = 1
+
+
+@contextlib.contextmanager
+def launch_log():
+    """Record which kernel instantiations the library launches inside the ``with`` block, over every engine and thread of the process
+    (``ldpc_hip_debug_launch_log``): yields a dict that holds ``name -> launches`` once the block is left, names spelt as
+    tools/list_instantiations.py spells them (``"bp_edge8_kernel<12, 3, true>"``).  Not re-entrant: entering clears the table."""
+    lib = _lib.load()
+    counts: dict = {}
+    lib.ldpc_hip_debug_launch_log(1)
+    try:
+        yield counts
+    finally:
+        need = int(lib.ldpc_hip_debug_launch_log_read(None, 0))
+        buf = C.create_string_buffer(need)
+        lib.ldpc_hip_debug_launch_log_read(buf, need)
+        lib.ldpc_hip_debug_launch_log(0)
+        for line in buf.value.decode("utf-8", "replace").splitlines():
+            count, name = line.split("\t", 1)
+            counts[name] = int(count)
 
 
 def _is_torch(x) -> bool:

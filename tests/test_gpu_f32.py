@@ -13,8 +13,10 @@ import time
 
 import numpy as np
 import pytest
+import scipy.sparse as sp
 
 import f32_util as fu
+import launch_util
 from golden_util import load_case
 from oracle import bits_equal
 
@@ -113,8 +115,16 @@ def test_non_temporal_instantiations(key):
     c = CASES[key]()
     eng = _engine(c)
     eng.set_debug_switch("F32_NT", 1)
-    _same(eng.decode_batch(c["synd"]), fu.expected(key, c, np.float32), f"{key}/non-temporal")
+    with launch_util.launch_log() as log:
+        got = eng.decode_batch(c["synd"])
+    _same(got, fu.expected(key, c, np.float32), f"{key}/non-temporal")
     eng.close()
+    # <DR, NT = 1> and <DC, NT = 1> ran, and no temporal instantiation beside them (host_f32.h: pick_f32)
+    hh = sp.csr_matrix(c["h"])
+    dr = 8 if int(hh.sum(axis=1).max()) <= 8 else 16
+    dc = 4 if int(hh.sum(axis=0).max()) <= 4 else 8
+    assert launch_util.of(log, "bp_f32_check_kernel") == [f"bp_f32_check_kernel<{dr}, 1>"], sorted(log)
+    assert launch_util.of(log, "bp_f32_bit_kernel") == [f"bp_f32_bit_kernel<{dc}, 1>"], sorted(log)
 
 
 def test_pipelined_host_arrays():

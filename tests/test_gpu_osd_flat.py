@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+import launch_util
+
 pytestmark = pytest.mark.gpu
 
 # (n, dv, dc) -> m = n dv / dc; the kernel the host picks: <R, D>
@@ -39,13 +41,19 @@ def test_flat_osd0_every_instantiation(oracle_built, n, dv, dc, kern, method):
     orc = oracle_built.BpOracle(h, error_channel=probs, max_iter=max_iter, bp_method=method, ms_scaling_factor=0.8)
     want = orc.bposd0_decode_batch(s)
     eng = HipBpEngine(h.indptr, h.indices, n, probs, max_iter, 0 if method == "product_sum" else 1, 0.8)
-    got = eng.decode_batch(s, osd0=True)
+    with launch_util.launch_log() as log:
+        got = eng.decode_batch(s, osd0=True)
+    # the instantiation is OBSERVED, not only re-derived: the first pass and the second (rows outside the image) both run it
+    assert launch_util.of(log, "osd0_flat_kernel", "osd0_reg_kernel", "osd0_kernel", "osd_big_kernel") == [f"osd0_flat_kernel<{kern[0]}, {kern[1]}>"], sorted(log)
     assert np.array_equal(got[0], want[0]) and np.array_equal(got[2], want[2]) and np.array_equal(got[3], want[3])
     status = eng.osd_status(B)
     solves = np.all((got[0].astype(np.int64) @ h.T.toarray().astype(np.int64)) % 2 == s, axis=1)
     assert np.array_equal(status, np.where(got[3] != 0, 0, np.where(solves, 1, 2)))
     assert (status > 0).sum() >= 20, "the case is meant to send rows through OSD"
     eng.set_debug_switch("OSD_NO_FLAT", 1)
-    reg = eng.decode_batch(s, osd0=True)
+    with launch_util.launch_log() as log:
+        reg = eng.decode_batch(s, osd0=True)
+    launch_util.assert_ran(log, "osd0_reg_kernel")
+    launch_util.assert_not_ran(log, "osd0_flat_kernel")
     assert np.array_equal(reg[0], got[0]) and np.array_equal(eng.osd_status(B), status)
     eng.close()

@@ -13,6 +13,8 @@ Nothing here reads /root/reference; oracle/ is used only as the checker.
 import numpy as np
 import pytest
 
+import launch_util
+
 from golden_util import bits_equal, case_names, load_case, llr_close, rowsum
 
 pytestmark = pytest.mark.gpu
@@ -487,11 +489,18 @@ def test_workgroup_osd_kernel_variants(name, unblocked, monkeypatch):
     for kernel in (2, -1):  # 2: workgroup kernel, H in HBM whatever the size; -1: the default dispatch (400 x 900: workgroup kernel, copy in LDS)
         eng.set_osd_kernel(kernel)
         eng.set_osd(c["osd_method"], c["osd_order"])
-        dec, _, it, cv = eng.decode_batch(c["syndromes"], want_llr=False, osd=True)
+        with launch_util.launch_log() as log_w:
+            dec, _, it, cv = eng.decode_batch(c["syndromes"], want_llr=False, osd=True)
         assert np.array_equal(cv, c["converge"]) and np.array_equal(it, c["iterations"])
         assert np.array_equal(dec, c["decoding"]), (kernel, unblocked)
         eng.set_osd(1, 0)
-        assert np.array_equal(eng.decode_batch(c["syndromes"], want_llr=False, osd=True)[0], c["osd0_decoding"]), (kernel, unblocked)
+        with launch_util.launch_log() as log_0:
+            assert np.array_equal(eng.decode_batch(c["syndromes"], want_llr=False, osd=True)[0], c["osd0_decoding"]), (kernel, unblocked)
+        # osd_big_kernel<HIGHER, MAT_LDS>: forced (2), the working copy of H stays in its HBM slot; the 400 x 900 matrix takes it by default, copy in LDS
+        mat_lds = "false" if kernel == 2 else "true" if "random400x900" in name else None
+        if mat_lds:
+            assert launch_util.of(log_w, "osd_big_kernel") == [f"osd_big_kernel<true, {mat_lds}>"], (kernel, sorted(log_w))
+            assert launch_util.of(log_0, "osd_big_kernel") == [f"osd_big_kernel<false, {mat_lds}>"], (kernel, sorted(log_0))
 
 
 @pytest.mark.parametrize("planes", ["1", "2", "4"])
@@ -505,8 +514,10 @@ def test_workgroup_osd_kernel_staged_planes(name, planes, monkeypatch):
     eng.set_debug_switch("OSD_PLANES", int(planes))
     eng.set_osd_kernel(2)
     eng.set_osd(c["osd_method"], c["osd_order"])
-    dec = eng.decode_batch(c["syndromes"], want_llr=False, osd=True)[0]
+    with launch_util.launch_log() as log:
+        dec = eng.decode_batch(c["syndromes"], want_llr=False, osd=True)[0]
     assert np.array_equal(dec, c["decoding"])
+    assert launch_util.of(log, "osd_big_kernel") == ["osd_big_kernel<true, false>"], sorted(log)
 
 
 def test_bposdw_device_pointers_and_oracle_at_batch(oracle_built):
@@ -826,11 +837,21 @@ def _poisoned_outputs(b, n):
     return dec, llr, it, cv
 
 
-@pytest.mark.parametrize("path", ["streamed", "streamed_two_pass", "spread", "wave_ps", "edge", "wave", "small", "serial_level", "serial_walk", "serial_stream",
+# the kernels that make each path of test_no_output_element_is_left_unwritten what it is called (a tuple: either -- the levels of the shuffled orders decide)
+_PATH_KERNELS = {
+    "streamed": ["bp_decode_kernel"], "streamed_two_pass": ["bp_decode_kernel", "gather_lane_state_kernel"], "spread": ["bp_spread_check_kernel", "bp_spread_bit_kernel"],
+    "wave_ps": ["bp_wave_ps_kernel"], "edge": ["bp_edge_kernel"], "edge8": ["bp_edge8_kernel"], "wave": ["bp_wave_kernel"], "small": ["bp_small_kernel"],
+    "serial_level": ["bp_serial_level_kernel"], "serial_walk": ["bp_serial_kernel"], "serial_stream": ["bp_serial_stream_kernel"],
+    "serial_lanes": ["bp_serial_lane_kernel"], "serial_relative": ["bp_relative_lds_kernel"], "serial_relative_per_lane": ["bp_serial_relative_kernel"],
+    "random_serial": [("bp_serial_level_kernel", "bp_serial_kernel")], "osd0": ["osd0_flat_kernel"], "osd_cs": ["osdw_reg_kernel"],
+}
+
+
+@pytest.mark.parametrize("path", ["streamed", "streamed_two_pass", "spread", "wave_ps", "edge", "edge8", "wave", "small", "serial_level", "serial_walk", "serial_stream",
                                   "serial_lanes", "serial_relative", "serial_relative_per_lane", "random_serial", "osd0", "osd_cs"])
 def test_no_output_element_is_left_unwritten(path):
     """Outputs pre-filled with a poison pattern come back without it on every kernel path (a path that skipped rows would hand out
-    uninitialised memory: the result arrays are not zero-filled)."""
+    uninitialised memory: the result arrays are not zero-filled).  The launch log shows that the path's kernel did run."""
     import torch
     from ldpc_amd.engine import HipBpEngine
     from ldpc_amd import codes
@@ -840,6 +861,7 @@ def test_no_output_element_is_left_unwritten(path):
         "spread": (codes.regular_ldpc_code(1200, 3, 6, seed=3), 0.07, 12, 0, 1.0, 333),
         "wave_ps": (codes.bivariate_bicycle_hx(), 0.05, 20, 0, 1.0, 1000),
         "edge": (codes.rotated_surface_code_x(9), 0.05, 15, 1, 0.625, 1000),
+        "edge8": (codes.bivariate_bicycle_hx(), 0.05, 20, 1, 0.8, 1000),  # (min-sum on BB144 by default: what "wave" ran until the launch log showed it)
         "wave": (codes.bivariate_bicycle_hx(), 0.05, 20, 1, 0.8, 1000),
         "small": (codes.hamming_code(6), 0.03, 10, 0, 1.0, 300),
         "serial_level": (codes.bivariate_bicycle_hx(), 0.06, 20, 0, 1.0, 1000),
@@ -860,6 +882,8 @@ def test_no_output_element_is_left_unwritten(path):
         eng.set_small_code_kernel(0)
     if path == "small":
         eng.set_small_code_kernel(2)
+    if path == "wave":
+        eng.set_small_code_kernel(3)  # the lane = node kernel: by default min-sum on this code takes bp_edge8_kernel (path "edge8")
     if path.startswith("serial_") and not path.startswith("serial_relative"):
         eng.set_schedule("serial")
         eng.set_serial_kernel({"serial_level": 1, "serial_walk": 0, "serial_stream": 2, "serial_lanes": 2}[path])
@@ -878,8 +902,13 @@ def test_no_output_element_is_left_unwritten(path):
     s = eng.gen_bsc_syndromes(3, p, shot0=0, shots=b, device="cuda:0")
     for rep in range(2):  # (the second call of the streamed path is steered by the first one's histogram: two passes)
         out = _poisoned_outputs(b, n)
-        dec, llr, it, cv = eng.decode_batch(s, out=out, **kw)
+        with launch_util.launch_log() as log:
+            dec, llr, it, cv = eng.decode_batch(s, out=out, **kw)
         torch.cuda.synchronize()
+        if path != "streamed_two_pass" or rep == 1:
+            for kernel in _PATH_KERNELS[path]:  # (a tuple: any of them)
+                assert launch_util.of(log, *((kernel,) if isinstance(kernel, str) else kernel)), (path, kernel, sorted(log))
+            launch_util.assert_resolved(log)
         assert int((dec > 1).sum()) == 0, path
         assert int((cv > 1).sum()) == 0, path
         assert int((it < 0).sum()) == 0 and int((it > max(max_iter, 0)).sum()) == 0, path

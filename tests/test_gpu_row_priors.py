@@ -5,6 +5,7 @@ tensors, both bindings), the C ABI (sync, async), every forced kernel path, and 
 import numpy as np
 import pytest
 
+import launch_util
 import oracle
 from row_priors_util import case_names, llr_digest, load_case, ran_bp
 
@@ -147,7 +148,16 @@ def test_forced_kernel_family(name, small_mode):
     eng = _engine(c)
     try:
         eng.set_small_code_kernel(small_mode)
-        _same_as_fixture(c, *eng.decode_batch(c["syndromes"], osd0=c["osd"], channel_probs=c["probs"]), rows=ran_bp(c))
+        with launch_util.launch_log() as log:
+            out = eng.decode_batch(c["syndromes"], osd0=c["osd"], channel_probs=c["probs"])
+        _same_as_fixture(c, *out, rows=ran_bp(c))
+        # the forced family ran, in its row-prior form (RP, the last template argument) and in no other
+        family = ("bp_spread_init_kernel", "bp_spread_bit_kernel", "bp_spread_finish_kernel") if small_mode == 0 else ("bp_small_kernel",)
+        for kernel in family:
+            ran = launch_util.of(log, kernel)
+            assert ran and all(k.endswith(", true>") for k in ran), (kernel, sorted(log))
+        others = {"bp_small_kernel", "bp_wave_kernel", "bp_wave_ps_kernel", "bp_edge_kernel", "bp_edge8_kernel", "bp_decode_kernel", "bp_spread_init_kernel"} - set(family)
+        launch_util.assert_not_ran(log, *sorted(others))
     finally:
         eng.close()
 

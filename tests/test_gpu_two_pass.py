@@ -5,6 +5,8 @@ partial last tile."""
 import numpy as np
 import pytest
 
+import launch_util
+
 pytestmark = pytest.mark.gpu
 
 
@@ -36,8 +38,10 @@ def test_two_pass_decode_gives_the_plain_decodes_bits(code, method, alpha, p, ma
     for k1 in (2, 3, 5):
         eng.set_repack(k1)
         for want_llr in (True, False):
-            got = _decode(eng, s, want_llr=want_llr)
+            with launch_util.launch_log() as log:
+                got = _decode(eng, s, want_llr=want_llr)
             tag = (code, method, k1, want_llr)
+            launch_util.assert_ran(log, "gather_lane_state_kernel")  # a second pass there was: the rows still decoding were compacted lane by lane
             assert np.array_equal(got[0], ref[0]) and np.array_equal(got[2], ref[2]) and np.array_equal(got[3], ref[3]), tag
             assert got[1] is None if not want_llr else bits_equal(got[1], ref[1]), tag
     # steered by the histogram of the previous decode (repack -1): whatever it chooses, the same bits
@@ -75,7 +79,12 @@ def test_second_pass_with_compacted_late_rounds_gives_the_plain_decodes_bits(ora
     assert np.array_equal(ref[0][rows], want[0]) and np.array_equal(ref[2][rows], want[2]) and np.array_equal(conv[rows], want[3].astype(bool))
     assert bits_equal(ref[1][rows], want[1])
     eng.set_repack(-1)
+    logs = []
     for i in range(3):  # the first leaves a histogram, the next two are steered by one
-        got = _decode(eng, s, want_llr=True)
+        with launch_util.launch_log() as log:
+            got = _decode(eng, s, want_llr=True)
+        logs.append(log)
         assert np.array_equal(got[0], ref[0]) and np.array_equal(got[2], ref[2]) and np.array_equal(got[3], ref[3]) and bits_equal(got[1], ref[1]), i
+    # ... and a steered decode did compact its parked tiles: the kernel this test is about ran
+    launch_util.assert_ran(logs[-1], "bp_spread_compact_kernel", "gather_lane_state_kernel")
     eng.close()

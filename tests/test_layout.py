@@ -65,3 +65,29 @@ def test_required_top_level_files_exist():
     for rel in ("bench.py", "__graft_entry__.py", "include/ldpc_hip.h", "oracle/bp_oracle.c", "oracle/Makefile",
                 "oracle/ref_harness.cpp", "tests/golden/make_golden.py", "DESIGN.md", "INTEGRATION.md"):
         assert os.path.exists(os.path.join(ROOT, rel)), rel
+
+
+def test_every_kernel_launch_goes_through_the_logging_wrapper():
+    """The launch log (host_handle.h: LDPC_LAUNCH / LDPC_LAUNCH_TIMED / LDPC_LAUNCH_PTR) is complete only while no kernel is launched past it:
+    outside the three macro definitions, no source line of ldpc_amd/csrc calls a launch function of the runtime or uses the <<< >>> syntax."""
+    csrc = os.path.join(ROOT, "ldpc_amd", "csrc")
+    launch = re.compile(r"\b(hipLaunchKernelGGL|hipExtLaunchKernelGGL|hipLaunchKernel|hipExtLaunchKernel|hipModuleLaunchKernel|hipExtModuleLaunchKernel|"
+                        r"hipLaunchCooperativeKernel|hipLaunchKernelExC|hipGraphAddKernelNode)\s*\(|<<<")
+    strays, wrapped, sites = [], 0, 0
+    for name in sorted(os.listdir(csrc)):
+        if not name.endswith((".h", ".hip")):
+            continue
+        in_macro = False
+        for no, line in enumerate(open(os.path.join(csrc, name)), 1):
+            code = line.split("//")[0]
+            starts = name == "host_handle.h" and re.match(r"#define LDPC_LAUNCH(_TIMED|_PTR)?\(", code)
+            if launch.search(code):
+                if in_macro or starts:
+                    wrapped += 1
+                else:
+                    strays.append(f"{name}:{no}: {line.strip()[:100]}")
+            sites += len(re.findall(r"\bLDPC_LAUNCH(?:_TIMED|_PTR)?\(", code)) if not (in_macro or starts) else 0
+            in_macro = (in_macro or bool(starts)) and code.rstrip().endswith("\\")
+    assert not strays, "kernel launches outside the logging wrapper:\n" + "\n".join(strays)
+    assert wrapped == 3, "one runtime launch call in each of the three wrapper macros"
+    assert sites >= 90, "the scan no longer sees the launch sites"

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import scipy.sparse as sp
 
+import launch_util
 from golden_util import GOLDEN_DIR, bits_equal
 
 CASES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN_DIR, "stateful_*.npz")) if "_softrnd_" not in p)
@@ -170,9 +171,21 @@ def test_serial_relative_on_chip_kernel_against_the_per_lane_kernel_and_the_chec
             eng.set_debug_switch("REL_LDS", lds)
         s = eng.gen_bsc_syndromes(17, p, shot0=0, shots=B, device="cuda:0").cpu().numpy()
         s[7, 0] = 3  # a byte above 1: never converges
-        outs[lds] = eng.decode_batch(s) + (eng.schedule_order(),)
+        with launch_util.launch_log() as log:
+            outs[lds] = eng.decode_batch(s) + (eng.schedule_order(),)
         outs[(lds, "ms")] = eng.last_kernel_ms()
         eng.close()
+        # the form each switch names did run: the per-lane kernel, or ONE instantiation of the on-chip kernel <METHOD, MATH, DRT, GS, DCT, EXT> -- EXT = 1
+        # on request where the code has rows of 5 .. 16 and columns of 3 .. 8 entries (not surface21), and by default where the state is beyond LDS (hgp1600)
+        if lds == 0:
+            launch_util.assert_ran(log, "bp_serial_relative_kernel")
+            launch_util.assert_not_ran(log, "bp_relative_lds_kernel")
+        else:
+            launch_util.assert_not_ran(log, "bp_serial_relative_kernel")
+            ran = launch_util.of(log, "bp_relative_lds_kernel")
+            assert len(ran) == 1 and ran[0].startswith(f"bp_relative_lds_kernel<{method}, 0, "), (lds, sorted(log))
+            ext = 1 if code == "hgp1600" or (lds in ("ext", "ext_walk") and code != "surface21") else 0
+            assert ran[0].endswith(f", {ext}>"), (lds, ran)
     for lds in (64, "apart", "walk", 16, "ext", "ext_walk"):
         assert same(outs[lds][:4], outs[0][:4]) and np.array_equal(outs[lds][4], outs[0][4]), lds
     assert not outs[64][3][7]
