@@ -55,6 +55,7 @@ struct EdgeArgs {
 };
 
 __host__ __device__ inline size_t edge_lds_bytes(int rounds) { return ((size_t)rounds * 64 + 3) * 8; }  // slots, +0.0, +inf, a dummy (bp_edge8_kernel's phantom lanes park their output there)
+__host__ __device__ inline size_t edge_f32_lds_bytes(int rounds) { return ((size_t)rounds * 64 + 3) * 4; }  // the same slots at 4 bytes each (bp_edge_f32_kernel.h)
 
 // How many of the R rounds let the vector unit do what the scalar unit would (both issue one instruction per SIMD turn, and the
 // kernel's scalar work -- lane-mask parities -- outweighs its vector work): measured on BASELINE config 3, tools/bench_edge.py

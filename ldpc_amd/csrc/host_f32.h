@@ -37,6 +37,14 @@ static F32Kernels pick_f32(const ldpc_hip_bp *h, bool nt) {
 int decode_f32(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv) {
     int rc;
     if ((rc = f32_refusal(h, h->row_probs ? "per-row channel probabilities are" : nullptr))) return rc;
+    // Small codes of the lane = edge families stay on chip (host_onchip.h: decode_onchip_f32 -- one launch, messages in registers).  Off:
+    // small_mode 0 (never an on-chip kernel), the switch F32_ONCHIP 0, and any switch that names the per-pass kernels below (F32_NT,
+    // F32_GRID_ROWS, SPREAD_NODES: who sets one wants those kernels, on whatever code).
+    if (h->small_mode != 0 && h->sw("F32_ONCHIP") != 0 && h->sw("F32_NT") < 0 && h->sw("F32_GRID_ROWS") <= 0 && h->sw("SPREAD_NODES") <= 0) {
+        bool took = false;
+        rc = decode_onchip_f32(h, synd, batch, decoding, llr, iters, conv, &took);
+        if (took || rc) return rc;
+    }
     const int64_t tiles_total = (batch + LDPC_WAVE - 1) / LDPC_WAVE;
     const size_t m1 = (size_t)(h->m ? h->m : 1), n1 = (size_t)(h->n ? h->n : 1), nnz1 = (size_t)(h->nnz ? h->nnz : 1);
     const size_t per_tile_msg = sizeof(float) * nnz1 * LDPC_WAVE, per_tile_llr = llr ? sizeof(float) * n1 * LDPC_WAVE : 0;

@@ -377,6 +377,7 @@ static int decode_wave(ldpc_hip_bp *h, const WavePlan &p, const uint8_t *synd, i
 struct EdgePlan {
     int rounds = 0;  // 0: not applicable
     bool uniform = false;  // every column has the same prior: the form without prior registers (bp_edge_kernel<R, true>)
+    bool noclamp = false;  // ... and the clamp cannot bite (bp_edge_kernel<R, true, true>)
     void (*kern)(const EdgeArgs) = nullptr;
 };
 
@@ -402,6 +403,7 @@ static EdgePlan plan_edge(const ldpc_hip_bp *h) {
     // the form without the clamp to DBL_MAX (bp_edge_kernel.h, NOCLAMP): finite prior, |alpha| <= 1 (0 = the adaptive 1 - 2^-it), rows of two or more
     bool noclamp = p.uniform && std::isfinite(std::log((1 - h->channel_probs[0]) / h->channel_probs[0])) && std::fabs(h->ms_scaling_factor) <= 1.0 && !h->on("EDGE_CLAMP");
     for (int i = 0; i < h->m && noclamp; ++i) noclamp = h->h_row_ptr[(size_t)i + 1] - h->h_row_ptr[(size_t)i] >= 2;
+    p.noclamp = noclamp;
     p.kern = kerns[p.uniform ? (noclamp ? 2 : 1) : 0][rounds];
     return p;
 }
@@ -580,6 +582,79 @@ static int decode_edge8(ldpc_hip_bp *h, const Edge8Plan &p, const uint8_t *synd,
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     h->timed = true;
     HIPCHK(hipGetLastError());
+    return LDPC_HIP_OK;
+}
+
+// ---- the same two families with FP32 messages (bp_edge_f32_kernel.h; instantiated in tu_onchip_f32.hip): the float32 message mode's on-chip route ----
+// One plan answers for both dtypes (plan_edge, plan_edge8) and the slot tables are shared (ensure_edge_tables, ensure_edge8_tables, keyed by
+// h->edge_rounds).  e_prior is rewritten before every launch, here as floats, there as doubles, on the same stream: a handle that
+// changes its message dtype never reads one type's priors as the other's.
+__global__ void edge_prior_f32_kernel(const double *llr0, const int32_t *scol, const uint8_t *kind, int slots, float *out) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < slots) out[s] = kind[s] ? (float)llr0[scol[s]] : __builtin_inff();  // one rounding (v_cvt_f32_f64); phantom lanes: +inf
+}
+
+// what decode_edge_f32 and decode_edge8_f32 share: the per-slot priors, the work split, the launch between the timing events
+template <class ARGS>
+static int launch_edge_f32(ldpc_hip_bp *h, void (*kern)(const ARGS), int rounds, int waves_per_simd, int64_t batch, ARGS &a) {
+    if (!kern) return fail(LDPC_HIP_ERR_UNSUPPORTED, "float32 messages: no on-chip kernel was built for %d rounds", rounds);
+    const int slots = rounds * 64;
+    LDPC_LAUNCH(edge_prior_f32_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, h->stream, h->d_llr0, (const int32_t *)h->e_scol.p,
+                       (const uint8_t *)h->e_kind.p, slots, (float *)h->e_prior.p);
+    a.m = h->m; a.n = h->n; a.max_iter = h->max_iter;
+    a.ms_scaling_factor = h->ms_scaling_factor;
+    a.batch = batch;
+    a.prior_s = (const float *)h->e_prior.p;
+    a.prior_u = (float)std::log((1 - h->channel_probs[0]) / h->channel_probs[0]);  // the FP64 prior of upload_priors, rounded once; read by the uniform form only
+    a.kind = (const uint8_t *)h->e_kind.p; a.scol = (const int32_t *)h->e_scol.p;
+    const size_t dyn = edge_f32_lds_bytes(rounds);
+    // one wavefront per workgroup, as many resident as registers (edge_f32_waves / edge8_f32_waves per SIMD) and LDS allow
+    int64_t per_cu = (int64_t)((160u * 1024u) / (dyn + 64));
+    const int64_t by_regs = 4 * (int64_t)waves_per_simd;
+    if (per_cu > by_regs) per_cu = by_regs;
+    const int64_t groups = batch < 256 * per_cu ? batch : 256 * per_cu;
+    int rc;
+    if ((rc = edge_work_split(h, rounds, batch, groups, a))) return rc;
+    h->accumulated_ms = 0.f;  // (as decode_edge / decode_edge8: one launch between the two events)
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    LDPC_LAUNCH(kern, dim3((unsigned)groups), dim3(64), (unsigned)dyn, h->stream, a);
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    h->timed = true;
+    HIPCHK(hipGetLastError());
+    return LDPC_HIP_OK;
+}
+
+static int decode_edge_f32(ldpc_hip_bp *h, const EdgePlan &p, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr,
+                           int32_t *iters, uint8_t *conv) {
+    int rc;
+    if ((rc = ensure_edge_tables(h, p))) return rc;
+    EdgeF32Args a = {};
+    a.partner = (const uint16_t *)h->e_partner.p;
+    a.synd = synd; a.decoding = decoding; a.llr = llr; a.iters = iters; a.conv = conv;
+    return launch_edge_f32(h, edge_f32_kernel(p.rounds, p.uniform, p.noclamp), p.rounds, edge_f32_waves(p.rounds), batch, a);
+}
+
+static int decode_edge8_f32(ldpc_hip_bp *h, const Edge8Plan &p, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr,
+                            int32_t *iters, uint8_t *conv) {
+    int rc;
+    if ((rc = ensure_edge8_tables(h, p))) return rc;
+    Edge8F32Args a = {};
+    a.cpos = (const uint16_t *)h->e_partner.p;
+    a.synd = synd; a.decoding = decoding; a.llr = llr; a.iters = iters; a.conv = conv;
+    return launch_edge_f32(h, edge8_f32_kernel(p.rounds, p.dc, p.uniform), p.rounds, edge8_f32_waves(p.rounds, p.dc, p.uniform), batch, a);
+}
+
+// The float32 message mode's on-chip planner, called by decode_f32 (host_f32.h) after its refusals: decode_onchip's predicate for the lane =
+// edge families and their two plans, unchanged.  *took = false: neither takes the code -- decode_f32 goes on with its per-pass kernels (in
+// float32 nothing ever goes to bp_wave_kernel, bp_small_kernel or any FP64 kernel).
+int decode_onchip_f32(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv, bool *took) {
+    *took = false;
+    if (!(h->small_mode == -1 || h->small_mode == 1 || h->small_mode == 6)) return LDPC_HIP_OK;
+    if (!(h->m > 0 && h->n > 0 && h->nnz > 0 && (int64_t)h->nnz * 16 < (1 << 22) && batch < (1ll << 30))) return LDPC_HIP_OK;  // (32-bit syndrome indices in the work pools)
+    const EdgePlan ep = plan_edge(h);
+    if (ep.rounds) { *took = true; return decode_edge_f32(h, ep, synd, batch, decoding, llr, iters, conv); }
+    const Edge8Plan e8 = plan_edge8(h);
+    if (e8.rounds) { *took = true; return decode_edge8_f32(h, e8, synd, batch, decoding, llr, iters, conv); }
     return LDPC_HIP_OK;
 }
 

@@ -4,10 +4,15 @@
     python tools/bench_f32.py --agreement                 # share of rows whose decisions / converge flags differ between the modes
     python tools/bench_f32.py --speed                     # syndromes/s of both modes + the copy probe, same process, same box
     python tools/bench_f32.py --speed --modes float64 --tree <checkout>   # the float64 of another built checkout (the parent commit: A/B on one box)
+    python tools/bench_f32.py --speed --configs small     # the small codes the on-chip kernels take (each at its own batch sizes)
 
 Configurations: (3,6)-regular n = 10 000, min-sum 50 iterations, at p = 0.05 and 0.09; the irregular n = 10 000 code of
-``bench.py --full`` (speed only); BB144 min-sum 50 + OSD-0 (agreement only).  Syndromes are generated on the device; everything stays
-in HBM.  One JSON line per figure.  Reads nothing but this repository.
+``bench.py --full`` (speed only); BB144 min-sum 50 + OSD-0 (agreement only).  ``--configs small`` (speed only): the codes whose messages
+stay on chip in both modes -- BB144 min-sum 50 at p = 0.05 (B = 65 536 and 262 144; bp_edge8, DC 3), the rotated surface code d = 21 min-sum
+30 at p = 0.05 (B = 262 144; bp_edge) and the hypergraph product of hamming_code(3) with itself min-sum 30 at p = 0.05 (B = 262 144;
+bp_edge8, DC 4); every line names the BP kernels its decode launched (``bp_kernels``, from the launch log), so the route is on record.
+Syndromes are generated on the device; everything stays in HBM.  One JSON line per figure.  Reads nothing but this
+repository.
 """
 from __future__ import annotations
 
@@ -44,6 +49,58 @@ def _configs(which):
     if "bb144" in which:
         out += [("bb144_ms50_osd0_p050", codes.bivariate_bicycle_hx(), 0.05, True)]
     return out
+
+
+def _small_configs():
+    """(name, h, p, max_iter, batches): small codes of the lane = edge families, device-resident."""
+    from ldpc_amd import codes
+    hgp = codes.hypergraph_product_hx(codes.hamming_code(3)).tocsr()
+    hgp.eliminate_zeros()  # (the product stores explicit zeros and the engine takes the STRUCTURE; without them: 21 rows of 5 .. 7 entries, columns of 1 .. 4)
+    return [("bb144_ms50_p050", codes.bivariate_bicycle_hx(), 0.05, 50, (65536, 262144)),
+            ("surface_d21_ms30_p050", codes.rotated_surface_code_x(21), 0.05, 30, (262144,)),
+            ("hgp_hamming3_ms30_p050", hgp, 0.05, 30, (262144,))]
+
+
+def speed_small(modes, reps, warmup, tag, tree_name=None):
+    """Small codes: one on-chip launch per decode in float64, and in float32 where the tree has the on-chip float32 kernels (else the
+    per-pass route).  `warmup` untimed decodes, then `reps` timed ones; wall time around a synchronised call and the kernel's own time."""
+    import torch
+    try:
+        from ldpc_amd.engine import launch_log as _launch_log
+    except ImportError:  # (a checkout from before the launch log)
+        _launch_log = None
+    assert warmup >= 1
+    for name, h, p, max_iter, batches in _small_configs():
+        eng = _engine(h, p, max_iter)
+        for batch in batches:
+            synd = eng.gen_bsc_syndromes(12345, p, 0, batch, device="cuda")
+            for mode in modes:
+                if mode != "float64" or hasattr(eng, "set_message_dtype"):
+                    eng.set_message_dtype(mode)
+                out = None
+                rates, kms = [], []
+                kernels = None
+                for r in range(reps + warmup):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    if r == 0 and _launch_log is not None:  # (an untimed decode: which BP kernels it launched, and how often)
+                        with _launch_log() as log:
+                            out = eng.decode_batch(synd, want_llr=False, out=out)
+                            torch.cuda.synchronize()
+                        kernels = {k: v for k, v in sorted(log.items()) if k.startswith("bp_")}
+                    else:
+                        out = eng.decode_batch(synd, want_llr=False, out=out)
+                    torch.cuda.synchronize()
+                    dt = time.perf_counter() - t0
+                    if r >= warmup:
+                        rates.append(batch / dt)
+                        kms.append(eng.last_kernel_ms())
+                print(json.dumps(dict(kind="speed_small", config=name, mode=mode, tree=tree_name or os.path.relpath(_TREE), tag=tag, batch=batch, bp_kernels=kernels,
+                                      syndromes_per_s=[round(x) for x in rates], median_syndromes_per_s=round(float(np.median(rates))),
+                                      min_syndromes_per_s=round(min(rates)), max_syndromes_per_s=round(max(rates)),
+                                      kernel_ms=[round(x, 3) for x in kms], converged=int(out[3].sum()),
+                                      mean_iterations=round(float(out[2].double().mean()), 3))), flush=True)
+        eng.close()
 
 
 def agreement(batch):
@@ -114,10 +171,16 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--modes", default="float64,float32")
     ap.add_argument("--tree", default=None, help="another built checkout to take ldpc_amd from (default: this one)")
+    ap.add_argument("--configs", default="large", choices=["large", "small"], help="--speed: the n = 10 000 codes, or the small codes of the on-chip kernels")
+    ap.add_argument("--warmup", type=int, default=3, help="--configs small: untimed decodes before the timed ones")
+    ap.add_argument("--tag", default="", help="--configs small: copied into every line (which leg of a comparison this is)")
+    ap.add_argument("--tree-name", default=None, help="--configs small: what the lines call the tree (default: its path)")
     a = ap.parse_args()
     if a.agreement:
         agreement(a.batch)
-    if a.speed:
+    if a.speed and a.configs == "small":
+        speed_small(a.modes.split(","), a.reps, a.warmup, a.tag, a.tree_name)
+    elif a.speed:
         speed(a.batch, a.modes.split(","), a.reps)
 
 
