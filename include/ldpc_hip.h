@@ -265,7 +265,12 @@ int ldpc_hip_bposd_get_status(ldpc_hip_bp *h, uint8_t *status, int64_t batch);
  * there can be: the device lists the unconverged rows, counts them, and every kernel of the second pass reads that count and
  * reaches the caller's arrays through the list (no rows are copied out and back; no extra message memory: the compacted state
  * is gathered into the first pass's check_to_bit array, which is dead by then).  A batch that does not fit in one chunk of
- * device memory runs plain. */
+ * device memory runs plain.
+ * The float32 message mode (ldpc_hip_bp_set_message_dtype) is steered by the same setting in the same way on its per-pass route
+ * (codes its on-chip kernels do not take): -1 = the last landed histogram decides (default), 0 = off, k = a first pass of k
+ * iterations; it applies for 2 <= k < max_iter, max_iter >= 8, batches of >= 32768 syndromes that fit one chunk, and gives every
+ * row the bits of the plain float32 decode.  The handle keeps ONE histogram: one left by a float64 decode may steer a float32
+ * decode and the other way round (results do not depend on it). */
 int ldpc_hip_bp_set_repack(ldpc_hip_bp *h, int32_t first_pass_iters);
 /* Serial schedule kernels: bits that share no check commute, so the schedule is cut into levels of mutually check-disjoint
  * bits (level = 1 + the highest level among the EARLIER bits sharing a check) and a workgroup runs a tile level by level

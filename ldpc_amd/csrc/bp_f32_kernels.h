@@ -41,10 +41,28 @@ struct F32Args {
     unsigned *counters;                 // [1] tiles in `list`, [2] tiles still running
     int32_t *list;                      // [tiles] the running tiles first (bp_f32_compact_kernel)
     int32_t nodes;                      // rows / columns per wavefront
-    int32_t round;                      // 0-based; the iteration is round + 1
+    int32_t round;                      // 0-based and ABSOLUTE (a second pass starts at round0); the iteration is round + 1
     unsigned *host_flag;                // host-mapped word: receives `seq` when the last tile becomes final
     unsigned seq;
+    // The two-pass decode (host_f32.h: decode_f32_repacked; the analogue of StreamPass::max_iter / keep_state and BpArgs::it_start, rows_dev, row_map).
+    // pass_end: the iteration at which every tile of this pass ends.  == max_iter: a plain decode, or a second pass.  < max_iter: a first
+    // pass whose state a second pass carries on -- max_iter stays the decode's own, so the bit pass of iteration pass_end still writes its
+    // messages and the finish kernel reports the rows still decoding as conv = 0, iters = max_iter (the second pass overwrites both, and
+    // their decisions and posteriors).  alpha and "the last iteration" keep using the absolute iteration and max_iter.
+    int32_t pass_end;
+    // round0: the rounds this pass's rows have behind them (0 unless a second pass): bp_f32_state_init_kernel writes the state a tile
+    // reads in that round (done[round0 & 1]).  A second pass's A already holds the gathered bit_to_check state (bp_f32_gather_lanes_kernel).
+    int32_t round0;
+    // Rows known to the device only (a second pass).  rows_dev (if not null): [0] the rows of this pass, [1] their 64-row tiles (written
+    // by repack_rows_kernel) -- they override `batch` and the host's tile count, whose grids follow an estimate (every kernel loops).
+    // row_map (if not null): row r of the pass is row row_map[r] of the caller's `iters` / `conv`.
+    const unsigned *rows_dev;
+    const int32_t *row_map;
 };
+
+__device__ __forceinline__ int64_t f32_rows(const F32Args &a) {
+    return a.rows_dev ? (int64_t)__hip_atomic_load(a.rows_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : a.batch;
+}
 
 // one tile's [rows][64] floats behind a buffer descriptor (as MsgBufT, for 4-byte elements): SGPR descriptor + SGPR edge offset +
 // VGPR lane offset; an access outside the tile's rows reads 0 / is dropped.  AUX 2 = non-temporal.
@@ -74,19 +92,30 @@ __device__ __forceinline__ bool f32_tile(const F32Args &a, int slot, int64_t &ti
     return a.round <= st->end_round;
 }
 
+// n_tiles: the host's tile count (the grid covers it); a second pass takes rows and tiles from rows_dev -- never more than that.  A second
+// pass without a row reports the decode finished itself: no finish kernel will (the host then stops queueing its rounds).
 __global__ void __launch_bounds__(256) bp_f32_state_init_kernel(const F32Args a, int n_tiles) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t rows = f32_rows(a);
+    if (a.rows_dev) {
+        const int64_t tiles_dev = (rows + LDPC_WAVE - 1) / LDPC_WAVE;
+        if (tiles_dev < n_tiles) n_tiles = (int)tiles_dev;
+    }
+    if (t == 0) {
+        a.counters[1] = a.counters[2] = (unsigned)n_tiles;
+        if (n_tiles == 0 && a.host_flag) __hip_atomic_store(a.host_flag, a.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
     if (t >= n_tiles) return;
     TileState *st = a.state + t;
-    const int64_t valid = a.batch - (int64_t)t * LDPC_WAVE;
-    st->done[0] = valid >= LDPC_WAVE ? 0ull : ~((1ull << valid) - 1ull);
+    const int64_t valid = rows - (int64_t)t * LDPC_WAVE;
+    const int par = a.round0 & 1;
+    st->done[par] = valid >= LDPC_WAVE ? 0ull : ~((1ull << valid) - 1ull);
     st->unsat[0] = st->unsat[1] = 0ull;
     st->it0 = 0;
     st->end_round = INT32_MAX;
-    st->llr_each[0] = 0;
+    st->llr_each[par] = 0;
     for (int l = 0; l < 64; ++l) st->lane_iter[l] = 0;
     a.list[t] = t;
-    if (t == 0) a.counters[1] = a.counters[2] = (unsigned)n_tiles;
 }
 
 // the handle's FP64 priors, each rounded once to FP32
@@ -103,6 +132,26 @@ __global__ void __launch_bounds__(256) bp_f32_init_kernel(const F32Args a) {
     const MsgBuf32T<0> At = make_msgbuf32<MsgBuf32T<0>>(a.A + (size_t)tile * (size_t)a.nnz * LDPC_WAVE, (unsigned)a.nnz);
     const int e0 = (blockIdx.x * 4 + wave) * 16;
     for (int e = e0; e < e0 + 16 && e < a.nnz; ++e) At.st(lane * 4, e, sload(a.llr0 + sload(a.col_idx + e)));
+}
+
+// The two-pass decode: the message state of the listed rows, lane by lane, out of the first pass's tiles into dense tiles -- the float32
+// form of gather_lane_state_kernel (io_kernels.h).  Row list[r] (tile list[r] / 64, lane list[r] % 64) becomes lane r % 64 of tile r / 64;
+// src, dst: [tiles][nnz][64] floats.  One wavefront per (destination tile, edge): 64 gathered 4-byte loads (the live lanes of a source
+// tile share sectors), one coalesced 256-byte store; lanes beyond the count are written 0.  The count is the device's (rows_dev[0]), the
+// grid an estimate: workgroup row y serves tiles y, y + gridDim.y, ...  grid (ceil(nnz / (4 * edges_per_wave)), estimate).
+__global__ void __launch_bounds__(256) bp_f32_gather_lanes_kernel(const float *__restrict__ src, const int32_t *__restrict__ list, const unsigned *__restrict__ rows_dev,
+                                                                  int nnz, int edges_per_wave, float *__restrict__ dst) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t count = (int64_t)__hip_atomic_load(rows_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (int64_t tile = blockIdx.y; tile * LDPC_WAVE < count; tile += gridDim.y) {
+        const int64_t r = tile * LDPC_WAVE + lane;
+        const bool live = r < count;
+        const int64_t b = live ? (int64_t)list[r] : 0;
+        const float *from = src + ((b >> 6) * (int64_t)nnz) * LDPC_WAVE + (b & 63);
+        float *to = dst + (tile * (int64_t)nnz) * LDPC_WAVE + lane;
+        const int e0 = (blockIdx.x * 4 + wave) * edges_per_wave;
+        for (int e = e0; e < e0 + edges_per_wave && e < nnz; ++e) to[(int64_t)e * LDPC_WAVE] = live ? from[(int64_t)e * LDPC_WAVE] : 0.0f;
+    }
 }
 
 // the list without the tiles that are final (in place, one wavefront; counters[1] = how many are left)
@@ -303,7 +352,7 @@ __global__ void __launch_bounds__(256) bp_f32_finish_kernel(const F32Args a) {
         const uint64_t unsat = cst->unsat[par] | a.invalid[tile];
         const uint64_t newly = ~unsat & ~done;
         const uint64_t ndone = done | newly;
-        const bool over = ndone == ~0ull || last;
+        const bool over = ndone == ~0ull || it == a.pass_end;  // (pass_end < max_iter: a first pass -- the rows still decoding leave as unconverged, for the second)
         const bool mine = (newly >> lane) & 1ull;
         const bool each = cst->llr_each[par] != 0;
         if (newly || (over && ndone != ~0ull)) {
@@ -330,8 +379,9 @@ __global__ void __launch_bounds__(256) bp_f32_finish_kernel(const F32Args a) {
         if (wave == 0) {
             const int earlier = st->lane_iter[lane];
             if (mine) st->lane_iter[lane] = it;
-            const int64_t b = tile * LDPC_WAVE + lane;
-            if (over && b < a.batch) {
+            const int64_t r = tile * LDPC_WAVE + lane;
+            if (over && r < f32_rows(a)) {
+                const int64_t b = a.row_map ? (int64_t)a.row_map[r] : r;
                 const bool cv = ((ndone >> lane) & 1ull) != 0;
                 if (a.iters) a.iters[b] = cv ? (mine ? it : earlier) : a.max_iter;  // bp.hpp:304
                 if (a.conv) a.conv[b] = cv ? 1 : 0;
@@ -351,19 +401,24 @@ __global__ void __launch_bounds__(256) bp_f32_finish_kernel(const F32Args a) {
 }
 
 // llr_t [tiles][n][64] f32 -> llr [batch][n] f64 (each value widened exactly), 64 x 64 tiles through LDS; grid (ceil(n / 64), tiles)
-__global__ void __launch_bounds__(256) bp_f32_transpose_llr_kernel(const float *__restrict__ llr_t, int64_t batch, int n, double *out) {
+// row_map / count_dev: rows known to the device only, as transpose_llr_kernel takes them (io_kernels.h) -- grid.y is then an estimate, so the kernel loops over the tiles
+__global__ void __launch_bounds__(256) bp_f32_transpose_llr_kernel(const float *__restrict__ llr_t, int64_t batch_arg, int n, double *out,
+                                                                   const int32_t *__restrict__ row_map, const unsigned *count_dev) {
     __shared__ float tilebuf[LDPC_WAVE][LDPC_WAVE + 1];
     const int j0 = blockIdx.x * LDPC_WAVE;
     const int lo = threadIdx.x & 63, hi = threadIdx.x >> 6;
-    const int64_t tile = blockIdx.y;
-    for (int r = 0; r < 16; ++r) {
-        const int jj = r * 4 + hi;
-        if (j0 + jj < n) tilebuf[jj][lo] = llr_t[((size_t)tile * n + j0 + jj) * LDPC_WAVE + lo];
-    }
-    __syncthreads();
-    for (int r = 0; r < 16; ++r) {
-        const int l = r * 4 + hi;
-        const int64_t b = tile * LDPC_WAVE + l;
-        if (b < batch && j0 + lo < n) out[(size_t)b * n + j0 + lo] = (double)tilebuf[lo][l];
+    const int64_t batch = count_dev ? (int64_t)__hip_atomic_load(count_dev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : batch_arg;
+    for (int64_t tile = blockIdx.y; tile * LDPC_WAVE < batch; tile += gridDim.y) {
+        for (int r = 0; r < 16; ++r) {
+            const int jj = r * 4 + hi;
+            if (j0 + jj < n) tilebuf[jj][lo] = llr_t[((size_t)tile * n + j0 + jj) * LDPC_WAVE + lo];
+        }
+        __syncthreads();
+        for (int r = 0; r < 16; ++r) {
+            const int l = r * 4 + hi;
+            const int64_t b = tile * LDPC_WAVE + l;
+            if (b < batch && j0 + lo < n) out[(size_t)(row_map ? (int64_t)row_map[b] : b) * n + j0 + lo] = (double)tilebuf[lo][l];
+        }
+        __syncthreads();  // (the buffer is refilled for the next tile)
     }
 }

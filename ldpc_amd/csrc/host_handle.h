@@ -150,7 +150,7 @@ struct DeviceBuf {  // grow-only device allocation, freed with its owner (on the
 // creation, from the environment variables LDPC_HIP_<NAME>, changed afterwards only through ldpc_hip_bp_set_debug_switch -- no
 // getenv on the decode path, and nothing a test can change under a live handle by accident.
 static const char *const k_switch_names[] = {"PS_TEAM", "EXPLICIT_INIT", "OSD_UNBLOCKED", "OSD_PLANES",
-                                             "PS_TEAM_WAVES", "EDGE_STATIC_PCT", "EDGE_CHUNK", "NO_HOST_PIPELINE", "NO_DIRECT_LLR", "HOST_CHUNK_ROWS", "TIME_SMALL_CALLS", "REL_LDS", "HOST_PIPE_TIMING", "REL_LEVELS", "REL_PROF", "REL_SCRATCH_IN_L", "SER_RING", "SER_WAVES", "SER_LANE_MAX", "SER_LANE_THREADS", "SER_WAVES2", "RESIDENT", "SER_NO_REMAINDER", "SER_ROUND_TILES", "VAR_RING", "VAR_RING_UNITS", "SPREAD_NODES", "SER_VAR", "SER_VAR_UNITS", "REL_EXT", "OSD_COLLECT_AFTER", "EDGE_CLAMP", "OSD_NO_FLAT", "F32_NT", "F32_GRID_ROWS", "F32_ONCHIP"};
+                                             "PS_TEAM_WAVES", "EDGE_STATIC_PCT", "EDGE_CHUNK", "NO_HOST_PIPELINE", "NO_DIRECT_LLR", "HOST_CHUNK_ROWS", "TIME_SMALL_CALLS", "REL_LDS", "HOST_PIPE_TIMING", "REL_LEVELS", "REL_PROF", "REL_SCRATCH_IN_L", "SER_RING", "SER_WAVES", "SER_LANE_MAX", "SER_LANE_THREADS", "SER_WAVES2", "RESIDENT", "SER_NO_REMAINDER", "SER_ROUND_TILES", "VAR_RING", "VAR_RING_UNITS", "SPREAD_NODES", "SER_VAR", "SER_VAR_UNITS", "REL_EXT", "OSD_COLLECT_AFTER", "EDGE_CLAMP", "OSD_NO_FLAT", "F32_NT", "F32_GRID_ROWS", "F32_ONCHIP", "F32_REPACK_MIN_TILES"};
 constexpr int k_n_switches = (int)(sizeof(k_switch_names) / sizeof(k_switch_names[0]));
 
 struct ldpc_hip_bp {
@@ -450,6 +450,87 @@ static int chunk_timing_end(ldpc_hip_bp *h) {
     HIPCHK(hipGetLastError());
     return LDPC_HIP_OK;
 }
+
+// ---- what the two-pass decodes share (host_stream.h: decode_stream_repacked; host_f32.h: decode_f32_repacked) -----------------------------
+// The pricing is described at decode_stream_repacked.  The handle has ONE histogram: one left by an FP64 decode may steer a float32 decode
+// and the other way round (same code, same noise: same iteration counts up to the rows where the two arithmetics part); results do not
+// depend on it, only where a decode is cut.
+// *late_rows: rows (of the histogram's batch) still running 8 iterations into the second pass -- the stragglers its late rounds are for (-1: unknown)
+static int stream_first_pass_length(ldpc_hip_bp *h, double *live_after, int64_t *late_rows, double gather_cost = 0.25) {
+    *live_after = 0.5;
+    *late_rows = -1;
+    if (h->repack_iters > 0) return h->repack_iters < h->max_iter ? h->repack_iters : 0;
+    // The previous decode's histogram, IF its copy has landed -- a look, never a wait (the *_async entry points must not block): a
+    // caller that queues decodes back to back is steered by the last histogram that did land
+    if (h->hist_pending) {
+        const hipError_t q = hipEventQuery(h->ev_hist);
+        if (q == hipSuccess) {
+            std::memcpy(h->hist_landed, h->h_hist, sizeof h->hist_landed);
+            h->hist_landed_max_iter = h->hist_max_iter;
+            h->hist_landed_valid = true;
+            h->hist_pending = false;
+        } else {
+            (void)hipGetLastError();  // hipErrorNotReady is not an error
+        }
+    }
+    if (!h->hist_landed_valid || h->hist_landed_max_iter != h->max_iter) return 0;
+    const int full = h->max_iter, top = full < 255 ? full : 255;
+    double total = 0;
+    for (int j = 0; j < 256; ++j) total += h->hist_landed[j];
+    if (total <= 0) return 0;
+    std::vector<double> F((size_t)top + 1, 0.0);  // F[j]: converged within j iterations
+    double acc = 0;
+    for (int j = 1; j <= top; ++j) { acc += h->hist_landed[j]; F[(size_t)j] = acc / total; }
+    auto Fj = [&](int j) { return F[(size_t)(j < top ? j : top)]; };
+    auto tile_runs = [&](int j) { return 1.0 - std::pow(Fj(j - 1), 64.0); };  // still going at iteration j
+    double plain = 0;
+    for (int j = 1; j <= full; ++j) plain += tile_runs(j);
+    double best = plain, prefix = 0;
+    int best_k = 0;
+    for (int k = 1; k < full && k <= top; ++k) {
+        prefix += tile_runs(k);
+        const double live = 1.0 - Fj(k);
+        if (k < 2 || live <= 0.0 || live > 0.6) continue;
+        double rest = 0;
+        for (int j = k + 1; j <= full; ++j) {
+            const double g = (Fj(j - 1) - Fj(k)) / live;  // of the rows alive after k: done within j - 1
+            const double r = 1.0 - std::pow(g < 0 ? 0 : g, 64.0);
+            rest += r;
+            if (r < 1e-9 && j > top) break;
+        }
+        const double cost = prefix + gather_cost * (1.0 + live) + 0.1 + live * rest;
+        if (cost < best) { best = cost; best_k = k; *live_after = live; }
+    }
+    if (best_k > 0) {
+        double late = h->hist_landed[0];
+        for (int j = best_k + 9; j < 256; ++j) late += h->hist_landed[j];
+        *late_rows = (int64_t)late;
+    }
+    return best < 0.97 * plain ? best_k : 0;
+}
+
+static int stream_leave_histogram(ldpc_hip_bp *h, const int32_t *iters, const uint8_t *conv, int64_t batch) {
+    int rc;
+    if ((rc = h->sp_hist.ensure(256 * sizeof(unsigned)))) return rc;
+    if (!h->h_hist) HIPCHK(hipHostMalloc((void **)&h->h_hist, 256 * sizeof(unsigned), hipHostMallocDefault));
+    HIPCHK(hipMemsetAsync(h->sp_hist.p, 0, 256 * sizeof(unsigned), h->stream));
+    int64_t blocks = (batch + 255) / 256;
+    if (blocks > 1024) blocks = 1024;
+    LDPC_LAUNCH(iteration_histogram_kernel, dim3((unsigned)blocks), dim3(256), 0, h->stream, iters, conv, batch, (unsigned *)h->sp_hist.p);
+    HIPCHK(hipMemcpyAsync(h->h_hist, h->sp_hist.p, 256 * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipEventRecord(h->ev_hist, h->stream));
+    h->hist_pending = true;
+    h->hist_max_iter = h->max_iter;
+    return LDPC_HIP_OK;
+}
+
+// rows_dev[0] = rows listed by osd_collect_kernel, rows_dev[1] = their 64-row tiles (BpArgs::rows_dev)
+LDPC_IO_KERNEL void repack_rows_kernel(const unsigned *__restrict__ counters, unsigned *__restrict__ rows_dev) {
+    const unsigned c = counters[0];
+    rows_dev[0] = c;
+    rows_dev[1] = (c + LDPC_WAVE - 1) / LDPC_WAVE;
+}
+
 
 // ---- what the translation units call in each other (device pointers, on h->stream) -------------------------------------------------
 // tu_stream.hip: the dispatch of a batch to a kernel family, and the streamed kernels themselves

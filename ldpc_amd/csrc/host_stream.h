@@ -363,82 +363,8 @@ static int decode_streamed(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, u
 // gather = reading one message array of every tile and writing the live share = (1 + (1 - F(k))) * gather_cost of an iteration (the
 // flooding schedule moves four arrays per iteration: 1/4; the serial schedule six segments per edge: 1/6), plus the first pass's outputs for rows that are decoded on.  No work is wasted when nothing
 // converges (the first call, and every call whose predecessor says "plain", run plain); results do not depend on any of this.
-// *late_rows: rows (of the histogram's batch) still running 8 iterations into the second pass -- the stragglers its late rounds are for (-1: unknown)
-static int stream_first_pass_length(ldpc_hip_bp *h, double *live_after, int64_t *late_rows, double gather_cost = 0.25) {
-    *live_after = 0.5;
-    *late_rows = -1;
-    if (h->repack_iters > 0) return h->repack_iters < h->max_iter ? h->repack_iters : 0;
-    // The previous decode's histogram, IF its copy has landed -- a look, never a wait (the *_async entry points must not block): a
-    // caller that queues decodes back to back is steered by the last histogram that did land
-    if (h->hist_pending) {
-        const hipError_t q = hipEventQuery(h->ev_hist);
-        if (q == hipSuccess) {
-            std::memcpy(h->hist_landed, h->h_hist, sizeof h->hist_landed);
-            h->hist_landed_max_iter = h->hist_max_iter;
-            h->hist_landed_valid = true;
-            h->hist_pending = false;
-        } else {
-            (void)hipGetLastError();  // hipErrorNotReady is not an error
-        }
-    }
-    if (!h->hist_landed_valid || h->hist_landed_max_iter != h->max_iter) return 0;
-    const int full = h->max_iter, top = full < 255 ? full : 255;
-    double total = 0;
-    for (int j = 0; j < 256; ++j) total += h->hist_landed[j];
-    if (total <= 0) return 0;
-    std::vector<double> F((size_t)top + 1, 0.0);  // F[j]: converged within j iterations
-    double acc = 0;
-    for (int j = 1; j <= top; ++j) { acc += h->hist_landed[j]; F[(size_t)j] = acc / total; }
-    auto Fj = [&](int j) { return F[(size_t)(j < top ? j : top)]; };
-    auto tile_runs = [&](int j) { return 1.0 - std::pow(Fj(j - 1), 64.0); };  // still going at iteration j
-    double plain = 0;
-    for (int j = 1; j <= full; ++j) plain += tile_runs(j);
-    double best = plain, prefix = 0;
-    int best_k = 0;
-    for (int k = 1; k < full && k <= top; ++k) {
-        prefix += tile_runs(k);
-        const double live = 1.0 - Fj(k);
-        if (k < 2 || live <= 0.0 || live > 0.6) continue;
-        double rest = 0;
-        for (int j = k + 1; j <= full; ++j) {
-            const double g = (Fj(j - 1) - Fj(k)) / live;  // of the rows alive after k: done within j - 1
-            const double r = 1.0 - std::pow(g < 0 ? 0 : g, 64.0);
-            rest += r;
-            if (r < 1e-9 && j > top) break;
-        }
-        const double cost = prefix + gather_cost * (1.0 + live) + 0.1 + live * rest;
-        if (cost < best) { best = cost; best_k = k; *live_after = live; }
-    }
-    if (best_k > 0) {
-        double late = h->hist_landed[0];
-        for (int j = best_k + 9; j < 256; ++j) late += h->hist_landed[j];
-        *late_rows = (int64_t)late;
-    }
-    return best < 0.97 * plain ? best_k : 0;
-}
-
-static int stream_leave_histogram(ldpc_hip_bp *h, const int32_t *iters, const uint8_t *conv, int64_t batch) {
-    int rc;
-    if ((rc = h->sp_hist.ensure(256 * sizeof(unsigned)))) return rc;
-    if (!h->h_hist) HIPCHK(hipHostMalloc((void **)&h->h_hist, 256 * sizeof(unsigned), hipHostMallocDefault));
-    HIPCHK(hipMemsetAsync(h->sp_hist.p, 0, 256 * sizeof(unsigned), h->stream));
-    int64_t blocks = (batch + 255) / 256;
-    if (blocks > 1024) blocks = 1024;
-    LDPC_LAUNCH(iteration_histogram_kernel, dim3((unsigned)blocks), dim3(256), 0, h->stream, iters, conv, batch, (unsigned *)h->sp_hist.p);
-    HIPCHK(hipMemcpyAsync(h->h_hist, h->sp_hist.p, 256 * sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipEventRecord(h->ev_hist, h->stream));
-    h->hist_pending = true;
-    h->hist_max_iter = h->max_iter;
-    return LDPC_HIP_OK;
-}
-
-// rows_dev[0] = rows listed by osd_collect_kernel, rows_dev[1] = their 64-row tiles (BpArgs::rows_dev)
-__global__ void repack_rows_kernel(const unsigned *__restrict__ counters, unsigned *__restrict__ rows_dev) {
-    const unsigned c = counters[0];
-    rows_dev[0] = c;
-    rows_dev[1] = (c + LDPC_WAVE - 1) / LDPC_WAVE;
-}
-
+// (stream_first_pass_length -- the pricing --, stream_leave_histogram and repack_rows_kernel live in host_handle.h: the float32 mode's two-pass decode,
+// host_f32.h, shares them)
 // Nothing here waits for the device: the second pass is queued at once, sized for the most rows there can be (all of them), and
 // finds out on the device how many rows the first pass left -- osd_collect_kernel lists them, repack_rows_kernel turns the count
 // into rows / tiles, every kernel of the second pass reads those (BpArgs::rows_dev) and reaches the caller's arrays through the

@@ -165,7 +165,9 @@ class HipBpEngine:
         return out
 
     def set_repack(self, first_pass_iters):
-        """Serial schedule: iterations of the first pass before unconverged rows are repacked (-1 auto, 0 off)."""
+        """Iterations of the first pass before the rows still decoding are repacked into dense tiles (-1 automatic, 0 off): the serial
+        schedules, the streamed parallel schedule and the float32 message mode's per-pass route (include/ldpc_hip.h says how each
+        uses it; results never depend on it)."""
         _lib.check(self._lib.ldpc_hip_bp_set_repack(self._h, int(first_pass_iters)))
 
     def set_serial_kernel(self, mode):

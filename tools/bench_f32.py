@@ -5,6 +5,8 @@
     python tools/bench_f32.py --speed                     # syndromes/s of both modes + the copy probe, same process, same box
     python tools/bench_f32.py --speed --modes float64 --tree <checkout>   # the float64 of another built checkout (the parent commit: A/B on one box)
     python tools/bench_f32.py --speed --configs small     # the small codes the on-chip kernels take (each at its own batch sizes)
+    python tools/bench_f32.py --speed --repack 0          # ... with the two-pass decode off (set_repack; default -1: the previous decode's histogram decides)
+    python tools/bench_f32.py --agreement-two-pass        # float32 two-pass against float32 with set_repack(0): rows that differ, log-ratio bits included
 
 Configurations: (3,6)-regular n = 10 000, min-sum 50 iterations, at p = 0.05 and 0.09; the irregular n = 10 000 code of
 ``bench.py --full`` (speed only); BB144 min-sum 50 + OSD-0 (agreement only).  ``--configs small`` (speed only): the codes whose messages
@@ -126,10 +128,53 @@ def agreement(batch):
         eng.close()
 
 
-def speed(batch, modes, reps):
+def agreement_two_pass(batch, repack):
+    """float32 with the two-pass decode (``repack``: -1 = steered by the histogram the decodes before it left, k = forced) against float32
+    with set_repack(0), on the configurations and at the size of ``--speed``: rows whose decisions, flags, iteration counts or log-ratio
+    BITS differ -- the two must be the same decode."""
     import torch
+    from ldpc_amd.engine import launch_log
     for name, h, p, _ in _configs(("ldpc36", "irregular")):
         eng = _engine(h, p, 50)
+        eng.set_message_dtype("float32")
+        synd = eng.gen_bsc_syndromes(12345, p, 0, batch, device="cuda")
+        res = {}
+        for tag, k in (("plain", 0), ("two_pass", repack)):
+            eng.set_repack(k)
+            out = None
+            for r in range(3):  # (the first decode on a handle leaves the histogram, the third is certainly steered by one)
+                with launch_log() as log:
+                    out = eng.decode_batch(synd, want_llr=True, out=out)
+                    torch.cuda.synchronize()
+            res[tag] = out
+            res[tag + "_kernels"] = {k_: v for k_, v in sorted(log.items()) if k_.startswith("bp_")}
+        if "bp_f32_gather_lanes_kernel" not in res["two_pass_kernels"] or "bp_f32_gather_lanes_kernel" in res["plain_kernels"]:
+            # not a two-pass decode against a plain one (the histogram said "plain", as where nothing converges, or a tree without the two-pass decode): no counts to report
+            print(json.dumps(dict(kind="agreement_two_pass", config=name, batch=batch, repack=repack, two_pass_ran=False,
+                                  bp_kernels_plain=res["plain_kernels"], bp_kernels_two_pass=res["two_pass_kernels"])), flush=True)
+            del res
+            eng.close()
+            continue
+        a, b = res["plain"], res["two_pass"]
+        d = (a[0] != b[0]).any(dim=1)
+        l = (a[1].view(torch.int64) != b[1].view(torch.int64)).any(dim=1)
+        i, c = a[2] != b[2], a[3] != b[3]
+        print(json.dumps(dict(kind="agreement_two_pass", config=name, batch=batch, repack=repack, two_pass_ran=True, rows_decisions_differ=int(d.sum()), rows_llr_bits_differ=int(l.sum()),
+                              rows_iterations_differ=int(i.sum()), rows_converge_differ=int(c.sum()), rows_any_differ=int((d | l | i | c).sum()),
+                              converged=int(a[3].sum()), bp_kernels_plain=res["plain_kernels"], bp_kernels_two_pass=res["two_pass_kernels"])), flush=True)
+        del res, a, b
+        eng.close()
+
+
+def speed(batch, modes, reps, repack=-1, tag="", tree_name=None, configs=("ldpc36", "irregular")):
+    import torch
+    try:
+        from ldpc_amd.engine import launch_log as _launch_log
+    except ImportError:  # (a checkout from before the launch log)
+        _launch_log = None
+    for name, h, p, _ in _configs(configs):
+        eng = _engine(h, p, 50)
+        eng.set_repack(repack)
         synd = eng.gen_bsc_syndromes(12345, p, 0, batch, device="cuda")
         tiles = (batch + 63) // 64
         for mode in modes:
@@ -137,13 +182,22 @@ def speed(batch, modes, reps):
                 eng.set_message_dtype(mode)
             out = None
             rates, kms = [], []
-            for r in range(reps + 2):  # two untimed: allocations, and the histogram that steers the two-pass decode
+            kernels = None
+            # three untimed: allocations; the first decode on a handle always runs plain and only leaves the histogram that steers the
+            # two-pass decode; the third is steered like the timed ones and is the one whose BP kernels are put on record
+            for r in range(reps + 3):
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
-                out = eng.decode_batch(synd, want_llr=False, out=out)
+                if r == 2 and _launch_log is not None:
+                    with _launch_log() as log:
+                        out = eng.decode_batch(synd, want_llr=False, out=out)
+                        torch.cuda.synchronize()
+                    kernels = {k: v for k, v in sorted(log.items()) if k.startswith("bp_")}
+                else:
+                    out = eng.decode_batch(synd, want_llr=False, out=out)
                 torch.cuda.synchronize()
                 dt = time.perf_counter() - t0
-                if r >= 2:
+                if r >= 3:
                     rates.append(batch / dt)
                     kms.append(eng.last_kernel_ms())
             it = out[2].cpu().numpy().astype(np.int64)
@@ -154,7 +208,7 @@ def speed(batch, modes, reps):
             # what a tile-by-tile flooding decode has to move: 4 message-array passes per tile-iteration (float64: as if nothing were compacted)
             gbytes = tile_iters * 4 * eng.nnz * 64 * esize / 1e9
             _, probe = eng.copy_probe(min(tiles, 1024), eng.nnz, 4)
-            print(json.dumps(dict(kind="speed", config=name, mode=mode, tree=os.path.relpath(_TREE), batch=batch,
+            print(json.dumps(dict(kind="speed", config=name, mode=mode, tree=tree_name or os.path.relpath(_TREE), tag=tag, repack=repack, batch=batch, bp_kernels=kernels,
                                   syndromes_per_s=[round(x) for x in rates], median_syndromes_per_s=round(float(np.median(rates))),
                                   kernel_ms=[round(x, 2) for x in kms], tile_iterations=tile_iters, message_gbytes=round(gbytes, 1),
                                   message_gbytes_per_s=round(gbytes / (float(np.median(kms)) * 1e-3), 1), copy_probe_gbytes_per_s=round(probe, 1),
@@ -173,15 +227,20 @@ def main():
     ap.add_argument("--tree", default=None, help="another built checkout to take ldpc_amd from (default: this one)")
     ap.add_argument("--configs", default="large", choices=["large", "small"], help="--speed: the n = 10 000 codes, or the small codes of the on-chip kernels")
     ap.add_argument("--warmup", type=int, default=3, help="--configs small: untimed decodes before the timed ones")
-    ap.add_argument("--tag", default="", help="--configs small: copied into every line (which leg of a comparison this is)")
-    ap.add_argument("--tree-name", default=None, help="--configs small: what the lines call the tree (default: its path)")
+    ap.add_argument("--tag", default="", help="--speed: copied into every line (which leg of a comparison this is)")
+    ap.add_argument("--tree-name", default=None, help="--speed: what the lines call the tree (default: its path)")
+    ap.add_argument("--repack", type=int, default=-1, help="--speed (large), --agreement-two-pass: set_repack -- -1 the previous decode's histogram decides (default), 0 off, k a forced first pass")
+    ap.add_argument("--only", default="ldpc36,irregular", help="--speed (large): which of the code families to run")
+    ap.add_argument("--agreement-two-pass", action="store_true")
     a = ap.parse_args()
     if a.agreement:
         agreement(a.batch)
+    if a.agreement_two_pass:
+        agreement_two_pass(a.batch, a.repack)
     if a.speed and a.configs == "small":
         speed_small(a.modes.split(","), a.reps, a.warmup, a.tag, a.tree_name)
     elif a.speed:
-        speed(a.batch, a.modes.split(","), a.reps)
+        speed(a.batch, a.modes.split(","), a.reps, a.repack, a.tag, a.tree_name, tuple(a.only.split(",")))
 
 
 if __name__ == "__main__":
