@@ -186,8 +186,11 @@ int ldpc_hip_bposd0_decode_batch_async(ldpc_hip_bp *h, const uint8_t *syndromes,
  * [0, 1] or NaN: LDPC_HIP_ERR_INVALID), a device array is the caller's word.  The *_async forms take device pointers only and do not wait.
  * Parallel schedule only: any serial schedule -> LDPC_HIP_ERR_UNSUPPORTED (ldpc_hip_last_error says so).  Higher-order OSD weighs its
  * candidates by log(1 / p) (osd.hpp:134) and has no such form.  Kernels: codes that stream run the per-pass kernels from the first
- * iteration with a per-lane prior; codes an on-chip kernel takes run the slot kernel (csrc/bp_small_kernel.h), each slot holding its
- * syndrome's priors.  Extra workspace: 512 n bytes per 64-syndrome tile.
+ * iteration with a per-lane prior; min-sum on a code the lane = edge kernels take (ldpc_hip_bp_set_small_code_kernel: rows <= 4 and
+ * columns <= 2 with m <= 256, or rows <= 8 and columns <= 4 with 8 m <= 768; modes -1, 1, 6) runs their row-prior forms
+ * (csrc/bp_edge_rp_kernel.h), a wavefront reading its syndrome's priors from a row-major array of log-ratios; every other code an
+ * on-chip kernel takes runs the slot kernel (csrc/bp_small_kernel.h), each slot holding its syndrome's priors.  Extra workspace:
+ * 512 n bytes per 64-syndrome tile (8 n bytes per syndrome on the lane = edge kernels).
  */
 int ldpc_hip_bp_decode_batch_priors(ldpc_hip_bp *h, const uint8_t *syndromes, int64_t batch, uint8_t *decoding, double *llr,
                                     int32_t *iterations, uint8_t *converge, const double *channel_probs);
@@ -410,7 +413,10 @@ int ldpc_hip_bp_set_handoff(ldpc_hip_bp *h, int32_t threshold_tiles);
  * register for the whole decode (bp_edge_kernel.h: bp_edge_kernel); with rows of weight <= 8 and columns of weight <= 4
  * (8 m <= 768: the bivariate-bicycle family) the same idea with a row in EIGHT neighbouring lanes (bp_edge8_kernel).
  * 6 = those variants where they apply, else as -1.  The on-chip kernels take batches below 2^30 syndromes (larger ones
- * are streamed).  Results are identical. */
+ * are streamed).  Results are identical.
+ * Row priors (ldpc_hip_*_decode_batch_priors): mode 0 = the per-pass kernels; modes -1, 1, 6 with min-sum on a code of the lane = edge
+ * variants = their row-prior forms (bp_edge_rp_kernel, bp_edge8_rp_kernel); any other code an on-chip kernel would take, and mode 2
+ * always = the slot variant, the only other on-chip kernel that reads a prior per syndrome. */
 int ldpc_hip_bp_set_small_code_kernel(ldpc_hip_bp *h, int32_t mode);
 /* Measurement / test switches: kernel-shape choices that never change a result (profiles/README.md lists them: "PS_TEAM",
  * "OSD_UNBLOCKED", "OSD_PLANES", "EDGE_STATIC_PCT", "EDGE_CHUNK", ...; for schedule = serial_relative: "REL_LDS" 0 = the

@@ -28,8 +28,8 @@
 //
 // Built with: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared
 //
-// Seven translation units, compiled side by side and linked into one library (Makefile): this one carries the C ABI (handle, setup,
-// decode entry points, layout kernels); tu_stream.hip, tu_serial.hip, tu_onchip.hip, tu_onchip_f32.hip, tu_osd.hip and tu_f32.hip carry one kernel family each
+// Eight translation units, compiled side by side and linked into one library (Makefile): this one carries the C ABI (handle, setup,
+// decode entry points, layout kernels); tu_stream.hip, tu_serial.hip, tu_onchip.hip, tu_onchip_f32.hip, tu_onchip_rp.hip, tu_osd.hip and tu_f32.hip carry one kernel family each
 // together with its host side (host_stream.h, host_serial.h, host_onchip.h, host_osd.h, host_f32.h).  What they call in each other is
 // declared at the end of host_handle.h.  Device code lives in the kernel headers:
 //   bp_device_common.h   argument blocks, buffer-descriptor message addressing, per-node arithmetic, LDS-DMA helpers
@@ -43,6 +43,7 @@
 //   bp_serial_kernels.h  bp_serial_kernel, bp_softinfo_kernel   serial schedule, soft-syndrome serial min-sum
 //   bp_f32_kernels.h     bp_f32_*_kernel                    float32 message mode: min-sum, parallel schedule, one launch per pass (host_f32.h)
 //   bp_edge_f32_kernel.h bp_edge_f32_kernel, bp_edge8_f32_kernel   float32 message mode on the lane = edge families: messages in registers (tu_onchip_f32.hip)
+//   bp_edge_rp_kernel.h  bp_edge_rp_kernel, bp_edge8_rp_kernel     row priors on the lane = edge families: every syndrome its own priors (tu_onchip_rp.hip)
 //   osd_kernels.h        osd0[_reg]_kernel, osdw[_reg]_kernel, osd_big_kernel   OSD-0 / OSD-E / OSD-CS post-processing
 //   io_kernels.h         pack / unpack / transpose, H v, b8 shot data, synthetic BSC shots
 //   multi_device.h       ldpc_hip_bp_multi_*: a batch sharded over several GPUs inside one process (host code only)

@@ -1,5 +1,5 @@
 // host_handle.h -- the handle (struct ldpc_hip_bp), error reporting, device buffers, measurement switches
-// Part of libldpc_hip.so: included by every translation unit (bp_hip.hip = the C ABI; tu_stream / tu_serial / tu_onchip / tu_onchip_f32 / tu_osd / tu_f32.hip = one kernel
+// Part of libldpc_hip.so: included by every translation unit (bp_hip.hip = the C ABI; tu_stream / tu_serial / tu_onchip / tu_onchip_f32 / tu_onchip_rp / tu_osd / tu_f32.hip = one kernel
 // family each with its host side).  What one unit calls in another is declared at the end of this header.
 #pragma once
 
@@ -150,7 +150,7 @@ struct DeviceBuf {  // grow-only device allocation, freed with its owner (on the
 // creation, from the environment variables LDPC_HIP_<NAME>, changed afterwards only through ldpc_hip_bp_set_debug_switch -- no
 // getenv on the decode path, and nothing a test can change under a live handle by accident.
 static const char *const k_switch_names[] = {"PS_TEAM", "EXPLICIT_INIT", "OSD_UNBLOCKED", "OSD_PLANES",
-                                             "PS_TEAM_WAVES", "EDGE_STATIC_PCT", "EDGE_CHUNK", "NO_HOST_PIPELINE", "NO_DIRECT_LLR", "HOST_CHUNK_ROWS", "TIME_SMALL_CALLS", "REL_LDS", "HOST_PIPE_TIMING", "REL_LEVELS", "REL_PROF", "REL_SCRATCH_IN_L", "SER_RING", "SER_WAVES", "SER_LANE_MAX", "SER_LANE_THREADS", "SER_WAVES2", "RESIDENT", "SER_NO_REMAINDER", "SER_ROUND_TILES", "VAR_RING", "VAR_RING_UNITS", "SPREAD_NODES", "SER_VAR", "SER_VAR_UNITS", "REL_EXT", "OSD_COLLECT_AFTER", "EDGE_CLAMP", "OSD_NO_FLAT", "F32_NT", "F32_GRID_ROWS", "F32_ONCHIP", "F32_REPACK_MIN_TILES"};
+                                             "PS_TEAM_WAVES", "EDGE_STATIC_PCT", "EDGE_CHUNK", "NO_HOST_PIPELINE", "NO_DIRECT_LLR", "HOST_CHUNK_ROWS", "TIME_SMALL_CALLS", "REL_LDS", "HOST_PIPE_TIMING", "REL_LEVELS", "REL_PROF", "REL_SCRATCH_IN_L", "SER_RING", "SER_WAVES", "SER_LANE_MAX", "SER_LANE_THREADS", "SER_WAVES2", "RESIDENT", "SER_NO_REMAINDER", "SER_ROUND_TILES", "VAR_RING", "VAR_RING_UNITS", "SPREAD_NODES", "SER_VAR", "SER_VAR_UNITS", "REL_EXT", "OSD_COLLECT_AFTER", "EDGE_CLAMP", "OSD_NO_FLAT", "F32_NT", "F32_GRID_ROWS", "F32_ONCHIP", "F32_REPACK_MIN_TILES", "EDGE_RP"};
 constexpr int k_n_switches = (int)(sizeof(k_switch_names) / sizeof(k_switch_names[0]));
 
 struct ldpc_hip_bp {
@@ -313,7 +313,7 @@ struct ldpc_hip_bp {
     // Row priors (ldpc_hip_*_decode_batch_priors): the call's [batch][n] channel probabilities on the device while it runs, nullptr
     // otherwise -- decode_device, the streamed decode (host_stream.h: rp) and decode_onchip look here, nobody else; the handle's own channel_probs / d_llr0 are not touched.
     const double *row_probs = nullptr;
-    DeviceBuf rowp_llr;  // their log-ratios in tile layout [tiles of a chunk][n][64] (io_kernels.h: row_priors_kernel)
+    DeviceBuf rowp_llr;  // their log-ratios: in tile layout [tiles of a chunk][n][64] (io_kernels.h: row_priors_kernel), or row-major [batch][n] for the lane = edge kernels (row_priors_rowmajor_kernel)
     DeviceBuf st_probs;  // staging for a host pointer
 };
 

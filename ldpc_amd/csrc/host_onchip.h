@@ -644,6 +644,68 @@ static int decode_edge8_f32(ldpc_hip_bp *h, const Edge8Plan &p, const uint8_t *s
     return launch_edge_f32(h, edge8_f32_kernel(p.rounds, p.dc, p.uniform), p.rounds, edge8_f32_waves(p.rounds, p.dc, p.uniform), batch, a);
 }
 
+// ---- the same two families with row priors (bp_edge_rp_kernel.h; instantiated in tu_onchip_rp.hip): ldpc_hip_*_decode_batch_priors on the codes of plan_edge / plan_edge8 ----
+// Everything but the priors is decode_edge's / decode_edge8's: the shared slot tables, the work split, the grid of the general form (4 wavefronts per
+// SIMD), the timing events.  The priors: h->row_probs [batch][n] -> h->rowp_llr [batch][n] log-ratios, whole batch (row_priors_rowmajor_kernel,
+// io_kernels.h); e_prior is neither written nor read, so the next plain call finds it as its own last launch left it (and rewrites it anyway).
+template <class ARGS>
+static int launch_edge_rp(ldpc_hip_bp *h, void (*kern)(const ARGS), int rounds, int64_t batch, ARGS &ra) {
+    if (!kern) return fail(LDPC_HIP_ERR_UNSUPPORTED, "row priors: no lane = edge kernel was built for %d rounds", rounds);
+    int rc;
+    const size_t items = (size_t)batch * (size_t)h->n;
+    if ((rc = h->rowp_llr.ensure(sizeof(double) * items))) return rc;
+    LDPC_LAUNCH(row_priors_rowmajor_kernel, flat_grid(items), dim3(256), 0, h->stream, h->row_probs, (int64_t)items, (double *)h->rowp_llr.p);
+    HIPCHK(hipGetLastError());
+    ra.rowp = (const double *)h->rowp_llr.p;
+    auto &a = ra.e;
+    a.m = h->m; a.n = h->n; a.max_iter = h->max_iter;
+    a.ms_scaling_factor = h->ms_scaling_factor;
+    a.batch = batch;
+    a.kind = (const uint8_t *)h->e_kind.p; a.scol = (const int32_t *)h->e_scol.p;
+    const size_t dyn = edge_lds_bytes(rounds);
+    int64_t per_cu = (int64_t)((160u * 1024u) / (dyn + 64));
+    if (per_cu > 16) per_cu = 16;  // (__launch_bounds__(64, 4): the general form's four wavefronts per SIMD)
+    const int64_t groups = batch < 256 * per_cu ? batch : 256 * per_cu;
+    if ((rc = edge_work_split(h, rounds, batch, groups, a))) return rc;
+    h->accumulated_ms = 0.f;
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    LDPC_LAUNCH(kern, dim3((unsigned)groups), dim3(64), (unsigned)dyn, h->stream, ra);
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    h->timed = true;
+    HIPCHK(hipGetLastError());
+    return LDPC_HIP_OK;
+}
+
+static int decode_edge_rp(ldpc_hip_bp *h, const EdgePlan &p, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr,
+                          int32_t *iters, uint8_t *conv) {
+    int rc;
+    if ((rc = ensure_edge_tables(h, p))) return rc;
+    EdgeRpArgs ra = {};
+    ra.e.partner = (const uint16_t *)h->e_partner.p;
+    ra.e.synd = synd; ra.e.decoding = decoding; ra.e.llr = llr; ra.e.iters = iters; ra.e.conv = conv;
+    return launch_edge_rp(h, edge_rp_kernel(p.rounds), p.rounds, batch, ra);
+}
+
+static int decode_edge8_rp(ldpc_hip_bp *h, const Edge8Plan &p, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr,
+                           int32_t *iters, uint8_t *conv) {
+    int rc;
+    if ((rc = ensure_edge8_tables(h, p))) return rc;
+    Edge8RpArgs ra = {};
+    ra.e.cpos = (const uint16_t *)h->e_partner.p;
+    ra.e.synd = synd; ra.e.decoding = decoding; ra.e.llr = llr; ra.e.iters = iters; ra.e.conv = conv;
+    return launch_edge_rp(h, edge8_rp_kernel(p.rounds, p.dc), p.rounds, batch, ra);
+}
+
+// Row priors on the lane = edge kernels?  Debug switch EDGE_RP: 0 the slot kernel (bp_small_kernel<., ., true>), 1 bp_edge_rp_kernel /
+// bp_edge8_rp_kernel, unset: the default below -- the route, by the rule fixed before it was measured: on one MI355X in one
+// job it beat the slot kernel, the parent's row-prior decode, 3.1x on BB144 min-sum 50 (87.1 against 27.8 M syndromes/s) and 17.2x on the
+// surface code d = 21 min-sum 30 (43.7 against 2.54 M/s), the parent's two runs 0.3 % and 0.5 % apart (profiles/row_priors_edge.jsonl).
+static constexpr bool k_edge_rp_default = true;
+static bool edge_rp_route(const ldpc_hip_bp *h) {
+    const int s = h->sw("EDGE_RP");
+    return s >= 0 ? s != 0 : k_edge_rp_default;
+}
+
 // The float32 message mode's on-chip planner, called by decode_f32 (host_f32.h) after its refusals: decode_onchip's predicate for the lane =
 // edge families and their two plans, unchanged.  *took = false: neither takes the code -- decode_f32 goes on with its per-pass kernels (in
 // float32 nothing ever goes to bp_wave_kernel, bp_small_kernel or any FP64 kernel).
@@ -659,8 +721,9 @@ int decode_onchip_f32(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_
 }
 
 // Which on-chip kernel (if any) takes this batch: called by decode_device (host_stream.h) before it falls back to the streamed tiles.
-// Row priors (h->row_probs): a code that one of these kernels takes goes to the SLOT kernel, the one that reads every syndrome's own priors
-// (bp_small_kernel<., ., RP>) -- with as many slots as fit -- and to the per-pass kernels (took = false) if not even one slot fits.
+// Row priors (h->row_probs): min-sum on a code that plan_edge or plan_edge8 takes (modes -1, 1, 6) runs on their row-prior forms (bp_edge_rp_kernel,
+// bp_edge8_rp_kernel) where edge_rp_route says so; any other code that one of these kernels takes goes to the SLOT kernel, which reads every syndrome's
+// own priors too (bp_small_kernel<., ., RP>) -- with as many slots as fit -- and to the per-pass kernels (took = false) if not even one slot fits.
 int decode_onchip(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv, bool *took) {
     *took = false;
     const bool rp = h->row_probs != nullptr;
@@ -674,9 +737,17 @@ int decode_onchip(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
         }
         if (!*took && (h->small_mode == -1 || h->small_mode == 1 || h->small_mode == 6)) {  // min-sum on the surface-code family: lane = edge
             const EdgePlan ep = plan_edge(h);
-            if (ep.rounds) { *took = true; if (!rp) return decode_edge(h, ep, synd, batch, decoding, llr, iters, conv); }
+            if (ep.rounds) {
+                *took = true;
+                if (!rp) return decode_edge(h, ep, synd, batch, decoding, llr, iters, conv);
+                if (edge_rp_route(h)) return decode_edge_rp(h, ep, synd, batch, decoding, llr, iters, conv);
+            }
             const Edge8Plan e8 = plan_edge8(h);  // heavier nodes (rows <= 8, columns <= 4): rows in 8-lane groups
-            if (!*took && e8.rounds) { *took = true; if (!rp) return decode_edge8(h, e8, synd, batch, decoding, llr, iters, conv); }
+            if (!*took && e8.rounds) {
+                *took = true;
+                if (!rp) return decode_edge8(h, e8, synd, batch, decoding, llr, iters, conv);
+                if (edge_rp_route(h)) return decode_edge8_rp(h, e8, synd, batch, decoding, llr, iters, conv);
+            }
         }
         if (!*took && h->small_mode != 2) {
             const WavePlan wp = plan_wave(h, h->small_mode == 1 || (h->small_mode >= 3 && h->small_mode != 6), llr != nullptr, batch);

@@ -113,6 +113,19 @@ LDPC_IO_KERNEL void __launch_bounds__(256) row_priors_kernel(const double *__res
     }
 }
 
+// Row priors for the lane = edge kernels (bp_edge_rp_kernel.h): the same conversion, element by element -- the IEEE division and the bit-exact
+// log twin of row_priors_kernel above -- into a ROW-MAJOR array out [batch][n], the layout of `probs`: a wavefront of those kernels holds
+// one syndrome and its lanes read that syndrome's priors at their columns, 8 n contiguous bytes.  No padding: row b is read for syndrome b only.
+LDPC_IO_KERNEL void __launch_bounds__(256) row_priors_rowmajor_kernel(const double *__restrict__ probs, int64_t items, double *__restrict__ out) {
+    __shared__ __attribute__((aligned(16))) double log_tab[256];
+    log_tab[threadIdx.x] = ldpc_math::k_log_tab[threadIdx.x];
+    __syncthreads();
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < items; t += (int64_t)gridDim.x * blockDim.x) {
+        const double p = probs[t];
+        out[t] = ldpc_math::log_libm((1.0 - p) / p, log_tab);
+    }
+}
+
 // GF2Sparse::mulvec over a batch (gf2sparse.hpp:177-214): one thread per (vector, check)
 LDPC_IO_KERNEL void gf2_mulvec_kernel(const int32_t *__restrict__ row_ptr,
                                   const int32_t *__restrict__ col_idx, int m, int n,

@@ -4,13 +4,14 @@
     LDPC_HIP_LAUNCH_LOG=/tmp/launches.txt python -m pytest tests -m gpu          (the log: profiles/README.md)
     python tools/instantiation_coverage.py /tmp/ru.txt /tmp/launches.txt [more logs ...] > profiles/instantiation_coverage.txt
 Prints reached / total per template and every unreached name.  In the four families tests/test_gpu_instantiations.py walks (bp_edge_kernel,
-bp_edge8_kernel, bp_wave_kernel, bp_wave_ps_kernel) an unreached name is marked: "not selectable" where no size rule of host_onchip.h can pick
+bp_edge8_kernel, bp_wave_kernel, bp_wave_ps_kernel) and the two tests/test_gpu_row_priors_edge.py walks (bp_edge_rp_kernel, bp_edge8_rp_kernel) an
+unreached name is marked: "not selectable" where no size rule of host_onchip.h can pick
 it (NOT_SELECTABLE below, with the reason), else "gap"; the other families are listed only."""
 import re
 import subprocess
 import sys
 
-WALKED = ("bp_edge_kernel", "bp_edge8_kernel", "bp_wave_kernel", "bp_wave_ps_kernel")
+WALKED = ("bp_edge_kernel", "bp_edge8_kernel", "bp_wave_kernel", "bp_wave_ps_kernel", "bp_edge_rp_kernel", "bp_edge8_rp_kernel")
 # instantiation -> why no rule selects it (tests/ladder_util.py UNREACHABLE names the test that keeps each claim true)
 NOT_SELECTABLE = {}
 
