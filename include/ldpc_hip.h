@@ -428,7 +428,7 @@ int ldpc_hip_bp_set_small_code_kernel(ldpc_hip_bp *h, int32_t mode);
  * per-pass kernels from the start; "SER_VAR" 0 = the streamed serial schedule's item form (any degree profile) never, 1 = also
  * on (6,3)-regular matrices, "SER_VAR_UNITS" its KiB of LDS per wavefront (default 8); "REL_EXT" 0 / 1 = serial_relative's on-chip kernel never / always with the messages and
  * per-entry records in global memory (default: where the all-in-LDS form leaves fewer than four wavefronts per compute unit); "OSD_COLLECT_AFTER" 1 = BP + OSD lists the
- * rows BP left unconverged in a launch of its own after the BP kernel instead of inside the on-chip BP kernels; "OSD_NO_FLAT" 1 = OSD-0 on small matrices without the column permutation (osd0_reg_kernel instead of osd0_flat_kernel); "F32_NT" 0 / 1 = the float32 per-pass kernels with the default / the non-temporal cache policy whatever the batch size (default: non-temporal beyond 384 MiB of messages in flight); "F32_GRID_ROWS" k > 0 = the four per-round float32 kernels launched with at most k workgroup rows, so that each row loops over several tiles of the list at any batch size (default: all tiles while they are few, else ~16 384 workgroups and at least 256 rows); "F32_ONCHIP" 0 = the float32 mode never takes its on-chip lane = edge kernels (default: on the codes the FP64 lane = edge kernels take, unless one of "F32_NT", "F32_GRID_ROWS", "SPREAD_NODES" is set); "EDGE_CLAMP" 1 = the lane = edge min-sum kernel always
+ * rows BP left unconverged in a launch of its own after the BP kernel instead of inside the on-chip BP kernels; "OSD_NO_FLAT" 1 = OSD-0 on small matrices without the column permutation (osd0_reg_kernel instead of osd0_flat_kernel); "SPREAD_NT" 0 / 1 = the FP64 per-pass kernels with the default / the non-temporal cache policy whatever the batch size (default: non-temporal beyond 384 MiB of messages in flight); "REPACK_MIN_TILES" t > 0 = the FP64 streamed two-pass decode from t tiles on instead of from 512; "F32_NT" 0 / 1 = the float32 per-pass kernels with the default / the non-temporal cache policy whatever the batch size (default: non-temporal beyond 384 MiB of messages in flight); "F32_GRID_ROWS" k > 0 = the four per-round float32 kernels launched with at most k workgroup rows, so that each row loops over several tiles of the list at any batch size (default: all tiles while they are few, else ~16 384 workgroups and at least 256 rows); "F32_ONCHIP" 0 = the float32 mode never takes its on-chip lane = edge kernels (default: on the codes the FP64 lane = edge kernels take, unless one of "F32_NT", "F32_GRID_ROWS", "SPREAD_NODES" is set); "EDGE_CLAMP" 1 = the lane = edge min-sum kernel always
  * with its clamp to DBL_MAX (default: left out where it provably never bites)).  A handle reads the environment variables LDPC_HIP_<NAME> ONCE, when it is
  * created; afterwards only this call changes a switch (value < 0: back to "not set").  Unknown names are an error. */
 int ldpc_hip_bp_set_debug_switch(ldpc_hip_bp *h, const char *name, int32_t value);

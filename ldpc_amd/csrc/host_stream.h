@@ -247,7 +247,8 @@ static int stream_rounds(ldpc_hip_bp *h, const StreamPlan &p, const StreamPass &
     hipStream_t st = h->stream;
     const unsigned grid_tiles = r.grid_tiles;
     // messages of the tiles in flight: 2 arrays x nnz x 512 B each; beyond ~the MALL they are streamed, not cached
-    const bool nt = (double)grid_tiles * 2.0 * (double)p.per_tile_msg > 384.0 * 1024.0 * 1024.0;
+    // (switch SPREAD_NT 0 / 1: the policy whatever the size -- the tests run the non-temporal instantiations on a small case with it)
+    const bool nt = h->sw("SPREAD_NT") >= 0 ? h->sw("SPREAD_NT") > 0 : (double)grid_tiles * 2.0 * (double)p.per_tile_msg > 384.0 * 1024.0 * 1024.0;
     const SpreadKernels k = pick_spread(h, nt, p.rp);
     const unsigned per_wg = 4u * (unsigned)sa.nodes;
     const dim3 gc((unsigned)(h->m ? (h->m + per_wg - 1) / per_wg : 1), grid_tiles), gb((unsigned)(h->n ? (h->n + per_wg - 1) / per_wg : 1), grid_tiles);
@@ -436,7 +437,9 @@ int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
     }
     // streamed tiles: a tile runs until the slowest of its 64 syndromes is done.  Where most syndromes converge early
     // a short first pass + a second pass over the compacted rest does the same work in a fraction of the tile-iterations
-    if (!rp && h->repack_iters != 0 && h->max_iter >= 8 && tiles_total >= 512 && h->m > 0 && h->n > 0)
+    // (switch REPACK_MIN_TILES t > 0: t instead of the 512 tiles -- the tests cut batches of a few dozen tiles with it)
+    const int64_t min_tiles = h->sw("REPACK_MIN_TILES") > 0 ? h->sw("REPACK_MIN_TILES") : 512;
+    if (!rp && h->repack_iters != 0 && h->max_iter >= 8 && tiles_total >= min_tiles && h->m > 0 && h->n > 0)
         return decode_stream_repacked(h, synd, batch, decoding, llr, iters, conv);
     return decode_streamed(h, synd, batch, decoding, llr, iters, conv, StreamPass());
 }
