@@ -354,6 +354,35 @@ int ldpc_hip_gf2_mulvec_batch(ldpc_hip_bp *h, const uint8_t *vectors, int64_t ba
 int ldpc_hip_gen_bsc_syndromes(ldpc_hip_bp *h, uint64_t seed, uint64_t threshold, int64_t shot0,
                                int64_t batch, uint8_t *syndromes, uint8_t *errors);
 
+/*
+ * Sampling a detector error model on the device, and the loop around it: a logical error count for (H, L, p) with nothing but two
+ * counters crossing the link.  No reference counterpart (stim's compile_sampler plays that role for the reference's users): the
+ * specification is the NumPy twin ldpc_amd.noise_models.generate_dem_batch, reproduced bit for bit.
+ *   T[j]     = min(max(ceil(p[j] * 2^53), 0), 2^53)                         (float64 on the host; exact)
+ *   e[b][j]  = ((splitmix64(seed, (shot0 + b) * n + j) >> 11) < T[j])        (index in uint64: the convention of ldpc_hip_gen_bsc_syndromes,
+ *                                                                            whose errors these are when all p[j] are equal)
+ *   dets[b]  = H e[b] mod 2,  obs[b] = L e[b] mod 2                         (b8 rows as for ldpc_hip_bp_decode_b8, padding bits 0)
+ * ldpc_hip_bp_set_sampler: the per-column probabilities (NULL: the handle's channel probabilities as they are now), checked (outside
+ *   [0, 1] or NaN: LDPC_HIP_ERR_INVALID) and uploaded as thresholds.  Independent of the decoding priors: later ldpc_hip_bp_set_channel calls
+ *   do not change what is sampled.  L is the matrix of ldpc_hip_bp_set_observables, set before or after.
+ * ldpc_hip_bp_sample_b8: shots shot0 .. shot0 + batch - 1 of stream `seed`: dets_b8 [batch][ceil(m/8)], obs_b8 [batch][ceil(k/8)] (NULL
+ *   allowed), errors_b8 [batch][ceil(n/8)] (NULL allowed).  Device or host pointers.  No sampler set, obs_b8 without observables, negative
+ *   shot0 / batch: LDPC_HIP_ERR_INVALID; batch 0: LDPC_HIP_OK.  A shot's detectors and observables are accumulated in LDS:
+ *   ceil(m / 32) + ceil(k / 32) > 4096 words (k counted when obs_b8 is asked for) is LDPC_HIP_ERR_UNSUPPORTED, before anything is launched.
+ * ldpc_hip_count_mismatch_b8: *count = rows in which a_b8 and b_b8 ([batch][ceil(bits/8)]) differ in their first `bits` bits (padding is
+ *   ignored); row_flags [batch] (NULL allowed) = 1 for those rows.  Device or host pointers, each on its own.
+ * ldpc_hip_bp_simulate_b8: shots shot0 .. shot0 + shots - 1 in chunks of `chunk` (<= 0: the library chooses), per chunk on the handle's stream:
+ *   sample, decode as ldpc_hip_bp_decode_b8 does (with_osd as there; same refusals in the float32 message mode), predict observables, count.
+ *   out[0] = shots whose predicted observables differ from the true ones, out[1] = rows BP left unconverged (converge 0 of decode_b8).
+ *   Neither depends on `chunk`.  Needs a sampler and observables (else LDPC_HIP_ERR_INVALID).
+ */
+int ldpc_hip_bp_set_sampler(ldpc_hip_bp *h, const double *probs);
+int ldpc_hip_bp_sample_b8(ldpc_hip_bp *h, uint64_t seed, int64_t shot0, int64_t batch, uint8_t *dets_b8, uint8_t *obs_b8,
+                          uint8_t *errors_b8);
+int ldpc_hip_count_mismatch_b8(ldpc_hip_bp *h, const uint8_t *a_b8, const uint8_t *b_b8, int64_t batch, int32_t bits, uint64_t *count,
+                               uint8_t *row_flags);
+int ldpc_hip_bp_simulate_b8(ldpc_hip_bp *h, uint64_t seed, int64_t shot0, int64_t shots, int64_t chunk, int32_t with_osd, uint64_t *out);
+
 /* Duration in milliseconds of the BP kernel launch of the last decode call on this handle,
  * measured with HIP events on the launch stream (0 if none yet).  Also 0 after a call of at most four syndromes with host buffers
  * on a small code (a single decode()): there the two event packets would cost more than they tell -- debug switch
@@ -428,7 +457,7 @@ int ldpc_hip_bp_set_small_code_kernel(ldpc_hip_bp *h, int32_t mode);
  * per-pass kernels from the start; "SER_VAR" 0 = the streamed serial schedule's item form (any degree profile) never, 1 = also
  * on (6,3)-regular matrices, "SER_VAR_UNITS" its KiB of LDS per wavefront (default 8); "REL_EXT" 0 / 1 = serial_relative's on-chip kernel never / always with the messages and
  * per-entry records in global memory (default: where the all-in-LDS form leaves fewer than four wavefronts per compute unit); "OSD_COLLECT_AFTER" 1 = BP + OSD lists the
- * rows BP left unconverged in a launch of its own after the BP kernel instead of inside the on-chip BP kernels; "OSD_NO_FLAT" 1 = OSD-0 on small matrices without the column permutation (osd0_reg_kernel instead of osd0_flat_kernel); "SPREAD_NT" 0 / 1 = the FP64 per-pass kernels with the default / the non-temporal cache policy whatever the batch size (default: non-temporal beyond 384 MiB of messages in flight); "REPACK_MIN_TILES" t > 0 = the FP64 streamed two-pass decode from t tiles on instead of from 512; "F32_NT" 0 / 1 = the float32 per-pass kernels with the default / the non-temporal cache policy whatever the batch size (default: non-temporal beyond 384 MiB of messages in flight); "F32_GRID_ROWS" k > 0 = the four per-round float32 kernels launched with at most k workgroup rows, so that each row loops over several tiles of the list at any batch size (default: all tiles while they are few, else ~16 384 workgroups and at least 256 rows); "F32_ONCHIP" 0 = the float32 mode never takes its on-chip lane = edge kernels (default: on the codes the FP64 lane = edge kernels take, unless one of "F32_NT", "F32_GRID_ROWS", "SPREAD_NODES" is set); "EDGE_CLAMP" 1 = the lane = edge min-sum kernel always
+ * rows BP left unconverged in a launch of its own after the BP kernel instead of inside the on-chip BP kernels; "OSD_NO_FLAT" 1 = OSD-0 on small matrices without the column permutation (osd0_reg_kernel instead of osd0_flat_kernel); "SPREAD_NT" 0 / 1 = the FP64 per-pass kernels with the default / the non-temporal cache policy whatever the batch size (default: non-temporal beyond 384 MiB of messages in flight); "REPACK_MIN_TILES" t > 0 = the FP64 streamed two-pass decode from t tiles on instead of from 512; "DEM_GRID" k > 0 = dem_sample_b8_kernel launched with at most k workgroups, so its wavefronts loop over shots at any batch size; "F32_NT" 0 / 1 = the float32 per-pass kernels with the default / the non-temporal cache policy whatever the batch size (default: non-temporal beyond 384 MiB of messages in flight); "F32_GRID_ROWS" k > 0 = the four per-round float32 kernels launched with at most k workgroup rows, so that each row loops over several tiles of the list at any batch size (default: all tiles while they are few, else ~16 384 workgroups and at least 256 rows); "F32_ONCHIP" 0 = the float32 mode never takes its on-chip lane = edge kernels (default: on the codes the FP64 lane = edge kernels take, unless one of "F32_NT", "F32_GRID_ROWS", "SPREAD_NODES" is set); "EDGE_CLAMP" 1 = the lane = edge min-sum kernel always
  * with its clamp to DBL_MAX (default: left out where it provably never bites)).  A handle reads the environment variables LDPC_HIP_<NAME> ONCE, when it is
  * created; afterwards only this call changes a switch (value < 0: back to "not set").  Unknown names are an error. */
 int ldpc_hip_bp_set_debug_switch(ldpc_hip_bp *h, const char *name, int32_t value);

@@ -25,6 +25,7 @@ SYMBOLS = (
     "ldpc_hip_bp_multi_decode_batch", "ldpc_hip_bp_multi_last_kernel_ms", "ldpc_hip_bp_multi_set_staging",
     "ldpc_hip_bp_decode_batch_priors", "ldpc_hip_bp_decode_batch_priors_async", "ldpc_hip_bposd0_decode_batch_priors", "ldpc_hip_bposd0_decode_batch_priors_async",
     "ldpc_hip_bp_set_message_dtype", "ldpc_hip_bp_get_message_dtype",
+    "ldpc_hip_bp_set_sampler", "ldpc_hip_bp_sample_b8", "ldpc_hip_count_mismatch_b8", "ldpc_hip_bp_simulate_b8",
 )
 
 
@@ -96,6 +97,14 @@ def load():
     lib.ldpc_hip_bposd_decode_batch_async.argtypes = [vp, vp, i64, vp, vp, vp, vp]
     lib.ldpc_hip_gf2_mulvec_batch.argtypes = [vp, vp, i64, vp]
     lib.ldpc_hip_gen_bsc_syndromes.argtypes = [vp, u64, u64, i64, i64, vp, vp]
+    # LDPC_HIP_LIB names ANOTHER build of the library, for same-box A/B measurements against an earlier commit (tools/ab_bench.sh); such a
+    # build may predate these entry points, so under it -- and only under it -- their absence is tolerated here and shows as an
+    # AttributeError at the first call.  The package's own library must export every name in SYMBOLS (tests/test_cabi_symbols.py).
+    if not os.environ.get("LDPC_HIP_LIB") or hasattr(lib, "ldpc_hip_bp_set_sampler"):
+        lib.ldpc_hip_bp_set_sampler.argtypes = [vp, vp]
+        lib.ldpc_hip_bp_sample_b8.argtypes = [vp, u64, i64, i64, vp, vp, vp]
+        lib.ldpc_hip_count_mismatch_b8.argtypes = [vp, vp, vp, i64, i32, vp, vp]
+        lib.ldpc_hip_bp_simulate_b8.argtypes = [vp, u64, i64, i64, i64, i32, C.POINTER(u64)]
     lib.ldpc_hip_bp_last_kernel_ms.argtypes = [vp, C.POINTER(C.c_float)]
     lib.ldpc_hip_bp_last_phase_ms.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     lib.ldpc_hip_bp_clock_probe.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(C.c_double)]

@@ -101,6 +101,22 @@ class BaseOverlappingWindowDecoder:
             predictions = np.packbits(predictions, axis=1, bitorder="little")
         return predictions
 
+    def predict_on_device(self, shots_tensor):
+        """``decode_batch`` for shots that are on the GPU already and predictions that stay there: ``(B, num_detectors)`` uint8 CUDA
+        tensor (one byte per detector; updated in place, as ``decode_batch`` updates its unpacked shots) -> ``(B, k)`` uint8 CUDA tensor of
+        predicted observables.  The window loop and the ``L e`` product of ``decode_batch``, with no copy in either direction
+        (``MonteCarloDemSimulation(window_decoder=...)`` runs it per chunk).
+
+        Twin of the tail of ``decode_batch`` -- ``_corr_on_device``, then ``mulvec_batch`` of ``total & 1`` -- which keeps its own text
+        because it also writes the updated syndromes back into the caller's host array; a change to either belongs in both
+        (``tests/test_gpu_dem_sampler.py::test_monte_carlo_with_a_window_decoder`` compares the two)."""
+        import torch
+        total, _ = self._corr_on_device(shots_tensor)
+        k = self.logical_observables_matrix.shape[0]
+        if total is None:
+            return torch.zeros((0, k), dtype=torch.uint8, device=shots_tensor.device)
+        return self._observables_engine().mulvec_batch((total & 1).contiguous())
+
     def _observables_engine(self):
         """A handle on the logical-observables matrix, used only for its ``L e`` product (gf2sparse.hpp:177-214)."""
         if getattr(self, "_obs_engine", None) is None:

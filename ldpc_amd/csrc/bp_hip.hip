@@ -28,9 +28,9 @@
 //
 // Built with: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -shared
 //
-// Eight translation units, compiled side by side and linked into one library (Makefile): this one carries the C ABI (handle, setup,
-// decode entry points, layout kernels); tu_stream.hip, tu_serial.hip, tu_onchip.hip, tu_onchip_f32.hip, tu_onchip_rp.hip, tu_osd.hip and tu_f32.hip carry one kernel family each
-// together with its host side (host_stream.h, host_serial.h, host_onchip.h, host_osd.h, host_f32.h).  What they call in each other is
+// Nine translation units, compiled side by side and linked into one library (Makefile): this one carries the C ABI (handle, setup,
+// decode entry points, layout kernels); tu_stream.hip, tu_serial.hip, tu_onchip.hip, tu_onchip_f32.hip, tu_onchip_rp.hip, tu_osd.hip, tu_f32.hip and tu_dem.hip carry one kernel family each
+// together with its host side (host_stream.h, host_serial.h, host_onchip.h, host_osd.h, host_f32.h, host_dem.h).  What they call in each other is
 // declared at the end of host_handle.h.  Device code lives in the kernel headers:
 //   bp_device_common.h   argument blocks, buffer-descriptor message addressing, per-node arithmetic, LDS-DMA helpers
 //   bp_math.h            tanh / log / division: bit-identical twins of the host libm + the fast variants
@@ -46,6 +46,7 @@
 //   bp_edge_rp_kernel.h  bp_edge_rp_kernel, bp_edge8_rp_kernel     row priors on the lane = edge families: every syndrome its own priors (tu_onchip_rp.hip)
 //   osd_kernels.h        osd0[_reg]_kernel, osdw[_reg]_kernel, osd_big_kernel   OSD-0 / OSD-E / OSD-CS post-processing
 //   io_kernels.h         pack / unpack / transpose, H v, b8 shot data, synthetic BSC shots
+//   dem_sample_kernels.h dem_sample_b8_kernel, mismatch_b8_kernel   shots of a detector error model drawn on the device (one wavefront per shot, strips in LDS); rows that differ
 //   multi_device.h       ldpc_hip_bp_multi_*: a batch sharded over several GPUs inside one process (host code only)
 
 #include "bp_device_common.h"

@@ -564,6 +564,9 @@ int ldpc_hip_bp_set_observables(ldpc_hip_bp *h, int32_t k, const int32_t *csr_ro
     HIPCHK(hipMemcpy(h->obs_row_ptr.p, csr_row_ptr, sizeof(int32_t) * (size_t)(k + 1), hipMemcpyHostToDevice));
     if (nnz) HIPCHK(hipMemcpy(h->obs_col_idx.p, csr_col_idx, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice));
     h->obs_k = k;
+    h->h_obs_row_ptr.assign(csr_row_ptr, csr_row_ptr + k + 1);
+    h->h_obs_col_idx.assign(csr_col_idx, csr_col_idx + nnz);
+    if (h->sampler_set) return dem_upload_obs_csc(h);  // (the sampler came first: its column view of L is built here)
     return LDPC_HIP_OK;
 }
 
@@ -586,32 +589,18 @@ int ldpc_hip_bp_decode_b8(ldpc_hip_bp *h, const uint8_t *dets_b8, int64_t batch,
         HIPCHK(hipMemcpyAsync(h->b8_in.p, dets_b8, B * mb, hipMemcpyHostToDevice, h->stream));
         d_in = (const uint8_t *)h->b8_in.p;
     }
-    if ((rc = h->b8_synd.ensure(B * m ? B * m : 1))) return rc;
-    if ((rc = h->b8_dec.ensure(B * n ? B * n : 1))) return rc;
-    uint8_t *d_synd = (uint8_t *)h->b8_synd.p, *d_dec = (uint8_t *)h->b8_dec.p;
-    if (m) LDPC_LAUNCH(unpack_b8_kernel, flat_grid((size_t)(B * m)), dim3(256), 0, h->stream, d_in, batch, h->m, d_synd);
-    HIPCHK(hipGetLastError());
     const bool h_it = iters && !is_device_ptr(iters), h_cv = conv && !is_device_ptr(conv);
     int32_t *d_it = iters;
     uint8_t *d_cv = conv;
     if (h_it) { if ((rc = h->st_iters.ensure(B * 4))) return rc; d_it = (int32_t *)h->st_iters.p; }
     if (h_cv) { if ((rc = h->st_conv.ensure(B))) return rc; d_cv = (uint8_t *)h->st_conv.p; }
-    if ((rc = with_osd ? bposd_device(h, h->osd_method, h->osd_order, d_synd, batch, d_dec, nullptr, d_it, d_cv)
-                       : decode_device(h, d_synd, batch, d_dec, nullptr, d_it, d_cv))) return rc;
-    LDPC_LAUNCH(zero_shot_shortcut_kernel, flat_grid((size_t)(B)), dim3(256), 0, h->stream, d_in, batch, h->m, h->n,
-                       d_dec, d_it, d_cv);
     size_t off = 0;
     if ((rc = h->b8_out.ensure(B * (kb + nb) ? B * (kb + nb) : 1))) return rc;
     uint8_t *d_obs = obs_b8, *d_dec8 = decoding_b8;
     const bool h_obs = obs_b8 && !is_device_ptr(obs_b8), h_dec8 = decoding_b8 && !is_device_ptr(decoding_b8);
     if (h_obs) { d_obs = (uint8_t *)h->b8_out.p; off = B * kb; }
     if (h_dec8) d_dec8 = (uint8_t *)h->b8_out.p + off;
-    if (obs_b8 && kb)
-        LDPC_LAUNCH(observables_b8_kernel, flat_grid((size_t)(B * kb)), dim3(256), 0, h->stream,
-                           (const int32_t *)h->obs_row_ptr.p, (const int32_t *)h->obs_col_idx.p, h->obs_k, h->n, d_dec, batch, d_obs);
-    if (decoding_b8 && nb)
-        LDPC_LAUNCH(pack_b8_kernel, flat_grid((size_t)(B * nb)), dim3(256), 0, h->stream, d_dec, batch, h->n, d_dec8);
-    HIPCHK(hipGetLastError());
+    if ((rc = decode_b8_device(h, d_in, batch, with_osd, d_obs, d_dec8, d_it, d_cv))) return rc;
     if (h_obs && kb) HIPCHK(hipMemcpyAsync(obs_b8, d_obs, B * kb, hipMemcpyDeviceToHost, h->stream));
     if (h_dec8 && nb) HIPCHK(hipMemcpyAsync(decoding_b8, d_dec8, B * nb, hipMemcpyDeviceToHost, h->stream));
     if (h_it) HIPCHK(hipMemcpyAsync(iters, d_it, B * 4, hipMemcpyDeviceToHost, h->stream));
@@ -652,3 +641,28 @@ int ldpc_hip_gen_bsc_syndromes(ldpc_hip_bp *h, uint64_t seed, uint64_t threshold
 }
 
 }  // extern "C"
+
+// What ldpc_hip_bp_decode_b8 queues between its copies, on device pointers (declared in host_handle.h: ldpc_hip_bp_simulate_b8 in tu_dem.hip
+// runs the same steps per chunk).  The caller has checked its arguments and the float32 refusals; nothing here waits for the device.
+int decode_b8_device(ldpc_hip_bp *h, const uint8_t *d_in, int64_t batch, int32_t with_osd, uint8_t *d_obs, uint8_t *d_dec8, int32_t *d_it,
+                     uint8_t *d_cv) {
+    const size_t B = (size_t)batch, m = (size_t)h->m, n = (size_t)h->n;
+    const size_t nb = (n + 7) / 8, kb = d_obs ? ((size_t)h->obs_k + 7) / 8 : 0;
+    int rc;
+    if ((rc = h->b8_synd.ensure(B * m ? B * m : 1))) return rc;
+    if ((rc = h->b8_dec.ensure(B * n ? B * n : 1))) return rc;
+    uint8_t *d_synd = (uint8_t *)h->b8_synd.p, *d_dec = (uint8_t *)h->b8_dec.p;
+    if (m) LDPC_LAUNCH(unpack_b8_kernel, flat_grid((size_t)(B * m)), dim3(256), 0, h->stream, d_in, batch, h->m, d_synd);
+    HIPCHK(hipGetLastError());
+    if ((rc = with_osd ? bposd_device(h, h->osd_method, h->osd_order, d_synd, batch, d_dec, nullptr, d_it, d_cv)
+                       : decode_device(h, d_synd, batch, d_dec, nullptr, d_it, d_cv))) return rc;
+    LDPC_LAUNCH(zero_shot_shortcut_kernel, flat_grid((size_t)(B)), dim3(256), 0, h->stream, d_in, batch, h->m, h->n,
+                       d_dec, d_it, d_cv);
+    if (d_obs && kb)
+        LDPC_LAUNCH(observables_b8_kernel, flat_grid((size_t)(B * kb)), dim3(256), 0, h->stream,
+                           (const int32_t *)h->obs_row_ptr.p, (const int32_t *)h->obs_col_idx.p, h->obs_k, h->n, d_dec, batch, d_obs);
+    if (d_dec8 && nb)
+        LDPC_LAUNCH(pack_b8_kernel, flat_grid((size_t)(B * nb)), dim3(256), 0, h->stream, d_dec, batch, h->n, d_dec8);
+    HIPCHK(hipGetLastError());
+    return LDPC_HIP_OK;
+}

@@ -150,7 +150,7 @@ struct DeviceBuf {  // grow-only device allocation, freed with its owner (on the
 // creation, from the environment variables LDPC_HIP_<NAME>, changed afterwards only through ldpc_hip_bp_set_debug_switch -- no
 // getenv on the decode path, and nothing a test can change under a live handle by accident.
 static const char *const k_switch_names[] = {"PS_TEAM", "EXPLICIT_INIT", "OSD_UNBLOCKED", "OSD_PLANES",
-                                             "PS_TEAM_WAVES", "EDGE_STATIC_PCT", "EDGE_CHUNK", "NO_HOST_PIPELINE", "NO_DIRECT_LLR", "HOST_CHUNK_ROWS", "TIME_SMALL_CALLS", "REL_LDS", "HOST_PIPE_TIMING", "REL_LEVELS", "REL_PROF", "REL_SCRATCH_IN_L", "SER_RING", "SER_WAVES", "SER_LANE_MAX", "SER_LANE_THREADS", "SER_WAVES2", "RESIDENT", "SER_NO_REMAINDER", "SER_ROUND_TILES", "VAR_RING", "VAR_RING_UNITS", "SPREAD_NODES", "SER_VAR", "SER_VAR_UNITS", "REL_EXT", "OSD_COLLECT_AFTER", "EDGE_CLAMP", "OSD_NO_FLAT", "F32_NT", "F32_GRID_ROWS", "F32_ONCHIP", "F32_REPACK_MIN_TILES", "EDGE_RP", "SPREAD_NT", "REPACK_MIN_TILES"};
+                                             "PS_TEAM_WAVES", "EDGE_STATIC_PCT", "EDGE_CHUNK", "NO_HOST_PIPELINE", "NO_DIRECT_LLR", "HOST_CHUNK_ROWS", "TIME_SMALL_CALLS", "REL_LDS", "HOST_PIPE_TIMING", "REL_LEVELS", "REL_PROF", "REL_SCRATCH_IN_L", "SER_RING", "SER_WAVES", "SER_LANE_MAX", "SER_LANE_THREADS", "SER_WAVES2", "RESIDENT", "SER_NO_REMAINDER", "SER_ROUND_TILES", "VAR_RING", "VAR_RING_UNITS", "SPREAD_NODES", "SER_VAR", "SER_VAR_UNITS", "REL_EXT", "OSD_COLLECT_AFTER", "EDGE_CLAMP", "OSD_NO_FLAT", "F32_NT", "F32_GRID_ROWS", "F32_ONCHIP", "F32_REPACK_MIN_TILES", "EDGE_RP", "SPREAD_NT", "REPACK_MIN_TILES", "DEM_GRID"};
 constexpr int k_n_switches = (int)(sizeof(k_switch_names) / sizeof(k_switch_names[0]));
 
 struct ldpc_hip_bp {
@@ -309,6 +309,12 @@ struct ldpc_hip_bp {
     DeviceBuf soft_S, soft_in, soft_out;                             // soft-syndrome decoding: scaled analog syndromes, staging
     DeviceBuf b8_in, b8_out, b8_synd, b8_dec, obs_row_ptr, obs_col_idx;  // bit-packed shot I/O and the observables matrix
     int32_t obs_k = -1;                                              // rows of the observables matrix (-1: not set)
+    std::vector<int32_t> h_obs_row_ptr, h_obs_col_idx;               // host copy of the observables matrix (its column view is built from it: dem_upload_obs_csc)
+    // Sampling of the detector error model (host_dem.h, tu_dem.hip): the per-column thresholds of ldpc_hip_bp_set_sampler -- independent of the
+    // decoding priors -- the column view of the observables matrix, and what ldpc_hip_bp_simulate_b8 keeps on the device per chunk
+    bool sampler_set = false;
+    DeviceBuf dem_thr, dem_obs_col_ptr, dem_obs_csc_row;             // [n] u64; [n + 1], [nnz(L)]
+    DeviceBuf sim_dets, sim_obs, sim_err, sim_pred, sim_conv, sim_count;  // a chunk's sampled rows, true and predicted observables, converge flags; the two 64-bit counters
     int64_t max_chunk_tiles = 0;                                     // 0 = decide from free memory
     // Row priors (ldpc_hip_*_decode_batch_priors): the call's [batch][n] channel probabilities on the device while it runs, nullptr
     // otherwise -- decode_device, the streamed decode (host_stream.h: rp) and decode_onchip look here, nobody else; the handle's own channel_probs / d_llr0 are not touched.
@@ -552,6 +558,13 @@ int decode_f32(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *deco
 // tu_onchip.hip: the float32 mode's on-chip route (bp_edge_f32_kernel, bp_edge8_f32_kernel, instantiated in tu_onchip_f32.hip) for the codes
 // plan_edge / plan_edge8 take; *took = false: neither does (decode_f32 then runs its per-pass kernels)
 int decode_onchip_f32(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv, bool *took);
+// bp_hip.hip (host_decode_abi.h): the body of ldpc_hip_bp_decode_b8 on device pointers -- unpack, decode, zero-shot shortcut, observables / packed
+// decodings -- queued on h->stream without waiting (ldpc_hip_bp_simulate_b8 runs it per chunk)
+int decode_b8_device(ldpc_hip_bp *h, const uint8_t *d_dets_b8, int64_t batch, int32_t with_osd, uint8_t *d_obs_b8, uint8_t *d_decoding_b8,
+                     int32_t *d_iters, uint8_t *d_conv);
+// tu_dem.hip: the column view of the observables matrix for dem_sample_b8_kernel, from the handle's host copy (ldpc_hip_bp_set_observables calls it
+// when a sampler is set already, ldpc_hip_bp_set_sampler when observables are)
+int dem_upload_obs_csc(ldpc_hip_bp *h);
 // tu_osd.hip: BP followed by ordered-statistics post-processing of the rows it left unconverged
 int bposd_device(ldpc_hip_bp *h, int osd_method, int osd_order, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr,
                  int32_t *iters, uint8_t *conv);

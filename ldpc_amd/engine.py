@@ -453,6 +453,76 @@ class HipBpEngine:
                 self._h, seed, thr, shot0, shots, synd.ctypes.data, err.ctypes.data if want_errors else None))
         return (synd, err) if want_errors else synd
 
+    # -- sampling a detector error model (twin and specification: noise_models.generate_dem_batch) ----
+    def set_sampler(self, probs=None):
+        """Per-column probabilities of ``sample_b8`` / ``simulate_b8`` (``ldpc_hip_bp_set_sampler``); ``None``: the handle's channel
+        probabilities as they are now.  Independent of the decoding priors: a later ``set_channel`` does not change what is sampled."""
+        if probs is None:
+            _lib.check(self._lib.ldpc_hip_bp_set_sampler(self._h, None))
+            return
+        from ldpc_amd.noise_models.dem import check_dem_probabilities
+        p = check_dem_probabilities(probs, self.n)
+        _lib.check(self._lib.ldpc_hip_bp_set_sampler(self._h, p.ctypes.data))
+
+    def sample_b8(self, seed, shot0, shots, device=None, want_errors=False):
+        """Shots ``shot0 .. shot0 + shots - 1`` of stream ``seed`` drawn on the GPU (``ldpc_hip_bp_sample_b8``): ``(dets_b8, obs_b8)`` or
+        ``(dets_b8, obs_b8, errors_b8)``, b8-packed rows; ``obs_b8`` is None while no observables are set.  torch tensors on ``device``,
+        or NumPy arrays, as ``gen_bsc_syndromes``."""
+        shots = int(shots)
+        mb, nb = (self.m + 7) // 8, (self.n + 7) // 8
+        k = getattr(self, "k", None)
+        kb = (k + 7) // 8 if k is not None else 0
+        if device is not None:
+            import torch
+            self.set_stream(torch.cuda.current_stream(device).cuda_stream)
+            dets = torch.empty((max(shots, 0), mb), dtype=torch.uint8, device=device)
+            obs = torch.empty((max(shots, 0), kb), dtype=torch.uint8, device=device) if k is not None else None
+            err = torch.empty((max(shots, 0), nb), dtype=torch.uint8, device=device) if want_errors else None
+            ptr = [t.data_ptr() if t is not None and t.numel() else None for t in (dets, obs, err)]
+        else:
+            dets = np.zeros((max(shots, 0), mb), np.uint8)
+            obs = np.zeros((max(shots, 0), kb), np.uint8) if k is not None else None
+            err = np.zeros((max(shots, 0), nb), np.uint8) if want_errors else None
+            ptr = [a.ctypes.data if a is not None and a.size else None for a in (dets, obs, err)]
+        # (an output without bytes -- m, k or n of 0 -- goes as NULL: nothing would be written to it)
+        _lib.check(self._lib.ldpc_hip_bp_sample_b8(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(shot0), shots, ptr[0], ptr[1], ptr[2]))
+        return (dets, obs, err) if want_errors else (dets, obs)
+
+    def count_mismatch_b8(self, a, b, bits):
+        """Number of rows in which two ``(B, ceil(bits / 8))`` b8 arrays differ in their first ``bits`` bits -- padding is ignored
+        (``ldpc_hip_count_mismatch_b8``).  Both NumPy arrays or both CUDA tensors."""
+        bits = int(bits)
+        nb = (bits + 7) // 8
+        if _is_torch(a) != _is_torch(b):
+            raise ValueError("a and b must be in the same place: both NumPy arrays or both CUDA tensors")
+        count = C.c_uint64(0)
+        if _is_torch(a):
+            import torch
+            a, b = a.contiguous(), b.contiguous()
+            for t in (a, b):
+                if t.dtype != torch.uint8 or t.dim() != 2 or t.shape[1] != nb or not t.is_cuda or t.shape[0] != a.shape[0]:
+                    raise ValueError(f"a and b must be CUDA uint8 tensors of the same shape (B, {nb})")
+            self.set_stream(torch.cuda.current_stream(a.device).cuda_stream)
+            pa, pb, rows = a.data_ptr(), b.data_ptr(), int(a.shape[0])
+        else:
+            a, b = np.ascontiguousarray(a, np.uint8), np.ascontiguousarray(b, np.uint8)
+            if a.ndim != 2 or a.shape[1] != nb or a.shape != b.shape:
+                raise ValueError(f"a and b must have the same shape (B, {nb})")
+            pa, pb, rows = a.ctypes.data, b.ctypes.data, int(a.shape[0])
+        if rows == 0 or nb == 0:
+            return 0
+        _lib.check(self._lib.ldpc_hip_count_mismatch_b8(self._h, pa, pb, rows, bits, C.addressof(count), None))
+        return int(count.value)
+
+    def simulate_b8(self, seed, shot0, shots, chunk=0, with_osd=False):
+        """Sample, decode, predict observables and compare, ``chunk`` shots at a time, all on the GPU (``ldpc_hip_bp_simulate_b8``):
+        ``(logical failures, rows BP left unconverged)`` over shots ``shot0 .. shot0 + shots - 1``.  Neither depends on ``chunk``
+        (``<= 0``: the library chooses).  Needs ``set_sampler`` and ``set_observables``."""
+        out = (C.c_uint64 * 2)(0, 0)
+        _lib.check(self._lib.ldpc_hip_bp_simulate_b8(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, int(shot0), int(shots), int(chunk),
+                                                     int(bool(with_osd)), out))
+        return int(out[0]), int(out[1])
+
 
 class HipBpMultiEngine:
     """One decoder over several GPUs of the node inside ONE process (``ldpc_hip_bp_multi``, include/ldpc_hip.h).

@@ -59,3 +59,13 @@ def bernoulli_threshold(p: float) -> int:
         raise ValueError("p must be in [0, 1]")
     t = int(np.ceil(p * 9007199254740992.0))
     return min(max(t, 0), 1 << 53)
+
+
+def bernoulli_thresholds(p) -> np.ndarray:
+    """``bernoulli_threshold`` of every element of ``p`` as a uint64 array of the same shape (the product with 2**53 and the ceil are exact
+    in float64, so the two agree element for element).  Any element outside [0, 1], or NaN, is refused."""
+    p = np.asarray(p, dtype=np.float64)
+    if not np.all((p >= 0.0) & (p <= 1.0)):
+        raise ValueError("p must be in [0, 1]")
+    t = np.ceil(p * 9007199254740992.0)
+    return np.clip(t, 0.0, 9007199254740992.0).astype(np.uint64)
