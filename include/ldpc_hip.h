@@ -485,6 +485,29 @@ int ldpc_hip_bp_set_math(ldpc_hip_bp *h, int32_t math_mode);
 int ldpc_hip_bp_set_message_dtype(ldpc_hip_bp *h, int32_t dtype);
 int ldpc_hip_bp_get_message_dtype(const ldpc_hip_bp *h);
 
+/*
+ * Memory min-sum BP (opt-in; no counterpart in the reference): per-bit memory strengths gamma[n] -- Mem-BP, or with strengths that differ
+ * from bit to bit DMem-BP, the building block of Relay-BP.  Minimum-sum, parallel schedule, FP64 messages.  With L0[j] = log((1 - p[j]) / p[j])
+ * as the handle forms it and M[b][j] the posterior log-ratio of bit j of syndrome b -- L0[j] to begin with -- the bit pass of iteration it
+ * reads, wherever the plain decode reads L0[j] (the forward partial sums and so the posterior),
+ *       prior_it[b][j] = L0[j]                              if gamma[j] == 0.0   (a select, no arithmetic)
+ *                      = a[j] + gamma[j] * M_prev[b][j]     otherwise,           a[j] = (1.0 - gamma[j]) * L0[j] formed once on the host
+ * with every product and sum rounded on its own (no FMA); M_prev is the posterior the previous iteration's bit pass computed for that row.
+ * The check pass, the scaling factor (0 included), the initial messages L0[j], the convergence test and the freezing of a converged row's
+ * outputs are the plain decode's.  gamma all zero gives the plain decode's bits.  The results are those of the NumPy restatement
+ * tests/mem_bp_util.py, bit for bit.
+ *   ldpc_hip_bp_set_memory(h, gamma): gamma = host pointer to [n], each finite and in [-1, 1) (else LDPC_HIP_ERR_INVALID); NULL = off (the
+ *       plain decode and its kernels again).  ldpc_hip_bp_set_channel afterwards is followed: a[] is formed again.
+ *   ldpc_hip_bp_get_memory(h, out): 1 if memory is on (gamma copied to out[n] unless out is NULL), 0 if off, LDPC_HIP_ERR_INVALID for NULL.
+ * With memory on, ldpc_hip_bp_decode_batch[_async], the BP + OSD entry points, ldpc_hip_bp_decode_b8 and ldpc_hip_bp_simulate_b8 decode
+ * with it (OSD runs unchanged on the posteriors).  Refused with LDPC_HIP_ERR_UNSUPPORTED (ldpc_hip_last_error says why) before anything is
+ * staged or launched: product-sum, any serial schedule, LDPC_HIP_MSG_F32, the *_priors entry points, soft-syndrome decoding -- and, at
+ * decode time against the priors the handle holds then, a nonzero gamma[j] on a column whose channel probability is 0 or 1 (it needs
+ * probabilities strictly between 0 and 1; columns with gamma[j] == 0 may keep theirs).
+ */
+int ldpc_hip_bp_set_memory(ldpc_hip_bp *h, const double *gamma);
+int ldpc_hip_bp_get_memory(const ldpc_hip_bp *h, double *out);
+
 /* The shader clock the BP kernels actually ran at (a measurement aid; no counterpart in the reference).  Every workgroup of the
  * long-running BP kernels (bp_decode_kernel, bp_wave_kernel, bp_wave_ps_kernel, bp_edge_kernel, bp_edge8_kernel) adds the shader cycles
  * (s_memtime) and the constant-rate ticks (s_memrealtime) of its lifetime to two 64-bit words of the handle; the words only grow.

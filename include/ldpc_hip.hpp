@@ -178,6 +178,22 @@ public:
         return true;
     }
 
+    // Memory min-sum BP (ldpc_hip.h: ldpc_hip_bp_set_memory): one strength per bit, each finite and in [-1, 1); an empty vector switches it
+    // off.  Minimum-sum, parallel schedule, FP64 messages, one GPU -- anything else is refused when decoding, with its reason in last_error.
+    bool set_memory(const std::vector<double> &gamma) {
+        if (mh_) { fail_(LDPC_HIP_ERR_UNSUPPORTED, "memory min-sum is not sharded over several GPUs; decode on one GPU"); return false; }
+        if (!gamma.empty() && (int)gamma.size() != bit_count) { fail_(LDPC_HIP_ERR_INVALID, "memory strengths must have n entries"); return false; }
+        if (!gamma.empty() && !sync_()) return false;  // (a[] is formed from the channel probabilities the handle holds)
+        last_status = ldpc_hip_bp_set_memory(h_, gamma.empty() ? nullptr : gamma.data());
+        if (last_status != LDPC_HIP_OK) { last_error = ldpc_hip_last_error(); return false; }
+        return true;
+    }
+    std::vector<double> memory() const {  // empty: off
+        std::vector<double> g((size_t)bit_count);
+        if (ldpc_hip_bp_get_memory(h_, g.data()) != 1) g.clear();
+        return g;
+    }
+
     ldpc_hip_bp *handle() { return h_; }
     ldpc_hip_bp_multi *multi_handle() { return mh_; }  // null unless constructed with device_ids
     int device_count() const { return mh_ ? (int)ldpc_hip_bp_multi_devices(mh_) : 1; }

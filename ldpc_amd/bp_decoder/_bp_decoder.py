@@ -143,6 +143,8 @@ class BpDecoderBase:
         self._cy = None
         self._message_dtype = "float64"
         self._engine_dtype = "float64"  # what the engine's handle is set to (a new handle starts at float64)
+        self._memory = None             # memory_strength: None (off) or an (n,) float64 array
+        self._engine_memory = None      # what the engine's handle is set to (a new handle starts with memory off)
 
         self._h = _ingest(pcm)
         self.m, self.n = int(pcm.shape[0]), int(pcm.shape[1])
@@ -416,6 +418,58 @@ class BpDecoderBase:
         if self._device_ids is not None:
             raise NotImplementedError("message_dtype='float32' with device_ids=[...]: float32 messages are not sharded over several GPUs; decode on one GPU.")
 
+    # ---- memory min-sum BP (additive; not a constructor keyword either) ----------------------------------------
+    @property
+    def memory_strength(self):
+        """``None`` (default): plain BP.  A float (every bit) or an array of ``n`` memory strengths, each finite and in ``[-1, 1)``: memory
+        min-sum BP (Mem-BP; with per-bit strengths DMem-BP, the building block of Relay-BP) -- every iteration's bit pass takes
+        ``(1 - gamma[j]) * prior[j] + gamma[j] * (bit j's previous posterior)`` for the prior of bit j; strength 0 on every bit is plain
+        min-sum, bit for bit.  The getter returns ``None`` or a float64 array copy.  Minimum-sum, the parallel schedule and float64 messages
+        on one GPU: with memory on, product-sum, the serial schedules, soft-syndrome decoding, ``message_dtype='float32'``,
+        ``channel_probs=``, ``device_ids=[...]`` and a nonzero strength on a bit whose channel probability is 0 or 1 raise
+        ``NotImplementedError`` at decode time.  The results are those of the NumPy restatement of the algorithm (tests/mem_bp_util.py),
+        bit for bit."""
+        return None if self._memory is None else self._memory.copy()
+
+    @memory_strength.setter
+    def memory_strength(self, value) -> None:
+        if value is None:
+            self._memory = None
+            return
+        try:
+            g = np.array(value, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise ValueError(f"memory_strength must be None, a float or an array of {self.n} floats, not {value!r}.") from None
+        if g.ndim == 0:
+            g = np.full(self.n, float(g), np.float64)
+        if g.shape != (self.n,):
+            raise ValueError(f"memory_strength must be None, a float or an array of length {self.n}, not of shape {g.shape}.")
+        if not (np.isfinite(g).all() and (g >= -1.0).all() and (g < 1.0).all()):
+            raise ValueError("memory_strength: every strength must be finite and in [-1, 1).")
+        self._memory = g
+
+    def _require_memory(self, what=None):
+        """What memory min-sum cannot do is refused here, at decode time, with its reason (``what``: the call's own addition)."""
+        if self._memory is None:
+            return
+        if what is not None:
+            raise NotImplementedError(f"memory_strength with {what}; set memory_strength=None.")
+        if self._bp_method != MINIMUM_SUM:
+            raise NotImplementedError("memory_strength with bp_method='product_sum': the memory strengths are defined for "
+                                      "bp_method='minimum_sum' only.")
+        if self._schedule != PARALLEL or self._random_serial_schedule:
+            raise NotImplementedError(f"memory_strength with schedule='{self.schedule}'"
+                                      f"{' and random_serial_schedule' if self._random_serial_schedule else ''}: memory min-sum needs schedule='parallel'.")
+        if self._message_dtype != "float64":
+            raise NotImplementedError("memory_strength with message_dtype='float32': memory min-sum is decoded with float64 messages only.")
+        if self._device_ids is not None:
+            raise NotImplementedError("memory_strength with device_ids=[...]: memory min-sum is not sharded over several GPUs; decode on one GPU.")
+        p = self._channel_probs
+        bad = np.flatnonzero((self._memory != 0.0) & ~((p > 0.0) & (p < 1.0)))
+        if len(bad):
+            raise NotImplementedError(f"memory_strength: bit {int(bad[0])} has a nonzero memory strength and a channel probability of {p[bad[0]]!r}; "
+                                      "memory min-sum needs probabilities strictly between 0 and 1 there (or strength 0 on that bit).")
+
     # ---- device engine --------------------------------------------------------------------------
     def _get_engine(self):
         """Create / refresh the HIP handle lazily so that construction and validation need no GPU."""
@@ -448,6 +502,10 @@ class BpDecoderBase:
         if self._message_dtype != self._engine_dtype:
             self._engine.set_message_dtype(self._message_dtype)
             self._engine_dtype = self._message_dtype
+        if not (self._memory is self._engine_memory or (self._memory is not None and self._engine_memory is not None
+                                                         and np.array_equal(self._memory, self._engine_memory))):
+            self._engine.set_memory(self._memory)
+            self._engine_memory = None if self._memory is None else self._memory.copy()
         rnd = (bool(self._random_serial_schedule), self._random_schedule_seed, self._seed_epoch)
         if rnd != getattr(self, "_engine_random", (False, 0, 0)):
             self._engine.set_random_serial(rnd[0], rnd[1])  # re-seeds, as bpd.set_random_schedule_seed does (pyx:553-554)
@@ -483,7 +541,8 @@ class BpDecoderBase:
     def _decode_numpy(self, synd2d, want_llr=True, osd0=False, llr_out=None, channel_probs=None):
         """(B, m) uint8 NumPy -> (decoding, llr, iterations, converge) through the active backend.  ``llr_out``: a (B, n) float64
         C-contiguous array to receive the log-ratios instead of a new one.  ``channel_probs``: checked (B, n) row priors or None."""
-        cy = self._get_cy() if self._schedule == PARALLEL else None  # the schedule setters live on the ctypes engine
+        # (the schedule setters and the memory strengths live on the ctypes engine)
+        cy = self._get_cy() if self._schedule == PARALLEL and self._memory is None else None
         if cy is not None and channel_probs is not None:
             return cy.decode_batch(np.ascontiguousarray(synd2d, np.uint8), want_llr, osd0, llr_out, channel_probs)
         if cy is not None:
@@ -497,6 +556,7 @@ class BpDecoderBase:
         (``HipBpEngine._row_probs``) -- without a GPU: shape, dtype, range and place need none."""
         from ldpc_amd.engine import HipBpEngine
         self._require_message_dtype("channel_probs: per-row channel probabilities are decoded with float64 messages only")
+        self._require_memory("channel_probs: per-row channel probabilities are decoded without memory only")
         if self._schedule != PARALLEL:
             raise NotImplementedError(f"channel_probs with schedule='{self.schedule}': the serial schedules decode with the decoder's own "
                                       "channel probabilities only; per-row probabilities need schedule='parallel'.")
@@ -623,6 +683,7 @@ class BpDecoder(BpDecoderBase):
             return np.zeros(self.n, dtype=dtype)
         self._require_parallel()
         self._require_message_dtype()  # (float32: the one row goes through the batch kernels; the resident single-decode path is float64 only)
+        self._require_memory()  # (likewise)
         as_syndrome = self._bp_input_type == SYNDROME or (self._bp_input_type == AUTO and ln == self.m)
         if as_syndrome:
             dec, llr, it, cv = self._decode_numpy(vec[None, :])
@@ -675,6 +736,7 @@ class BpDecoder(BpDecoderBase):
             raise ValueError(f"The input_vector must have length {self.m} (for syndrome decoding) or length {self.n} (for received vector decoding). Not length {ln}.")
         self._require_parallel()
         self._require_message_dtype()
+        self._require_memory()
         as_syndrome = self._bp_input_type == SYNDROME or (self._bp_input_type == AUTO and ln == self.m)
         if channel_probs is not None:
             channel_probs = self._row_probs(input_vectors, channel_probs, as_syndrome)
@@ -786,6 +848,7 @@ class SoftInfoBpDecoder(BpDecoderBase):
         (bp.hpp:573-577: ``shuffle(order, std::default_random_engine(random_schedule_seed))``, a new engine each time); the engine
         does the same draws, every row of a batch from the order at the time of the call, and leaves its last row's order."""
         self._require_message_dtype("soft-syndrome decoding: it is a serial schedule (bp.hpp:547-660)")
+        self._require_memory("soft-syndrome decoding: it is a serial schedule (bp.hpp:547-660)")
         out = self._get_engine().soft_info_decode_batch(soft2d, self.cutoff, self.sigma)
         self._pull_schedule_state()
         return out

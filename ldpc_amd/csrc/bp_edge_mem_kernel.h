@@ -1,0 +1,351 @@
+// bp_edge_mem_kernel.h -- bp_edge_mem_kernel, bp_edge8_mem_kernel: the lane = edge min-sum kernels with MEMORY (per-bit memory strengths)
+// Part of libldpc_hip.so: instantiated in tu_onchip_mem.hip, launched by host_onchip.h (decode_edge_mem, decode_edge8_mem).
+#pragma once
+
+#include "bp_edge_kernel.h"
+
+// ldpc_hip_bp_set_memory on a code of the lane = edge families (bp_edge_kernel.h): the general forms of bp_edge_kernel and bp_edge8_kernel
+// (UNIFORM = false, NOCLAMP = false -- the clamp to DBL_MAX stays), restated operation by operation, with ONE difference: the prior registers
+// prv[r] hold M, and every bit pass forms its prior from them -- from the posterior of the lane's column that the previous bit pass formed:
+//     prior = gamma == 0 ? a : a + gamma * M           (the product rounded, then the sum: -ffp-contract=off)
+// with M the column's posterior of the previous iteration (the prior log-ratio L0 before the first), a = (1 - gamma) * L0 formed on the
+// host (mem_host.h) and a = L0 itself where gamma == 0 -- so the select needs no third table.  Every lane of a column forms the SAME posterior
+// -- (prior + c0) + c1 (+ c2 + c3) in the column's order, from the same prior -- hence the same prior again: by induction the lanes of a column
+// never disagree, and M is one more register per round, not an exchange.  The initial messages are L0 (EdgeArgs::prior_s), as in the plain kernel.
+// a and gamma come per slot from slot tables (EdgeMemArgs::a_s, g_s; edge_mem_table_kernel, host_onchip.h).  Up to KEEP rounds they stay in
+// registers for the whole kernel; above, they are RE-READ in every bit pass (512 R bytes a table that stay in cache), a few rounds at a time
+// beside the LDS reads of the same rounds, as the row-prior kernels re-read scol: with them in registers the higher instantiations spill.  A phantom lane has a = +inf and gamma = 0: its prior stays +inf.
+// The `0.0 + x` / `x + 0.0` argument of bp_edge_kernel.h holds as it does there.  It needs a prior that is never -0.0: a is never -0.0
+// (mem_host.h: 1 - gamma >= 2^-53 and |L0| >= 1.1e-16 or L0 = +0.0, the product neither underflows nor changes sign), and a sum is -0.0 only if
+// BOTH terms are -- so a + gamma * M is not, whatever gamma * M is (a - a is +0.0 in round-to-nearest).  With the prior not -0.0, no
+// prior + c0 (+ ...) is -0.0 either, and 0.0 + c feeding a sum with one of those cannot matter.
+// Results are bit-identical to the per-pass memory kernels (bp_spread_kernels.h: bp_spread_mem_*) and to the NumPy restatement (tests/mem_bp_util.py).
+struct EdgeMemArgs {
+    EdgeArgs e;           // prior_s: L0 per slot (the initial messages and M); prior_u: not read
+    const double *a_s;    // [R * 64] a of the slot's column; phantom: +inf
+    const double *g_s;    // [R * 64] gamma of the slot's column; phantom: 0
+};
+struct Edge8MemArgs {
+    Edge8Args e;
+    const double *a_s;
+    const double *g_s;
+};
+
+typedef void (*EdgeMemKernel)(const EdgeMemArgs);
+typedef void (*Edge8MemKernel)(const Edge8MemArgs);
+// The instantiations live in tu_onchip_mem.hip; the host side (host_onchip.h, in tu_onchip.hip) asks for them by the plan's numbers.
+// nullptr: no such instantiation (the ladders are those of plan_edge and plan_edge8).
+EdgeMemKernel edge_mem_kernel(int rounds);
+Edge8MemKernel edge8_mem_kernel(int rounds, int dc);
+
+// rounds up to which a and gamma stay in registers (above: re-read per bit pass), and the wavefronts per SIMD the instantiations are compiled
+// for -- the host sizes its grid by them (launch_edge_mem).  bp_edge_mem_kernel<14 .. 16> spill 12 .. 38 VGPRs at four (128 registers: M, the
+// message and the partner address of 14 rounds are 70 of them, the table reads of a group 16 more) and get three (168); nothing else spills
+// or uses scratch.  What each instantiation compiles to is listed in DESIGN.md section 7c.
+#ifndef EDGE_MEM_KEEP
+#define EDGE_MEM_KEEP 8
+#endif
+#ifndef EDGE8_MEM_KEEP
+#define EDGE8_MEM_KEEP 5
+#endif
+
+__host__ __device__ constexpr int edge_mem_waves(int rounds) { return rounds <= 13 ? 4 : 3; }
+__host__ __device__ constexpr int edge8_mem_waves(int, int) { return 4; }
+
+#define LDPC_EDGE_MEM_ARG(field) LDPC_KERNARG(ARGS_T, e.field)
+
+template <int R>
+__global__ void __launch_bounds__(64, edge_mem_waves(R)) bp_edge_mem_kernel(const EdgeMemArgs ma) {
+    using namespace edge_detail;
+    const EdgeArgs &a = ma.e;
+    typedef EdgeMemArgs ARGS_T;  // (cold fields: LDPC_KERNARG, bp_device_common.h)
+    extern __shared__ __attribute__((aligned(16))) unsigned char edge_lds[];
+    typedef __attribute__((address_space(3))) double lds_f64;
+    lds_f64 *X = (lds_f64 *)edge_lds;  // [R * 64] check_to_bit of every slot, [R * 64] = +0.0 for good
+    const int lane = threadIdx.x;
+    __shared__ unsigned long long clk_stamp[2];
+    if (lane == 0) clock_probe_begin(clk_stamp);
+    const int m = a.m, n = a.n;
+    constexpr int ZERO = R * 64;
+    constexpr uint64_t LOW = 0x1111111111111111ull;
+    typedef __attribute__((address_space(1))) const double *gtab_t;
+    constexpr bool KEEP = R <= EDGE_MEM_KEEP;
+    constexpr int G = EDGE_G;  // rounds per group of the bit pass
+
+    // per lane and round, for the whole kernel: partner address, (KEEP) a and gamma; per round: which lanes are first entries.  prv[r]: per ITERATION
+    double prv[R], msg[R], av[KEEP ? R : 1], gv[KEEP ? R : 1];
+    int paddr[R];
+    uint64_t k0[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int s = r * 64 + lane;
+        paddr[r] = (int)a.partner[s];
+        k0[r] = __ballot(a.kind[s] == 1);
+        if (KEEP) { av[r] = ma.a_s[s]; gv[r] = ma.g_s[s]; }
+    }
+    const double dbl_max = uniform_f64(DBL_MAX);
+    if (lane == 0) { X[ZERO] = 0.0; X[ZERO + 1] = __builtin_inf(); }
+
+    // Work: the static share, then chunks from the pooled work counters (work_pool_next, bp_device_common.h)
+    int b0 = (int)blockIdx.x * LDPC_EDGE_MEM_ARG(static_per), b1 = b0 + LDPC_EDGE_MEM_ARG(static_per);
+    int pool = (int)(blockIdx.x & (WORK_POOLS - 1));
+    for (;;) {
+      for (int b = b0; b < b1; ++b) {
+        const gtab_t a_t = KEEP ? (gtab_t)nullptr : global_ptr(LDPC_KERNARG(ARGS_T, a_s));  // (re-read per iteration above KEEP rounds)
+        const gtab_t g_t = KEEP ? (gtab_t)nullptr : global_ptr(LDPC_KERNARG(ARGS_T, g_s));
+        {   // M = L0: the initial messages (initialise_log_domain_bp, bp.hpp:147-157), and what the first iteration's prior is formed from
+            const auto l0_t = global_ptr(LDPC_EDGE_MEM_ARG(prior_s));
+#pragma unroll
+            for (int r = 0; r < R; ++r) msg[r] = l0_t[r * 64 + lane];  // (phantom lanes: +inf)
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) prv[r] = msg[r];
+        uint64_t sy[R];
+        bool never = false;
+        const auto sb = global_ptr(LDPC_EDGE_MEM_ARG(synd)) + (int64_t)b * m;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int row = r * 16 + (lane >> 2);
+            const int byte = row < m ? (int)sb[row] : 0;
+            sy[r] = __ballot((byte & 1) != 0) & LOW;
+            never = never || __ballot(byte > 1) != 0;
+        }
+
+        int it = 0;
+        bool unsat = true;
+        do {
+            ++it;
+            const double alpha = (a.ms_scaling_factor == 0.0) ? 1.0 - ldexp(1.0, -it) : a.ms_scaling_factor;
+            const int alo = __double2loint(alpha), ahi = __double2hiint(alpha), nhi = ahi ^ (int)0x80000000;
+            // ---- check pass: msg[r] (bit_to_check) -> msg[r] (check_to_bit), stored at the slot ----
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const double cur = msg[r];
+                const uint64_t neg = __ballot(cur <= 0.0);
+                const double x1 = quad_perm<0xB1>(cur);               // lane ^ 1
+                const double pairmin = min_abs(cur, x1);
+                const double other = quad_perm<0x4E>(pairmin);        // the other pair's minimum (lane ^ 2)
+                const double mag = fmin_pos(min_abs(x1, other), dbl_max);  // over the three other entries, from DBL_MAX down
+                int shi;  // high word of +-alpha: sign = row parity (syndrome included) + own
+                if (r < EDGE_V1) {
+                    const uint64_t par = nibble_parity_low(neg ^ sy[r]);
+                    const int own = select_by_mask(ahi, nhi, neg);
+                    const int rowbit = select_by_mask(0, (int)0x80000000, par);
+                    shi = own ^ __builtin_amdgcn_mov_dpp(rowbit, 0x00, 0xf, 0xf, true);  // quad_perm [0, 0, 0, 0]
+                } else {
+                    const uint64_t flip = spread_nibble(nibble_parity_low(neg ^ sy[r])) ^ neg;
+                    shi = select_by_mask(ahi, nhi, flip);
+                }
+                const double c = mag * __hiloint2double(shi, alo);
+                msg[r] = c;
+                X[r * 64 + lane] = c;
+            }
+            // ---- bit pass: the prior from M; the partner's message; log-ratio, decision, new bit_to_check; prv[r] <- the column's posterior ----
+            uint64_t bad = 0;
+#pragma unroll
+            for (int r0 = 0; r0 < R; r0 += G) {
+                double cpv[G], asv[G], gsv[G];
+#pragma unroll
+                for (int g = 0; g < G; ++g)
+                    if (r0 + g < R) {
+                        cpv[g] = X[paddr[r0 + g]];
+                        asv[g] = KEEP ? av[KEEP ? r0 + g : 0] : a_t[(r0 + g) * 64 + lane];  // (above KEEP rounds: beside the partner's message, a group at a time)
+                        gsv[g] = KEEP ? gv[KEEP ? r0 + g : 0] : g_t[(r0 + g) * 64 + lane];
+                    }
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int g = 0; g < G; ++g) {
+                    const int r = r0 + g;
+                    if (r >= R) break;
+                    const double cp = cpv[g];
+                    const double c = msg[r];
+                    const double pr = gsv[g] == 0.0 ? asv[g] : asv[g] + gsv[g] * prv[r];  // THIS iteration's prior, from M = prv[r]
+                    const double b2c = pr + cp;
+                    const double l1 = b2c + c;             // second entry of its column: (prior + c0) + c1 with c0 = the partner's
+                    const double l0 = (pr + c) + cp;       // first entry: c0 = its own
+                    // the column's posterior, the same value in both of its lanes
+                    const double l = __hiloint2double(select_by_mask(__double2hiint(l1), __double2hiint(l0), k0[r]),
+                                                      select_by_mask(__double2loint(l1), __double2loint(l0), k0[r]));
+                    const uint64_t d = __ballot(l <= 0.0);  // (phantom lanes: +inf or NaN, never <= 0)
+                    bad |= nibble_parity_low(d) ^ sy[r];  // candidate syndrome vs syndrome (bp.hpp:292-302), bit 0 of every nibble
+                    msg[r] = b2c;
+                    prv[r] = l;  // M of the next iteration; after the last one: the output
+                }
+            }
+            unsat = never || (bad & LOW) != 0;
+        } while (unsat && it < a.max_iter);
+
+        // ---- outputs (as bp_edge_kernel): the first entry of a column parks the column's log-ratio at X[column], whole rows leave.  The log-ratio
+        // is prv[r], formed by the last bit pass (the plain kernel adds it up again from the prior; that prior is history here) ----
+        const auto scol_t = global_ptr(LDPC_EDGE_MEM_ARG(scol));
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int j = scol_t[r * 64 + lane];
+            if ((k0[r] >> lane) & 1ull) X[j] = prv[r];
+        }
+        {
+            const auto dp = global_ptr(LDPC_EDGE_MEM_ARG(decoding)) + (int64_t)b * n;
+            auto lp = global_ptr(LDPC_EDGE_MEM_ARG(llr));
+            if (lp) lp += (int64_t)b * n;
+            for (int j = lane; j < n; j += 64) {
+                const double l0 = X[j];
+                dp[j] = l0 <= 0.0 ? 1 : 0;
+                if (lp) lp[j] = l0;
+            }
+        }
+        {
+            const auto ip = global_ptr(LDPC_EDGE_MEM_ARG(iters));
+            const auto cp = global_ptr(LDPC_EDGE_MEM_ARG(conv));
+            if (lane == 0) {
+                if (ip) ip[b] = it;
+                if (cp) cp[b] = unsat ? 0 : 1;
+            }
+        }
+        __builtin_amdgcn_wave_barrier();  // (see bp_edge_kernel: the wavefront is whole before lane 0 pulls the next syndrome)
+      }
+        if (!work_pool_next(LDPC_EDGE_MEM_ARG(next), LDPC_EDGE_MEM_ARG(dyn_base), LDPC_EDGE_MEM_ARG(pool_per), LDPC_EDGE_MEM_ARG(chunk), (int)LDPC_EDGE_MEM_ARG(batch), lane, pool, b0, b1)) break;
+    }
+    if (lane == 0) clock_probe_end(LDPC_EDGE_MEM_ARG(clk), clk_stamp);
+}
+
+template <int R, int DC>
+__global__ void __launch_bounds__(64, edge8_mem_waves(R, DC)) bp_edge8_mem_kernel(const Edge8MemArgs ma) {
+    using namespace edge_detail;
+    const Edge8Args &a = ma.e;
+    typedef Edge8MemArgs ARGS_T;  // (cold fields: LDPC_KERNARG, bp_device_common.h)
+    static_assert(DC >= 2 && DC <= 4, "columns of 2 .. 4 entries");
+    extern __shared__ __attribute__((aligned(16))) unsigned char edge_lds[];
+    typedef __attribute__((address_space(3))) double lds_f64;
+    lds_f64 *X = (lds_f64 *)edge_lds;
+    const int lane = threadIdx.x;
+    __shared__ unsigned long long clk_stamp[2];
+    if (lane == 0) clock_probe_begin(clk_stamp);
+    const int m = a.m, n = a.n;
+    constexpr int ZERO = R * 64;
+    constexpr uint64_t LOW = 0x0101010101010101ull;
+    typedef __attribute__((address_space(1))) const double *gtab_t;
+    constexpr bool KEEP = R <= EDGE8_MEM_KEEP;
+
+    double prv[R], msg[R], av[KEEP ? R : 1], gv[KEEP ? R : 1];
+    int caddr[R][DC];
+    uint64_t kmask[R][DC - 1];  // lanes whose entry is the (j + 1)-th of its column, j < DC - 1
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const int s = r * 64 + lane;
+#pragma unroll
+        for (int j = 0; j < DC; ++j) caddr[r][j] = (int)a.cpos[(size_t)j * (R * 64) + s];
+        const int kd = a.kind[s];
+#pragma unroll
+        for (int j = 0; j < DC - 1; ++j) kmask[r][j] = __ballot(kd == j + 2);
+        if (KEEP) { av[r] = ma.a_s[s]; gv[r] = ma.g_s[s]; }
+    }
+    const double dbl_max = uniform_f64(DBL_MAX);
+    if (lane == 0) { X[ZERO] = 0.0; X[ZERO + 1] = __builtin_inf(); }
+
+    int b0 = (int)blockIdx.x * LDPC_EDGE_MEM_ARG(static_per), b1 = b0 + LDPC_EDGE_MEM_ARG(static_per);
+    int pool = (int)(blockIdx.x & (WORK_POOLS - 1));
+    for (;;) {
+      for (int b = b0; b < b1; ++b) {
+        const gtab_t a_t = KEEP ? (gtab_t)nullptr : global_ptr(LDPC_KERNARG(ARGS_T, a_s));  // (re-read per iteration above KEEP rounds)
+        const gtab_t g_t = KEEP ? (gtab_t)nullptr : global_ptr(LDPC_KERNARG(ARGS_T, g_s));
+        {   // M = L0 (see bp_edge_mem_kernel)
+            const auto l0_t = global_ptr(LDPC_EDGE_MEM_ARG(prior_s));
+#pragma unroll
+            for (int r = 0; r < R; ++r) msg[r] = l0_t[r * 64 + lane];  // initialise_log_domain_bp (bp.hpp:147-157); phantom lanes: +inf
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) prv[r] = msg[r];
+        uint64_t sy[R];
+        bool never = false;
+        const auto sb = global_ptr(LDPC_EDGE_MEM_ARG(synd)) + (int64_t)b * m;
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int row = r * 8 + (lane >> 3);
+            const int byte = row < m ? (int)sb[row] : 0;
+            sy[r] = __ballot((byte & 1) != 0) & LOW;
+            never = never || __ballot(byte > 1) != 0;
+        }
+
+        int it = 0;
+        bool unsat = true;
+        do {
+            ++it;
+            const double alpha = (a.ms_scaling_factor == 0.0) ? 1.0 - ldexp(1.0, -it) : a.ms_scaling_factor;
+            const int alo = __double2loint(alpha), ahi = __double2hiint(alpha), nhi = ahi ^ (int)0x80000000;
+            // ---- check pass (bp.hpp:220-273): minimum over the seven other lanes of the group, sign by the group's parity ----
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const double cur = msg[r];
+                const uint64_t neg = __ballot(cur <= 0.0);
+                const double x1 = quad_perm<0xB1>(cur);                // lane ^ 1
+                const double pairmin = min_abs(cur, x1);
+                const double otherpair = quad_perm<0x4E>(pairmin);     // lane ^ 2: the other pair of the quad
+                const double inquad = min_abs(x1, otherpair);          // the three others of the quad
+                const double quadmin = min_abs(pairmin, otherpair);    // ... and the whole quad, for the other quad
+                const double otherquad = xor4(quadmin);
+                const double mag = fmin_pos(min_abs(inquad, otherquad), dbl_max);  // the seven other entries, from DBL_MAX down
+                const uint64_t flip = spread_byte(byte_parity_low(neg ^ sy[r])) ^ neg;
+                const double c = mag * __hiloint2double(select_by_mask(ahi, nhi, flip), alo);
+                msg[r] = c;
+                X[r * 64 + lane] = c;
+            }
+            // ---- bit pass (bp.hpp:276-318): the prior from M; the column's entries in order; log-ratio, decision, the lane's own bit_to_check; prv[r] <- the posterior ----
+            uint64_t bad = 0;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                double c[DC];
+#pragma unroll
+                for (int j = 0; j < DC; ++j) c[j] = X[caddr[r][j]];
+                const double as = KEEP ? av[KEEP ? r : 0] : a_t[r * 64 + lane], gs = KEEP ? gv[KEEP ? r : 0] : g_t[r * 64 + lane];
+                if (!KEEP && (r & 1)) __builtin_amdgcn_sched_barrier(0);  // (two rounds' table reads in flight, not all R: they would cost 4 R registers)
+                const double pr = gs == 0.0 ? as : as + gs * prv[r];  // THIS iteration's prior, from M = prv[r]
+                double pre[DC];  // pre[k] = prior + c0 + ... + c_{k-1}
+                double t = pr;
+#pragma unroll
+                for (int j = 0; j < DC; ++j) { pre[j] = t; t += c[j]; }
+                const uint64_t d = __ballot(t <= 0.0);  // (phantom lanes: +inf or NaN, never <= 0)
+                bad |= byte_parity_low(d) ^ sy[r];
+                double cand[DC];
+                double sfx = c[DC - 1];
+                cand[DC - 1] = pre[DC - 1];
+                cand[DC - 2] = pre[DC - 2] + sfx;
+#pragma unroll
+                for (int k = DC - 3; k >= 0; --k) { sfx += c[k + 1]; cand[k] = pre[k] + sfx; }
+                double b2c = cand[0];
+#pragma unroll
+                for (int k = 1; k < DC; ++k) b2c = select_f64(b2c, cand[k], kmask[r][k - 1]);
+                msg[r] = b2c;
+                prv[r] = t;  // M: the forward sum's end value, the same in every lane of the column
+            }
+            unsat = never || (bad & LOW) != 0;
+        } while (unsat && it < a.max_iter);
+
+        // ---- outputs: as bp_edge8_kernel, with the log-ratio the last bit pass formed (phantom lanes park theirs at the dummy slot behind +inf) ----
+        const auto scol_t = global_ptr(LDPC_EDGE_MEM_ARG(scol));
+#pragma unroll
+        for (int r = 0; r < R; ++r) X[scol_t[r * 64 + lane]] = prv[r];
+        {
+            const auto dp = global_ptr(LDPC_EDGE_MEM_ARG(decoding)) + (int64_t)b * n;
+            auto lp = global_ptr(LDPC_EDGE_MEM_ARG(llr));
+            if (lp) lp += (int64_t)b * n;
+            for (int j = lane; j < n; j += 64) {
+                const double t = X[j];
+                dp[j] = t <= 0.0 ? 1 : 0;
+                if (lp) lp[j] = t;
+            }
+        }
+        {
+            const auto ip = global_ptr(LDPC_EDGE_MEM_ARG(iters));
+            const auto cp = global_ptr(LDPC_EDGE_MEM_ARG(conv));
+            if (lane == 0) {
+                if (ip) ip[b] = it;
+                if (cp) cp[b] = unsat ? 0 : 1;
+            }
+        }
+        __builtin_amdgcn_wave_barrier();  // (see bp_edge_kernel)
+      }
+        if (!work_pool_next(LDPC_EDGE_MEM_ARG(next), LDPC_EDGE_MEM_ARG(dyn_base), LDPC_EDGE_MEM_ARG(pool_per), LDPC_EDGE_MEM_ARG(chunk), (int)LDPC_EDGE_MEM_ARG(batch), lane, pool, b0, b1)) break;
+    }
+    if (lane == 0) clock_probe_end(LDPC_EDGE_MEM_ARG(clk), clk_stamp);
+}
+#undef LDPC_EDGE_MEM_ARG

@@ -20,7 +20,18 @@ struct SpreadArgs {
     // probabilities, in the layout of the messages -- the reference's `update_channel_probs(p[shot]); decode(s[shot])` loop
     // (_bp_decoder.pyx:222) as one batch.  Read where the other forms read bp.llr0[j]; nullptr otherwise.
     const double *llr0_t;
+    // Memory min-sum (the bp_spread_mem_* kernels): llr0_t is then M [tiles][n][64], every lane's posterior of the previous
+    // iteration (the prior log-ratio to begin with: bp_spread_mem_init_kernel), read AND rewritten by every bit pass for all 64 lanes; mem_ag [2][n]
+    // = a[] = (1 - gamma) * llr0, then gamma[] (mem_host.h), read per column through the scalar path as llr0 is.  nullptr otherwise.
+    const double *mem_ag;
 };
+
+// the prior of column j's bit pass under memory: llr0[j] where gamma[j] == 0 (a select: a[j] IS llr0[j] there, infinities included), else
+// a[j] + gamma[j] * M -- the product rounded, then the sum (no FMA: -ffp-contract=off)
+__device__ __forceinline__ double mem_prior(const double *mem_ag, int n, int j, double m_prev) {
+    const double aj = sload(mem_ag + j), g = sload(mem_ag + n + j);
+    return g == 0.0 ? aj : aj + g * m_prev;
+}
 
 // Late rounds.  After a few rounds all but a handful of the tiles are final (what is left is what never converges), yet a launch of a row of
 // workgroups per parked tile -- 256 rows that leave at once -- costs ~50 us, four times a round, for the 40 rounds one hopeless syndrome keeps
@@ -105,8 +116,10 @@ __global__ void __launch_bounds__(256) bp_spread_check_kernel(const SpreadArgs a
     } while (LOOP && (slot += (int)gridDim.y) < spread_count(a));
 }
 
-template <int METHOD, int MATH, int DC, int NT, bool LOOP = false, bool RP = false>
-__global__ void __launch_bounds__(256) bp_spread_bit_kernel(const SpreadArgs a) {
+// (the body of bp_spread_bit_kernel and of its memory form bp_spread_mem_bit_kernel: MEM -- memory min-sum, see SpreadArgs::mem_ag)
+template <int METHOD, int MATH, int DC, int NT, bool LOOP, bool RP, bool MEM>
+__device__ __forceinline__ void spread_bit_pass(const SpreadArgs &a) {
+    static_assert(!(RP && MEM), "row priors and memory exclude each other (both live in llr0_t)");
     typedef MsgBufT<NT ? 2 : 0> Buf;
     int64_t tile;
     const TileState *st;
@@ -124,14 +137,15 @@ __global__ void __launch_bounds__(256) bp_spread_bit_kernel(const SpreadArgs a) 
     const Buf Ct = make_msgbuf<Buf>(a.bp.C + (size_t)tile * (size_t)nnz * LDPC_WAVE, (unsigned)nnz);
     const bool want_llr = a.bp.llr_t != nullptr;
     const Buf Lt = make_msgbuf<Buf>(want_llr ? a.bp.llr_t + (size_t)tile * (size_t)n * LDPC_WAVE : a.bp.A, want_llr ? (unsigned)n : 0u);
-    const Buf Pt = make_msgbuf<Buf>(RP ? const_cast<double *>(a.llr0_t) + (size_t)tile * (size_t)n * LDPC_WAVE : a.bp.A, RP ? (unsigned)n : 0u);
+    const Buf Pt = make_msgbuf<Buf>(RP || MEM ? const_cast<double *>(a.llr0_t) + (size_t)tile * (size_t)n * LDPC_WAVE : a.bp.A, RP || MEM ? (unsigned)n : 0u);
     const bool last = it == a.bp.max_iter;
     const bool lane_live = !((done >> lane) & 1ull);
     const bool each = st->llr_each[a.round & 1] != 0;  // (as the persistent kernel's llr_each)
     const int j0 = (blockIdx.x * 4 + wave) * a.nodes;
     for (int j = j0; j < j0 + a.nodes && j < n; ++j) {
         const int cs = sload(a.bp.col_ptr + j), d = sload(a.bp.col_ptr + j + 1) - cs;
-        const double prior = RP ? Pt.ld(l8, j) : sload(a.bp.llr0 + j);  // (RP: this lane's own prior)
+        const double prior = MEM ? mem_prior(a.mem_ag, n, j, Pt.ld(l8, j))  // (MEM: from this lane's previous posterior)
+                           : RP ? Pt.ld(l8, j) : sload(a.bp.llr0 + j);      // (RP: this lane's own prior)
         double llr;
         if (d <= DC) {
             int e[DC];
@@ -155,12 +169,21 @@ __global__ void __launch_bounds__(256) bp_spread_bit_kernel(const SpreadArgs a) 
                 sfx += Ct.ld(l8, ee);
             }
         }
+        if (MEM) Pt.st(l8, j, llr);  // M: every lane, whatever llr_each says (a column belongs to one wavefront: nobody else reads or writes it this pass)
         const uint64_t hard = __ballot(llr <= 0);
         if (lane == 0) a.bp.dcur[tile * n + j] = hard;
         if ((last || each) && want_llr && lane_live) Lt.st(l8, j, llr);
     }
     } while (LOOP && (slot += (int)gridDim.y) < spread_count(a));
 }
+
+template <int METHOD, int MATH, int DC, int NT, bool LOOP = false, bool RP = false>
+__global__ void __launch_bounds__(256) bp_spread_bit_kernel(const SpreadArgs a) { spread_bit_pass<METHOD, MATH, DC, NT, LOOP, RP, false>(a); }
+
+// Memory min-sum (minimum-sum only, never a compacted pass: no LOOP form): both column paths -- d <= DC in registers, d > DC in two sweeps
+// through memory -- start from the prior formed from M and leave the posterior in M.
+template <int DC, int NT>
+__global__ void __launch_bounds__(256) bp_spread_mem_bit_kernel(const SpreadArgs a) { spread_bit_pass<LDPC_HIP_MINIMUM_SUM, 0, DC, NT, false, false, true>(a); }
 
 // candidate syndrome vs syndrome (bp.hpp:292-294, 300-302) for the parked tiles, one thread per (tile, row); the
 // per-tile verdict is OR-accumulated into TileState::unsat for bp_spread_finish_kernel
@@ -206,8 +229,9 @@ __global__ void __launch_bounds__(256) bp_spread_state_init_kernel(const SpreadA
     if (t == 0) a.bp.counters[1] = a.bp.counters[2] = (unsigned)a.n_tiles;  // parked, live
 }
 
-template <int METHOD, int MATH, bool RP = false>
-__global__ void __launch_bounds__(256) bp_spread_init_kernel(const SpreadArgs a) {  // bp.hpp:147-157
+// (MEM: the initial messages are the plain ones; M starts as the prior log-ratio in every lane)
+template <int METHOD, int MATH, bool RP, bool MEM>
+__device__ __forceinline__ void spread_init(const SpreadArgs &a) {  // bp.hpp:147-157
     const int64_t tile = blockIdx.y;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -219,7 +243,17 @@ __global__ void __launch_bounds__(256) bp_spread_init_kernel(const SpreadArgs a)
         const int j = sload(a.bp.col_idx + e);
         At.st(l8, e, edge_form<METHOD, MATH>(RP ? Pt.ld(l8, j) : sload(a.bp.llr0 + j)));
     }
+    if (MEM) {  // the same grid covers the columns: 64 per workgroup, nnz >= n where every column has an entry -- and a loop where not
+        const MsgBuf Mt = make_msgbuf(const_cast<double *>(a.llr0_t) + (size_t)tile * (size_t)a.bp.n * LDPC_WAVE, (unsigned)a.bp.n);
+        for (int j0 = (blockIdx.x * 4 + wave) * 16; j0 < a.bp.n; j0 += (int)gridDim.x * 64)
+            for (int j = j0; j < j0 + 16 && j < a.bp.n; ++j) Mt.st(l8, j, sload(a.bp.llr0 + j));
+    }
 }
+
+template <int METHOD, int MATH, bool RP = false>
+__global__ void __launch_bounds__(256) bp_spread_init_kernel(const SpreadArgs a) { spread_init<METHOD, MATH, RP, false>(a); }
+
+__global__ void __launch_bounds__(256) bp_spread_mem_init_kernel(const SpreadArgs a) { spread_init<LDPC_HIP_MINIMUM_SUM, 0, false, true>(a); }
 
 // [n] initial edge values for BpArgs::edge0
 template <int METHOD, int MATH>
@@ -232,8 +266,9 @@ __global__ void __launch_bounds__(256) bp_edge0_kernel(const double *llr0, int n
 // (decisions + posterior of THIS iteration), a tile whose lanes are all frozen or that reached max_iter gets its
 // outputs.  64 bits per workgroup; workgroup 0 of a tile also advances its state.  Almost always there is nothing
 // to freeze and every workgroup but the first leaves at once.
-template <bool LOOP = false, bool RP = false>
-__global__ void __launch_bounds__(256) bp_spread_finish_kernel(const SpreadArgs a) {
+// (MEM: the posterior of THIS iteration is what the bit pass has just left in M -- the prior it used is gone, and there is nothing to add up)
+template <bool LOOP, bool RP, bool MEM>
+__device__ __forceinline__ void spread_finish(const SpreadArgs &a) {
     int64_t tile;
     const TileState *cst;
     int it;
@@ -260,7 +295,7 @@ __global__ void __launch_bounds__(256) bp_spread_finish_kernel(const SpreadArgs 
         const MsgBuf Ct = make_msgbuf(a.bp.C + (size_t)tile * (size_t)nnz * LDPC_WAVE, (unsigned)nnz);
         const bool want_llr = a.bp.llr_t != nullptr;
         const MsgBuf Lt = make_msgbuf(want_llr ? a.bp.llr_t + (size_t)tile * (size_t)n * LDPC_WAVE : a.bp.A, want_llr ? (unsigned)n : 0u);
-        const MsgBuf Pt = make_msgbuf(RP ? const_cast<double *>(a.llr0_t) + (size_t)tile * (size_t)n * LDPC_WAVE : a.bp.A, RP ? (unsigned)n : 0u);
+        const MsgBuf Pt = make_msgbuf(RP || MEM ? const_cast<double *>(a.llr0_t) + (size_t)tile * (size_t)n * LDPC_WAVE : a.bp.A, RP || MEM ? (unsigned)n : 0u);
         const int j0 = blockIdx.x * 64 + wave * 16;
         for (int j = j0; j < j0 + 16 && j < n; ++j) {
             if (lane == 0) {
@@ -270,8 +305,9 @@ __global__ void __launch_bounds__(256) bp_spread_finish_kernel(const SpreadArgs 
                 dec[j] = d;
             }
             if (newly && !last && want_llr && !each) {  // (at the last iteration, or under llr_each, the bit pass has stored the posterior already)
-                double temp = RP ? Pt.ld(l8, j) : a.bp.llr0[j];
-                for (int p = a.bp.col_ptr[j]; p < a.bp.col_ptr[j + 1]; ++p) temp += Ct.ld(l8, a.bp.csc_edge[p]);
+                double temp = RP || MEM ? Pt.ld(l8, j) : a.bp.llr0[j];
+                if (!MEM)
+                    for (int p = a.bp.col_ptr[j]; p < a.bp.col_ptr[j + 1]; ++p) temp += Ct.ld(l8, a.bp.csc_edge[p]);
                 if (mine) Lt.st(l8, j, temp);
             }
         }
@@ -299,3 +335,8 @@ __global__ void __launch_bounds__(256) bp_spread_finish_kernel(const SpreadArgs 
     }
     } while (LOOP && (slot += (int)gridDim.y) < spread_count(a));
 }
+
+template <bool LOOP = false, bool RP = false>
+__global__ void __launch_bounds__(256) bp_spread_finish_kernel(const SpreadArgs a) { spread_finish<LOOP, RP, false>(a); }
+
+__global__ void __launch_bounds__(256) bp_spread_mem_finish_kernel(const SpreadArgs a) { spread_finish<false, false, true>(a); }

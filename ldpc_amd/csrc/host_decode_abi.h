@@ -11,6 +11,7 @@ int ldpc_hip_bposd0_decode_batch_async(ldpc_hip_bp *h, const uint8_t *synd, int6
     if (batch == 0) return LDPC_HIP_OK;
     if (!synd || !decoding) return fail(LDPC_HIP_ERR_INVALID, "syndromes and decoding must not be NULL");
     { const int refused = f32_refusal(h, nullptr); if (refused) return refused; }
+    { const int refused = mem_refusal(h, nullptr); if (refused) return refused; }
     HIPCHK(hipSetDevice(h->device));
     return mark_queued(h, bposd_device(h, 1, 0, synd, batch, decoding, llr, iters, conv));
 }
@@ -60,6 +61,7 @@ int ldpc_hip_bposd_decode_batch_async(ldpc_hip_bp *h, const uint8_t *synd, int64
     if (batch == 0) return LDPC_HIP_OK;
     if (!synd || !decoding) return fail(LDPC_HIP_ERR_INVALID, "syndromes and decoding must not be NULL");
     { const int refused = f32_refusal(h, nullptr); if (refused) return refused; }
+    { const int refused = mem_refusal(h, nullptr); if (refused) return refused; }
     HIPCHK(hipSetDevice(h->device));
     return mark_queued(h, bposd_device(h, h->osd_method, h->osd_order, synd, batch, decoding, llr, iters, conv));
 }
@@ -72,6 +74,7 @@ int ldpc_hip_bp_decode_batch_async(ldpc_hip_bp *h, const uint8_t *synd, int64_t 
     if (!synd || !decoding) return fail(LDPC_HIP_ERR_INVALID, "syndromes and decoding must not be NULL");
     if (batch > (1ll << 40)) return fail(LDPC_HIP_ERR_INVALID, "batch too large");
     { const int refused = f32_refusal(h, nullptr); if (refused) return refused; }
+    { const int refused = mem_refusal(h, nullptr); if (refused) return refused; }
     HIPCHK(hipSetDevice(h->device));
     return mark_queued(h, decode_device(h, synd, batch, decoding, llr, iters, conv));
 }
@@ -86,7 +89,7 @@ static int row_priors_refusal(const ldpc_hip_bp *h) {
     { const int refused = f32_refusal(h, "per-row channel probabilities are"); if (refused) return refused; }
     if (h->schedule != 1 || h->random_serial)
         return fail(LDPC_HIP_ERR_UNSUPPORTED, "per-row channel probabilities: the serial schedules read the handle's priors only (parallel schedule required)");
-    return LDPC_HIP_OK;
+    return mem_refusal(h, "per-row channel probabilities are");
 }
 
 int ldpc_hip_bp_decode_batch_priors(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr,
@@ -346,6 +349,7 @@ static int decode_batch_staged(ldpc_hip_bp *h, int osd, const uint8_t *synd, int
     if (!synd || !decoding) return fail(LDPC_HIP_ERR_INVALID, "syndromes and decoding must not be NULL");
     if (probs) { const int refused = row_priors_refusal(h); if (refused) return refused; }
     { const int refused = f32_refusal(h, nullptr); if (refused) return refused; }
+    { const int refused = mem_refusal(h, nullptr); if (refused) return refused; }
     HIPCHK(hipSetDevice(h->device));
     const size_t B = (size_t)batch, m = (size_t)h->m, n = (size_t)h->n;
     const uint8_t *d_synd = synd;
@@ -379,7 +383,7 @@ static int decode_batch_staged(ldpc_hip_bp *h, int osd, const uint8_t *synd, int
             double *p_llr = (llr || osd >= 0) ? (double *)(dv + o_llr) : nullptr;
             uint8_t *p_cv = (conv || osd >= 0) ? (uint8_t *)(dv + o_cv) : nullptr;
             int32_t *p_it = iters ? (int32_t *)(dv + o_it) : nullptr;
-            if (batch == 1 && osd < 0 && h->msg_dtype == LDPC_HIP_MSG_F64 && !h->on("TIME_SMALL_CALLS")) {  // ONE syndrome: the resident workgroup, where one applies
+            if (batch == 1 && osd < 0 && h->msg_dtype == LDPC_HIP_MSG_F64 && !h->mem_on && !h->on("TIME_SMALL_CALLS")) {  // ONE syndrome: the resident workgroup, where one applies
                 bool took = false;
                 if ((rc = decode_onchip_resident(h, llr != nullptr, &took))) return rc;
                 if (took) {
@@ -487,6 +491,7 @@ int ldpc_hip_bp_soft_info_decode_batch(ldpc_hip_bp *h, const double *soft_syndro
     if (!soft_syndromes || !decoding) return fail(LDPC_HIP_ERR_INVALID, "soft syndromes and decoding must not be NULL");
     if (!(sigma > 0)) return fail(LDPC_HIP_ERR_INVALID, "The sigma value must be a float greater than 0.");  // _bp_decoder.pyx:748-749
     { const int refused = f32_refusal(h, "soft-syndrome decoding is"); if (refused) return refused; }
+    { const int refused = mem_refusal(h, "soft-syndrome decoding is"); if (refused) return refused; }
     HIPCHK(hipSetDevice(h->device));
     const size_t B = (size_t)batch, m = (size_t)h->m, n = (size_t)h->n;
     int rc;
@@ -579,6 +584,7 @@ int ldpc_hip_bp_decode_b8(ldpc_hip_bp *h, const uint8_t *dets_b8, int64_t batch,
     if (!obs_b8 && !decoding_b8) return fail(LDPC_HIP_ERR_INVALID, "neither obs_b8 nor decoding_b8 requested");
     if (obs_b8 && h->obs_k < 0) return fail(LDPC_HIP_ERR_INVALID, "obs_b8 requested but ldpc_hip_bp_set_observables was never called");
     { const int refused = f32_refusal(h, nullptr); if (refused) return refused; }
+    { const int refused = mem_refusal(h, nullptr); if (refused) return refused; }
     HIPCHK(hipSetDevice(h->device));
     const size_t B = (size_t)batch, m = (size_t)h->m, n = (size_t)h->n;
     const size_t mb = (m + 7) / 8, nb = (n + 7) / 8, kb = obs_b8 ? ((size_t)h->obs_k + 7) / 8 : 0;

@@ -1,5 +1,5 @@
 // host_handle.h -- the handle (struct ldpc_hip_bp), error reporting, device buffers, measurement switches
-// Part of libldpc_hip.so: included by every translation unit (bp_hip.hip = the C ABI; tu_stream / tu_serial / tu_onchip / tu_onchip_f32 / tu_onchip_rp / tu_osd / tu_f32.hip = one kernel
+// Part of libldpc_hip.so: included by every translation unit (bp_hip.hip = the C ABI; tu_stream / tu_serial / tu_onchip / tu_onchip_f32 / tu_onchip_rp / tu_onchip_mem / tu_osd / tu_f32.hip = one kernel
 // family each with its host side).  What one unit calls in another is declared at the end of this header.
 #pragma once
 
@@ -18,6 +18,8 @@
 #include <unistd.h>
 
 #include <sys/mman.h>
+
+#include "mem_host.h"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -321,6 +323,15 @@ struct ldpc_hip_bp {
     const double *row_probs = nullptr;
     DeviceBuf rowp_llr;  // their log-ratios: in tile layout [tiles of a chunk][n][64] (io_kernels.h: row_priors_kernel), or row-major [batch][n] for the lane = edge kernels (row_priors_rowmajor_kernel)
     DeviceBuf st_probs;  // staging for a host pointer
+    // Memory min-sum BP (ldpc_hip_bp_set_memory): every iteration's bit pass takes a[j] + gamma[j] * (the column's previous
+    // posterior) for the prior.  decode_device looks at mem_on and sends the batch to the memory kernels (bp_edge_mem_kernel.h, the bp_spread_mem_* kernels of
+    // bp_spread_kernels.h); with it off nothing below is read.  The per-pass route keeps the posteriors M [tiles of a chunk][n][64] in rowp_llr
+    // (row priors and memory exclude each other).
+    bool mem_on = false;
+    std::vector<double> mem_gamma;  // [n] the strengths as given
+    int mem_bad_col = -1;           // first column with gamma != 0 whose prior is not finite, for the priors the handle holds NOW (-1: none)
+    DeviceBuf mem_ag;               // [2][n]: a[] = (1 - gamma) * log((1 - p) / p) (mem_host.h), then gamma[]; rewritten by upload_memory
+    DeviceBuf e_mem;                // [2][R * 64]: a and gamma of every slot of the lane = edge tables (edge_mem_table_kernel, before every launch)
 };
 
 // h->counter: work_pool_bytes() of work counters for the on-chip BP kernels, then OSD_COUNTER_BYTES for BP + OSD -- {listed, next} of the first
@@ -340,8 +351,39 @@ static auto with_method_math(const ldpc_hip_bp *h, Fn &&f) {
     return f(std::integral_constant<int, LDPC_HIP_PRODUCT_SUM>{}, std::integral_constant<int, 0>{});
 }
 
+// Memory min-sum: a[] and gamma[] of the priors and strengths the handle holds now -> mem_ag (the stream is idle: ldpc_hip_bp_set_memory and
+// ldpc_hip_bp_set_channel wait for it first).  mem_bad_col: what a decode has to refuse (mem_refusal).
+static int upload_memory(ldpc_hip_bp *h) {
+    const size_t n = (size_t)h->n;
+    std::vector<double> ag(2 * (n ? n : 1), 0.0);
+    h->mem_bad_col = mem_form_a(h->channel_probs.data(), h->mem_gamma.data(), h->n, ag.data());
+    std::copy(h->mem_gamma.begin(), h->mem_gamma.end(), ag.begin() + (std::ptrdiff_t)n);
+    int rc;
+    if ((rc = h->mem_ag.ensure(sizeof(double) * ag.size()))) return rc;
+    HIPCHK(hipMemcpy(h->mem_ag.p, ag.data(), sizeof(double) * ag.size(), hipMemcpyHostToDevice));
+    return LDPC_HIP_OK;
+}
+
+// What the handle is set up for that a memory decode cannot do; `what`: the call's own addition (row priors, soft syndromes, several GPUs) or
+// nullptr.  LDPC_HIP_OK when memory is off.  Called beside f32_refusal by every decode entry point, before anything is staged or launched.
+static int mem_refusal(const ldpc_hip_bp *h, const char *what) {
+    if (!h->mem_on) return LDPC_HIP_OK;
+    if (what) return fail(LDPC_HIP_ERR_UNSUPPORTED, "memory min-sum: %s not available (switch the memory off: ldpc_hip_bp_set_memory(h, NULL))", what);
+    if (h->bp_method != LDPC_HIP_MINIMUM_SUM)
+        return fail(LDPC_HIP_ERR_UNSUPPORTED, "memory min-sum: product-sum is not available (the memory strengths are defined for minimum-sum only)");
+    if (h->schedule != 1 || h->random_serial)
+        return fail(LDPC_HIP_ERR_UNSUPPORTED, "memory min-sum: the serial schedules are not available (parallel schedule required)");
+    if (h->msg_dtype != LDPC_HIP_MSG_F64)
+        return fail(LDPC_HIP_ERR_UNSUPPORTED, "memory min-sum: float32 messages are not available (set the message dtype to float64)");
+    if (h->mem_bad_col >= 0)
+        return fail(LDPC_HIP_ERR_UNSUPPORTED, "memory min-sum: column %d has a nonzero memory strength and a channel probability of 0 or 1 -- "
+                    "it needs probabilities strictly between 0 and 1 (or strength 0 on that column)", h->mem_bad_col);
+    return LDPC_HIP_OK;
+}
+
 static int upload_priors(ldpc_hip_bp *h) {
     ++h->priors_version;
+    if (h->mem_on) { const int rc = upload_memory(h); if (rc) return rc; }  // a[] follows the priors
     // bp.hpp:150-151, evaluated by the host libm so that priors are bit-identical to the reference's
     std::vector<double> llr0((size_t)h->n);
     for (int j = 0; j < h->n; ++j)

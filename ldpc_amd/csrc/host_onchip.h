@@ -706,6 +706,70 @@ static bool edge_rp_route(const ldpc_hip_bp *h) {
     return s >= 0 ? s != 0 : k_edge_rp_default;
 }
 
+// ---- the same two families with memory (bp_edge_mem_kernel.h; instantiated in tu_onchip_mem.hip): ldpc_hip_bp_set_memory on the codes of plan_edge / plan_edge8 ----
+// Everything but the priors is decode_edge's / decode_edge8's: the shared slot tables, e_prior (the log-ratios per slot: the initial messages),
+// the work split, the grid of the general form (4 wavefronts per SIMD), the timing events.  The memory: a[] and gamma[] of the handle (mem_ag,
+// upload_memory) per slot into e_mem, before every launch as e_prior is -- the priors or the strengths may have changed since the last one.
+__global__ void edge_mem_table_kernel(const double *ag, int n, const int32_t *scol, const uint8_t *kind, int slots, double *out) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= slots) return;
+    out[s] = kind[s] ? ag[scol[s]] : __builtin_inf();   // phantom lanes: prior +inf for good ...
+    out[slots + s] = kind[s] ? ag[n + scol[s]] : 0.0;   // ... by strength 0 (bp_edge_mem_kernel.h)
+}
+
+template <class ARGS>
+static int launch_edge_mem(ldpc_hip_bp *h, void (*kern)(const ARGS), int rounds, int waves_per_simd, int64_t batch, ARGS &ma) {
+    if (!kern) return fail(LDPC_HIP_ERR_UNSUPPORTED, "memory min-sum: no lane = edge kernel was built for %d rounds", rounds);
+    int rc;
+    const int slots = rounds * 64;
+    if ((rc = h->e_mem.ensure(sizeof(double) * 2 * (size_t)slots))) return rc;
+    const dim3 gt((unsigned)((slots + 255) / 256));
+    LDPC_LAUNCH(edge_prior_kernel, gt, dim3(256), 0, h->stream, h->d_llr0, (const int32_t *)h->e_scol.p, (const uint8_t *)h->e_kind.p, slots, (double *)h->e_prior.p);
+    LDPC_LAUNCH(edge_mem_table_kernel, gt, dim3(256), 0, h->stream, (const double *)h->mem_ag.p, h->n, (const int32_t *)h->e_scol.p, (const uint8_t *)h->e_kind.p,
+                slots, (double *)h->e_mem.p);
+    HIPCHK(hipGetLastError());
+    ma.a_s = (const double *)h->e_mem.p;
+    ma.g_s = (const double *)h->e_mem.p + slots;
+    auto &a = ma.e;
+    a.m = h->m; a.n = h->n; a.max_iter = h->max_iter;
+    a.ms_scaling_factor = h->ms_scaling_factor;
+    a.batch = batch;
+    a.prior_s = (const double *)h->e_prior.p;
+    a.kind = (const uint8_t *)h->e_kind.p; a.scol = (const int32_t *)h->e_scol.p;
+    const size_t dyn = edge_lds_bytes(rounds);
+    int64_t per_cu = (int64_t)((160u * 1024u) / (dyn + 64));
+    if (per_cu > 4 * waves_per_simd) per_cu = 4 * waves_per_simd;  // (edge_mem_waves / edge8_mem_waves: what the instantiation was compiled for)
+    const int64_t groups = batch < 256 * per_cu ? batch : 256 * per_cu;
+    if ((rc = edge_work_split(h, rounds, batch, groups, a))) return rc;
+    h->accumulated_ms = 0.f;
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    LDPC_LAUNCH(kern, dim3((unsigned)groups), dim3(64), (unsigned)dyn, h->stream, ma);
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    h->timed = true;
+    HIPCHK(hipGetLastError());
+    return LDPC_HIP_OK;
+}
+
+static int decode_edge_mem(ldpc_hip_bp *h, const EdgePlan &p, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr,
+                           int32_t *iters, uint8_t *conv) {
+    int rc;
+    if ((rc = ensure_edge_tables(h, p))) return rc;
+    EdgeMemArgs ma = {};
+    ma.e.partner = (const uint16_t *)h->e_partner.p;
+    ma.e.synd = synd; ma.e.decoding = decoding; ma.e.llr = llr; ma.e.iters = iters; ma.e.conv = conv;
+    return launch_edge_mem(h, edge_mem_kernel(p.rounds), p.rounds, edge_mem_waves(p.rounds), batch, ma);
+}
+
+static int decode_edge8_mem(ldpc_hip_bp *h, const Edge8Plan &p, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr,
+                            int32_t *iters, uint8_t *conv) {
+    int rc;
+    if ((rc = ensure_edge8_tables(h, p))) return rc;
+    Edge8MemArgs ma = {};
+    ma.e.cpos = (const uint16_t *)h->e_partner.p;
+    ma.e.synd = synd; ma.e.decoding = decoding; ma.e.llr = llr; ma.e.iters = iters; ma.e.conv = conv;
+    return launch_edge_mem(h, edge8_mem_kernel(p.rounds, p.dc), p.rounds, edge8_mem_waves(p.rounds, p.dc), batch, ma);
+}
+
 // The float32 message mode's on-chip planner, called by decode_f32 (host_f32.h) after its refusals: decode_onchip's predicate for the lane =
 // edge families and their two plans, unchanged.  *took = false: neither takes the code -- decode_f32 goes on with its per-pass kernels (in
 // float32 nothing ever goes to bp_wave_kernel, bp_small_kernel or any FP64 kernel).
@@ -727,6 +791,18 @@ int decode_onchip_f32(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_
 int decode_onchip(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv, bool *took) {
     *took = false;
     const bool rp = h->row_probs != nullptr;
+    if (h->mem_on) {
+        // Memory min-sum (ldpc_hip_bp_set_memory): a code that plan_edge or plan_edge8 takes runs on their memory forms unless the on-chip kernels are
+        // switched off (mode 0); every other code -- and every code under mode 0 -- goes to the per-pass memory kernels (took = false).  The
+        // persistent ring kernel, bp_wave_kernel, the slot kernel and the resident workgroup know nothing of the memory and never see such a decode.
+        if (h->small_mode != 0 && h->m > 0 && h->n > 0 && h->nnz > 0 && (int64_t)h->nnz * 16 < (1 << 22) && batch < (1ll << 30)) {
+            const EdgePlan ep = plan_edge(h);
+            if (ep.rounds) { *took = true; return decode_edge_mem(h, ep, synd, batch, decoding, llr, iters, conv); }
+            const Edge8Plan e8 = plan_edge8(h);
+            if (e8.rounds) { *took = true; return decode_edge8_mem(h, e8, synd, batch, decoding, llr, iters, conv); }
+        }
+        return LDPC_HIP_OK;
+    }
     if (h->small_mode != 0 && h->m > 0 && h->n > 0 && h->nnz > 0 && (int64_t)h->nnz * 16 < (1 << 22) && batch < (1ll << 30)) {  // (32-bit syndrome indices in the work pools)
         // small code: keep the messages on chip.  Bounded degrees: one wavefront per syndrome (bp_wave_kernel).
         // Otherwise the slot kernel -- auto: the most resident syndromes (<= 4) per workgroup that still leave

@@ -312,6 +312,33 @@ int ldpc_hip_bp_get_message_dtype(const ldpc_hip_bp *h) {
     return h->msg_dtype;
 }
 
+int ldpc_hip_bp_set_memory(ldpc_hip_bp *h, const double *gamma) {
+    if (!h) return fail(LDPC_HIP_ERR_INVALID, "null handle");
+    HIPCHK(hipSetDevice(h->device));
+    if (!gamma) {  // off: the plain decode and its kernels again
+        HIPCHK(hipStreamSynchronize(h->stream));  // (a memory decode still queued reads the tables)
+        h->mem_on = false;
+        h->mem_gamma.clear();
+        h->mem_bad_col = -1;
+        h->mem_ag.release();
+        h->e_mem.release();
+        return LDPC_HIP_OK;
+    }
+    const int bad = mem_gamma_first_invalid(gamma, h->n);
+    if (bad >= 0) return fail(LDPC_HIP_ERR_INVALID, "memory strength %d is %g: every strength must be finite and in [-1, 1)", bad, gamma[bad]);
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->mem_gamma.assign(gamma, gamma + h->n);
+    h->mem_on = true;
+    return upload_memory(h);
+}
+
+int ldpc_hip_bp_get_memory(const ldpc_hip_bp *h, double *out) {
+    if (!h) return fail(LDPC_HIP_ERR_INVALID, "null handle");
+    if (!h->mem_on) return 0;
+    if (out) std::copy(h->mem_gamma.begin(), h->mem_gamma.end(), out);
+    return 1;
+}
+
 int64_t ldpc_hip_bp_workspace_bytes(const ldpc_hip_bp *h, int64_t batch) {
     if (!h || batch < 0) return -1;
     const int64_t tiles = (batch + LDPC_WAVE - 1) / LDPC_WAVE;

@@ -6,9 +6,14 @@
 // The LOOP forms serve the slots beyond the first 32 of a compacted list.  rp: every lane's own prior (row priors: SpreadArgs::llr0_t) in the
 // bit and finish kernels; no LOOP forms -- such a decode is never a compacted second pass.
 struct SpreadKernels { spread_kernel_t check = nullptr, bit = nullptr, check_loop = nullptr, bit_loop = nullptr, finish = nullptr; };
-static SpreadKernels pick_spread(const ldpc_hip_bp *h, bool nt, bool rp) {
+static SpreadKernels pick_spread(const ldpc_hip_bp *h, bool nt, bool rp, bool mem) {
     SpreadKernels k;
     const int dr = h->max_row_deg, dc = h->max_col_deg;
+    if (mem) {  // memory min-sum (mem_refusal: minimum-sum only); no LOOP forms either -- such a decode is not cut in two passes
+        pick_spread_mem(dr, dc, nt, k.check, k.bit);
+        k.finish = bp_spread_mem_finish_kernel;
+        return k;
+    }
     if (rp) with_method_math(h, [&](auto M, auto F) { pick_spread_m<M, F, false, true>(dr, dc, nt, k.check, k.bit); });
     else {
         with_method_math(h, [&](auto M, auto F) { pick_spread_m<M, F, false>(dr, dc, nt, k.check, k.bit); });
@@ -85,6 +90,7 @@ static int stream_chunk_tiles(const ldpc_hip_bp *h, int64_t tiles_total, bool wa
 // What a pass decides once, before its first chunk.
 struct StreamPlan {
     int max_iter = 0;     // the pass's iteration limit
+    bool mem = false;     // memory min-sum (h->mem_on): as rp -- the per-pass kernels from the first iteration, bp_spread_mem_*; M lives where the row priors would
     bool rp = false;      // row priors (h->row_probs [batch][n]): the per-pass kernels from the first iteration whatever the batch size -- no persistent kernel, no edge0, no hand-off
     int64_t chunk = 0;    // tiles per chunk
     size_t per_tile_msg = 0, per_tile_llr = 0;  // bytes of one message array / of the log-ratios (0: not wanted) per tile
@@ -97,10 +103,11 @@ struct StreamPlan {
 static int plan_stream(const ldpc_hip_bp *h, int64_t tiles_total, bool want_llr, const StreamPass &pass, StreamPlan &p) {
     p.max_iter = pass.max_iter < 0 ? h->max_iter : pass.max_iter;
     p.rp = h->row_probs != nullptr;
+    p.mem = h->mem_on;
     p.per_tile_msg = sizeof(double) * (size_t)(h->nnz ? h->nnz : 1) * LDPC_WAVE;
     p.per_tile_llr = want_llr ? sizeof(double) * (size_t)(h->n ? h->n : 1) * LDPC_WAVE : 0;
     int rc;
-    if ((rc = stream_chunk_tiles(h, tiles_total, want_llr, p.rp, &p.chunk))) return rc;
+    if ((rc = stream_chunk_tiles(h, tiles_total, want_llr, p.rp || p.mem, &p.chunk))) return rc;
     if (pass.continues() && p.chunk < tiles_total) return fail(LDPC_HIP_ERR_NOMEM, "internal: the second pass of a compacted decode must be one chunk");
     const int ring = h->regular ? h->ring_depth : 0;
     // the variable-degree ring (bp_stream_kernel.h, LDPC_RING_VAR) on request (VAR_RING 1) wherever it applies -- rows <= 16, columns <= 8.
@@ -156,7 +163,7 @@ static int stream_workspace(ldpc_hip_bp *h, const StreamPlan &p) {
     if ((rc = h->par.ensure(sizeof(uint64_t) * m1 * chunk)) || (rc = h->nzm.ensure(sizeof(uint64_t) * m1 * chunk)) || (rc = h->invalid.ensure(sizeof(uint64_t) * chunk))) return rc;
     if ((rc = h->dec.ensure(sizeof(uint64_t) * n1 * chunk)) || (rc = h->dcur.ensure(sizeof(uint64_t) * n1 * chunk))) return rc;
     if (p.per_tile_llr && (rc = h->llr_t.ensure(p.per_tile_llr * chunk))) return rc;
-    if (p.rp && (rc = h->rowp_llr.ensure(sizeof(double) * n1 * LDPC_WAVE * chunk))) return rc;  // (per chunk, like the messages)
+    if ((p.rp || p.mem) && (rc = h->rowp_llr.ensure(sizeof(double) * n1 * LDPC_WAVE * chunk))) return rc;  // (per chunk, like the messages; memory: M)
     if ((rc = h->tile_state.ensure(sizeof(TileState) * chunk)) || (rc = h->handoff_list.ensure(sizeof(int32_t) * chunk)) || (rc = h->counter.ensure(16))) return rc;
     if (!h->h_counters) HIPCHK(hipHostMalloc((void **)&h->h_counters, 16, hipHostMallocDefault));
     return LDPC_HIP_OK;
@@ -206,7 +213,9 @@ static int stream_start_per_pass(ldpc_hip_bp *h, const StreamPlan &p, int64_t ti
     sa.nodes = h->sw("SPREAD_NODES") > 0 ? h->sw("SPREAD_NODES") : tiles <= 8 ? 1 : tiles < 512 ? 4 : 16;
     LDPC_LAUNCH(bp_spread_state_init_kernel, dim3((r.grid_tiles + 255) / 256), dim3(256), 0, h->stream, sa);
     const dim3 gi((unsigned)(h->nnz ? (h->nnz + 63) / 64 : 1), r.grid_tiles);  // (a grid dimension must not be 0: empty matrices)
-    if (p.rp)
+    if (p.mem)
+        LDPC_LAUNCH(bp_spread_mem_init_kernel, gi, dim3(256), 0, h->stream, sa);
+    else if (p.rp)
         with_method_math(h, [&](auto M, auto F) { LDPC_LAUNCH((bp_spread_init_kernel<M, F, true>), gi, dim3(256), 0, h->stream, sa); });
     else if (sa.bp.it_start == 0)  // (else the message state is there already)
         with_method_math(h, [&](auto M, auto F) { LDPC_LAUNCH((bp_spread_init_kernel<M, F>), gi, dim3(256), 0, h->stream, sa); });
@@ -249,7 +258,7 @@ static int stream_rounds(ldpc_hip_bp *h, const StreamPlan &p, const StreamPass &
     // messages of the tiles in flight: 2 arrays x nnz x 512 B each; beyond ~the MALL they are streamed, not cached
     // (switch SPREAD_NT 0 / 1: the policy whatever the size -- the tests run the non-temporal instantiations on a small case with it)
     const bool nt = h->sw("SPREAD_NT") >= 0 ? h->sw("SPREAD_NT") > 0 : (double)grid_tiles * 2.0 * (double)p.per_tile_msg > 384.0 * 1024.0 * 1024.0;
-    const SpreadKernels k = pick_spread(h, nt, p.rp);
+    const SpreadKernels k = pick_spread(h, nt, p.rp, p.mem);
     const unsigned per_wg = 4u * (unsigned)sa.nodes;
     const dim3 gc((unsigned)(h->m ? (h->m + per_wg - 1) / per_wg : 1), grid_tiles), gb((unsigned)(h->n ? (h->n + per_wg - 1) / per_wg : 1), grid_tiles);
     const dim3 gs((unsigned)(h->m ? (h->m + 255) / 256 : 1), grid_tiles), gf((unsigned)(h->n ? (h->n + 63) / 64 : 1), grid_tiles);
@@ -342,8 +351,12 @@ static int decode_streamed(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, u
             HIPCHK(hipGetLastError());
             sa.llr0_t = (const double *)h->rowp_llr.p;
         }
+        if (p.mem) {  // M of this chunk's tiles (filled by bp_spread_mem_init_kernel), a[] and gamma[]
+            sa.llr0_t = (const double *)h->rowp_llr.p;
+            sa.mem_ag = (const double *)h->mem_ag.p;
+        }
         SpreadRounds r;
-        const bool per_pass = p.rp || (p.handoff > 0 && c.tiles <= p.handoff && p.max_iter - pass.it_start > 1 && !pass.rows_dev);
+        const bool per_pass = p.rp || p.mem || (p.handoff > 0 && c.tiles <= p.handoff && p.max_iter - pass.it_start > 1 && !pass.rows_dev);
         if ((rc = per_pass ? stream_start_per_pass(h, p, c.tiles, sa, r) : stream_persistent(h, p, c.tiles, waves, a, sa, r))) return rc;
         if (r.grid_tiles > 0 && (rc = stream_rounds(h, p, pass, sa, r))) return rc;
         if ((rc = chunk_timing_end(h)) || (rc = stream_outputs(h, pass, c, loop_tiles, decoding, llr))) return rc;
@@ -426,6 +439,10 @@ int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
     h->timed_prev = h->timed_prev_mid = false;  // (what a two-pass decode before this one left)
     // Row priors (ldpc_hip_*_decode_batch_priors): every row is decoded with its own channel probabilities, h->row_probs [batch][n].  Two kernel
     // families read them: the slot kernel (decode_onchip sends there whatever an on-chip kernel would take) and the per-pass kernels (StreamPlan::rp).
+    if (h->mem_on) {  // (the entry points have said so already, before staging anything: nothing wrong is ever decoded from here either)
+        const int refused = mem_refusal(h, h->row_probs ? "per-row channel probabilities are" : nullptr);
+        if (refused) return refused;
+    }
     if (h->msg_dtype == LDPC_HIP_MSG_F32) return decode_f32(h, synd, batch, decoding, llr, iters, conv);  // (never an FP64 kernel: what the mode cannot do is refused there)
     const bool rp = h->row_probs != nullptr;
     if (rp && h->schedule != 1) return fail(LDPC_HIP_ERR_UNSUPPORTED, "per-row channel probabilities: the serial schedules read the handle's priors only (parallel schedule required)");
@@ -439,7 +456,8 @@ int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
     // a short first pass + a second pass over the compacted rest does the same work in a fraction of the tile-iterations
     // (switch REPACK_MIN_TILES t > 0: t instead of the 512 tiles -- the tests cut batches of a few dozen tiles with it)
     const int64_t min_tiles = h->sw("REPACK_MIN_TILES") > 0 ? h->sw("REPACK_MIN_TILES") : 512;
-    if (!rp && h->repack_iters != 0 && h->max_iter >= 8 && tiles_total >= min_tiles && h->m > 0 && h->n > 0)
+    // (memory min-sum is not cut in two passes: the compaction would have to gather M too -- DESIGN.md section 7c)
+    if (!rp && !h->mem_on && h->repack_iters != 0 && h->max_iter >= 8 && tiles_total >= min_tiles && h->m > 0 && h->n > 0)
         return decode_stream_repacked(h, synd, batch, decoding, llr, iters, conv);
     return decode_streamed(h, synd, batch, decoding, llr, iters, conv, StreamPass());
 }

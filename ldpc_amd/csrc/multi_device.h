@@ -226,6 +226,8 @@ extern "C" int ldpc_hip_bp_multi_decode_batch(ldpc_hip_bp_multi *mh, int32_t wit
     for (const MultiDev &md : mh->devs) {
         const int refused = f32_refusal(md.h, "decoding over several GPUs (ldpc_hip_bp_multi) is");
         if (refused) return refused;
+        const int refused_mem = mem_refusal(md.h, "decoding over several GPUs (ldpc_hip_bp_multi) is");
+        if (refused_mem) return refused_mem;
     }
     // where the caller's arrays live: all in host memory, or all on ONE GPU
     const int pd = pointer_device(synd);

@@ -24,6 +24,15 @@ static void pick_spread_m(int max_row, int max_col, bool nt, spread_kernel_t &kc
     }
 }
 
+// memory min-sum (bp_spread_mem_*: the bit kernel forms its prior from the lane's previous posterior, SpreadArgs::llr0_t / mem_ag; the check
+// kernel never sees a prior and is the plain min-sum one)
+static void pick_spread_mem(int max_row, int max_col, bool nt, spread_kernel_t &kc, spread_kernel_t &kb) {
+    spread_kernel_t plain_bit;
+    pick_spread_m<LDPC_HIP_MINIMUM_SUM, 0, false>(max_row, max_col, nt, kc, plain_bit);
+    kb = nt ? (max_col <= 4 ? bp_spread_mem_bit_kernel<4, 1> : bp_spread_mem_bit_kernel<8, 1>)
+            : (max_col <= 4 ? bp_spread_mem_bit_kernel<4, 0> : bp_spread_mem_bit_kernel<8, 0>);
+}
+
 struct KernelChoice {
     bp_kernel_t fn;
     int ring_slot_bytes;  // 0: register-prefetch variant, no dynamic LDS

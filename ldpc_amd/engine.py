@@ -144,6 +144,29 @@ class HipBpEngine:
     def message_dtype(self) -> str:
         return ("float64", "float32")[int(self._lib.ldpc_hip_bp_get_message_dtype(self._h))]
 
+    def set_memory(self, gamma):
+        """Memory min-sum BP (``ldpc_hip_bp_set_memory``): ``gamma`` = one memory strength per bit, each finite and in ``[-1, 1)`` -- every
+        iteration's bit pass then takes ``(1 - gamma) * prior + gamma * (the bit's previous posterior)`` for the prior -- or ``None``: off.
+        Minimum-sum, parallel schedule, float64 messages; what it cannot do is refused when decoding, with its reason."""
+        if gamma is None:
+            _lib.check(self._lib.ldpc_hip_bp_set_memory(self._h, None))
+            return
+        g = np.ascontiguousarray(gamma, np.float64)
+        if g.shape != (self.n,):
+            raise ValueError(f"memory strengths must have shape ({self.n},), not {g.shape}.")
+        rc = self._lib.ldpc_hip_bp_set_memory(self._h, g.ctypes.data_as(C.c_void_p))
+        if rc == -1:  # LDPC_HIP_ERR_INVALID: a strength outside [-1, 1) or not finite
+            raise ValueError(self._lib.ldpc_hip_last_error().decode("utf-8", "replace"))
+        _lib.check(rc)
+
+    def memory(self):
+        """The memory strengths as a float64 array, or ``None`` when memory is off."""
+        out = np.empty(self.n, np.float64)
+        rc = int(self._lib.ldpc_hip_bp_get_memory(self._h, out.ctypes.data_as(C.c_void_p)))
+        if rc < 0:
+            _lib.check(rc)
+        return out if rc == 1 else None
+
     def set_ring(self, depth):
         """LDS-DMA ring for regular-degree matrices: False/0 = off, True/1 = default depth, 2 or 3 = slots per wave."""
         _lib.check(self._lib.ldpc_hip_bp_set_ring(self._h, int(depth)))

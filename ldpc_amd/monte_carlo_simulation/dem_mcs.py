@@ -51,14 +51,16 @@ class MonteCarloDemSimulation:
 
     The errors are drawn with the model's probabilities exactly; the decoder's priors are the same values clipped to
     ``[1e-9, 1 - 1e-9]``, so a mechanism at p = 0 or p = 1 keeps a finite log-ratio.  ``message_dtype="float32"`` decodes with FP32
-    messages (minimum-sum only: ``bp_method="ps"`` is then refused at ``run()``, as everywhere in the library).
+    messages (minimum-sum only: ``bp_method="ps"`` is then refused at ``run()``, as everywhere in the library).  ``memory_strength``
+    (``None``, a float, or one strength per mechanism in ``[-1, 1)``): memory min-sum BP, as ``BpDecoder.memory_strength``; minimum-sum with
+    float64 messages only, and not together with a ``window_decoder``.
 
     One GPU (``device``; -1: the current one).  For several, run one simulation per device over disjoint shot ranges.
     """
 
     def __init__(self, model, *, target_run_count, batch_size: int = 65536, seed: int = 0, max_iter: int = 0, bp_method="ms",
                  ms_scaling_factor: float = 0.625, osd_method="osd0", osd_order: int = 0, message_dtype="float64", window_decoder=None,
-                 device: int = -1) -> None:
+                 device: int = -1, memory_strength=None) -> None:
         from ldpc_amd.bp_decoder._bp_decoder import _bp_method_code
         from ldpc_amd.noise_models.dem import check_dem_probabilities
         from ldpc_amd.sinter_decoders.sinter_bposd_decoder import _osd_code
@@ -98,6 +100,19 @@ class MonteCarloDemSimulation:
                     window_decoder.logical_observables_matrix.shape[0] != self.observables_matrix.shape[0]:
                 raise ValueError("Invalid window_decoder provided. Its detectors and observables must be the model's.")
         self.window_decoder = window_decoder
+        # memory min-sum BP (BpDecoder.memory_strength): None, a float (every mechanism) or one strength per mechanism, each finite and in [-1, 1)
+        if memory_strength is not None:
+            if window_decoder is not None:
+                raise ValueError("memory_strength with a window_decoder: the windows decode with their own decoders, which have no memory; "
+                                 "leave memory_strength at None.")
+            n = self.check_matrix.shape[1]
+            g = np.array(memory_strength, dtype=np.float64)
+            if g.ndim == 0:
+                g = np.full(n, float(g), np.float64)
+            if g.shape != (n,) or not (np.isfinite(g).all() and (g >= -1.0).all() and (g < 1.0).all()):
+                raise ValueError(f"Invalid memory_strength provided. It must be None, a float or {n} floats, each finite and in [-1, 1).")
+            memory_strength = g
+        self.memory_strength = memory_strength
         if not isinstance(device, int) or isinstance(device, bool):
             raise ValueError("Invalid device provided.")
         self.device = device
@@ -123,6 +138,7 @@ class MonteCarloDemSimulation:
                               self.ms_scaling_factor, device=self.device)
             eng.set_osd(self._osd_code, 0 if self._osd_code == 1 else self.osd_order)
             eng.set_message_dtype(self.message_dtype)
+            eng.set_memory(self.memory_strength)  # (what memory min-sum cannot do -- product-sum, float32 -- is refused at run(), by the library)
             eng.set_observables(self.observables_matrix)
             eng.set_sampler(self.priors)
             self._engine = eng
