@@ -508,6 +508,33 @@ int ldpc_hip_bp_get_message_dtype(const ldpc_hip_bp *h);
 int ldpc_hip_bp_set_memory(ldpc_hip_bp *h, const double *gamma);
 int ldpc_hip_bp_get_memory(const ldpc_hip_bp *h, double *out);
 
+/*
+ * Relay-BP (opt-in; no counterpart in the reference): `legs` memory min-sum legs chained per syndrome and decoded in one call.  Leg l runs at
+ * most leg_iters[l] iterations with the strengths gamma[l][0 .. n) -- leg_iters takes the place of the handle's max_iter -- exactly as the memory
+ * decode above iterates (a scaling factor of 0 counts the LEG's iterations), with two differences from the second leg on: M starts as the
+ * posteriors the previous leg ended with (of its last bit pass: the iteration it converged at, or its last), and the initial bit-to-check
+ * message of every entry of column j is gamma[l][j] == 0 ? L0[j] : a[l][j] + gamma[l][j] * M[j] (the product rounded, then the sum).
+ * A leg that reproduces the syndrome is a solution; its weight is the sum of L0[j] over its decided bits, an FP64 sum in one fixed order
+ * (relay_common.h: relay_weight).  The row stops after stop_after solutions.  Outputs: the lightest solution -- the first among equal weights --
+ * with the posteriors of its leg, converge = 1; a row without any solution gets the last leg's last decisions and posteriors, converge = 0;
+ * iterations = the sum over the legs the row ran.  A syndrome byte > 1 never converges.  The results are those of the NumPy restatement
+ * tests/relay_bp_util.py, bit for bit, on both routes: the lane = edge relay kernels (all legs in one launch, nothing leaves the chip between
+ * legs) for the codes those kernels take, and otherwise a loop of per-pass memory decodes with a selection kernel after each leg (correct
+ * everywhere, not fast); nothing is read back between legs, so the *_async entry points stay asynchronous.
+ *   ldpc_hip_bp_set_relay(h, legs, gamma, leg_iters, stop_after): gamma = host pointer to [legs * n], each finite and in [-1, 1); leg_iters =
+ *       host pointer to [legs], each >= 1; stop_after >= 1 (else LDPC_HIP_ERR_INVALID).  legs = 0 or gamma = NULL: off.  Relay and
+ *       ldpc_hip_bp_set_memory exclude each other: setting one while the other is on is LDPC_HIP_ERR_UNSUPPORTED.  ldpc_hip_bp_set_channel
+ *       afterwards is followed: a[] of every leg is formed again.
+ *   ldpc_hip_bp_get_relay(h, &legs, &stop_after, gamma_out, leg_iters_out): 1 if the relay is on (legs and stop_after set; gamma_out[legs * n]
+ *       and leg_iters_out[legs] filled unless NULL), 0 if off (legs = stop_after = 0), LDPC_HIP_ERR_INVALID for a NULL handle.
+ * With the relay on, ldpc_hip_bp_decode_batch[_async], the BP + OSD-0 entry points (OSD sees the rows the relay leaves without a solution, with
+ * the last leg's posteriors), ldpc_hip_bp_decode_b8 and ldpc_hip_bp_simulate_b8 decode with it.  Refused with LDPC_HIP_ERR_UNSUPPORTED before
+ * anything is staged or launched: product-sum, any serial schedule, LDPC_HIP_MSG_F32, the *_priors entry points, soft-syndrome decoding,
+ * several GPUs, OSD-E / OSD-CS -- and, at decode time, a nonzero gamma[l][j] in any leg on a column whose channel probability is 0 or 1.
+ */
+int ldpc_hip_bp_set_relay(ldpc_hip_bp *h, int32_t legs, const double *gamma, const int32_t *leg_iters, int32_t stop_after);
+int ldpc_hip_bp_get_relay(const ldpc_hip_bp *h, int32_t *legs, int32_t *stop_after, double *gamma_out, int32_t *leg_iters_out);
+
 /* The shader clock the BP kernels actually ran at (a measurement aid; no counterpart in the reference).  Every workgroup of the
  * long-running BP kernels (bp_decode_kernel, bp_wave_kernel, bp_wave_ps_kernel, bp_edge_kernel, bp_edge8_kernel) adds the shader cycles
  * (s_memtime) and the constant-rate ticks (s_memrealtime) of its lifetime to two 64-bit words of the handle; the words only grow.

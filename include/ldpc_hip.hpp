@@ -194,6 +194,21 @@ public:
         return g;
     }
 
+    // Relay-BP (ldpc_hip.h: ldpc_hip_bp_set_relay): strengths = legs rows of n memory strengths, each finite and in [-1, 1); one iteration
+    // limit >= 1 per leg (they take the place of max_iter); stop_after >= 1 solutions end a row.  Empty vectors switch it off.  It excludes set_memory.
+    bool set_relay(const std::vector<double> &strengths, const std::vector<int32_t> &leg_iters, int32_t stop_after) {
+        if (mh_) { fail_(LDPC_HIP_ERR_UNSUPPORTED, "Relay-BP is not sharded over several GPUs; decode on one GPU"); return false; }
+        if (!strengths.empty() && (leg_iters.empty() || strengths.size() != leg_iters.size() * (size_t)bit_count)) {
+            fail_(LDPC_HIP_ERR_INVALID, "relay strengths must have legs * n entries, leg_iters one per leg");
+            return false;
+        }
+        if (!strengths.empty() && !sync_()) return false;  // (a[] of every leg is formed from the channel probabilities the handle holds)
+        last_status = ldpc_hip_bp_set_relay(h_, (int32_t)leg_iters.size(), strengths.empty() ? nullptr : strengths.data(),
+                                            leg_iters.empty() ? nullptr : leg_iters.data(), stop_after);
+        if (last_status != LDPC_HIP_OK) { last_error = ldpc_hip_last_error(); return false; }
+        return true;
+    }
+
     ldpc_hip_bp *handle() { return h_; }
     ldpc_hip_bp_multi *multi_handle() { return mh_; }  // null unless constructed with device_ids
     int device_count() const { return mh_ ? (int)ldpc_hip_bp_multi_devices(mh_) : 1; }

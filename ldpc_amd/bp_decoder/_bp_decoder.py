@@ -145,6 +145,8 @@ class BpDecoderBase:
         self._engine_dtype = "float64"  # what the engine's handle is set to (a new handle starts at float64)
         self._memory = None             # memory_strength: None (off) or an (n,) float64 array
         self._engine_memory = None      # what the engine's handle is set to (a new handle starts with memory off)
+        self._relay = None              # relay: None (off) or (strengths (legs, n), leg_iters (legs,), stop_after)
+        self._engine_relay = None       # ... what the engine's handle is set to
 
         self._h = _ingest(pcm)
         self.m, self.n = int(pcm.shape[0]), int(pcm.shape[1])
@@ -448,8 +450,52 @@ class BpDecoderBase:
             raise ValueError("memory_strength: every strength must be finite and in [-1, 1).")
         self._memory = g
 
+    # ---- Relay-BP (additive; not a constructor keyword either) ---------------------------------------------------
+    @property
+    def relay(self):
+        """``None`` (default): off.  Set to a dict of ``ldpc_amd.relay_decoder.relay_schedule`` keywords (``gamma0``, ``pre_iter``,
+        ``num_sets``, ``set_max_iter``, ``gamma_dist_interval``, ``stop_nconv``, ``strengths``, ``seed``): every decode then runs Relay-BP
+        (``ldpc_hip_bp_set_relay``) -- chained memory min-sum legs whose iteration limits take the place of ``max_iter``.
+        Read back as ``(strengths, leg_iters, stop_after)``.  Minimum-sum, parallel schedule, float64 messages, one GPU, OSD_0 at most; not
+        together with ``memory_strength``, ``channel_probs=`` or soft syndromes -- ``NotImplementedError`` at decode time."""
+        return None if self._relay is None else (self._relay[0].copy(), self._relay[1].copy(), self._relay[2])
+
+    @relay.setter
+    def relay(self, value) -> None:
+        if value is None:
+            self._relay = None
+            return
+        if not isinstance(value, dict):
+            raise ValueError(f"relay must be None or a dict of relay_schedule keywords, not {value!r}.")
+        from ldpc_amd.relay_decoder import relay_schedule
+        self._relay = relay_schedule(self.n, **value)
+
+    def _require_relay(self, what=None):
+        if self._relay is None:
+            return
+        if what is not None:
+            raise NotImplementedError(f"relay with {what.replace('without memory only', 'without the relay only')}; set relay=None.")
+        if self._memory is not None:
+            raise NotImplementedError("relay with memory_strength: the relay's legs carry their own strengths; set memory_strength=None.")
+        if self._bp_method != MINIMUM_SUM:
+            raise NotImplementedError("relay with bp_method='product_sum': the memory strengths are defined for bp_method='minimum_sum' only.")
+        if self._schedule != PARALLEL or self._random_serial_schedule:
+            raise NotImplementedError(f"relay with schedule='{self.schedule}'"
+                                      f"{' and random_serial_schedule' if self._random_serial_schedule else ''}: Relay-BP needs schedule='parallel'.")
+        if self._message_dtype != "float64":
+            raise NotImplementedError("relay with message_dtype='float32': Relay-BP is decoded with float64 messages only.")
+        if self._device_ids is not None:
+            raise NotImplementedError("relay with device_ids=[...]: Relay-BP is not sharded over several GPUs; decode on one GPU.")
+        p = self._channel_probs
+        bad = np.flatnonzero((self._relay[0] != 0.0).any(axis=0) & ~((p > 0.0) & (p < 1.0)))
+        if len(bad):
+            raise NotImplementedError(f"relay: bit {int(bad[0])} has a nonzero memory strength and a channel probability of {p[bad[0]]!r}; "
+                                      "Relay-BP needs probabilities strictly between 0 and 1 there (or strength 0 on that bit in every leg).")
+
     def _require_memory(self, what=None):
-        """What memory min-sum cannot do is refused here, at decode time, with its reason (``what``: the call's own addition)."""
+        """What memory min-sum cannot do is refused here, at decode time, with its reason (``what``: the call's own addition) -- and what
+        Relay-BP cannot (``_require_relay``)."""
+        self._require_relay(what)
         if self._memory is None:
             return
         if what is not None:
@@ -502,10 +548,17 @@ class BpDecoderBase:
         if self._message_dtype != self._engine_dtype:
             self._engine.set_message_dtype(self._message_dtype)
             self._engine_dtype = self._message_dtype
+        relay_changed = self._relay is not self._engine_relay
+        if relay_changed and self._relay is None:  # (off before the memory may go on: the two exclude each other on the handle)
+            self._engine.set_relay(None)
+            self._engine_relay = None
         if not (self._memory is self._engine_memory or (self._memory is not None and self._engine_memory is not None
                                                          and np.array_equal(self._memory, self._engine_memory))):
             self._engine.set_memory(self._memory)
             self._engine_memory = None if self._memory is None else self._memory.copy()
+        if relay_changed and self._relay is not None:
+            self._engine.set_relay(*self._relay)
+            self._engine_relay = self._relay
         rnd = (bool(self._random_serial_schedule), self._random_schedule_seed, self._seed_epoch)
         if rnd != getattr(self, "_engine_random", (False, 0, 0)):
             self._engine.set_random_serial(rnd[0], rnd[1])  # re-seeds, as bpd.set_random_schedule_seed does (pyx:553-554)
@@ -542,7 +595,7 @@ class BpDecoderBase:
         """(B, m) uint8 NumPy -> (decoding, llr, iterations, converge) through the active backend.  ``llr_out``: a (B, n) float64
         C-contiguous array to receive the log-ratios instead of a new one.  ``channel_probs``: checked (B, n) row priors or None."""
         # (the schedule setters and the memory strengths live on the ctypes engine)
-        cy = self._get_cy() if self._schedule == PARALLEL and self._memory is None else None
+        cy = self._get_cy() if self._schedule == PARALLEL and self._memory is None and self._relay is None else None
         if cy is not None and channel_probs is not None:
             return cy.decode_batch(np.ascontiguousarray(synd2d, np.uint8), want_llr, osd0, llr_out, channel_probs)
         if cy is not None:

@@ -3,6 +3,7 @@
 #pragma once
 
 #include "bp_device_common.h"
+#include "relay_common.h"
 
 // ---- per-pass kernels for handed-off tiles ---------------------------------------------------------------
 // Same arithmetic, same arrays, but one launch per pass and one wavefront per NODE, so the rows / columns of a
@@ -24,6 +25,9 @@ struct SpreadArgs {
     // iteration (the prior log-ratio to begin with: bp_spread_mem_init_kernel), read AND rewritten by every bit pass for all 64 lanes; mem_ag [2][n]
     // = a[] = (1 - gamma) * llr0, then gamma[] (mem_host.h), read per column through the scalar path as llr0 is.  nullptr otherwise.
     const double *mem_ag;
+    // Relay-BP, a leg after the first (bp_spread_relay_init_kernel): [bp.batch][n] row-major, the previous leg's posteriors of
+    // this chunk's rows -- what M starts from instead of the prior log-ratios.  nullptr otherwise.
+    const double *relay_seed;
 };
 
 // the prior of column j's bit pass under memory: llr0[j] where gamma[j] == 0 (a select: a[j] IS llr0[j] there, infinities included), else
@@ -230,8 +234,12 @@ __global__ void __launch_bounds__(256) bp_spread_state_init_kernel(const SpreadA
 }
 
 // (MEM: the initial messages are the plain ones; M starts as the prior log-ratio in every lane)
-template <int METHOD, int MATH, bool RP, bool MEM>
+// (SEED, with MEM -- a leg of Relay-BP after the first: M starts as the lane's row of relay_seed, the previous leg's posteriors, and the initial
+// message of every entry of column j is the prior the first bit pass will form from it, mem_prior(j, M) -- a[j] = L0[j] itself where gamma[j] == 0.
+// Lanes beyond the batch in a ragged last tile take the prior log-ratios: nothing of them is ever read back.)
+template <int METHOD, int MATH, bool RP, bool MEM, bool SEED = false>
 __device__ __forceinline__ void spread_init(const SpreadArgs &a) {  // bp.hpp:147-157
+    static_assert(!SEED || MEM, "a seeded start is a memory decode");
     const int64_t tile = blockIdx.y;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -239,14 +247,18 @@ __device__ __forceinline__ void spread_init(const SpreadArgs &a) {  // bp.hpp:14
     const MsgBuf At = make_msgbuf(a.bp.A + (size_t)tile * (size_t)nnz * LDPC_WAVE, (unsigned)nnz);
     const MsgBuf Pt = make_msgbuf(RP ? const_cast<double *>(a.llr0_t) + (size_t)tile * (size_t)a.bp.n * LDPC_WAVE : a.bp.A, RP ? (unsigned)a.bp.n : 0u);
     const int e0 = (blockIdx.x * 4 + wave) * 16;
+    const int64_t row = tile * LDPC_WAVE + lane;  // (SEED) this lane's row of the chunk
+    const bool seeded = SEED && row < a.bp.batch;
+    const double *seed = SEED ? a.relay_seed + (seeded ? row : 0) * (int64_t)a.bp.n : nullptr;
     for (int e = e0; e < e0 + 16 && e < nnz; ++e) {
         const int j = sload(a.bp.col_idx + e);
-        At.st(l8, e, edge_form<METHOD, MATH>(RP ? Pt.ld(l8, j) : sload(a.bp.llr0 + j)));
+        if (SEED) At.st(l8, e, mem_prior(a.mem_ag, a.bp.n, j, seeded ? seed[j] : sload(a.bp.llr0 + j)));
+        else At.st(l8, e, edge_form<METHOD, MATH>(RP ? Pt.ld(l8, j) : sload(a.bp.llr0 + j)));
     }
     if (MEM) {  // the same grid covers the columns: 64 per workgroup, nnz >= n where every column has an entry -- and a loop where not
         const MsgBuf Mt = make_msgbuf(const_cast<double *>(a.llr0_t) + (size_t)tile * (size_t)a.bp.n * LDPC_WAVE, (unsigned)a.bp.n);
         for (int j0 = (blockIdx.x * 4 + wave) * 16; j0 < a.bp.n; j0 += (int)gridDim.x * 64)
-            for (int j = j0; j < j0 + 16 && j < a.bp.n; ++j) Mt.st(l8, j, sload(a.bp.llr0 + j));
+            for (int j = j0; j < j0 + 16 && j < a.bp.n; ++j) Mt.st(l8, j, seeded ? seed[j] : sload(a.bp.llr0 + j));
     }
 }
 
@@ -254,6 +266,8 @@ template <int METHOD, int MATH, bool RP = false>
 __global__ void __launch_bounds__(256) bp_spread_init_kernel(const SpreadArgs a) { spread_init<METHOD, MATH, RP, false>(a); }
 
 __global__ void __launch_bounds__(256) bp_spread_mem_init_kernel(const SpreadArgs a) { spread_init<LDPC_HIP_MINIMUM_SUM, 0, false, true>(a); }
+
+__global__ void __launch_bounds__(256) bp_spread_relay_init_kernel(const SpreadArgs a) { spread_init<LDPC_HIP_MINIMUM_SUM, 0, false, true, true>(a); }
 
 // [n] initial edge values for BpArgs::edge0
 template <int METHOD, int MATH>
@@ -340,3 +354,59 @@ template <bool LOOP = false, bool RP = false>
 __global__ void __launch_bounds__(256) bp_spread_finish_kernel(const SpreadArgs a) { spread_finish<LOOP, RP, false>(a); }
 
 __global__ void __launch_bounds__(256) bp_spread_mem_finish_kernel(const SpreadArgs a) { spread_finish<false, false, true>(a); }
+
+// ---- Relay-BP, the per-pass leg loop (host_stream.h: decode_relay): the per-row bookkeeping after each leg ----
+// What a leg of the per-pass loop leaves per row, and what the loop keeps per row between legs.
+struct RelaySelectArgs {
+    int64_t batch;
+    int32_t n, stop_after;
+    int32_t first, last;            // this is leg 0 (the state starts here) / the last leg
+    const double *llr0;             // [n]
+    const uint8_t *leg_dec;         // [batch][n] the leg's decisions ...
+    const double *leg_llr;          // [batch][n] ... posteriors (a converged row's: frozen at its convergence iteration) ...
+    const int32_t *leg_iters;       // [batch]    ... iterations run ...
+    const uint8_t *leg_conv;        // [batch]    ... and whether it reproduced the syndrome
+    double *best_w;                 // [batch] the weight of the lightest solution so far (+inf: none)
+    int32_t *nsol, *total;          // [batch] solutions so far; iterations so far
+    uint8_t *decoding;              // the caller's outputs: [batch][n]
+    double *llr;                    // [batch][n] or nullptr
+    int32_t *iters;                 // [batch] or nullptr
+    uint8_t *conv;                  // [batch] or nullptr
+};
+
+// One wavefront per row, after each leg: a row with stop_after solutions is finished and ignored; otherwise the leg's iterations are added, a
+// solution is counted and -- if strictly lighter than the lightest so far (NaN never is) -- copied to the caller's outputs; a row without any
+// solution gets the last leg's outputs.
+__global__ void __launch_bounds__(256) relay_select_kernel(const RelaySelectArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int64_t b = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= a.batch) return;
+    double best = a.first ? __builtin_inf() : a.best_w[b];
+    int nsol = a.first ? 0 : a.nsol[b], total = a.first ? 0 : a.total[b];
+    if (nsol < a.stop_after) {
+        total += a.leg_iters[b];
+        const uint8_t *dec = a.leg_dec + b * a.n;
+        bool take = false;
+        if (a.leg_conv[b]) {
+            const double w = relay_weight(a.llr0, a.n, lane, [&](int j) { return dec[j] != 0; });
+            ++nsol;
+            if (w < best) { best = w; take = true; }
+        } else if (a.last && nsol == 0) {
+            take = true;
+        }
+        if (take) {
+            const double *src = a.leg_llr + b * a.n;
+            for (int j = lane; j < a.n; j += LDPC_WAVE) {
+                a.decoding[b * a.n + j] = dec[j];
+                if (a.llr) a.llr[b * a.n + j] = src[j];
+            }
+        }
+    }
+    if (lane == 0) {
+        a.best_w[b] = best;
+        a.nsol[b] = nsol;
+        a.total[b] = total;
+        if (a.iters) a.iters[b] = total;
+        if (a.conv) a.conv[b] = nsol > 0 ? 1 : 0;
+    }
+}

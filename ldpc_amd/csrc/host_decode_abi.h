@@ -62,6 +62,7 @@ int ldpc_hip_bposd_decode_batch_async(ldpc_hip_bp *h, const uint8_t *synd, int64
     if (!synd || !decoding) return fail(LDPC_HIP_ERR_INVALID, "syndromes and decoding must not be NULL");
     { const int refused = f32_refusal(h, nullptr); if (refused) return refused; }
     { const int refused = mem_refusal(h, nullptr); if (refused) return refused; }
+    { const int refused = relay_osd_refusal(h, true); if (refused) return refused; }
     HIPCHK(hipSetDevice(h->device));
     return mark_queued(h, bposd_device(h, h->osd_method, h->osd_order, synd, batch, decoding, llr, iters, conv));
 }
@@ -350,6 +351,7 @@ static int decode_batch_staged(ldpc_hip_bp *h, int osd, const uint8_t *synd, int
     if (probs) { const int refused = row_priors_refusal(h); if (refused) return refused; }
     { const int refused = f32_refusal(h, nullptr); if (refused) return refused; }
     { const int refused = mem_refusal(h, nullptr); if (refused) return refused; }
+    { const int refused = relay_osd_refusal(h, osd == 1); if (refused) return refused; }
     HIPCHK(hipSetDevice(h->device));
     const size_t B = (size_t)batch, m = (size_t)h->m, n = (size_t)h->n;
     const uint8_t *d_synd = synd;
@@ -383,7 +385,7 @@ static int decode_batch_staged(ldpc_hip_bp *h, int osd, const uint8_t *synd, int
             double *p_llr = (llr || osd >= 0) ? (double *)(dv + o_llr) : nullptr;
             uint8_t *p_cv = (conv || osd >= 0) ? (uint8_t *)(dv + o_cv) : nullptr;
             int32_t *p_it = iters ? (int32_t *)(dv + o_it) : nullptr;
-            if (batch == 1 && osd < 0 && h->msg_dtype == LDPC_HIP_MSG_F64 && !h->mem_on && !h->on("TIME_SMALL_CALLS")) {  // ONE syndrome: the resident workgroup, where one applies
+            if (batch == 1 && osd < 0 && h->msg_dtype == LDPC_HIP_MSG_F64 && !h->mem_on && !h->relay_on && !h->on("TIME_SMALL_CALLS")) {  // ONE syndrome: the resident workgroup, where one applies
                 bool took = false;
                 if ((rc = decode_onchip_resident(h, llr != nullptr, &took))) return rc;
                 if (took) {
@@ -585,6 +587,7 @@ int ldpc_hip_bp_decode_b8(ldpc_hip_bp *h, const uint8_t *dets_b8, int64_t batch,
     if (obs_b8 && h->obs_k < 0) return fail(LDPC_HIP_ERR_INVALID, "obs_b8 requested but ldpc_hip_bp_set_observables was never called");
     { const int refused = f32_refusal(h, nullptr); if (refused) return refused; }
     { const int refused = mem_refusal(h, nullptr); if (refused) return refused; }
+    { const int refused = relay_osd_refusal(h, with_osd != 0); if (refused) return refused; }
     HIPCHK(hipSetDevice(h->device));
     const size_t B = (size_t)batch, m = (size_t)h->m, n = (size_t)h->n;
     const size_t mb = (m + 7) / 8, nb = (n + 7) / 8, kb = obs_b8 ? ((size_t)h->obs_k + 7) / 8 : 0;

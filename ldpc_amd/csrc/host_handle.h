@@ -1,5 +1,5 @@
 // host_handle.h -- the handle (struct ldpc_hip_bp), error reporting, device buffers, measurement switches
-// Part of libldpc_hip.so: included by every translation unit (bp_hip.hip = the C ABI; tu_stream / tu_serial / tu_onchip / tu_onchip_f32 / tu_onchip_rp / tu_onchip_mem / tu_osd / tu_f32.hip = one kernel
+// Part of libldpc_hip.so: included by every translation unit (bp_hip.hip = the C ABI; tu_stream / tu_serial / tu_onchip / tu_onchip_f32 / tu_onchip_rp / tu_onchip_mem / tu_onchip_relay / tu_osd / tu_f32.hip = one kernel
 // family each with its host side).  What one unit calls in another is declared at the end of this header.
 #pragma once
 
@@ -332,6 +332,19 @@ struct ldpc_hip_bp {
     int mem_bad_col = -1;           // first column with gamma != 0 whose prior is not finite, for the priors the handle holds NOW (-1: none)
     DeviceBuf mem_ag;               // [2][n]: a[] = (1 - gamma) * log((1 - p) / p) (mem_host.h), then gamma[]; rewritten by upload_memory
     DeviceBuf e_mem;                // [2][R * 64]: a and gamma of every slot of the lane = edge tables (edge_mem_table_kernel, before every launch)
+    // Relay-BP (ldpc_hip_bp_set_relay): relay_legs memory legs chained per syndrome -- leg l runs up to relay_iters[l] iterations
+    // with the strengths relay_gamma[l][.] and starts from the posteriors the leg before it ended with; the lightest of the first relay_stop
+    // solutions is the result.  decode_device looks at relay_on and sends the batch to decode_relay (host_stream.h): the lane = edge relay kernels
+    // (bp_edge_relay_kernel.h), or a loop of per-pass memory decodes with relay_select_kernel after each.  Relay and memory exclude each other.
+    bool relay_on = false;
+    int32_t relay_legs = 0, relay_stop = 0;
+    std::vector<double> relay_gamma;    // [legs][n] the strengths as given
+    std::vector<int32_t> relay_iters;   // [legs]
+    int relay_bad_col = -1;             // as mem_bad_col, over all legs
+    DeviceBuf relay_ag;                 // [legs][2][n]: a[] then gamma[] of every leg (mem_host.h: mem_form_a); rewritten by upload_relay
+    DeviceBuf relay_it;                 // [legs] int32: relay_iters on the device
+    DeviceBuf e_relay;                  // [legs][2][R * 64]: a and gamma of every slot, per leg (edge_relay_table_kernel, before every launch)
+    DeviceBuf relay_dec, relay_llr, relay_li, relay_cv, relay_state;  // the leg loop: a leg's outputs [batch][n] / [batch]; {best weight f64, solutions i32, iterations i32} per row
 };
 
 // h->counter: work_pool_bytes() of work counters for the on-chip BP kernels, then OSD_COUNTER_BYTES for BP + OSD -- {listed, next} of the first
@@ -364,9 +377,46 @@ static int upload_memory(ldpc_hip_bp *h) {
     return LDPC_HIP_OK;
 }
 
+// Relay-BP: a[] and gamma[] of every leg, and the legs' iteration limits -> relay_ag, relay_it (the stream is idle, as for upload_memory).
+static int upload_relay(ldpc_hip_bp *h) {
+    const size_t n = (size_t)h->n, legs = (size_t)h->relay_legs, n1 = n ? n : 1;
+    std::vector<double> ag(legs * 2 * n1, 0.0);
+    h->relay_bad_col = -1;
+    for (size_t l = 0; l < legs; ++l) {
+        const double *g = h->relay_gamma.data() + l * n;
+        const int bad = mem_form_a(h->channel_probs.data(), g, h->n, ag.data() + l * 2 * n);
+        if (bad >= 0 && (h->relay_bad_col < 0 || bad < h->relay_bad_col)) h->relay_bad_col = bad;
+        std::copy(g, g + n, ag.begin() + (std::ptrdiff_t)(l * 2 * n + n));
+    }
+    int rc;
+    if ((rc = h->relay_ag.ensure(sizeof(double) * ag.size())) || (rc = h->relay_it.ensure(sizeof(int32_t) * legs))) return rc;
+    HIPCHK(hipMemcpy(h->relay_ag.p, ag.data(), sizeof(double) * ag.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->relay_it.p, h->relay_iters.data(), sizeof(int32_t) * legs, hipMemcpyHostToDevice));
+    return LDPC_HIP_OK;
+}
+
+// What the handle is set up for that Relay-BP cannot do: the memory decode's list (`what` as there).  OSD of a higher order than OSD-0 is
+// refused by the BP + OSD entry points themselves.
+static int relay_refusal(const ldpc_hip_bp *h, const char *what) {
+    if (!h->relay_on) return LDPC_HIP_OK;
+    if (what) return fail(LDPC_HIP_ERR_UNSUPPORTED, "Relay-BP: %s not available (switch the relay off: ldpc_hip_bp_set_relay(h, 0, NULL, NULL, 0))", what);
+    if (h->bp_method != LDPC_HIP_MINIMUM_SUM)
+        return fail(LDPC_HIP_ERR_UNSUPPORTED, "Relay-BP: product-sum is not available (the memory strengths are defined for minimum-sum only)");
+    if (h->schedule != 1 || h->random_serial)
+        return fail(LDPC_HIP_ERR_UNSUPPORTED, "Relay-BP: the serial schedules are not available (parallel schedule required)");
+    if (h->msg_dtype != LDPC_HIP_MSG_F64)
+        return fail(LDPC_HIP_ERR_UNSUPPORTED, "Relay-BP: float32 messages are not available (set the message dtype to float64)");
+    if (h->relay_bad_col >= 0)
+        return fail(LDPC_HIP_ERR_UNSUPPORTED, "Relay-BP: column %d has a nonzero memory strength and a channel probability of 0 or 1 -- "
+                    "it needs probabilities strictly between 0 and 1 (or strength 0 on that column in every leg)", h->relay_bad_col);
+    return LDPC_HIP_OK;
+}
+
 // What the handle is set up for that a memory decode cannot do; `what`: the call's own addition (row priors, soft syndromes, several GPUs) or
 // nullptr.  LDPC_HIP_OK when memory is off.  Called beside f32_refusal by every decode entry point, before anything is staged or launched.
+// (With Relay-BP on instead -- the two exclude each other -- it answers for the relay: relay_refusal.)
 static int mem_refusal(const ldpc_hip_bp *h, const char *what) {
+    if (h->relay_on) return relay_refusal(h, what);
     if (!h->mem_on) return LDPC_HIP_OK;
     if (what) return fail(LDPC_HIP_ERR_UNSUPPORTED, "memory min-sum: %s not available (switch the memory off: ldpc_hip_bp_set_memory(h, NULL))", what);
     if (h->bp_method != LDPC_HIP_MINIMUM_SUM)
@@ -381,9 +431,18 @@ static int mem_refusal(const ldpc_hip_bp *h, const char *what) {
     return LDPC_HIP_OK;
 }
 
+// Relay-BP with ordered-statistics post-processing: OSD-0 only (osd_order 0 takes the OSD-0 branch whatever the method).  `with_osd`: the call
+// runs the handle's osd_method / osd_order.
+static int relay_osd_refusal(const ldpc_hip_bp *h, bool with_osd) {
+    if (h->relay_on && with_osd && h->osd_method >= 2 && h->osd_order > 0)
+        return fail(LDPC_HIP_ERR_UNSUPPORTED, "Relay-BP: OSD-E and OSD-CS are not available (OSD-0 only: ldpc_hip_bp_set_osd(h, 1, 0), or switch the relay off)");
+    return LDPC_HIP_OK;
+}
+
 static int upload_priors(ldpc_hip_bp *h) {
     ++h->priors_version;
     if (h->mem_on) { const int rc = upload_memory(h); if (rc) return rc; }  // a[] follows the priors
+    if (h->relay_on) { const int rc = upload_relay(h); if (rc) return rc; }  // ... of every leg
     // bp.hpp:150-151, evaluated by the host libm so that priors are bit-identical to the reference's
     std::vector<double> llr0((size_t)h->n);
     for (int j = 0; j < h->n; ++j)
@@ -589,6 +648,9 @@ int decode_onchip_resident(ldpc_hip_bp *h, bool want_llr, bool *took);
 void resident_retire(ldpc_hip_bp *h);
 // tu_onchip.hip: the kernels that keep a syndrome's messages on chip; *took = false: no such kernel applies to this matrix
 int decode_onchip(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv, bool *took);
+// tu_onchip.hip: Relay-BP on the lane = edge relay kernels (bp_edge_relay_kernel.h, instantiated in tu_onchip_relay.hip), all legs in one launch, for the
+// codes plan_edge / plan_edge8 take unless the on-chip kernels are switched off; *took = false: decode_relay (host_stream.h) runs its leg loop
+int decode_onchip_relay(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv, bool *took);
 // tu_serial.hip: serial / serial_relative / random serial schedules, soft-syndrome decoding
 int decode_serial(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv);
 int soft_info_device(ldpc_hip_bp *h, const double *soft, int64_t batch, double cutoff, double sigma, uint8_t *decoding, double *llr,

@@ -770,6 +770,83 @@ static int decode_edge8_mem(ldpc_hip_bp *h, const Edge8Plan &p, const uint8_t *s
     return launch_edge_mem(h, edge8_mem_kernel(p.rounds, p.dc), p.rounds, edge8_mem_waves(p.rounds, p.dc), batch, ma);
 }
 
+// ---- the same two families as Relay-BP (bp_edge_relay_kernel.h; instantiated in tu_onchip_relay.hip): ldpc_hip_bp_set_relay on the codes of plan_edge / plan_edge8 ----
+// Everything is launch_edge_mem's -- the shared slot tables, e_prior, the work pools, the grid sizing (by the wavefronts per SIMD the instantiation
+// was compiled for), the clock probe, the timing events -- except that the slot tables of a and gamma are per leg: relay_ag [legs][2][n]
+// (upload_relay) -> e_relay [legs][2][R * 64], before every launch.
+__global__ void edge_relay_table_kernel(const double *ag, int n, int legs, const int32_t *scol, const uint8_t *kind, int slots, double *out) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= slots) return;
+    const bool real = kind[s] != 0;
+    const int j = real ? scol[s] : 0;
+    for (int l = 0; l < legs; ++l) {
+        out[(size_t)l * 2 * slots + s] = real ? ag[(size_t)l * 2 * n + j] : __builtin_inf();    // phantom lanes: prior +inf for good ...
+        out[(size_t)l * 2 * slots + slots + s] = real ? ag[(size_t)l * 2 * n + n + j] : 0.0;    // ... by strength 0
+    }
+}
+
+template <class ARGS>
+static int launch_edge_relay(ldpc_hip_bp *h, void (*kern)(const ARGS), int rounds, int waves_per_simd, int64_t batch, ARGS &ma) {
+    if (!kern) return fail(LDPC_HIP_ERR_UNSUPPORTED, "Relay-BP: no lane = edge kernel was built for %d rounds", rounds);
+    int rc;
+    const int slots = rounds * 64;
+    if ((rc = h->e_relay.ensure(sizeof(double) * 2 * (size_t)slots * (size_t)h->relay_legs))) return rc;
+    const dim3 gt((unsigned)((slots + 255) / 256));
+    LDPC_LAUNCH(edge_prior_kernel, gt, dim3(256), 0, h->stream, h->d_llr0, (const int32_t *)h->e_scol.p, (const uint8_t *)h->e_kind.p, slots, (double *)h->e_prior.p);
+    LDPC_LAUNCH(edge_relay_table_kernel, gt, dim3(256), 0, h->stream, (const double *)h->relay_ag.p, h->n, h->relay_legs, (const int32_t *)h->e_scol.p,
+                (const uint8_t *)h->e_kind.p, slots, (double *)h->e_relay.p);
+    HIPCHK(hipGetLastError());
+    ma.ag_s = (const double *)h->e_relay.p;
+    ma.leg_iters = (const int32_t *)h->relay_it.p;
+    ma.llr0 = h->d_llr0;
+    ma.legs = h->relay_legs; ma.stop_after = h->relay_stop;
+    auto &a = ma.e;
+    a.m = h->m; a.n = h->n; a.max_iter = h->max_iter;  // (not read: leg_iters takes its place)
+    a.ms_scaling_factor = h->ms_scaling_factor;
+    a.batch = batch;
+    a.prior_s = (const double *)h->e_prior.p;
+    a.kind = (const uint8_t *)h->e_kind.p; a.scol = (const int32_t *)h->e_scol.p;
+    const size_t dyn = edge_lds_bytes(rounds);
+    int64_t per_cu = (int64_t)((160u * 1024u) / (dyn + 64));
+    if (per_cu > 4 * waves_per_simd) per_cu = 4 * waves_per_simd;  // (edge_relay_waves / edge8_relay_waves: what the instantiation was compiled for)
+    const int64_t groups = batch < 256 * per_cu ? batch : 256 * per_cu;
+    if ((rc = edge_work_split(h, rounds, batch, groups, a))) return rc;
+    h->accumulated_ms = 0.f;
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    LDPC_LAUNCH(kern, dim3((unsigned)groups), dim3(64), (unsigned)dyn, h->stream, ma);
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    h->timed = true;
+    HIPCHK(hipGetLastError());
+    return LDPC_HIP_OK;
+}
+
+// Relay-BP on the lane = edge relay kernels: a code plan_edge or plan_edge8 takes, unless the on-chip kernels are switched off (mode 0) -- the
+// predicate of the memory decode in decode_onchip.  *took = false: the per-pass leg loop (host_stream.h: decode_relay).
+int decode_onchip_relay(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv, bool *took) {
+    *took = false;
+    if (!(h->small_mode != 0 && h->m > 0 && h->n > 0 && h->nnz > 0 && (int64_t)h->nnz * 16 < (1 << 22) && batch < (1ll << 30))) return LDPC_HIP_OK;
+    int rc;
+    const EdgePlan ep = plan_edge(h);
+    if (ep.rounds) {
+        *took = true;
+        if ((rc = ensure_edge_tables(h, ep))) return rc;
+        EdgeRelayArgs ma = {};
+        ma.e.partner = (const uint16_t *)h->e_partner.p;
+        ma.e.synd = synd; ma.e.decoding = decoding; ma.e.llr = llr; ma.e.iters = iters; ma.e.conv = conv;
+        return launch_edge_relay(h, edge_relay_kernel(ep.rounds), ep.rounds, edge_relay_waves(ep.rounds), batch, ma);
+    }
+    const Edge8Plan e8 = plan_edge8(h);
+    if (e8.rounds) {
+        *took = true;
+        if ((rc = ensure_edge8_tables(h, e8))) return rc;
+        Edge8RelayArgs ma = {};
+        ma.e.cpos = (const uint16_t *)h->e_partner.p;
+        ma.e.synd = synd; ma.e.decoding = decoding; ma.e.llr = llr; ma.e.iters = iters; ma.e.conv = conv;
+        return launch_edge_relay(h, edge8_relay_kernel(e8.rounds, e8.dc), e8.rounds, edge8_relay_waves(e8.rounds, e8.dc), batch, ma);
+    }
+    return LDPC_HIP_OK;
+}
+
 // The float32 message mode's on-chip planner, called by decode_f32 (host_f32.h) after its refusals: decode_onchip's predicate for the lane =
 // edge families and their two plans, unchanged.  *took = false: neither takes the code -- decode_f32 goes on with its per-pass kernels (in
 // float32 nothing ever goes to bp_wave_kernel, bp_small_kernel or any FP64 kernel).

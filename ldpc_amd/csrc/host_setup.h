@@ -324,6 +324,8 @@ int ldpc_hip_bp_set_memory(ldpc_hip_bp *h, const double *gamma) {
         h->e_mem.release();
         return LDPC_HIP_OK;
     }
+    if (h->relay_on)
+        return fail(LDPC_HIP_ERR_UNSUPPORTED, "memory min-sum and Relay-BP exclude each other: switch the relay off first (ldpc_hip_bp_set_relay(h, 0, NULL, NULL, 0))");
     const int bad = mem_gamma_first_invalid(gamma, h->n);
     if (bad >= 0) return fail(LDPC_HIP_ERR_INVALID, "memory strength %d is %g: every strength must be finite and in [-1, 1)", bad, gamma[bad]);
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -336,6 +338,50 @@ int ldpc_hip_bp_get_memory(const ldpc_hip_bp *h, double *out) {
     if (!h) return fail(LDPC_HIP_ERR_INVALID, "null handle");
     if (!h->mem_on) return 0;
     if (out) std::copy(h->mem_gamma.begin(), h->mem_gamma.end(), out);
+    return 1;
+}
+
+int ldpc_hip_bp_set_relay(ldpc_hip_bp *h, int32_t legs, const double *gamma, const int32_t *leg_iters, int32_t stop_after) {
+    if (!h) return fail(LDPC_HIP_ERR_INVALID, "null handle");
+    HIPCHK(hipSetDevice(h->device));
+    if (legs == 0 || !gamma) {  // off: the plain decode and its kernels again
+        HIPCHK(hipStreamSynchronize(h->stream));  // (a relay decode still queued reads the tables)
+        h->relay_on = false;
+        h->relay_legs = h->relay_stop = 0;
+        h->relay_gamma.clear();
+        h->relay_iters.clear();
+        h->relay_bad_col = -1;
+        for (DeviceBuf *b : {&h->relay_ag, &h->relay_it, &h->e_relay, &h->relay_dec, &h->relay_llr, &h->relay_li, &h->relay_cv, &h->relay_state}) b->release();
+        return LDPC_HIP_OK;
+    }
+    if (h->mem_on)
+        return fail(LDPC_HIP_ERR_UNSUPPORTED, "Relay-BP and memory min-sum exclude each other: switch the memory off first (ldpc_hip_bp_set_memory(h, NULL))");
+    if (legs < 0 || legs > (1 << 20)) return fail(LDPC_HIP_ERR_INVALID, "Relay-BP: %d legs", (int)legs);
+    if (!leg_iters) return fail(LDPC_HIP_ERR_INVALID, "Relay-BP: leg_iters must not be NULL");
+    if (stop_after < 1) return fail(LDPC_HIP_ERR_INVALID, "Relay-BP: stop_after is %d: it must be at least 1", (int)stop_after);
+    for (int32_t l = 0; l < legs; ++l) {
+        if (leg_iters[l] < 1) return fail(LDPC_HIP_ERR_INVALID, "Relay-BP: leg %d has %d iterations: every leg needs at least 1", (int)l, (int)leg_iters[l]);
+        const int bad = mem_gamma_first_invalid(gamma + (size_t)l * (size_t)h->n, h->n);
+        if (bad >= 0)
+            return fail(LDPC_HIP_ERR_INVALID, "Relay-BP: memory strength %d of leg %d is %g: every strength must be finite and in [-1, 1)", bad, (int)l,
+                        gamma[(size_t)l * (size_t)h->n + (size_t)bad]);
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->relay_gamma.assign(gamma, gamma + (size_t)legs * (size_t)h->n);
+    h->relay_iters.assign(leg_iters, leg_iters + legs);
+    h->relay_legs = legs;
+    h->relay_stop = stop_after;
+    h->relay_on = true;
+    return upload_relay(h);
+}
+
+int ldpc_hip_bp_get_relay(const ldpc_hip_bp *h, int32_t *legs, int32_t *stop_after, double *gamma_out, int32_t *leg_iters_out) {
+    if (!h) return fail(LDPC_HIP_ERR_INVALID, "null handle");
+    if (legs) *legs = h->relay_on ? h->relay_legs : 0;
+    if (stop_after) *stop_after = h->relay_on ? h->relay_stop : 0;
+    if (!h->relay_on) return 0;
+    if (gamma_out) std::copy(h->relay_gamma.begin(), h->relay_gamma.end(), gamma_out);
+    if (leg_iters_out) std::copy(h->relay_iters.begin(), h->relay_iters.end(), leg_iters_out);
     return 1;
 }
 

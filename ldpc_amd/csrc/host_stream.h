@@ -76,6 +76,8 @@ struct StreamPass {
     const unsigned *rows_dev = nullptr;   // ... {rows, tiles} on the device (BpArgs::rows_dev)
     int64_t grid_tiles = 0;               // ... grid.y of its tile-looping kernels (an estimate; they loop)
     int64_t late_rows = -1;               // ... rows the steering histogram expects to be still running 8 iterations into it (-1: unknown)
+    const double *relay_ag = nullptr;     // a leg of Relay-BP (decode_relay): a[] and gamma[] of the leg, [2][n] -- a memory decode with them, to max_iter
+    const double *relay_seed = nullptr;   // ... after the first: the previous leg's posteriors [batch][n], what M and the initial messages start from
     bool continues() const { return A != nullptr; }
 };
 
@@ -103,7 +105,7 @@ struct StreamPlan {
 static int plan_stream(const ldpc_hip_bp *h, int64_t tiles_total, bool want_llr, const StreamPass &pass, StreamPlan &p) {
     p.max_iter = pass.max_iter < 0 ? h->max_iter : pass.max_iter;
     p.rp = h->row_probs != nullptr;
-    p.mem = h->mem_on;
+    p.mem = h->mem_on || pass.relay_ag != nullptr;
     p.per_tile_msg = sizeof(double) * (size_t)(h->nnz ? h->nnz : 1) * LDPC_WAVE;
     p.per_tile_llr = want_llr ? sizeof(double) * (size_t)(h->n ? h->n : 1) * LDPC_WAVE : 0;
     int rc;
@@ -213,7 +215,9 @@ static int stream_start_per_pass(ldpc_hip_bp *h, const StreamPlan &p, int64_t ti
     sa.nodes = h->sw("SPREAD_NODES") > 0 ? h->sw("SPREAD_NODES") : tiles <= 8 ? 1 : tiles < 512 ? 4 : 16;
     LDPC_LAUNCH(bp_spread_state_init_kernel, dim3((r.grid_tiles + 255) / 256), dim3(256), 0, h->stream, sa);
     const dim3 gi((unsigned)(h->nnz ? (h->nnz + 63) / 64 : 1), r.grid_tiles);  // (a grid dimension must not be 0: empty matrices)
-    if (p.mem)
+    if (p.mem && sa.relay_seed)
+        LDPC_LAUNCH(bp_spread_relay_init_kernel, gi, dim3(256), 0, h->stream, sa);
+    else if (p.mem)
         LDPC_LAUNCH(bp_spread_mem_init_kernel, gi, dim3(256), 0, h->stream, sa);
     else if (p.rp)
         with_method_math(h, [&](auto M, auto F) { LDPC_LAUNCH((bp_spread_init_kernel<M, F, true>), gi, dim3(256), 0, h->stream, sa); });
@@ -353,7 +357,8 @@ static int decode_streamed(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, u
         }
         if (p.mem) {  // M of this chunk's tiles (filled by bp_spread_mem_init_kernel), a[] and gamma[]
             sa.llr0_t = (const double *)h->rowp_llr.p;
-            sa.mem_ag = (const double *)h->mem_ag.p;
+            sa.mem_ag = pass.relay_ag ? pass.relay_ag : (const double *)h->mem_ag.p;
+            sa.relay_seed = pass.relay_seed ? pass.relay_seed + (size_t)c.b0 * (size_t)h->n : nullptr;
         }
         SpreadRounds r;
         const bool per_pass = p.rp || p.mem || (p.handoff > 0 && c.tiles <= p.handoff && p.max_iter - pass.it_start > 1 && !pass.rows_dev);
@@ -432,6 +437,46 @@ static int decode_stream_repacked(ldpc_hip_bp *h, const uint8_t *synd, int64_t b
     return stream_leave_histogram(h, iters, conv, batch);
 }
 
+// Relay-BP (ldpc_hip_bp_set_relay).  A code the lane = edge families take runs all its legs in one launch of their relay
+// forms (decode_onchip_relay).  Every other code, and every code with the on-chip kernels switched off, runs the leg loop below: leg l is a per-pass
+// memory decode of the whole batch to relay_iters[l] iterations with the leg's a[] / gamma[] -- from the second leg on started from the
+// posteriors the leg before it left (relay_llr, read by bp_spread_relay_init_kernel before the chunk's outputs overwrite its rows: a converged
+// row's posteriors are frozen at its convergence iteration, so a leg's llr output IS the row's M at the leg's end) -- followed by
+// relay_select_kernel, which keeps the lightest solution in the caller's arrays, adds up the iterations and counts the solutions.  A row that has
+// its relay_stop solutions is still decoded in the later legs and the result ignored: nothing is read back, the call stays asynchronous.
+// Correct everywhere, not fast: legs x iterations x four launches over every tile.
+static int decode_relay(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv) {
+    int rc;
+    {
+        bool took = false;
+        rc = decode_onchip_relay(h, synd, batch, decoding, llr, iters, conv, &took);
+        if (took || rc) return rc;
+    }
+    const size_t B = (size_t)batch, n1 = (size_t)(h->n ? h->n : 1);
+    if ((rc = h->relay_dec.ensure(B * n1)) || (rc = h->relay_llr.ensure(sizeof(double) * B * n1)) || (rc = h->relay_li.ensure(sizeof(int32_t) * B)) ||
+        (rc = h->relay_cv.ensure(B)) || (rc = h->relay_state.ensure(16 * B))) return rc;
+    RelaySelectArgs ra = {};
+    ra.batch = batch; ra.n = h->n; ra.stop_after = h->relay_stop;
+    ra.llr0 = h->d_llr0;
+    ra.leg_dec = (const uint8_t *)h->relay_dec.p; ra.leg_llr = (const double *)h->relay_llr.p;
+    ra.leg_iters = (const int32_t *)h->relay_li.p; ra.leg_conv = (const uint8_t *)h->relay_cv.p;
+    ra.best_w = (double *)h->relay_state.p;
+    ra.nsol = (int32_t *)((char *)h->relay_state.p + 8 * B);
+    ra.total = ra.nsol + B;
+    ra.decoding = decoding; ra.llr = llr; ra.iters = iters; ra.conv = conv;
+    for (int l = 0; l < h->relay_legs; ++l) {
+        StreamPass leg;
+        leg.max_iter = h->relay_iters[(size_t)l];
+        leg.relay_ag = (const double *)h->relay_ag.p + (size_t)l * 2 * (size_t)h->n;
+        leg.relay_seed = l ? (const double *)h->relay_llr.p : nullptr;
+        if ((rc = decode_streamed(h, synd, batch, (uint8_t *)h->relay_dec.p, (double *)h->relay_llr.p, (int32_t *)h->relay_li.p, (uint8_t *)h->relay_cv.p, leg))) return rc;
+        ra.first = l == 0; ra.last = l == h->relay_legs - 1;
+        LDPC_LAUNCH(relay_select_kernel, dim3((unsigned)((batch + 3) / 4)), dim3(256), 0, h->stream, ra);
+        HIPCHK(hipGetLastError());
+    }
+    return LDPC_HIP_OK;
+}
+
 // The dispatch of a batch to a kernel family.
 int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv) {
     const int64_t tiles_total = (batch + LDPC_WAVE - 1) / LDPC_WAVE;
@@ -439,10 +484,11 @@ int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
     h->timed_prev = h->timed_prev_mid = false;  // (what a two-pass decode before this one left)
     // Row priors (ldpc_hip_*_decode_batch_priors): every row is decoded with its own channel probabilities, h->row_probs [batch][n].  Two kernel
     // families read them: the slot kernel (decode_onchip sends there whatever an on-chip kernel would take) and the per-pass kernels (StreamPlan::rp).
-    if (h->mem_on) {  // (the entry points have said so already, before staging anything: nothing wrong is ever decoded from here either)
+    if (h->mem_on || h->relay_on) {  // (the entry points have said so already, before staging anything: nothing wrong is ever decoded from here either)
         const int refused = mem_refusal(h, h->row_probs ? "per-row channel probabilities are" : nullptr);
         if (refused) return refused;
     }
+    if (h->relay_on) return decode_relay(h, synd, batch, decoding, llr, iters, conv);
     if (h->msg_dtype == LDPC_HIP_MSG_F32) return decode_f32(h, synd, batch, decoding, llr, iters, conv);  // (never an FP64 kernel: what the mode cannot do is refused there)
     const bool rp = h->row_probs != nullptr;
     if (rp && h->schedule != 1) return fail(LDPC_HIP_ERR_UNSUPPORTED, "per-row channel probabilities: the serial schedules read the handle's priors only (parallel schedule required)");

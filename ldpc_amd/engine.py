@@ -167,6 +167,41 @@ class HipBpEngine:
             _lib.check(rc)
         return out if rc == 1 else None
 
+    def set_relay(self, strengths, leg_iters=None, stop_after=1):
+        """Relay-BP (``ldpc_hip_bp_set_relay``): ``strengths`` = ``(legs, n)`` memory strengths, each finite and in ``[-1, 1)``, ``leg_iters`` =
+        one iteration limit >= 1 per leg (they take the place of ``max_iter``), ``stop_after`` >= 1 solutions end a row -- or ``strengths=None``:
+        off.  Every leg after the first starts from the posteriors the leg before it ended with; the lightest solution is the result.
+        Minimum-sum, parallel schedule, float64 messages; it excludes ``set_memory``; what it cannot do is refused when decoding."""
+        if strengths is None:
+            _lib.check(self._lib.ldpc_hip_bp_set_relay(self._h, 0, None, None, 0))
+            return
+        g = np.ascontiguousarray(strengths, np.float64)
+        if g.ndim != 2 or g.shape[1] != self.n or g.shape[0] < 1:
+            raise ValueError(f"relay strengths must have shape (legs, {self.n}), not {g.shape}.")
+        if leg_iters is None:
+            raise ValueError("leg_iters: one iteration limit per leg is required.")
+        li = np.ascontiguousarray(leg_iters, np.int32)
+        if li.shape != (g.shape[0],):
+            raise ValueError(f"leg_iters must have shape ({g.shape[0]},), not {li.shape}.")
+        rc = self._lib.ldpc_hip_bp_set_relay(self._h, int(g.shape[0]), g.ctypes.data_as(C.c_void_p), li.ctypes.data_as(C.c_void_p), int(stop_after))
+        if rc == -1:  # LDPC_HIP_ERR_INVALID: a strength outside [-1, 1) or not finite, a leg without iterations, stop_after < 1
+            raise ValueError(self._lib.ldpc_hip_last_error().decode("utf-8", "replace"))
+        _lib.check(rc)
+
+    @property
+    def relay(self):
+        """``None`` when the relay is off, else ``(strengths (legs, n) float64, leg_iters (legs,) int32, stop_after)``."""
+        legs, stop = C.c_int32(0), C.c_int32(0)
+        rc = int(self._lib.ldpc_hip_bp_get_relay(self._h, C.byref(legs), C.byref(stop), None, None))
+        if rc < 0:
+            _lib.check(rc)
+        if rc != 1:
+            return None
+        g = np.empty((legs.value, self.n), np.float64)
+        li = np.empty(legs.value, np.int32)
+        _lib.check(min(0, int(self._lib.ldpc_hip_bp_get_relay(self._h, None, None, g.ctypes.data_as(C.c_void_p), li.ctypes.data_as(C.c_void_p)))))
+        return g, li, int(stop.value)
+
     def set_ring(self, depth):
         """LDS-DMA ring for regular-degree matrices: False/0 = off, True/1 = default depth, 2 or 3 = slots per wave."""
         _lib.check(self._lib.ldpc_hip_bp_set_ring(self._h, int(depth)))

@@ -53,14 +53,17 @@ class MonteCarloDemSimulation:
     ``[1e-9, 1 - 1e-9]``, so a mechanism at p = 0 or p = 1 keeps a finite log-ratio.  ``message_dtype="float32"`` decodes with FP32
     messages (minimum-sum only: ``bp_method="ps"`` is then refused at ``run()``, as everywhere in the library).  ``memory_strength``
     (``None``, a float, or one strength per mechanism in ``[-1, 1)``): memory min-sum BP, as ``BpDecoder.memory_strength``; minimum-sum with
-    float64 messages only, and not together with a ``window_decoder``.
+    float64 messages only, and not together with a ``window_decoder``.  ``relay`` (a dict of ``ldpc_amd.relay_decoder.relay_schedule``
+    keywords -- ``gamma0``, ``pre_iter``, ``num_sets``, ``set_max_iter``, ``gamma_dist_interval``, ``stop_nconv``, ``strengths``, ``seed``):
+    Relay-BP, whose legs take the place of ``max_iter``; with ``osd_method`` OSD_0 only, and not together with ``memory_strength`` or a
+    ``window_decoder``.
 
     One GPU (``device``; -1: the current one).  For several, run one simulation per device over disjoint shot ranges.
     """
 
     def __init__(self, model, *, target_run_count, batch_size: int = 65536, seed: int = 0, max_iter: int = 0, bp_method="ms",
                  ms_scaling_factor: float = 0.625, osd_method="osd0", osd_order: int = 0, message_dtype="float64", window_decoder=None,
-                 device: int = -1, memory_strength=None) -> None:
+                 device: int = -1, memory_strength=None, relay=None) -> None:
         from ldpc_amd.bp_decoder._bp_decoder import _bp_method_code
         from ldpc_amd.noise_models.dem import check_dem_probabilities
         from ldpc_amd.sinter_decoders.sinter_bposd_decoder import _osd_code
@@ -113,6 +116,19 @@ class MonteCarloDemSimulation:
                 raise ValueError(f"Invalid memory_strength provided. It must be None, a float or {n} floats, each finite and in [-1, 1).")
             memory_strength = g
         self.memory_strength = memory_strength
+        # Relay-BP (RelayBpDecoder's keywords): (strengths (legs, n), leg_iters (legs,), stop_after) or None
+        if relay is not None:
+            if memory_strength is not None:
+                raise NotImplementedError("relay with memory_strength: the relay's legs carry their own strengths; leave memory_strength at None.")
+            if window_decoder is not None:
+                raise NotImplementedError("relay with a window_decoder: the windows decode with their own decoders; leave relay at None.")
+            if self._osd_code in (2, 3) and self.osd_order > 0:
+                raise NotImplementedError("relay with osd_method OSD_E / OSD_CS: Relay-BP is followed by OSD_0 only.")
+            if not isinstance(relay, dict):
+                raise ValueError("Invalid relay provided. It must be None or a dict of relay_schedule keywords.")
+            from ldpc_amd.relay_decoder import relay_schedule
+            relay = relay_schedule(self.check_matrix.shape[1], **relay)
+        self.relay = relay
         if not isinstance(device, int) or isinstance(device, bool):
             raise ValueError("Invalid device provided.")
         self.device = device
@@ -139,6 +155,8 @@ class MonteCarloDemSimulation:
             eng.set_osd(self._osd_code, 0 if self._osd_code == 1 else self.osd_order)
             eng.set_message_dtype(self.message_dtype)
             eng.set_memory(self.memory_strength)  # (what memory min-sum cannot do -- product-sum, float32 -- is refused at run(), by the library)
+            if self.relay is not None:
+                eng.set_relay(*self.relay)  # (likewise)
             eng.set_observables(self.observables_matrix)
             eng.set_sampler(self.priors)
             self._engine = eng
