@@ -518,9 +518,10 @@ int ldpc_hip_bp_get_memory(const ldpc_hip_bp *h, double *out);
  * (relay_common.h: relay_weight).  The row stops after stop_after solutions.  Outputs: the lightest solution -- the first among equal weights --
  * with the posteriors of its leg, converge = 1; a row without any solution gets the last leg's last decisions and posteriors, converge = 0;
  * iterations = the sum over the legs the row ran.  A syndrome byte > 1 never converges.  The results are those of the NumPy restatement
- * tests/relay_bp_util.py, bit for bit, on both routes: the lane = edge relay kernels (all legs in one launch, nothing leaves the chip between
- * legs) for the codes those kernels take, and otherwise a loop of per-pass memory decodes with a selection kernel after each leg (correct
- * everywhere, not fast); nothing is read back between legs, so the *_async entry points stay asynchronous.
+ * tests/relay_bp_util.py, bit for bit, on every route (ldpc_hip_bp_relay_route names the one a handle takes): the lane = edge relay kernels (all
+ * legs in one launch, nothing leaves the chip between legs) for the codes those kernels take, the lane = node kernel bp_wave_relay_kernel (the
+ * same, messages and memory in LDS) where the small-code kernel mode asks for it, and otherwise a loop of per-pass memory decodes with a selection
+ * kernel after each leg (correct everywhere, not fast); nothing is read back between legs, so the *_async entry points stay asynchronous.
  *   ldpc_hip_bp_set_relay(h, legs, gamma, leg_iters, stop_after): gamma = host pointer to [legs * n], each finite and in [-1, 1); leg_iters =
  *       host pointer to [legs], each >= 1; stop_after >= 1 (else LDPC_HIP_ERR_INVALID).  legs = 0 or gamma = NULL: off.  Relay and
  *       ldpc_hip_bp_set_memory exclude each other: setting one while the other is on is LDPC_HIP_ERR_UNSUPPORTED.  ldpc_hip_bp_set_channel
@@ -534,6 +535,14 @@ int ldpc_hip_bp_get_memory(const ldpc_hip_bp *h, double *out);
  */
 int ldpc_hip_bp_set_relay(ldpc_hip_bp *h, int32_t legs, const double *gamma, const int32_t *leg_iters, int32_t stop_after);
 int ldpc_hip_bp_get_relay(const ldpc_hip_bp *h, int32_t *legs, int32_t *stop_after, double *gamma_out, int32_t *leg_iters_out);
+
+/* Which kernel route a Relay-BP or memory min-sum decode of `batch` syndromes takes on this handle as it is set now (code, small-code kernel mode):
+ *   0  the per-pass kernels (Relay-BP: the leg loop -- legs x iterations x four launches over every tile; correct everywhere, not fast)
+ *   1  bp_edge: lane = edge, rows <= 4, columns <= 2         2  bp_edge8: lane = edge, rows <= 8, columns <= 4
+ *   3  bp_wave: lane = node, messages and memory in LDS, one wavefront per syndrome      4  bp_wave, a whole workgroup (team) per syndrome
+ * Routes 1 - 4 run all legs of a syndrome in one launch; the results are the same bits on every route.  Launches nothing.
+ * LDPC_HIP_ERR_INVALID: NULL argument, negative batch, or neither ldpc_hip_bp_set_relay nor ldpc_hip_bp_set_memory is on. */
+int ldpc_hip_bp_relay_route(const ldpc_hip_bp *h, int64_t batch, int32_t *route);
 
 /* The shader clock the BP kernels actually ran at (a measurement aid; no counterpart in the reference).  Every workgroup of the
  * long-running BP kernels (bp_decode_kernel, bp_wave_kernel, bp_wave_ps_kernel, bp_edge_kernel, bp_edge8_kernel) adds the shader cycles

@@ -470,6 +470,16 @@ class BpDecoderBase:
         from ldpc_amd.relay_decoder import relay_schedule
         self._relay = relay_schedule(self.n, **value)
 
+    @property
+    def relay_route(self) -> str:
+        """The kernel route the relay (or ``memory_strength``) decode takes on this decoder as it is set now, for the batch size last decoded
+        through NumPy arrays (1 before any): ``HipBpEngine.relay_route`` -- ``"per_pass"`` is 10 - 60x slower than the other four.
+        ``ValueError`` when neither ``relay`` nor ``memory_strength`` is set."""
+        if self._relay is None and self._memory is None:
+            raise ValueError("relay_route: neither relay nor memory_strength is set.")
+        self._require_memory()
+        return self._get_engine().relay_route(getattr(self, "_relay_batch", 1))
+
     def _require_relay(self, what=None):
         if self._relay is None:
             return
@@ -596,6 +606,8 @@ class BpDecoderBase:
         C-contiguous array to receive the log-ratios instead of a new one.  ``channel_probs``: checked (B, n) row priors or None."""
         # (the schedule setters and the memory strengths live on the ctypes engine)
         cy = self._get_cy() if self._schedule == PARALLEL and self._memory is None and self._relay is None else None
+        if cy is None:
+            self._relay_batch = max(1, len(synd2d))  # (relay_route)
         if cy is not None and channel_probs is not None:
             return cy.decode_batch(np.ascontiguousarray(synd2d, np.uint8), want_llr, osd0, llr_out, channel_probs)
         if cy is not None:

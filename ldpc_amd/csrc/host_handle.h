@@ -1,5 +1,5 @@
 // host_handle.h -- the handle (struct ldpc_hip_bp), error reporting, device buffers, measurement switches
-// Part of libldpc_hip.so: included by every translation unit (bp_hip.hip = the C ABI; tu_stream / tu_serial / tu_onchip / tu_onchip_f32 / tu_onchip_rp / tu_onchip_mem / tu_onchip_relay / tu_osd / tu_f32.hip = one kernel
+// Part of libldpc_hip.so: included by every translation unit (bp_hip.hip = the C ABI; tu_stream / tu_serial / tu_onchip / tu_onchip_f32 / tu_onchip_rp / tu_onchip_mem / tu_onchip_relay / tu_onchip_wave_relay / tu_osd / tu_f32.hip = one kernel
 // family each with its host side).  What one unit calls in another is declared at the end of this header.
 #pragma once
 
@@ -335,7 +335,7 @@ struct ldpc_hip_bp {
     // Relay-BP (ldpc_hip_bp_set_relay): relay_legs memory legs chained per syndrome -- leg l runs up to relay_iters[l] iterations
     // with the strengths relay_gamma[l][.] and starts from the posteriors the leg before it ended with; the lightest of the first relay_stop
     // solutions is the result.  decode_device looks at relay_on and sends the batch to decode_relay (host_stream.h): the lane = edge relay kernels
-    // (bp_edge_relay_kernel.h), or a loop of per-pass memory decodes with relay_select_kernel after each.  Relay and memory exclude each other.
+    // (bp_edge_relay_kernel.h), the lane = node kernel (bp_wave_relay_kernel.h), or a loop of per-pass memory decodes with relay_select_kernel after each.  Relay and memory exclude each other.
     bool relay_on = false;
     int32_t relay_legs = 0, relay_stop = 0;
     std::vector<double> relay_gamma;    // [legs][n] the strengths as given
@@ -344,6 +344,7 @@ struct ldpc_hip_bp {
     DeviceBuf relay_ag;                 // [legs][2][n]: a[] then gamma[] of every leg (mem_host.h: mem_form_a); rewritten by upload_relay
     DeviceBuf relay_it;                 // [legs] int32: relay_iters on the device
     DeviceBuf e_relay;                  // [legs][2][R * 64]: a and gamma of every slot, per leg (edge_relay_table_kernel, before every launch)
+    DeviceBuf w_relay;                  // bp_wave_relay_kernel: [np + 2] the padded priors, then [legs][2][np] a and gamma of every column padded to np, per leg -- the relay's, or the memory's as one leg (before every launch)
     DeviceBuf relay_dec, relay_llr, relay_li, relay_cv, relay_state;  // the leg loop: a leg's outputs [batch][n] / [batch]; {best weight f64, solutions i32, iterations i32} per row
 };
 
@@ -648,8 +649,9 @@ int decode_onchip_resident(ldpc_hip_bp *h, bool want_llr, bool *took);
 void resident_retire(ldpc_hip_bp *h);
 // tu_onchip.hip: the kernels that keep a syndrome's messages on chip; *took = false: no such kernel applies to this matrix
 int decode_onchip(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv, bool *took);
-// tu_onchip.hip: Relay-BP on the lane = edge relay kernels (bp_edge_relay_kernel.h, instantiated in tu_onchip_relay.hip), all legs in one launch, for the
-// codes plan_edge / plan_edge8 take unless the on-chip kernels are switched off; *took = false: decode_relay (host_stream.h) runs its leg loop
+// tu_onchip.hip: Relay-BP on chip, all legs in one launch -- the lane = edge relay kernels (bp_edge_relay_kernel.h, tu_onchip_relay.hip) for the codes
+// plan_edge / plan_edge8 take, the lane = node kernel (bp_wave_relay_kernel.h, tu_onchip_wave_relay.hip) for those plan_wave_relay takes, by the small-code
+// kernel mode (plan_relay_route); *took = false: decode_relay (host_stream.h) runs its leg loop
 int decode_onchip_relay(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv, bool *took);
 // tu_serial.hip: serial / serial_relative / random serial schedules, soft-syndrome decoding
 int decode_serial(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv);

@@ -1,4 +1,4 @@
-// host_onchip.h -- host side of the on-chip kernels: plans (LDS / occupancy), tables and launches of bp_small / bp_wave / bp_wave_ps / bp_edge
+// host_onchip.h -- host side of the on-chip kernels: plans (LDS / occupancy), tables and launches of bp_small / bp_wave / bp_wave_ps / bp_edge / bp_wave_relay
 // Part of libldpc_hip.so: included by bp_hip.hip (one translation unit), in the order given there.
 #pragma once
 
@@ -820,29 +820,169 @@ static int launch_edge_relay(ldpc_hip_bp *h, void (*kern)(const ARGS), int round
     return LDPC_HIP_OK;
 }
 
-// Relay-BP on the lane = edge relay kernels: a code plan_edge or plan_edge8 takes, unless the on-chip kernels are switched off (mode 0) -- the
-// predicate of the memory decode in decode_onchip.  *took = false: the per-pass leg loop (host_stream.h: decode_relay).
+// ---- Relay-BP and memory min-sum on the lane = node kernel (bp_wave_relay_kernel.h; instantiated in tu_onchip_wave_relay.hip): the codes beyond both lane = edge ladders ----
+// plan_wave with the posterior copy forced into LDS (it IS the memory), min-sum only, the priors always read from the padded device array: the
+// rungs of pick_wave, the same 16-bit table limits, the same padding rule, the same choice between one wavefront and a team per syndrome (modes 4
+// and 5 force either), capped by the wavefronts the instantiation was compiled for (wave_relay_waves).  waves == 0: not applicable.
+static WavePlan plan_wave_relay(const ldpc_hip_bp *h, bool forced, int64_t batch) {
+    WavePlan p;
+    if (h->bp_method != LDPC_HIP_MINIMUM_SUM || h->m <= 0 || h->n <= 0 || h->nnz <= 0 || h->max_row_deg > 16 || h->max_col_deg > 8) return p;
+    static const int rungs[6][2] = {{4, 2}, {4, 4}, {6, 3}, {8, 4}, {8, 8}, {16, 8}};  // pick_wave's
+    for (const auto &r : rungs)
+        if (!p.dr && h->max_row_deg <= r[0] && h->max_col_deg <= r[1]) { p.dr = r[0]; p.dc = r[1]; }
+    if (!p.dr) { p.dr = 16; p.dc = 8; }
+    p.mp = (h->m + 63) / 64 * 64;
+    p.np = (h->n + 63) / 64 * 64;
+    const size_t rm = (size_t)p.dr * p.mp;
+    if (rm + 2 >= 65536 || p.np + 1 >= 65536) return p;               // positions and column numbers are 16 bits
+    if (!forced && rm > 2 * (size_t)h->nnz + 1024) return p;          // a few heavy rows would pad every row
+    p.shared = wave_relay_lds_shared(p.mp, p.np, p.dr, p.dc);
+    p.per_wave = wave_relay_lds_private(p.mp, p.np, p.dr);
+    p.prior_global = true;
+    const size_t lds = 160u * 1024u - 64u;  // (the kernel's few bytes of static LDS come on top of the dynamic part)
+    if (p.shared + p.per_wave > lds) return p;
+    size_t w = (lds - p.shared) / p.per_wave;
+    if (w > (size_t)wave_relay_waves(p.dr, p.dc, false)) w = (size_t)wave_relay_waves(p.dr, p.dc, false);
+    const int u = p.dr <= 4 ? 4 : p.dr <= 8 ? 2 : 1;  // (plan_wave's rule, min-sum)
+    const bool team = h->small_mode == 5 || (h->small_mode != 4 && (w < 6 || 2 * p.np > 3 * 64 * u || batch <= 256 * (int64_t)w));
+    if (team) {
+        int tw = (p.np + 64 * u - 1) / (64 * u);
+        if (tw < 2) tw = 2;
+        if (tw > wave_relay_waves(p.dr, p.dc, true)) tw = wave_relay_waves(p.dr, p.dc, true);
+        p.team = true;
+        p.waves = tw;
+        p.groups_per_cu = (int)(lds / (p.shared + p.per_wave));
+        if (p.groups_per_cu >= 2 && p.waves > 8) p.waves = 8;
+        if (p.groups_per_cu * p.waves > 16) p.groups_per_cu = 16 / p.waves;
+        if (p.groups_per_cu < 1) p.groups_per_cu = 1;
+        return p;
+    }
+    if (!forced && w < 2) return p;
+    p.waves = (int)w;
+    p.groups_per_cu = (int)(lds / (p.shared + (size_t)p.waves * p.per_wave));
+    if (p.groups_per_cu * p.waves > 16) p.groups_per_cu = 16 / p.waves;  // (the kernel's 87 .. 150 VGPRs: 16 wavefronts per compute unit, 12 where compiled for 12)
+    if (p.groups_per_cu < 1) p.groups_per_cu = 1;
+    return p;
+}
+
+// a and gamma of every leg as the kernel reads them: [legs][2][np], beyond n a = 1.0 and gamma = 0 (the padding columns form the finite prior 1.0)
+__global__ void wave_relay_table_kernel(const double *ag, int n, int np, int legs, double *out) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= np) return;
+    for (int l = 0; l < legs; ++l) {
+        out[(size_t)l * 2 * np + q] = q < n ? ag[(size_t)l * 2 * n + q] : 1.0;
+        out[(size_t)l * 2 * np + np + q] = q < n ? ag[(size_t)l * 2 * n + n + q] : 0.0;
+    }
+}
+
+// The launch: decode_wave's -- the shared position tables, the padded priors, the static share for a handful of syndromes and work_pool_next beyond,
+// the grid sizing, the clock probe, the timing events on the dispatch.  ag [legs][2][n]: relay_ag, or mem_ag as one leg (leg_iters == nullptr: to
+// h->max_iter).  The OSD hook is left alone: bposd_device lists the unsolved rows itself, as after the lane = edge relay kernels.
+static int decode_wave_relay(ldpc_hip_bp *h, const WavePlan &p, const double *ag, int legs, const int32_t *leg_iters, int stop_after, const uint8_t *synd,
+                             int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv) {
+    const WaveRelayKernel kern = wave_relay_kernel(p.dr, p.dc, p.team);
+    if (!kern) return fail(LDPC_HIP_ERR_UNSUPPORTED, "Relay-BP / memory min-sum: no lane = node kernel was built for rows of %d, columns of %d", p.dr, p.dc);
+    int rc;
+    if ((rc = ensure_wave_tables(h, p))) return rc;
+    const bool static_teams = p.team && batch <= 256 * (int64_t)p.groups_per_cu;
+    if ((rc = h->counter.ensure(counter_bytes()))) return rc;
+    if (!static_teams) HIPCHK(hipMemsetAsync(h->counter.p, 0, work_pool_bytes(), h->stream));
+    // w_relay: [np + 2] the padded priors, then [legs][2][np] the padded tables (its own buffer: it goes when the relay or the memory is switched off)
+    if ((rc = h->w_relay.ensure(sizeof(double) * ((size_t)(p.np + 2) + 2 * (size_t)p.np * (size_t)legs)))) return rc;
+    double *const prior_p = (double *)h->w_relay.p, *const ag_p = prior_p + p.np + 2;
+    // (the priors, the strengths or the legs may have changed since the last call)
+    LDPC_LAUNCH(wave_prior_pad_kernel, dim3((unsigned)((p.np + 2 + 255) / 256)), dim3(256), 0, h->stream, h->d_llr0, h->n, p.np, prior_p);
+    LDPC_LAUNCH(wave_relay_table_kernel, dim3((unsigned)((p.np + 255) / 256)), dim3(256), 0, h->stream, ag, h->n, p.np, legs, ag_p);
+    HIPCHK(hipGetLastError());
+    WaveRelayArgs ra = {};
+    ra.ag_p = ag_p;
+    ra.leg_iters = leg_iters;
+    ra.legs = legs; ra.stop_after = stop_after;
+    WaveArgs &a = ra.w;
+    a.pool_per = work_pool_share(batch, 0);
+    a.m = h->m; a.n = h->n; a.mp = p.mp; a.np = p.np; a.max_iter = h->max_iter;
+    a.ms_scaling_factor = h->ms_scaling_factor;
+    a.batch = batch;
+    a.rdeg = (const uint8_t *)h->w_rdeg.p; a.cdeg = (const uint8_t *)h->w_cdeg.p;
+    a.col = (const uint16_t *)h->w_col.p; a.apos = (const uint16_t *)h->w_apos.p;
+    a.llr0 = h->d_llr0;
+    a.prior_g = prior_p;
+    a.synd = synd; a.decoding = decoding; a.llr = llr; a.iters = iters; a.conv = conv;
+    a.next = static_teams ? nullptr : (unsigned long long *)h->counter.p;
+    a.clk = h->d_clk;
+    a.lds_shared = (int32_t)p.shared; a.lds_per_wave = (int32_t)p.per_wave;
+    const size_t dyn = p.shared + (size_t)(p.team ? 1 : p.waves) * p.per_wave;
+    if (dyn > 48u * 1024u)
+        HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+    int64_t groups = p.team ? batch : (batch + p.waves - 1) / p.waves;
+    const int64_t resident = 256 * (int64_t)p.groups_per_cu;
+    if (groups > resident) groups = resident;
+    h->accumulated_ms = 0.f;
+    const bool timed = !(h->untimed_call && static_teams);
+    if (timed) LDPC_LAUNCH_TIMED(kern, dim3((unsigned)groups), dim3((unsigned)(p.waves * 64)), (unsigned)dyn, h->stream, h->ev0, h->ev1, 0, ra);
+    else LDPC_LAUNCH(kern, dim3((unsigned)groups), dim3((unsigned)(p.waves * 64)), (unsigned)dyn, h->stream, ra);
+    h->timed = timed;
+    HIPCHK(hipGetLastError());
+    return LDPC_HIP_OK;
+}
+
+// Is the lane = node route what the default modes (-1, 1) take?  By the rule of DESIGN.md section 7d, stated there before the measurement: the
+// default only if it beats the per-pass route by more than the run-to-run spread of the two on both measured codes.  It does, on one MI355X in one
+// job (profiles/relay_wave.jsonl): Relay-BP 48.1x on the [[1600,64]] hypergraph product and 48.8x on HGP [[400,16]] (7.64 against 0.159 and 30.4
+// against 0.622 M syndromes/s, spreads <= 2.1 %), the memory decode 12.4x and 17.5x (spreads <= 0.15 %).  false: modes 3 / 4 / 5 only.
+static constexpr bool k_wave_relay_default = true;
+
+// Which route a Relay-BP or memory decode of `batch` syndromes takes -- one decision for decode_onchip_relay, the memory branch of decode_onchip
+// and ldpc_hip_bp_relay_route: 0 the per-pass kernels (the relay's leg loop), 1 bp_edge, 2 bp_edge8, 3 / 4 bp_wave_relay with one wavefront / a team
+// per syndrome.  small_mode: 0 everything per pass; 6 stops after the lane = edge families; 4 and 5 force the one-wavefront and the team form, 3 takes
+// the plan's own choice; -1 and 1 take it where k_wave_relay_default says so.
+struct RelayRoute { int route = 0; EdgePlan ep; Edge8Plan e8; WavePlan wp; };
+static RelayRoute plan_relay_route(const ldpc_hip_bp *h, int64_t batch) {
+    RelayRoute r;
+    if (!(h->small_mode != 0 && h->m > 0 && h->n > 0 && h->nnz > 0 && (int64_t)h->nnz * 16 < (1 << 22) && batch < (1ll << 30))) return r;
+    r.ep = plan_edge(h);
+    if (r.ep.rounds) { r.route = 1; return r; }
+    r.e8 = plan_edge8(h);
+    if (r.e8.rounds) { r.route = 2; return r; }
+    const bool asked = h->small_mode >= 3 && h->small_mode <= 5;
+    if (!asked && !(k_wave_relay_default && (h->small_mode == -1 || h->small_mode == 1))) return r;
+    r.wp = plan_wave_relay(h, asked || h->small_mode == 1, batch);
+    if (r.wp.waves) r.route = r.wp.team ? 4 : 3;
+    return r;
+}
+
+int ldpc_hip_bp_relay_route(const ldpc_hip_bp *h, int64_t batch, int32_t *route) {
+    if (!h || !route) return fail(LDPC_HIP_ERR_INVALID, "null argument");
+    if (batch < 0) return fail(LDPC_HIP_ERR_INVALID, "negative batch");
+    if (!h->relay_on && !h->mem_on) return fail(LDPC_HIP_ERR_INVALID, "neither Relay-BP nor memory min-sum is on (ldpc_hip_bp_set_relay, ldpc_hip_bp_set_memory)");
+    *route = plan_relay_route(h, batch).route;
+    return LDPC_HIP_OK;
+}
+
+// Relay-BP on chip: plan_edge, plan_edge8, plan_wave_relay in that order (plan_relay_route).  *took = false: the per-pass leg loop (host_stream.h: decode_relay).
 int decode_onchip_relay(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv, bool *took) {
     *took = false;
-    if (!(h->small_mode != 0 && h->m > 0 && h->n > 0 && h->nnz > 0 && (int64_t)h->nnz * 16 < (1 << 22) && batch < (1ll << 30))) return LDPC_HIP_OK;
+    const RelayRoute r = plan_relay_route(h, batch);
     int rc;
-    const EdgePlan ep = plan_edge(h);
-    if (ep.rounds) {
+    if (r.route == 1) {
         *took = true;
-        if ((rc = ensure_edge_tables(h, ep))) return rc;
+        if ((rc = ensure_edge_tables(h, r.ep))) return rc;
         EdgeRelayArgs ma = {};
         ma.e.partner = (const uint16_t *)h->e_partner.p;
         ma.e.synd = synd; ma.e.decoding = decoding; ma.e.llr = llr; ma.e.iters = iters; ma.e.conv = conv;
-        return launch_edge_relay(h, edge_relay_kernel(ep.rounds), ep.rounds, edge_relay_waves(ep.rounds), batch, ma);
+        return launch_edge_relay(h, edge_relay_kernel(r.ep.rounds), r.ep.rounds, edge_relay_waves(r.ep.rounds), batch, ma);
     }
-    const Edge8Plan e8 = plan_edge8(h);
-    if (e8.rounds) {
+    if (r.route == 2) {
         *took = true;
-        if ((rc = ensure_edge8_tables(h, e8))) return rc;
+        if ((rc = ensure_edge8_tables(h, r.e8))) return rc;
         Edge8RelayArgs ma = {};
         ma.e.cpos = (const uint16_t *)h->e_partner.p;
         ma.e.synd = synd; ma.e.decoding = decoding; ma.e.llr = llr; ma.e.iters = iters; ma.e.conv = conv;
-        return launch_edge_relay(h, edge8_relay_kernel(e8.rounds, e8.dc), e8.rounds, edge8_relay_waves(e8.rounds, e8.dc), batch, ma);
+        return launch_edge_relay(h, edge8_relay_kernel(r.e8.rounds, r.e8.dc), r.e8.rounds, edge8_relay_waves(r.e8.rounds, r.e8.dc), batch, ma);
+    }
+    if (r.route >= 3) {
+        *took = true;
+        return decode_wave_relay(h, r.wp, (const double *)h->relay_ag.p, h->relay_legs, (const int32_t *)h->relay_it.p, h->relay_stop, synd, batch, decoding, llr, iters, conv);
     }
     return LDPC_HIP_OK;
 }
@@ -869,15 +1009,14 @@ int decode_onchip(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
     *took = false;
     const bool rp = h->row_probs != nullptr;
     if (h->mem_on) {
-        // Memory min-sum (ldpc_hip_bp_set_memory): a code that plan_edge or plan_edge8 takes runs on their memory forms unless the on-chip kernels are
-        // switched off (mode 0); every other code -- and every code under mode 0 -- goes to the per-pass memory kernels (took = false).  The
-        // persistent ring kernel, bp_wave_kernel, the slot kernel and the resident workgroup know nothing of the memory and never see such a decode.
-        if (h->small_mode != 0 && h->m > 0 && h->n > 0 && h->nnz > 0 && (int64_t)h->nnz * 16 < (1 << 22) && batch < (1ll << 30)) {
-            const EdgePlan ep = plan_edge(h);
-            if (ep.rounds) { *took = true; return decode_edge_mem(h, ep, synd, batch, decoding, llr, iters, conv); }
-            const Edge8Plan e8 = plan_edge8(h);
-            if (e8.rounds) { *took = true; return decode_edge8_mem(h, e8, synd, batch, decoding, llr, iters, conv); }
-        }
+        // Memory min-sum (ldpc_hip_bp_set_memory), by plan_relay_route: a code that plan_edge or plan_edge8 takes runs on their memory forms, a code
+        // plan_wave_relay takes on bp_wave_relay_kernel as ONE relay leg of max_iter iterations that stops at its first solution -- that decode's bits;
+        // every other code -- and every code under mode 0 -- goes to the per-pass memory kernels (took = false).  The persistent ring kernel,
+        // bp_wave_kernel, the slot kernel and the resident workgroup know nothing of the memory and never see such a decode.
+        const RelayRoute r = plan_relay_route(h, batch);
+        if (r.route == 1) { *took = true; return decode_edge_mem(h, r.ep, synd, batch, decoding, llr, iters, conv); }
+        if (r.route == 2) { *took = true; return decode_edge8_mem(h, r.e8, synd, batch, decoding, llr, iters, conv); }
+        if (r.route >= 3) { *took = true; return decode_wave_relay(h, r.wp, (const double *)h->mem_ag.p, 1, nullptr, 1, synd, batch, decoding, llr, iters, conv); }
         return LDPC_HIP_OK;
     }
     if (h->small_mode != 0 && h->m > 0 && h->n > 0 && h->nnz > 0 && (int64_t)h->nnz * 16 < (1 << 22) && batch < (1ll << 30)) {  // (32-bit syndrome indices in the work pools)

@@ -322,6 +322,7 @@ int ldpc_hip_bp_set_memory(ldpc_hip_bp *h, const double *gamma) {
         h->mem_bad_col = -1;
         h->mem_ag.release();
         h->e_mem.release();
+        h->w_relay.release();
         return LDPC_HIP_OK;
     }
     if (h->relay_on)
@@ -351,7 +352,7 @@ int ldpc_hip_bp_set_relay(ldpc_hip_bp *h, int32_t legs, const double *gamma, con
         h->relay_gamma.clear();
         h->relay_iters.clear();
         h->relay_bad_col = -1;
-        for (DeviceBuf *b : {&h->relay_ag, &h->relay_it, &h->e_relay, &h->relay_dec, &h->relay_llr, &h->relay_li, &h->relay_cv, &h->relay_state}) b->release();
+        for (DeviceBuf *b : {&h->relay_ag, &h->relay_it, &h->e_relay, &h->w_relay, &h->relay_dec, &h->relay_llr, &h->relay_li, &h->relay_cv, &h->relay_state}) b->release();
         return LDPC_HIP_OK;
     }
     if (h->mem_on)

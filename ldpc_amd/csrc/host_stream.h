@@ -437,8 +437,8 @@ static int decode_stream_repacked(ldpc_hip_bp *h, const uint8_t *synd, int64_t b
     return stream_leave_histogram(h, iters, conv, batch);
 }
 
-// Relay-BP (ldpc_hip_bp_set_relay).  A code the lane = edge families take runs all its legs in one launch of their relay
-// forms (decode_onchip_relay).  Every other code, and every code with the on-chip kernels switched off, runs the leg loop below: leg l is a per-pass
+// Relay-BP (ldpc_hip_bp_set_relay).  A code the lane = edge families or the lane = node kernel take runs all its legs in one
+// launch (decode_onchip_relay: plan_relay_route).  Every other code, and every code with the on-chip kernels switched off, runs the leg loop below: leg l is a per-pass
 // memory decode of the whole batch to relay_iters[l] iterations with the leg's a[] / gamma[] -- from the second leg on started from the
 // posteriors the leg before it left (relay_llr, read by bp_spread_relay_init_kernel before the chunk's outputs overwrite its rows: a converged
 // row's posteriors are frozen at its convergence iteration, so a leg's llr output IS the row's M at the leg's end) -- followed by

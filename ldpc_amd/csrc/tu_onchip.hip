@@ -10,6 +10,7 @@
 #include "bp_edge_rp_kernel.h"   // (likewise: the row-prior instantiations are tu_onchip_rp.hip's)
 #include "bp_edge_mem_kernel.h"  // (likewise: the memory instantiations are tu_onchip_mem.hip's)
 #include "bp_edge_relay_kernel.h"  // (likewise: the Relay-BP instantiations are tu_onchip_relay.hip's)
+#include "bp_wave_relay_kernel.h"  // (likewise: tu_onchip_wave_relay.hip's)
 #include "io_kernels.h"
 
 #include "host_handle.h"

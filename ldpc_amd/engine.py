@@ -202,6 +202,20 @@ class HipBpEngine:
         _lib.check(min(0, int(self._lib.ldpc_hip_bp_get_relay(self._h, None, None, g.ctypes.data_as(C.c_void_p), li.ctypes.data_as(C.c_void_p)))))
         return g, li, int(stop.value)
 
+    RELAY_ROUTES = ("per_pass", "bp_edge", "bp_edge8", "bp_wave", "bp_wave_team")
+
+    def relay_route(self, batch=1) -> str:
+        """The kernel route a Relay-BP or memory decode of ``batch`` syndromes takes on this engine as it is set now
+        (``ldpc_hip_bp_relay_route``; nothing is launched): ``"per_pass"`` (Relay-BP: the leg loop -- correct everywhere, 10 - 60x slower),
+        ``"bp_edge"``, ``"bp_edge8"``, ``"bp_wave"`` (one wavefront per syndrome) or ``"bp_wave_team"`` (a workgroup per syndrome) -- the
+        last four run all legs in one launch.  ``ValueError`` when neither the relay nor the memory is on."""
+        route = C.c_int32(-1)
+        rc = int(self._lib.ldpc_hip_bp_relay_route(self._h, int(batch), C.byref(route)))
+        if rc == -1:
+            raise ValueError(self._lib.ldpc_hip_last_error().decode("utf-8", "replace"))
+        _lib.check(rc)
+        return self.RELAY_ROUTES[route.value]
+
     def set_ring(self, depth):
         """LDS-DMA ring for regular-degree matrices: False/0 = off, True/1 = default depth, 2 or 3 = slots per wave."""
         _lib.check(self._lib.ldpc_hip_bp_set_ring(self._h, int(depth)))

@@ -1,7 +1,8 @@
 """Relay-BP: a first memory min-sum leg with one strength everywhere, then ``num_sets`` legs with per-bit strengths drawn once, each started
 from the posteriors the leg before it ended with; the lightest of the first ``stop_nconv`` solutions is the result.  The legs of a batch are
-decoded in ONE call of the library (``ldpc_hip_bp_set_relay``): on the lane = edge relay kernels where the code fits them, else as a loop of
-per-pass memory decodes on the device -- the results are the same bits (tests/relay_bp_util.py is the contract)."""
+decoded in ONE call of the library (``ldpc_hip_bp_set_relay``): on the lane = edge relay kernels where the code fits them, on the lane = node
+kernel ``bp_wave_relay_kernel`` where the small-code kernel mode asks for it, else as a loop of per-pass memory decodes on the device -- the
+results are the same bits (tests/relay_bp_util.py is the contract); ``RelayBpDecoder.route`` names the route taken."""
 from __future__ import annotations
 
 import numpy as np
@@ -83,3 +84,8 @@ class RelayBpDecoder(BpDecoder):
     @property
     def stop_nconv(self) -> int:
         return self._relay[2]
+
+    @property
+    def route(self) -> str:
+        """``BpDecoder.relay_route``: ``"per_pass"``, ``"bp_edge"``, ``"bp_edge8"``, ``"bp_wave"`` or ``"bp_wave_team"``."""
+        return self.relay_route
