@@ -33,6 +33,11 @@
 // to DBL_MAX in the minimum, positive in the sign ballot, and their "log-ratio" is +inf or, at worst, inf - inf = NaN:
 // never <= 0, so they drop out of the decision ballots by themselves.
 // Results are bit-identical to bp_wave_kernel and to the reference (tests/test_gpu_parity.py, test_gpu_fuzz.py).
+// The variants (bp_edge_rp_kernel.h: row priors, bp_edge_mem_kernel.h: memory, bp_edge_relay_kernel.h: Relay-BP) restate these passes operation
+// by operation, deliberately for now: as __forceinline__ function templates -- whole passes on the register arrays, or one round on values --
+// they compile to other instruction streams in many instantiations (profiles/edge_passes_isa.txt).  Shared as code: edge_detail below, the two
+// ladders, and ONE launch on the host (launch_edge, host_onchip.h).  The arguments about -0.0, phantom lanes, the clamp and the wave_barrier
+// are kept with bp_edge_kernel; the copies point here.
 struct EdgeArgs {
     int32_t m, n, max_iter;
     double ms_scaling_factor;
@@ -54,6 +59,14 @@ struct EdgeArgs {
     unsigned long long *clk;   // shader-clock probe (clock_probe_*, bp_device_common.h) or nullptr
 };
 
+// The instantiations of the two families, written once: bp_edge_kernel and its variants exist for LDPC_EDGE_LADDER's rounds (plan_edge,
+// host_onchip.h, takes the code's own (4 m + 63) / 64), bp_edge8_kernel and its variants for LDPC_EDGE8_LADDER's (rounds, column weight) rungs
+// (plan_edge8 takes the first of its column weight that holds 8 m slots: they ascend).  X is applied to every rung.
+#define LDPC_EDGE_LADDER(X) X(1) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
+#define LDPC_EDGE8_LADDER(X)                                                             \
+    X(2, 3) X(3, 3) X(4, 3) X(5, 3) X(6, 3) X(7, 3) X(8, 3) X(9, 3) X(10, 3) X(12, 3) \
+    X(2, 4) X(3, 4) X(4, 4) X(5, 4) X(6, 4) X(7, 4) X(8, 4) X(9, 4)
+
 __host__ __device__ inline size_t edge_lds_bytes(int rounds) { return ((size_t)rounds * 64 + 3) * 8; }  // slots, +0.0, +inf, a dummy (bp_edge8_kernel's phantom lanes park their output there)
 __host__ __device__ inline size_t edge_f32_lds_bytes(int rounds) { return ((size_t)rounds * 64 + 3) * 4; }  // the same slots at 4 bytes each (bp_edge_f32_kernel.h)
 
@@ -72,7 +85,11 @@ __host__ __device__ inline size_t edge_f32_lds_bytes(int rounds) { return ((size
 #ifndef EDGE_G
 #define EDGE_G 4
 #endif
+// a cold field (LDPC_KERNARG, bp_device_common.h) of the EdgeArgs / Edge8Args block `e` inside a variant kernel's arguments ARGS_T
+#define LDPC_EDGE_VARIANT_ARG(field) LDPC_KERNARG(ARGS_T, e.field)
 namespace edge_detail {
+typedef __attribute__((address_space(3))) double lds_f64;         // the wave-private LDS array of messages
+typedef __attribute__((address_space(1))) const double *gtab_t;  // a slot table of doubles in global memory
 // quad permutations of a double (two 32-bit DPP moves: 64-bit DPP allows row_newbcast only)
 template <int CTRL>
 __device__ __forceinline__ double quad_perm(double x) {
@@ -111,6 +128,14 @@ __device__ __forceinline__ uint64_t spread_nibble(uint64_t low) {  // bit 0 of e
     const uint32_t a = ((uint32_t)low & 0x11111111u) * 15u, b = ((uint32_t)(low >> 32) & 0x11111111u) * 15u;
     return ((uint64_t)b << 32) | a;
 }
+// +-alpha of iteration `it` as words -- the low word, the high word, the high word of -alpha: a check pass multiplies the magnitude by the double
+// it puts together from `lo` and one of the high words (scaling factor 0: the adaptive 1 - 2^-it, bp.hpp:264-266)
+struct AlphaWords { int lo, hi, nhi; };
+__device__ __forceinline__ AlphaWords alpha_words(double ms_scaling_factor, int it) {
+    const double alpha = (ms_scaling_factor == 0.0) ? 1.0 - ldexp(1.0, -it) : ms_scaling_factor;
+    const int ahi = __double2hiint(alpha);
+    return {__double2loint(alpha), ahi, ahi ^ (int)0x80000000};
+}
 }  // namespace edge_detail
 
 // UNIFORM: all columns have the same prior (a decoder built from `error_rate`): it is a scalar, which frees 2 R registers per
@@ -125,7 +150,6 @@ __global__ void __launch_bounds__(64, UNIFORM ? 5 : 4) bp_edge_kernel(const Edge
     using namespace edge_detail;
     typedef EdgeArgs ARGS_T;  // (cold fields: LDPC_KERNARG, bp_device_common.h)
     extern __shared__ __attribute__((aligned(16))) unsigned char edge_lds[];
-    typedef __attribute__((address_space(3))) double lds_f64;
     lds_f64 *X = (lds_f64 *)edge_lds;  // [R * 64] check_to_bit of every slot, [R * 64] = +0.0 for good
     const int lane = threadIdx.x;
     __shared__ unsigned long long clk_stamp[2];
@@ -174,8 +198,7 @@ __global__ void __launch_bounds__(64, UNIFORM ? 5 : 4) bp_edge_kernel(const Edge
         bool unsat = true;
         do {
             ++it;
-            const double alpha = (a.ms_scaling_factor == 0.0) ? 1.0 - ldexp(1.0, -it) : a.ms_scaling_factor;
-            const int alo = __double2loint(alpha), ahi = __double2hiint(alpha), nhi = ahi ^ (int)0x80000000;
+            const AlphaWords al = alpha_words(a.ms_scaling_factor, it);
             // ---- check pass: msg[r] (bit_to_check) -> msg[r] (check_to_bit), stored at the slot ----
 #pragma unroll
             for (int r = 0; r < R; ++r) {
@@ -190,14 +213,14 @@ __global__ void __launch_bounds__(64, UNIFORM ? 5 : 4) bp_edge_kernel(const Edge
                     // the vector unit spreads the row's parity: lane 0 of the quad picks it up from the (unspread) scalar mask, a DPP
                     // broadcast inside the quad XORs it onto everyone's own sign -- 2 vector instructions more, 5 scalar ones fewer
                     const uint64_t par = nibble_parity_low(neg ^ sy[r]);
-                    const int own = select_by_mask(ahi, nhi, neg);
+                    const int own = select_by_mask(al.hi, al.nhi, neg);
                     const int rowbit = select_by_mask(0, (int)0x80000000, par);
                     shi = own ^ __builtin_amdgcn_mov_dpp(rowbit, 0x00, 0xf, 0xf, true);  // quad_perm [0, 0, 0, 0]
                 } else {
                     const uint64_t flip = spread_nibble(nibble_parity_low(neg ^ sy[r])) ^ neg;  // row parity incl. the syndrome, own sign out
-                    shi = select_by_mask(ahi, nhi, flip);
+                    shi = select_by_mask(al.hi, al.nhi, flip);
                 }
-                const double c = mag * __hiloint2double(shi, alo);
+                const double c = mag * __hiloint2double(shi, al.lo);
                 msg[r] = c;
                 X[r * 64 + lane] = c;
             }
@@ -340,7 +363,6 @@ __global__ void __launch_bounds__(64, UNIFORM ? 5 : 4) bp_edge8_kernel(const Edg
     typedef Edge8Args ARGS_T;  // (cold fields: LDPC_KERNARG, bp_device_common.h)
     static_assert(DC >= 2 && DC <= 4, "columns of 2 .. 4 entries");
     extern __shared__ __attribute__((aligned(16))) unsigned char edge_lds[];
-    typedef __attribute__((address_space(3))) double lds_f64;
     lds_f64 *X = (lds_f64 *)edge_lds;
     const int lane = threadIdx.x;
     __shared__ unsigned long long clk_stamp[2];
@@ -391,8 +413,7 @@ __global__ void __launch_bounds__(64, UNIFORM ? 5 : 4) bp_edge8_kernel(const Edg
         bool unsat = true;
         do {
             ++it;
-            const double alpha = (a.ms_scaling_factor == 0.0) ? 1.0 - ldexp(1.0, -it) : a.ms_scaling_factor;
-            const int alo = __double2loint(alpha), ahi = __double2hiint(alpha), nhi = ahi ^ (int)0x80000000;
+            const AlphaWords al = alpha_words(a.ms_scaling_factor, it);
             // ---- check pass (bp.hpp:220-273): minimum over the seven other lanes of the group, sign by the group's parity ----
 #pragma unroll
             for (int r = 0; r < R; ++r) {
@@ -406,7 +427,7 @@ __global__ void __launch_bounds__(64, UNIFORM ? 5 : 4) bp_edge8_kernel(const Edg
                 const double otherquad = xor4(quadmin);
                 const double mag = fmin_pos(min_abs(inquad, otherquad), dbl_max);  // the seven other entries, from DBL_MAX down
                 const uint64_t flip = spread_byte(byte_parity_low(neg ^ sy[r])) ^ neg;
-                const double c = mag * __hiloint2double(select_by_mask(ahi, nhi, flip), alo);
+                const double c = mag * __hiloint2double(select_by_mask(al.hi, al.nhi, flip), al.lo);
                 msg[r] = c;
                 X[r * 64 + lane] = c;
             }

@@ -52,15 +52,12 @@ Edge8MemKernel edge8_mem_kernel(int rounds, int dc);
 __host__ __device__ constexpr int edge_mem_waves(int rounds) { return rounds <= 13 ? 4 : 3; }
 __host__ __device__ constexpr int edge8_mem_waves(int, int) { return 4; }
 
-#define LDPC_EDGE_MEM_ARG(field) LDPC_KERNARG(ARGS_T, e.field)
-
 template <int R>
 __global__ void __launch_bounds__(64, edge_mem_waves(R)) bp_edge_mem_kernel(const EdgeMemArgs ma) {
     using namespace edge_detail;
     const EdgeArgs &a = ma.e;
     typedef EdgeMemArgs ARGS_T;  // (cold fields: LDPC_KERNARG, bp_device_common.h)
     extern __shared__ __attribute__((aligned(16))) unsigned char edge_lds[];
-    typedef __attribute__((address_space(3))) double lds_f64;
     lds_f64 *X = (lds_f64 *)edge_lds;  // [R * 64] check_to_bit of every slot, [R * 64] = +0.0 for good
     const int lane = threadIdx.x;
     __shared__ unsigned long long clk_stamp[2];
@@ -68,7 +65,6 @@ __global__ void __launch_bounds__(64, edge_mem_waves(R)) bp_edge_mem_kernel(cons
     const int m = a.m, n = a.n;
     constexpr int ZERO = R * 64;
     constexpr uint64_t LOW = 0x1111111111111111ull;
-    typedef __attribute__((address_space(1))) const double *gtab_t;
     constexpr bool KEEP = R <= EDGE_MEM_KEEP;
     constexpr int G = EDGE_G;  // rounds per group of the bit pass
 
@@ -87,14 +83,14 @@ __global__ void __launch_bounds__(64, edge_mem_waves(R)) bp_edge_mem_kernel(cons
     if (lane == 0) { X[ZERO] = 0.0; X[ZERO + 1] = __builtin_inf(); }
 
     // Work: the static share, then chunks from the pooled work counters (work_pool_next, bp_device_common.h)
-    int b0 = (int)blockIdx.x * LDPC_EDGE_MEM_ARG(static_per), b1 = b0 + LDPC_EDGE_MEM_ARG(static_per);
+    int b0 = (int)blockIdx.x * LDPC_EDGE_VARIANT_ARG(static_per), b1 = b0 + LDPC_EDGE_VARIANT_ARG(static_per);
     int pool = (int)(blockIdx.x & (WORK_POOLS - 1));
     for (;;) {
       for (int b = b0; b < b1; ++b) {
         const gtab_t a_t = KEEP ? (gtab_t)nullptr : global_ptr(LDPC_KERNARG(ARGS_T, a_s));  // (re-read per iteration above KEEP rounds)
         const gtab_t g_t = KEEP ? (gtab_t)nullptr : global_ptr(LDPC_KERNARG(ARGS_T, g_s));
         {   // M = L0: the initial messages (initialise_log_domain_bp, bp.hpp:147-157), and what the first iteration's prior is formed from
-            const auto l0_t = global_ptr(LDPC_EDGE_MEM_ARG(prior_s));
+            const auto l0_t = global_ptr(LDPC_EDGE_VARIANT_ARG(prior_s));
 #pragma unroll
             for (int r = 0; r < R; ++r) msg[r] = l0_t[r * 64 + lane];  // (phantom lanes: +inf)
         }
@@ -102,7 +98,7 @@ __global__ void __launch_bounds__(64, edge_mem_waves(R)) bp_edge_mem_kernel(cons
         for (int r = 0; r < R; ++r) prv[r] = msg[r];
         uint64_t sy[R];
         bool never = false;
-        const auto sb = global_ptr(LDPC_EDGE_MEM_ARG(synd)) + (int64_t)b * m;
+        const auto sb = global_ptr(LDPC_EDGE_VARIANT_ARG(synd)) + (int64_t)b * m;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int row = r * 16 + (lane >> 2);
@@ -115,8 +111,7 @@ __global__ void __launch_bounds__(64, edge_mem_waves(R)) bp_edge_mem_kernel(cons
         bool unsat = true;
         do {
             ++it;
-            const double alpha = (a.ms_scaling_factor == 0.0) ? 1.0 - ldexp(1.0, -it) : a.ms_scaling_factor;
-            const int alo = __double2loint(alpha), ahi = __double2hiint(alpha), nhi = ahi ^ (int)0x80000000;
+            const AlphaWords al = alpha_words(a.ms_scaling_factor, it);
             // ---- check pass: msg[r] (bit_to_check) -> msg[r] (check_to_bit), stored at the slot ----
 #pragma unroll
             for (int r = 0; r < R; ++r) {
@@ -129,14 +124,14 @@ __global__ void __launch_bounds__(64, edge_mem_waves(R)) bp_edge_mem_kernel(cons
                 int shi;  // high word of +-alpha: sign = row parity (syndrome included) + own
                 if (r < EDGE_V1) {
                     const uint64_t par = nibble_parity_low(neg ^ sy[r]);
-                    const int own = select_by_mask(ahi, nhi, neg);
+                    const int own = select_by_mask(al.hi, al.nhi, neg);
                     const int rowbit = select_by_mask(0, (int)0x80000000, par);
                     shi = own ^ __builtin_amdgcn_mov_dpp(rowbit, 0x00, 0xf, 0xf, true);  // quad_perm [0, 0, 0, 0]
                 } else {
                     const uint64_t flip = spread_nibble(nibble_parity_low(neg ^ sy[r])) ^ neg;
-                    shi = select_by_mask(ahi, nhi, flip);
+                    shi = select_by_mask(al.hi, al.nhi, flip);
                 }
-                const double c = mag * __hiloint2double(shi, alo);
+                const double c = mag * __hiloint2double(shi, al.lo);
                 msg[r] = c;
                 X[r * 64 + lane] = c;
             }
@@ -177,15 +172,15 @@ __global__ void __launch_bounds__(64, edge_mem_waves(R)) bp_edge_mem_kernel(cons
 
         // ---- outputs (as bp_edge_kernel): the first entry of a column parks the column's log-ratio at X[column], whole rows leave.  The log-ratio
         // is prv[r], formed by the last bit pass (the plain kernel adds it up again from the prior; that prior is history here) ----
-        const auto scol_t = global_ptr(LDPC_EDGE_MEM_ARG(scol));
+        const auto scol_t = global_ptr(LDPC_EDGE_VARIANT_ARG(scol));
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int j = scol_t[r * 64 + lane];
             if ((k0[r] >> lane) & 1ull) X[j] = prv[r];
         }
         {
-            const auto dp = global_ptr(LDPC_EDGE_MEM_ARG(decoding)) + (int64_t)b * n;
-            auto lp = global_ptr(LDPC_EDGE_MEM_ARG(llr));
+            const auto dp = global_ptr(LDPC_EDGE_VARIANT_ARG(decoding)) + (int64_t)b * n;
+            auto lp = global_ptr(LDPC_EDGE_VARIANT_ARG(llr));
             if (lp) lp += (int64_t)b * n;
             for (int j = lane; j < n; j += 64) {
                 const double l0 = X[j];
@@ -194,8 +189,8 @@ __global__ void __launch_bounds__(64, edge_mem_waves(R)) bp_edge_mem_kernel(cons
             }
         }
         {
-            const auto ip = global_ptr(LDPC_EDGE_MEM_ARG(iters));
-            const auto cp = global_ptr(LDPC_EDGE_MEM_ARG(conv));
+            const auto ip = global_ptr(LDPC_EDGE_VARIANT_ARG(iters));
+            const auto cp = global_ptr(LDPC_EDGE_VARIANT_ARG(conv));
             if (lane == 0) {
                 if (ip) ip[b] = it;
                 if (cp) cp[b] = unsat ? 0 : 1;
@@ -203,9 +198,9 @@ __global__ void __launch_bounds__(64, edge_mem_waves(R)) bp_edge_mem_kernel(cons
         }
         __builtin_amdgcn_wave_barrier();  // (see bp_edge_kernel: the wavefront is whole before lane 0 pulls the next syndrome)
       }
-        if (!work_pool_next(LDPC_EDGE_MEM_ARG(next), LDPC_EDGE_MEM_ARG(dyn_base), LDPC_EDGE_MEM_ARG(pool_per), LDPC_EDGE_MEM_ARG(chunk), (int)LDPC_EDGE_MEM_ARG(batch), lane, pool, b0, b1)) break;
+        if (!work_pool_next(LDPC_EDGE_VARIANT_ARG(next), LDPC_EDGE_VARIANT_ARG(dyn_base), LDPC_EDGE_VARIANT_ARG(pool_per), LDPC_EDGE_VARIANT_ARG(chunk), (int)LDPC_EDGE_VARIANT_ARG(batch), lane, pool, b0, b1)) break;
     }
-    if (lane == 0) clock_probe_end(LDPC_EDGE_MEM_ARG(clk), clk_stamp);
+    if (lane == 0) clock_probe_end(LDPC_EDGE_VARIANT_ARG(clk), clk_stamp);
 }
 
 template <int R, int DC>
@@ -215,7 +210,6 @@ __global__ void __launch_bounds__(64, edge8_mem_waves(R, DC)) bp_edge8_mem_kerne
     typedef Edge8MemArgs ARGS_T;  // (cold fields: LDPC_KERNARG, bp_device_common.h)
     static_assert(DC >= 2 && DC <= 4, "columns of 2 .. 4 entries");
     extern __shared__ __attribute__((aligned(16))) unsigned char edge_lds[];
-    typedef __attribute__((address_space(3))) double lds_f64;
     lds_f64 *X = (lds_f64 *)edge_lds;
     const int lane = threadIdx.x;
     __shared__ unsigned long long clk_stamp[2];
@@ -223,7 +217,6 @@ __global__ void __launch_bounds__(64, edge8_mem_waves(R, DC)) bp_edge8_mem_kerne
     const int m = a.m, n = a.n;
     constexpr int ZERO = R * 64;
     constexpr uint64_t LOW = 0x0101010101010101ull;
-    typedef __attribute__((address_space(1))) const double *gtab_t;
     constexpr bool KEEP = R <= EDGE8_MEM_KEEP;
 
     double prv[R], msg[R], av[KEEP ? R : 1], gv[KEEP ? R : 1];
@@ -242,14 +235,14 @@ __global__ void __launch_bounds__(64, edge8_mem_waves(R, DC)) bp_edge8_mem_kerne
     const double dbl_max = uniform_f64(DBL_MAX);
     if (lane == 0) { X[ZERO] = 0.0; X[ZERO + 1] = __builtin_inf(); }
 
-    int b0 = (int)blockIdx.x * LDPC_EDGE_MEM_ARG(static_per), b1 = b0 + LDPC_EDGE_MEM_ARG(static_per);
+    int b0 = (int)blockIdx.x * LDPC_EDGE_VARIANT_ARG(static_per), b1 = b0 + LDPC_EDGE_VARIANT_ARG(static_per);
     int pool = (int)(blockIdx.x & (WORK_POOLS - 1));
     for (;;) {
       for (int b = b0; b < b1; ++b) {
         const gtab_t a_t = KEEP ? (gtab_t)nullptr : global_ptr(LDPC_KERNARG(ARGS_T, a_s));  // (re-read per iteration above KEEP rounds)
         const gtab_t g_t = KEEP ? (gtab_t)nullptr : global_ptr(LDPC_KERNARG(ARGS_T, g_s));
         {   // M = L0 (see bp_edge_mem_kernel)
-            const auto l0_t = global_ptr(LDPC_EDGE_MEM_ARG(prior_s));
+            const auto l0_t = global_ptr(LDPC_EDGE_VARIANT_ARG(prior_s));
 #pragma unroll
             for (int r = 0; r < R; ++r) msg[r] = l0_t[r * 64 + lane];  // initialise_log_domain_bp (bp.hpp:147-157); phantom lanes: +inf
         }
@@ -257,7 +250,7 @@ __global__ void __launch_bounds__(64, edge8_mem_waves(R, DC)) bp_edge8_mem_kerne
         for (int r = 0; r < R; ++r) prv[r] = msg[r];
         uint64_t sy[R];
         bool never = false;
-        const auto sb = global_ptr(LDPC_EDGE_MEM_ARG(synd)) + (int64_t)b * m;
+        const auto sb = global_ptr(LDPC_EDGE_VARIANT_ARG(synd)) + (int64_t)b * m;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int row = r * 8 + (lane >> 3);
@@ -270,8 +263,7 @@ __global__ void __launch_bounds__(64, edge8_mem_waves(R, DC)) bp_edge8_mem_kerne
         bool unsat = true;
         do {
             ++it;
-            const double alpha = (a.ms_scaling_factor == 0.0) ? 1.0 - ldexp(1.0, -it) : a.ms_scaling_factor;
-            const int alo = __double2loint(alpha), ahi = __double2hiint(alpha), nhi = ahi ^ (int)0x80000000;
+            const AlphaWords al = alpha_words(a.ms_scaling_factor, it);
             // ---- check pass (bp.hpp:220-273): minimum over the seven other lanes of the group, sign by the group's parity ----
 #pragma unroll
             for (int r = 0; r < R; ++r) {
@@ -285,7 +277,7 @@ __global__ void __launch_bounds__(64, edge8_mem_waves(R, DC)) bp_edge8_mem_kerne
                 const double otherquad = xor4(quadmin);
                 const double mag = fmin_pos(min_abs(inquad, otherquad), dbl_max);  // the seven other entries, from DBL_MAX down
                 const uint64_t flip = spread_byte(byte_parity_low(neg ^ sy[r])) ^ neg;
-                const double c = mag * __hiloint2double(select_by_mask(ahi, nhi, flip), alo);
+                const double c = mag * __hiloint2double(select_by_mask(al.hi, al.nhi, flip), al.lo);
                 msg[r] = c;
                 X[r * 64 + lane] = c;
             }
@@ -321,12 +313,12 @@ __global__ void __launch_bounds__(64, edge8_mem_waves(R, DC)) bp_edge8_mem_kerne
         } while (unsat && it < a.max_iter);
 
         // ---- outputs: as bp_edge8_kernel, with the log-ratio the last bit pass formed (phantom lanes park theirs at the dummy slot behind +inf) ----
-        const auto scol_t = global_ptr(LDPC_EDGE_MEM_ARG(scol));
+        const auto scol_t = global_ptr(LDPC_EDGE_VARIANT_ARG(scol));
 #pragma unroll
         for (int r = 0; r < R; ++r) X[scol_t[r * 64 + lane]] = prv[r];
         {
-            const auto dp = global_ptr(LDPC_EDGE_MEM_ARG(decoding)) + (int64_t)b * n;
-            auto lp = global_ptr(LDPC_EDGE_MEM_ARG(llr));
+            const auto dp = global_ptr(LDPC_EDGE_VARIANT_ARG(decoding)) + (int64_t)b * n;
+            auto lp = global_ptr(LDPC_EDGE_VARIANT_ARG(llr));
             if (lp) lp += (int64_t)b * n;
             for (int j = lane; j < n; j += 64) {
                 const double t = X[j];
@@ -335,8 +327,8 @@ __global__ void __launch_bounds__(64, edge8_mem_waves(R, DC)) bp_edge8_mem_kerne
             }
         }
         {
-            const auto ip = global_ptr(LDPC_EDGE_MEM_ARG(iters));
-            const auto cp = global_ptr(LDPC_EDGE_MEM_ARG(conv));
+            const auto ip = global_ptr(LDPC_EDGE_VARIANT_ARG(iters));
+            const auto cp = global_ptr(LDPC_EDGE_VARIANT_ARG(conv));
             if (lane == 0) {
                 if (ip) ip[b] = it;
                 if (cp) cp[b] = unsat ? 0 : 1;
@@ -344,8 +336,7 @@ __global__ void __launch_bounds__(64, edge8_mem_waves(R, DC)) bp_edge8_mem_kerne
         }
         __builtin_amdgcn_wave_barrier();  // (see bp_edge_kernel)
       }
-        if (!work_pool_next(LDPC_EDGE_MEM_ARG(next), LDPC_EDGE_MEM_ARG(dyn_base), LDPC_EDGE_MEM_ARG(pool_per), LDPC_EDGE_MEM_ARG(chunk), (int)LDPC_EDGE_MEM_ARG(batch), lane, pool, b0, b1)) break;
+        if (!work_pool_next(LDPC_EDGE_VARIANT_ARG(next), LDPC_EDGE_VARIANT_ARG(dyn_base), LDPC_EDGE_VARIANT_ARG(pool_per), LDPC_EDGE_VARIANT_ARG(chunk), (int)LDPC_EDGE_VARIANT_ARG(batch), lane, pool, b0, b1)) break;
     }
-    if (lane == 0) clock_probe_end(LDPC_EDGE_MEM_ARG(clk), clk_stamp);
+    if (lane == 0) clock_probe_end(LDPC_EDGE_VARIANT_ARG(clk), clk_stamp);
 }
-#undef LDPC_EDGE_MEM_ARG

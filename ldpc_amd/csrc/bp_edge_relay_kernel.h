@@ -45,8 +45,6 @@ Edge8RelayKernel edge8_relay_kernel(int rounds, int dc);
 __host__ __device__ constexpr int edge_relay_waves(int rounds) { return rounds <= 12 ? 4 : 3; }
 __host__ __device__ constexpr int edge8_relay_waves(int, int) { return 4; }
 
-#define LDPC_EDGE_RELAY_ARG(field) LDPC_KERNARG(ARGS_T, e.field)
-
 // What both kernels do with a leg's end (X, lane, n, b, unsat, last and the row's running best / nsol are the kernel's): see the header comment.
 // PARK: the statement that parks prv[] at X[column].
 #define LDPC_EDGE_RELAY_LEG_END(PARK)                                                                                     \
@@ -59,8 +57,8 @@ __host__ __device__ constexpr int edge8_relay_waves(int, int) { return 4; }
             if (__ballot(w < best) != 0) { best = w; take = true; }  /* (every lane holds the same w: the ballot keeps the branch scalar) */ \
         }                                                                                                                 \
         if (take) {                                                                                                       \
-            const auto dp = global_ptr(LDPC_EDGE_RELAY_ARG(decoding)) + (int64_t)b * n;                                    \
-            auto lp = global_ptr(LDPC_EDGE_RELAY_ARG(llr));                                                                \
+            const auto dp = global_ptr(LDPC_EDGE_VARIANT_ARG(decoding)) + (int64_t)b * n;                                    \
+            auto lp = global_ptr(LDPC_EDGE_VARIANT_ARG(llr));                                                                \
             if (lp) lp += (int64_t)b * n;                                                                                 \
             for (int j = lane; j < n; j += 64) {                                                                          \
                 const double t = X[j];                                                                                    \
@@ -76,7 +74,6 @@ __global__ void __launch_bounds__(64, edge_relay_waves(R)) bp_edge_relay_kernel(
     const EdgeArgs &a = ma.e;
     typedef EdgeRelayArgs ARGS_T;  // (cold fields: LDPC_KERNARG, bp_device_common.h)
     extern __shared__ __attribute__((aligned(16))) unsigned char edge_lds[];
-    typedef __attribute__((address_space(3))) double lds_f64;
     lds_f64 *X = (lds_f64 *)edge_lds;  // [R * 64] check_to_bit of every slot, [R * 64] = +0.0 for good
     const int lane = threadIdx.x;
     __shared__ unsigned long long clk_stamp[2];
@@ -84,7 +81,6 @@ __global__ void __launch_bounds__(64, edge_relay_waves(R)) bp_edge_relay_kernel(
     const int m = a.m, n = a.n;
     constexpr int ZERO = R * 64;
     constexpr uint64_t LOW = 0x1111111111111111ull;
-    typedef __attribute__((address_space(1))) const double *gtab_t;
     constexpr bool KEEP = R <= EDGE_MEM_KEEP;
     constexpr int G = EDGE_G;  // rounds per group of the bit pass
 
@@ -102,12 +98,12 @@ __global__ void __launch_bounds__(64, edge_relay_waves(R)) bp_edge_relay_kernel(
     if (lane == 0) { X[ZERO] = 0.0; X[ZERO + 1] = __builtin_inf(); }
 
     // Work: the static share, then chunks from the pooled work counters (work_pool_next, bp_device_common.h)
-    int b0 = (int)blockIdx.x * LDPC_EDGE_RELAY_ARG(static_per), b1 = b0 + LDPC_EDGE_RELAY_ARG(static_per);
+    int b0 = (int)blockIdx.x * LDPC_EDGE_VARIANT_ARG(static_per), b1 = b0 + LDPC_EDGE_VARIANT_ARG(static_per);
     int pool = (int)(blockIdx.x & (WORK_POOLS - 1));
     for (;;) {
       for (int b = b0; b < b1; ++b) {
         {   // M = L0: leg 0's initial messages (initialise_log_domain_bp, bp.hpp:147-157), and what its first iteration's prior is formed from
-            const auto l0_t = global_ptr(LDPC_EDGE_RELAY_ARG(prior_s));
+            const auto l0_t = global_ptr(LDPC_EDGE_VARIANT_ARG(prior_s));
 #pragma unroll
             for (int r = 0; r < R; ++r) msg[r] = l0_t[r * 64 + lane];  // (phantom lanes: +inf)
         }
@@ -115,7 +111,7 @@ __global__ void __launch_bounds__(64, edge_relay_waves(R)) bp_edge_relay_kernel(
         for (int r = 0; r < R; ++r) prv[r] = msg[r];
         uint64_t sy[R];
         bool never = false;
-        const auto sb = global_ptr(LDPC_EDGE_RELAY_ARG(synd)) + (int64_t)b * m;
+        const auto sb = global_ptr(LDPC_EDGE_VARIANT_ARG(synd)) + (int64_t)b * m;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int row = r * 16 + (lane >> 2);
@@ -127,7 +123,7 @@ __global__ void __launch_bounds__(64, edge_relay_waves(R)) bp_edge_relay_kernel(
         double best = __builtin_inf();
         int nsol = 0, total = 0;
         const int legs = LDPC_KERNARG(ARGS_T, legs), stop_after = LDPC_KERNARG(ARGS_T, stop_after);
-        const auto scol_t = global_ptr(LDPC_EDGE_RELAY_ARG(scol));
+        const auto scol_t = global_ptr(LDPC_EDGE_VARIANT_ARG(scol));
         for (int leg = 0; leg < legs; ++leg) {
             const gtab_t a_t = global_ptr(LDPC_KERNARG(ARGS_T, ag_s)) + (size_t)leg * (2 * R * 64);  // the leg's tables: a, then gamma
             const gtab_t g_t = a_t + R * 64;
@@ -149,8 +145,7 @@ __global__ void __launch_bounds__(64, edge_relay_waves(R)) bp_edge_relay_kernel(
             bool unsat = true;
             do {
                 ++it;
-                const double alpha = (a.ms_scaling_factor == 0.0) ? 1.0 - ldexp(1.0, -it) : a.ms_scaling_factor;
-                const int alo = __double2loint(alpha), ahi = __double2hiint(alpha), nhi = ahi ^ (int)0x80000000;
+                const AlphaWords al = alpha_words(a.ms_scaling_factor, it);
                 // ---- check pass: msg[r] (bit_to_check) -> msg[r] (check_to_bit), stored at the slot ----
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
@@ -163,14 +158,14 @@ __global__ void __launch_bounds__(64, edge_relay_waves(R)) bp_edge_relay_kernel(
                     int shi;  // high word of +-alpha: sign = row parity (syndrome included) + own
                     if (r < EDGE_V1) {
                         const uint64_t par = nibble_parity_low(neg ^ sy[r]);
-                        const int own = select_by_mask(ahi, nhi, neg);
+                        const int own = select_by_mask(al.hi, al.nhi, neg);
                         const int rowbit = select_by_mask(0, (int)0x80000000, par);
                         shi = own ^ __builtin_amdgcn_mov_dpp(rowbit, 0x00, 0xf, 0xf, true);  // quad_perm [0, 0, 0, 0]
                     } else {
                         const uint64_t flip = spread_nibble(nibble_parity_low(neg ^ sy[r])) ^ neg;
-                        shi = select_by_mask(ahi, nhi, flip);
+                        shi = select_by_mask(al.hi, al.nhi, flip);
                     }
-                    const double c = mag * __hiloint2double(shi, alo);
+                    const double c = mag * __hiloint2double(shi, al.lo);
                     msg[r] = c;
                     X[r * 64 + lane] = c;
                 }
@@ -219,8 +214,8 @@ __global__ void __launch_bounds__(64, edge_relay_waves(R)) bp_edge_relay_kernel(
             if (nsol == stop_after) break;
         }
         {
-            const auto ip = global_ptr(LDPC_EDGE_RELAY_ARG(iters));
-            const auto cp = global_ptr(LDPC_EDGE_RELAY_ARG(conv));
+            const auto ip = global_ptr(LDPC_EDGE_VARIANT_ARG(iters));
+            const auto cp = global_ptr(LDPC_EDGE_VARIANT_ARG(conv));
             if (lane == 0) {
                 if (ip) ip[b] = total;
                 if (cp) cp[b] = nsol > 0 ? 1 : 0;
@@ -228,9 +223,9 @@ __global__ void __launch_bounds__(64, edge_relay_waves(R)) bp_edge_relay_kernel(
         }
         __builtin_amdgcn_wave_barrier();  // (see bp_edge_kernel: the wavefront is whole before lane 0 pulls the next syndrome)
       }
-        if (!work_pool_next(LDPC_EDGE_RELAY_ARG(next), LDPC_EDGE_RELAY_ARG(dyn_base), LDPC_EDGE_RELAY_ARG(pool_per), LDPC_EDGE_RELAY_ARG(chunk), (int)LDPC_EDGE_RELAY_ARG(batch), lane, pool, b0, b1)) break;
+        if (!work_pool_next(LDPC_EDGE_VARIANT_ARG(next), LDPC_EDGE_VARIANT_ARG(dyn_base), LDPC_EDGE_VARIANT_ARG(pool_per), LDPC_EDGE_VARIANT_ARG(chunk), (int)LDPC_EDGE_VARIANT_ARG(batch), lane, pool, b0, b1)) break;
     }
-    if (lane == 0) clock_probe_end(LDPC_EDGE_RELAY_ARG(clk), clk_stamp);
+    if (lane == 0) clock_probe_end(LDPC_EDGE_VARIANT_ARG(clk), clk_stamp);
 }
 
 template <int R, int DC>
@@ -240,7 +235,6 @@ __global__ void __launch_bounds__(64, edge8_relay_waves(R, DC)) bp_edge8_relay_k
     typedef Edge8RelayArgs ARGS_T;  // (cold fields: LDPC_KERNARG, bp_device_common.h)
     static_assert(DC >= 2 && DC <= 4, "columns of 2 .. 4 entries");
     extern __shared__ __attribute__((aligned(16))) unsigned char edge_lds[];
-    typedef __attribute__((address_space(3))) double lds_f64;
     lds_f64 *X = (lds_f64 *)edge_lds;
     const int lane = threadIdx.x;
     __shared__ unsigned long long clk_stamp[2];
@@ -248,7 +242,6 @@ __global__ void __launch_bounds__(64, edge8_relay_waves(R, DC)) bp_edge8_relay_k
     const int m = a.m, n = a.n;
     constexpr int ZERO = R * 64;
     constexpr uint64_t LOW = 0x0101010101010101ull;
-    typedef __attribute__((address_space(1))) const double *gtab_t;
     constexpr bool KEEP = R <= EDGE8_MEM_KEEP;
 
     double prv[R], msg[R], av[KEEP ? R : 1], gv[KEEP ? R : 1];
@@ -266,12 +259,12 @@ __global__ void __launch_bounds__(64, edge8_relay_waves(R, DC)) bp_edge8_relay_k
     const double dbl_max = uniform_f64(DBL_MAX);
     if (lane == 0) { X[ZERO] = 0.0; X[ZERO + 1] = __builtin_inf(); }
 
-    int b0 = (int)blockIdx.x * LDPC_EDGE_RELAY_ARG(static_per), b1 = b0 + LDPC_EDGE_RELAY_ARG(static_per);
+    int b0 = (int)blockIdx.x * LDPC_EDGE_VARIANT_ARG(static_per), b1 = b0 + LDPC_EDGE_VARIANT_ARG(static_per);
     int pool = (int)(blockIdx.x & (WORK_POOLS - 1));
     for (;;) {
       for (int b = b0; b < b1; ++b) {
         {   // M = L0 (see bp_edge_relay_kernel)
-            const auto l0_t = global_ptr(LDPC_EDGE_RELAY_ARG(prior_s));
+            const auto l0_t = global_ptr(LDPC_EDGE_VARIANT_ARG(prior_s));
 #pragma unroll
             for (int r = 0; r < R; ++r) msg[r] = l0_t[r * 64 + lane];  // initialise_log_domain_bp (bp.hpp:147-157); phantom lanes: +inf
         }
@@ -279,7 +272,7 @@ __global__ void __launch_bounds__(64, edge8_relay_waves(R, DC)) bp_edge8_relay_k
         for (int r = 0; r < R; ++r) prv[r] = msg[r];
         uint64_t sy[R];
         bool never = false;
-        const auto sb = global_ptr(LDPC_EDGE_RELAY_ARG(synd)) + (int64_t)b * m;
+        const auto sb = global_ptr(LDPC_EDGE_VARIANT_ARG(synd)) + (int64_t)b * m;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int row = r * 8 + (lane >> 3);
@@ -291,7 +284,7 @@ __global__ void __launch_bounds__(64, edge8_relay_waves(R, DC)) bp_edge8_relay_k
         double best = __builtin_inf();
         int nsol = 0, total = 0;
         const int legs = LDPC_KERNARG(ARGS_T, legs), stop_after = LDPC_KERNARG(ARGS_T, stop_after);
-        const auto scol_t = global_ptr(LDPC_EDGE_RELAY_ARG(scol));
+        const auto scol_t = global_ptr(LDPC_EDGE_VARIANT_ARG(scol));
         for (int leg = 0; leg < legs; ++leg) {
             const gtab_t a_t = global_ptr(LDPC_KERNARG(ARGS_T, ag_s)) + (size_t)leg * (2 * R * 64);  // the leg's tables: a, then gamma
             const gtab_t g_t = a_t + R * 64;
@@ -313,8 +306,7 @@ __global__ void __launch_bounds__(64, edge8_relay_waves(R, DC)) bp_edge8_relay_k
             bool unsat = true;
             do {
                 ++it;
-                const double alpha = (a.ms_scaling_factor == 0.0) ? 1.0 - ldexp(1.0, -it) : a.ms_scaling_factor;
-                const int alo = __double2loint(alpha), ahi = __double2hiint(alpha), nhi = ahi ^ (int)0x80000000;
+                const AlphaWords al = alpha_words(a.ms_scaling_factor, it);
                 // ---- check pass (bp.hpp:220-273): minimum over the seven other lanes of the group, sign by the group's parity ----
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
@@ -328,7 +320,7 @@ __global__ void __launch_bounds__(64, edge8_relay_waves(R, DC)) bp_edge8_relay_k
                     const double otherquad = xor4(quadmin);
                     const double mag = fmin_pos(min_abs(inquad, otherquad), dbl_max);  // the seven other entries, from DBL_MAX down
                     const uint64_t flip = spread_byte(byte_parity_low(neg ^ sy[r])) ^ neg;
-                    const double c = mag * __hiloint2double(select_by_mask(ahi, nhi, flip), alo);
+                    const double c = mag * __hiloint2double(select_by_mask(al.hi, al.nhi, flip), al.lo);
                     msg[r] = c;
                     X[r * 64 + lane] = c;
                 }
@@ -370,8 +362,8 @@ __global__ void __launch_bounds__(64, edge8_relay_waves(R, DC)) bp_edge8_relay_k
             if (nsol == stop_after) break;
         }
         {
-            const auto ip = global_ptr(LDPC_EDGE_RELAY_ARG(iters));
-            const auto cp = global_ptr(LDPC_EDGE_RELAY_ARG(conv));
+            const auto ip = global_ptr(LDPC_EDGE_VARIANT_ARG(iters));
+            const auto cp = global_ptr(LDPC_EDGE_VARIANT_ARG(conv));
             if (lane == 0) {
                 if (ip) ip[b] = total;
                 if (cp) cp[b] = nsol > 0 ? 1 : 0;
@@ -379,9 +371,8 @@ __global__ void __launch_bounds__(64, edge8_relay_waves(R, DC)) bp_edge8_relay_k
         }
         __builtin_amdgcn_wave_barrier();  // (see bp_edge_kernel)
       }
-        if (!work_pool_next(LDPC_EDGE_RELAY_ARG(next), LDPC_EDGE_RELAY_ARG(dyn_base), LDPC_EDGE_RELAY_ARG(pool_per), LDPC_EDGE_RELAY_ARG(chunk), (int)LDPC_EDGE_RELAY_ARG(batch), lane, pool, b0, b1)) break;
+        if (!work_pool_next(LDPC_EDGE_VARIANT_ARG(next), LDPC_EDGE_VARIANT_ARG(dyn_base), LDPC_EDGE_VARIANT_ARG(pool_per), LDPC_EDGE_VARIANT_ARG(chunk), (int)LDPC_EDGE_VARIANT_ARG(batch), lane, pool, b0, b1)) break;
     }
-    if (lane == 0) clock_probe_end(LDPC_EDGE_RELAY_ARG(clk), clk_stamp);
+    if (lane == 0) clock_probe_end(LDPC_EDGE_VARIANT_ARG(clk), clk_stamp);
 }
 #undef LDPC_EDGE_RELAY_LEG_END
-#undef LDPC_EDGE_RELAY_ARG

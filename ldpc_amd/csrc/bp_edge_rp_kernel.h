@@ -34,15 +34,12 @@ typedef void (*Edge8RpKernel)(const Edge8RpArgs);
 EdgeRpKernel edge_rp_kernel(int rounds);
 Edge8RpKernel edge8_rp_kernel(int rounds, int dc);
 
-#define LDPC_EDGE_RP_ARG(field) LDPC_KERNARG(ARGS_T, e.field)
-
 template <int R>
 __global__ void __launch_bounds__(64, 4) bp_edge_rp_kernel(const EdgeRpArgs ra) {
     using namespace edge_detail;
     const EdgeArgs &a = ra.e;
     typedef EdgeRpArgs ARGS_T;  // (cold fields: LDPC_KERNARG, bp_device_common.h)
     extern __shared__ __attribute__((aligned(16))) unsigned char edge_lds[];
-    typedef __attribute__((address_space(3))) double lds_f64;
     lds_f64 *X = (lds_f64 *)edge_lds;  // [R * 64] check_to_bit of every slot, [R * 64] = +0.0 for good
     const int lane = threadIdx.x;
     __shared__ unsigned long long clk_stamp[2];
@@ -65,18 +62,18 @@ __global__ void __launch_bounds__(64, 4) bp_edge_rp_kernel(const EdgeRpArgs ra) 
     if (lane == 0) { X[ZERO] = 0.0; X[ZERO + 1] = __builtin_inf(); }
 
     // Work: the static share, then chunks from the pooled work counters (work_pool_next, bp_device_common.h)
-    int b0 = (int)blockIdx.x * LDPC_EDGE_RP_ARG(static_per), b1 = b0 + LDPC_EDGE_RP_ARG(static_per);
+    int b0 = (int)blockIdx.x * LDPC_EDGE_VARIANT_ARG(static_per), b1 = b0 + LDPC_EDGE_VARIANT_ARG(static_per);
     int pool = (int)(blockIdx.x & (WORK_POOLS - 1));
     for (;;) {
       for (int b = b0; b < b1; ++b) {
         // THIS syndrome's priors (b is wave-uniform: whichever row the wavefront pulled, never its slot's or its predecessor's)
         const auto pb = global_ptr(LDPC_KERNARG(ARGS_T, rowp)) + (int64_t)b * n;
-        const auto scol_t = global_ptr(LDPC_EDGE_RP_ARG(scol));
+        const auto scol_t = global_ptr(LDPC_EDGE_VARIANT_ARG(scol));
 #pragma unroll
         for (int r = 0; r < R; ++r) prv[r] = paddr[r] == ZERO + 1 ? __builtin_inf() : pb[scol_t[r * 64 + lane]];  // phantom lanes: +inf (bp_edge_kernel.h); theirs is column 0 in the table
         uint64_t sy[R];
         bool never = false;
-        const auto sb = global_ptr(LDPC_EDGE_RP_ARG(synd)) + (int64_t)b * m;
+        const auto sb = global_ptr(LDPC_EDGE_VARIANT_ARG(synd)) + (int64_t)b * m;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int row = r * 16 + (lane >> 2);
@@ -91,8 +88,7 @@ __global__ void __launch_bounds__(64, 4) bp_edge_rp_kernel(const EdgeRpArgs ra) 
         bool unsat = true;
         do {
             ++it;
-            const double alpha = (a.ms_scaling_factor == 0.0) ? 1.0 - ldexp(1.0, -it) : a.ms_scaling_factor;
-            const int alo = __double2loint(alpha), ahi = __double2hiint(alpha), nhi = ahi ^ (int)0x80000000;
+            const AlphaWords al = alpha_words(a.ms_scaling_factor, it);
             // ---- check pass: msg[r] (bit_to_check) -> msg[r] (check_to_bit), stored at the slot ----
 #pragma unroll
             for (int r = 0; r < R; ++r) {
@@ -105,14 +101,14 @@ __global__ void __launch_bounds__(64, 4) bp_edge_rp_kernel(const EdgeRpArgs ra) 
                 int shi;  // high word of +-alpha: sign = row parity (syndrome included) + own
                 if (r < EDGE_V1) {
                     const uint64_t par = nibble_parity_low(neg ^ sy[r]);
-                    const int own = select_by_mask(ahi, nhi, neg);
+                    const int own = select_by_mask(al.hi, al.nhi, neg);
                     const int rowbit = select_by_mask(0, (int)0x80000000, par);
                     shi = own ^ __builtin_amdgcn_mov_dpp(rowbit, 0x00, 0xf, 0xf, true);  // quad_perm [0, 0, 0, 0]
                 } else {
                     const uint64_t flip = spread_nibble(nibble_parity_low(neg ^ sy[r])) ^ neg;
-                    shi = select_by_mask(ahi, nhi, flip);
+                    shi = select_by_mask(al.hi, al.nhi, flip);
                 }
-                const double c = mag * __hiloint2double(shi, alo);
+                const double c = mag * __hiloint2double(shi, al.lo);
                 msg[r] = c;
                 X[r * 64 + lane] = c;
             }
@@ -159,8 +155,8 @@ __global__ void __launch_bounds__(64, 4) bp_edge_rp_kernel(const EdgeRpArgs ra) 
             if ((k0[r] >> lane) & 1ull) X[j] = msg[r];
         }
         {
-            const auto dp = global_ptr(LDPC_EDGE_RP_ARG(decoding)) + (int64_t)b * n;
-            auto lp = global_ptr(LDPC_EDGE_RP_ARG(llr));
+            const auto dp = global_ptr(LDPC_EDGE_VARIANT_ARG(decoding)) + (int64_t)b * n;
+            auto lp = global_ptr(LDPC_EDGE_VARIANT_ARG(llr));
             if (lp) lp += (int64_t)b * n;
             for (int j = lane; j < n; j += 64) {
                 const double l0 = X[j];
@@ -169,8 +165,8 @@ __global__ void __launch_bounds__(64, 4) bp_edge_rp_kernel(const EdgeRpArgs ra) 
             }
         }
         {
-            const auto ip = global_ptr(LDPC_EDGE_RP_ARG(iters));
-            const auto cp = global_ptr(LDPC_EDGE_RP_ARG(conv));
+            const auto ip = global_ptr(LDPC_EDGE_VARIANT_ARG(iters));
+            const auto cp = global_ptr(LDPC_EDGE_VARIANT_ARG(conv));
             if (lane == 0) {
                 if (ip) ip[b] = it;
                 if (cp) cp[b] = unsat ? 0 : 1;
@@ -178,9 +174,9 @@ __global__ void __launch_bounds__(64, 4) bp_edge_rp_kernel(const EdgeRpArgs ra) 
         }
         __builtin_amdgcn_wave_barrier();  // (see bp_edge_kernel: the wavefront is whole before lane 0 pulls the next syndrome)
       }
-        if (!work_pool_next(LDPC_EDGE_RP_ARG(next), LDPC_EDGE_RP_ARG(dyn_base), LDPC_EDGE_RP_ARG(pool_per), LDPC_EDGE_RP_ARG(chunk), (int)LDPC_EDGE_RP_ARG(batch), lane, pool, b0, b1)) break;
+        if (!work_pool_next(LDPC_EDGE_VARIANT_ARG(next), LDPC_EDGE_VARIANT_ARG(dyn_base), LDPC_EDGE_VARIANT_ARG(pool_per), LDPC_EDGE_VARIANT_ARG(chunk), (int)LDPC_EDGE_VARIANT_ARG(batch), lane, pool, b0, b1)) break;
     }
-    if (lane == 0) clock_probe_end(LDPC_EDGE_RP_ARG(clk), clk_stamp);
+    if (lane == 0) clock_probe_end(LDPC_EDGE_VARIANT_ARG(clk), clk_stamp);
 }
 
 template <int R, int DC>
@@ -190,7 +186,6 @@ __global__ void __launch_bounds__(64, 4) bp_edge8_rp_kernel(const Edge8RpArgs ra
     typedef Edge8RpArgs ARGS_T;  // (cold fields: LDPC_KERNARG, bp_device_common.h)
     static_assert(DC >= 2 && DC <= 4, "columns of 2 .. 4 entries");
     extern __shared__ __attribute__((aligned(16))) unsigned char edge_lds[];
-    typedef __attribute__((address_space(3))) double lds_f64;
     lds_f64 *X = (lds_f64 *)edge_lds;
     const int lane = threadIdx.x;
     __shared__ unsigned long long clk_stamp[2];
@@ -214,18 +209,18 @@ __global__ void __launch_bounds__(64, 4) bp_edge8_rp_kernel(const Edge8RpArgs ra
     const double dbl_max = uniform_f64(DBL_MAX);
     if (lane == 0) { X[ZERO] = 0.0; X[ZERO + 1] = __builtin_inf(); }
 
-    int b0 = (int)blockIdx.x * LDPC_EDGE_RP_ARG(static_per), b1 = b0 + LDPC_EDGE_RP_ARG(static_per);
+    int b0 = (int)blockIdx.x * LDPC_EDGE_VARIANT_ARG(static_per), b1 = b0 + LDPC_EDGE_VARIANT_ARG(static_per);
     int pool = (int)(blockIdx.x & (WORK_POOLS - 1));
     for (;;) {
       for (int b = b0; b < b1; ++b) {
         // THIS syndrome's priors (see bp_edge_rp_kernel)
         const auto pb = global_ptr(LDPC_KERNARG(ARGS_T, rowp)) + (int64_t)b * n;
-        const auto scol_t = global_ptr(LDPC_EDGE_RP_ARG(scol));
+        const auto scol_t = global_ptr(LDPC_EDGE_VARIANT_ARG(scol));
 #pragma unroll
         for (int r = 0; r < R; ++r) prv[r] = caddr[r][0] == ZERO + 1 ? __builtin_inf() : pb[scol_t[r * 64 + lane]];  // phantom lanes (theirs is the dummy slot in the table): +inf
         uint64_t sy[R];
         bool never = false;
-        const auto sb = global_ptr(LDPC_EDGE_RP_ARG(synd)) + (int64_t)b * m;
+        const auto sb = global_ptr(LDPC_EDGE_VARIANT_ARG(synd)) + (int64_t)b * m;
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int row = r * 8 + (lane >> 3);
@@ -240,8 +235,7 @@ __global__ void __launch_bounds__(64, 4) bp_edge8_rp_kernel(const Edge8RpArgs ra
         bool unsat = true;
         do {
             ++it;
-            const double alpha = (a.ms_scaling_factor == 0.0) ? 1.0 - ldexp(1.0, -it) : a.ms_scaling_factor;
-            const int alo = __double2loint(alpha), ahi = __double2hiint(alpha), nhi = ahi ^ (int)0x80000000;
+            const AlphaWords al = alpha_words(a.ms_scaling_factor, it);
             // ---- check pass (bp.hpp:220-273): minimum over the seven other lanes of the group, sign by the group's parity ----
 #pragma unroll
             for (int r = 0; r < R; ++r) {
@@ -255,7 +249,7 @@ __global__ void __launch_bounds__(64, 4) bp_edge8_rp_kernel(const Edge8RpArgs ra
                 const double otherquad = xor4(quadmin);
                 const double mag = fmin_pos(min_abs(inquad, otherquad), dbl_max);  // the seven other entries, from DBL_MAX down
                 const uint64_t flip = spread_byte(byte_parity_low(neg ^ sy[r])) ^ neg;
-                const double c = mag * __hiloint2double(select_by_mask(ahi, nhi, flip), alo);
+                const double c = mag * __hiloint2double(select_by_mask(al.hi, al.nhi, flip), al.lo);
                 msg[r] = c;
                 X[r * 64 + lane] = c;
             }
@@ -298,8 +292,8 @@ __global__ void __launch_bounds__(64, 4) bp_edge8_rp_kernel(const Edge8RpArgs ra
 #pragma unroll
         for (int r = 0; r < R; ++r) X[scol_t[r * 64 + lane]] = msg[r];
         {
-            const auto dp = global_ptr(LDPC_EDGE_RP_ARG(decoding)) + (int64_t)b * n;
-            auto lp = global_ptr(LDPC_EDGE_RP_ARG(llr));
+            const auto dp = global_ptr(LDPC_EDGE_VARIANT_ARG(decoding)) + (int64_t)b * n;
+            auto lp = global_ptr(LDPC_EDGE_VARIANT_ARG(llr));
             if (lp) lp += (int64_t)b * n;
             for (int j = lane; j < n; j += 64) {
                 const double t = X[j];
@@ -308,8 +302,8 @@ __global__ void __launch_bounds__(64, 4) bp_edge8_rp_kernel(const Edge8RpArgs ra
             }
         }
         {
-            const auto ip = global_ptr(LDPC_EDGE_RP_ARG(iters));
-            const auto cp = global_ptr(LDPC_EDGE_RP_ARG(conv));
+            const auto ip = global_ptr(LDPC_EDGE_VARIANT_ARG(iters));
+            const auto cp = global_ptr(LDPC_EDGE_VARIANT_ARG(conv));
             if (lane == 0) {
                 if (ip) ip[b] = it;
                 if (cp) cp[b] = unsat ? 0 : 1;
@@ -317,8 +311,7 @@ __global__ void __launch_bounds__(64, 4) bp_edge8_rp_kernel(const Edge8RpArgs ra
         }
         __builtin_amdgcn_wave_barrier();  // (see bp_edge_kernel)
       }
-        if (!work_pool_next(LDPC_EDGE_RP_ARG(next), LDPC_EDGE_RP_ARG(dyn_base), LDPC_EDGE_RP_ARG(pool_per), LDPC_EDGE_RP_ARG(chunk), (int)LDPC_EDGE_RP_ARG(batch), lane, pool, b0, b1)) break;
+        if (!work_pool_next(LDPC_EDGE_VARIANT_ARG(next), LDPC_EDGE_VARIANT_ARG(dyn_base), LDPC_EDGE_VARIANT_ARG(pool_per), LDPC_EDGE_VARIANT_ARG(chunk), (int)LDPC_EDGE_VARIANT_ARG(batch), lane, pool, b0, b1)) break;
     }
-    if (lane == 0) clock_probe_end(LDPC_EDGE_RP_ARG(clk), clk_stamp);
+    if (lane == 0) clock_probe_end(LDPC_EDGE_VARIANT_ARG(clk), clk_stamp);
 }
-#undef LDPC_EDGE_RP_ARG

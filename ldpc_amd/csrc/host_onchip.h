@@ -390,12 +390,13 @@ static EdgePlan plan_edge(const ldpc_hip_bp *h) {
     std::vector<char> seen((size_t)h->n, 0);  // a column without entries has no lane to write its outputs
     for (int32_t j : h->h_col_idx) seen[(size_t)j] = 1;
     for (char c : seen) if (!c) return p;
-#define LDPC_EDGE_ROW(...) {nullptr, bp_edge_kernel<1, __VA_ARGS__>, bp_edge_kernel<2, __VA_ARGS__>, bp_edge_kernel<3, __VA_ARGS__>, bp_edge_kernel<4, __VA_ARGS__>, \
-        bp_edge_kernel<5, __VA_ARGS__>, bp_edge_kernel<6, __VA_ARGS__>, bp_edge_kernel<7, __VA_ARGS__>, bp_edge_kernel<8, __VA_ARGS__>, bp_edge_kernel<9, __VA_ARGS__>, \
-        bp_edge_kernel<10, __VA_ARGS__>, bp_edge_kernel<11, __VA_ARGS__>, bp_edge_kernel<12, __VA_ARGS__>, bp_edge_kernel<13, __VA_ARGS__>, bp_edge_kernel<14, __VA_ARGS__>, \
-        bp_edge_kernel<15, __VA_ARGS__>, bp_edge_kernel<16, __VA_ARGS__>}
-    static void (*const kerns[3][17])(const EdgeArgs) = {LDPC_EDGE_ROW(false), LDPC_EDGE_ROW(true), LDPC_EDGE_ROW(true, true)};
-#undef LDPC_EDGE_ROW
+#define LDPC_GENERAL(R) bp_edge_kernel<R, false>,
+#define LDPC_UNIFORM(R) bp_edge_kernel<R, true>,
+#define LDPC_NOCLAMP(R) bp_edge_kernel<R, true, true>,
+    static void (*const kerns[3][17])(const EdgeArgs) = {{nullptr, LDPC_EDGE_LADDER(LDPC_GENERAL)}, {nullptr, LDPC_EDGE_LADDER(LDPC_UNIFORM)}, {nullptr, LDPC_EDGE_LADDER(LDPC_NOCLAMP)}};
+#undef LDPC_GENERAL
+#undef LDPC_UNIFORM
+#undef LDPC_NOCLAMP
     p.uniform = true;
     for (int j = 1; j < h->n && p.uniform; ++j)
         p.uniform = std::memcmp(&h->channel_probs[(size_t)j], &h->channel_probs[0], sizeof(double)) == 0;
@@ -411,6 +412,11 @@ static EdgePlan plan_edge(const ldpc_hip_bp *h) {
 __global__ void edge_prior_kernel(const double *llr0, const int32_t *scol, const uint8_t *kind, int slots, double *out) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s < slots) out[s] = kind[s] ? llr0[scol[s]] : __builtin_inf();  // phantom lanes: +inf (bp_edge_kernel.h)
+}
+// h->d_llr0 per slot into h->e_prior, before every launch that reads it (the priors may have changed since the last call: ldpc_hip_bp_set_channel)
+static void launch_edge_prior(ldpc_hip_bp *h, int slots) {
+    LDPC_LAUNCH(edge_prior_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, h->stream, h->d_llr0, (const int32_t *)h->e_scol.p,
+                (const uint8_t *)h->e_kind.p, slots, (double *)h->e_prior.p);
 }
 
 // slot tables of bp_edge_kernel: entry k of row i sits in slot 4 i + k (see bp_edge_kernel.h)
@@ -459,36 +465,50 @@ static int edge_work_split(ldpc_hip_bp *h, int rounds, int64_t batch, int64_t gr
     return LDPC_HIP_OK;
 }
 
-static int decode_edge(ldpc_hip_bp *h, const EdgePlan &p, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr,
-                       int32_t *iters, uint8_t *conv) {
-    int rc;
-    if ((rc = ensure_edge_tables(h, p))) return rc;
-    const int slots = p.rounds * 64;
-    // (the priors may have changed since the last call: ldpc_hip_bp_set_channel)
-    LDPC_LAUNCH(edge_prior_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, h->stream, h->d_llr0, (const int32_t *)h->e_scol.p,
-                       (const uint8_t *)h->e_kind.p, slots, (double *)h->e_prior.p);
-    EdgeArgs a = {};
+// what a decode is given (decode_onchip and its kin hand it on): device pointers, on h->stream
+struct EdgeIo {
+    const uint8_t *synd;
+    int64_t batch;
+    uint8_t *decoding;
+    double *llr;
+    int32_t *iters;
+    uint8_t *conv;
+};
+
+// The launch of EVERY lane = edge kernel -- FP64 and FP32, rows in four and in eight lanes, plain, row priors, memory, Relay-BP.  `args` is the
+// kernel's argument block and `a` the EdgeArgs / Edge8Args / EdgeF32Args / Edge8F32Args in it (the plain kernels: args itself); the caller has set
+// what is its own -- partner / cpos, the priors, a variant's tables -- and launched the kernels that fill them.  Here: the fields all share, one
+// wavefront per workgroup and as many of them resident as LDS (`dyn` bytes and the kernels' few static ones, of 160 KiB) and the registers (the
+// wavefronts per SIMD the instantiation was compiled for) allow, the work split, the launch between the two timing events.
+template <class KARGS, class EARGS>
+static int launch_edge(ldpc_hip_bp *h, void (*kern)(const KARGS), KARGS &args, EARGS &a, int rounds, size_t dyn, int waves_per_simd, const EdgeIo &io) {
     a.m = h->m; a.n = h->n; a.max_iter = h->max_iter;
     a.ms_scaling_factor = h->ms_scaling_factor;
-    a.batch = batch;
-    a.prior_s = (const double *)h->e_prior.p; a.partner = (const uint16_t *)h->e_partner.p;
-    a.prior_u = std::log((1 - h->channel_probs[0]) / h->channel_probs[0]);  // as upload_priors (bp.hpp:150-151); read by the uniform form only
+    a.batch = io.batch;
     a.kind = (const uint8_t *)h->e_kind.p; a.scol = (const int32_t *)h->e_scol.p;
-    a.synd = synd; a.decoding = decoding; a.llr = llr; a.iters = iters; a.conv = conv;
-    const size_t dyn = edge_lds_bytes(p.rounds);
-    // one wavefront per workgroup, as many resident as registers (4 or 5 per SIMD) and LDS allow
+    a.synd = io.synd; a.decoding = io.decoding; a.llr = io.llr; a.iters = io.iters; a.conv = io.conv;
     int64_t per_cu = (int64_t)((160u * 1024u) / (dyn + 64));
-    const int64_t by_regs = p.uniform ? 20 : 16;
-    if (per_cu > by_regs) per_cu = by_regs;
-    int64_t groups = batch < 256 * per_cu ? batch : 256 * per_cu;
-    if ((rc = edge_work_split(h, p.rounds, batch, groups, a))) return rc;
+    if (per_cu > 4 * (int64_t)waves_per_simd) per_cu = 4 * (int64_t)waves_per_simd;
+    const int64_t groups = io.batch < 256 * per_cu ? io.batch : 256 * per_cu;
+    int rc;
+    if ((rc = edge_work_split(h, rounds, io.batch, groups, a))) return rc;
     h->accumulated_ms = 0.f;
     HIPCHK(hipEventRecord(h->ev0, h->stream));
-    LDPC_LAUNCH(p.kern, dim3((unsigned)groups), dim3(64), (unsigned)dyn, h->stream, a);
+    LDPC_LAUNCH(kern, dim3((unsigned)groups), dim3(64), (unsigned)dyn, h->stream, args);
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     h->timed = true;
     HIPCHK(hipGetLastError());
     return LDPC_HIP_OK;
+}
+
+static int decode_edge(ldpc_hip_bp *h, const EdgePlan &p, const EdgeIo &io) {
+    int rc;
+    if ((rc = ensure_edge_tables(h, p))) return rc;
+    launch_edge_prior(h, p.rounds * 64);
+    EdgeArgs a = {};
+    a.prior_s = (const double *)h->e_prior.p; a.partner = (const uint16_t *)h->e_partner.p;
+    a.prior_u = std::log((1 - h->channel_probs[0]) / h->channel_probs[0]);  // as upload_priors (bp.hpp:150-151); read by the uniform form only
+    return launch_edge(h, p.kern, a, a, p.rounds, edge_lds_bytes(p.rounds), p.uniform ? 5 : 4, io);  // (__launch_bounds__(64, UNIFORM ? 5 : 4))
 }
 
 // ---- bp_edge8_kernel (min-sum, lane = edge, rows in 8-lane groups): rows <= 8, columns 1 .. 4 entries, 8 m <= 64 R slots ----
@@ -504,10 +524,10 @@ static Edge8Plan plan_edge8(const ldpc_hip_bp *h) {
     if (h->max_row_deg > 8 || h->max_col_deg > 4 || h->n > 65535) return p;
     const int dc = h->max_col_deg <= 3 ? 3 : 4;
     const int need = (8 * h->m + 63) / 64;
-    static const int r3[] = {2, 3, 4, 5, 6, 7, 8, 9, 10, 12}, r4[] = {2, 3, 4, 5, 6, 7, 8, 9};
-    int rounds = 0;
-    for (int v : r3) if (dc == 3 && !rounds && v >= need) rounds = v;
-    for (int v : r4) if (dc == 4 && !rounds && v >= need) rounds = v;
+    int rounds = 0;  // the first rung of the column weight (they ascend) that holds the code
+#define LDPC_RUNG(R, C) if (dc == C && !rounds && R >= need) rounds = R;
+    LDPC_EDGE8_LADDER(LDPC_RUNG)
+#undef LDPC_RUNG
     if (!rounds) return p;
     std::vector<char> seen((size_t)h->n, 0);  // a column without entries has no lane to write its outputs
     for (int32_t j : h->h_col_idx) seen[(size_t)j] = 1;
@@ -516,8 +536,7 @@ static Edge8Plan plan_edge8(const ldpc_hip_bp *h) {
     for (int j = 1; j < h->n && p.uniform; ++j)
         p.uniform = std::memcmp(&h->channel_probs[(size_t)j], &h->channel_probs[0], sizeof(double)) == 0;
 #define LDPC_E8(R, C) if (rounds == R && dc == C) p.kern = p.uniform ? bp_edge8_kernel<R, C, true> : bp_edge8_kernel<R, C, false>;
-    LDPC_E8(2, 3) LDPC_E8(3, 3) LDPC_E8(4, 3) LDPC_E8(5, 3) LDPC_E8(6, 3) LDPC_E8(7, 3) LDPC_E8(8, 3) LDPC_E8(9, 3) LDPC_E8(10, 3) LDPC_E8(12, 3)
-    LDPC_E8(2, 4) LDPC_E8(3, 4) LDPC_E8(4, 4) LDPC_E8(5, 4) LDPC_E8(6, 4) LDPC_E8(7, 4) LDPC_E8(8, 4) LDPC_E8(9, 4)
+    LDPC_EDGE8_LADDER(LDPC_E8)
 #undef LDPC_E8
     p.rounds = rounds;
     p.dc = dc;
@@ -555,34 +574,14 @@ static int ensure_edge8_tables(ldpc_hip_bp *h, const Edge8Plan &p) {
     return LDPC_HIP_OK;
 }
 
-static int decode_edge8(ldpc_hip_bp *h, const Edge8Plan &p, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr,
-                        int32_t *iters, uint8_t *conv) {
+static int decode_edge8(ldpc_hip_bp *h, const Edge8Plan &p, const EdgeIo &io) {
     int rc;
     if ((rc = ensure_edge8_tables(h, p))) return rc;
-    const int slots = p.rounds * 64;
-    LDPC_LAUNCH(edge_prior_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, h->stream, h->d_llr0, (const int32_t *)h->e_scol.p,
-                       (const uint8_t *)h->e_kind.p, slots, (double *)h->e_prior.p);
+    launch_edge_prior(h, p.rounds * 64);
     Edge8Args a = {};
-    a.m = h->m; a.n = h->n; a.max_iter = h->max_iter;
-    a.ms_scaling_factor = h->ms_scaling_factor;
-    a.batch = batch;
     a.prior_s = (const double *)h->e_prior.p; a.cpos = (const uint16_t *)h->e_partner.p;
     a.prior_u = std::log((1 - h->channel_probs[0]) / h->channel_probs[0]);
-    a.kind = (const uint8_t *)h->e_kind.p; a.scol = (const int32_t *)h->e_scol.p;
-    a.synd = synd; a.decoding = decoding; a.llr = llr; a.iters = iters; a.conv = conv;
-    const size_t dyn = edge_lds_bytes(p.rounds);
-    int64_t per_cu = (int64_t)((160u * 1024u) / (dyn + 64));
-    const int64_t by_regs = p.uniform ? 20 : 16;
-    if (per_cu > by_regs) per_cu = by_regs;
-    int64_t groups = batch < 256 * per_cu ? batch : 256 * per_cu;
-    if ((rc = edge_work_split(h, p.rounds, batch, groups, a))) return rc;
-    h->accumulated_ms = 0.f;
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    LDPC_LAUNCH(p.kern, dim3((unsigned)groups), dim3(64), (unsigned)dyn, h->stream, a);
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    HIPCHK(hipGetLastError());
-    return LDPC_HIP_OK;
+    return launch_edge(h, p.kern, a, a, p.rounds, edge_lds_bytes(p.rounds), p.uniform ? 5 : 4, io);
 }
 
 // ---- the same two families with FP32 messages (bp_edge_f32_kernel.h; instantiated in tu_onchip_f32.hip): the float32 message mode's on-chip route ----
@@ -594,54 +593,32 @@ __global__ void edge_prior_f32_kernel(const double *llr0, const int32_t *scol, c
     if (s < slots) out[s] = kind[s] ? (float)llr0[scol[s]] : __builtin_inff();  // one rounding (v_cvt_f32_f64); phantom lanes: +inf
 }
 
-// what decode_edge_f32 and decode_edge8_f32 share: the per-slot priors, the work split, the launch between the timing events
+// what decode_edge_f32 and decode_edge8_f32 share: the per-slot priors as floats, then launch_edge
 template <class ARGS>
-static int launch_edge_f32(ldpc_hip_bp *h, void (*kern)(const ARGS), int rounds, int waves_per_simd, int64_t batch, ARGS &a) {
+static int launch_edge_f32(ldpc_hip_bp *h, void (*kern)(const ARGS), int rounds, int waves_per_simd, ARGS &a, const EdgeIo &io) {
     if (!kern) return fail(LDPC_HIP_ERR_UNSUPPORTED, "float32 messages: no on-chip kernel was built for %d rounds", rounds);
     const int slots = rounds * 64;
     LDPC_LAUNCH(edge_prior_f32_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, h->stream, h->d_llr0, (const int32_t *)h->e_scol.p,
                        (const uint8_t *)h->e_kind.p, slots, (float *)h->e_prior.p);
-    a.m = h->m; a.n = h->n; a.max_iter = h->max_iter;
-    a.ms_scaling_factor = h->ms_scaling_factor;
-    a.batch = batch;
     a.prior_s = (const float *)h->e_prior.p;
     a.prior_u = (float)std::log((1 - h->channel_probs[0]) / h->channel_probs[0]);  // the FP64 prior of upload_priors, rounded once; read by the uniform form only
-    a.kind = (const uint8_t *)h->e_kind.p; a.scol = (const int32_t *)h->e_scol.p;
-    const size_t dyn = edge_f32_lds_bytes(rounds);
-    // one wavefront per workgroup, as many resident as registers (edge_f32_waves / edge8_f32_waves per SIMD) and LDS allow
-    int64_t per_cu = (int64_t)((160u * 1024u) / (dyn + 64));
-    const int64_t by_regs = 4 * (int64_t)waves_per_simd;
-    if (per_cu > by_regs) per_cu = by_regs;
-    const int64_t groups = batch < 256 * per_cu ? batch : 256 * per_cu;
-    int rc;
-    if ((rc = edge_work_split(h, rounds, batch, groups, a))) return rc;
-    h->accumulated_ms = 0.f;  // (as decode_edge / decode_edge8: one launch between the two events)
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    LDPC_LAUNCH(kern, dim3((unsigned)groups), dim3(64), (unsigned)dyn, h->stream, a);
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    HIPCHK(hipGetLastError());
-    return LDPC_HIP_OK;
+    return launch_edge(h, kern, a, a, rounds, edge_f32_lds_bytes(rounds), waves_per_simd, io);  // (edge_f32_waves / edge8_f32_waves)
 }
 
-static int decode_edge_f32(ldpc_hip_bp *h, const EdgePlan &p, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr,
-                           int32_t *iters, uint8_t *conv) {
+static int decode_edge_f32(ldpc_hip_bp *h, const EdgePlan &p, const EdgeIo &io) {
     int rc;
     if ((rc = ensure_edge_tables(h, p))) return rc;
     EdgeF32Args a = {};
     a.partner = (const uint16_t *)h->e_partner.p;
-    a.synd = synd; a.decoding = decoding; a.llr = llr; a.iters = iters; a.conv = conv;
-    return launch_edge_f32(h, edge_f32_kernel(p.rounds, p.uniform, p.noclamp), p.rounds, edge_f32_waves(p.rounds), batch, a);
+    return launch_edge_f32(h, edge_f32_kernel(p.rounds, p.uniform, p.noclamp), p.rounds, edge_f32_waves(p.rounds), a, io);
 }
 
-static int decode_edge8_f32(ldpc_hip_bp *h, const Edge8Plan &p, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr,
-                            int32_t *iters, uint8_t *conv) {
+static int decode_edge8_f32(ldpc_hip_bp *h, const Edge8Plan &p, const EdgeIo &io) {
     int rc;
     if ((rc = ensure_edge8_tables(h, p))) return rc;
     Edge8F32Args a = {};
     a.cpos = (const uint16_t *)h->e_partner.p;
-    a.synd = synd; a.decoding = decoding; a.llr = llr; a.iters = iters; a.conv = conv;
-    return launch_edge_f32(h, edge8_f32_kernel(p.rounds, p.dc, p.uniform), p.rounds, edge8_f32_waves(p.rounds, p.dc, p.uniform), batch, a);
+    return launch_edge_f32(h, edge8_f32_kernel(p.rounds, p.dc, p.uniform), p.rounds, edge8_f32_waves(p.rounds, p.dc, p.uniform), a, io);
 }
 
 // ---- the same two families with row priors (bp_edge_rp_kernel.h; instantiated in tu_onchip_rp.hip): ldpc_hip_*_decode_batch_priors on the codes of plan_edge / plan_edge8 ----
@@ -649,51 +626,31 @@ static int decode_edge8_f32(ldpc_hip_bp *h, const Edge8Plan &p, const uint8_t *s
 // SIMD), the timing events.  The priors: h->row_probs [batch][n] -> h->rowp_llr [batch][n] log-ratios, whole batch (row_priors_rowmajor_kernel,
 // io_kernels.h); e_prior is neither written nor read, so the next plain call finds it as its own last launch left it (and rewrites it anyway).
 template <class ARGS>
-static int launch_edge_rp(ldpc_hip_bp *h, void (*kern)(const ARGS), int rounds, int64_t batch, ARGS &ra) {
+static int launch_edge_rp(ldpc_hip_bp *h, void (*kern)(const ARGS), int rounds, ARGS &ra, const EdgeIo &io) {
     if (!kern) return fail(LDPC_HIP_ERR_UNSUPPORTED, "row priors: no lane = edge kernel was built for %d rounds", rounds);
     int rc;
-    const size_t items = (size_t)batch * (size_t)h->n;
+    const size_t items = (size_t)io.batch * (size_t)h->n;
     if ((rc = h->rowp_llr.ensure(sizeof(double) * items))) return rc;
     LDPC_LAUNCH(row_priors_rowmajor_kernel, flat_grid(items), dim3(256), 0, h->stream, h->row_probs, (int64_t)items, (double *)h->rowp_llr.p);
     HIPCHK(hipGetLastError());
     ra.rowp = (const double *)h->rowp_llr.p;
-    auto &a = ra.e;
-    a.m = h->m; a.n = h->n; a.max_iter = h->max_iter;
-    a.ms_scaling_factor = h->ms_scaling_factor;
-    a.batch = batch;
-    a.kind = (const uint8_t *)h->e_kind.p; a.scol = (const int32_t *)h->e_scol.p;
-    const size_t dyn = edge_lds_bytes(rounds);
-    int64_t per_cu = (int64_t)((160u * 1024u) / (dyn + 64));
-    if (per_cu > 16) per_cu = 16;  // (__launch_bounds__(64, 4): the general form's four wavefronts per SIMD)
-    const int64_t groups = batch < 256 * per_cu ? batch : 256 * per_cu;
-    if ((rc = edge_work_split(h, rounds, batch, groups, a))) return rc;
-    h->accumulated_ms = 0.f;
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    LDPC_LAUNCH(kern, dim3((unsigned)groups), dim3(64), (unsigned)dyn, h->stream, ra);
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    HIPCHK(hipGetLastError());
-    return LDPC_HIP_OK;
+    return launch_edge(h, kern, ra, ra.e, rounds, edge_lds_bytes(rounds), 4, io);  // (__launch_bounds__(64, 4): the general form's four wavefronts per SIMD)
 }
 
-static int decode_edge_rp(ldpc_hip_bp *h, const EdgePlan &p, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr,
-                          int32_t *iters, uint8_t *conv) {
+static int decode_edge_rp(ldpc_hip_bp *h, const EdgePlan &p, const EdgeIo &io) {
     int rc;
     if ((rc = ensure_edge_tables(h, p))) return rc;
     EdgeRpArgs ra = {};
     ra.e.partner = (const uint16_t *)h->e_partner.p;
-    ra.e.synd = synd; ra.e.decoding = decoding; ra.e.llr = llr; ra.e.iters = iters; ra.e.conv = conv;
-    return launch_edge_rp(h, edge_rp_kernel(p.rounds), p.rounds, batch, ra);
+    return launch_edge_rp(h, edge_rp_kernel(p.rounds), p.rounds, ra, io);
 }
 
-static int decode_edge8_rp(ldpc_hip_bp *h, const Edge8Plan &p, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr,
-                           int32_t *iters, uint8_t *conv) {
+static int decode_edge8_rp(ldpc_hip_bp *h, const Edge8Plan &p, const EdgeIo &io) {
     int rc;
     if ((rc = ensure_edge8_tables(h, p))) return rc;
     Edge8RpArgs ra = {};
     ra.e.cpos = (const uint16_t *)h->e_partner.p;
-    ra.e.synd = synd; ra.e.decoding = decoding; ra.e.llr = llr; ra.e.iters = iters; ra.e.conv = conv;
-    return launch_edge_rp(h, edge8_rp_kernel(p.rounds, p.dc), p.rounds, batch, ra);
+    return launch_edge_rp(h, edge8_rp_kernel(p.rounds, p.dc), p.rounds, ra, io);
 }
 
 // Row priors on the lane = edge kernels?  Debug switch EDGE_RP: 0 the slot kernel (bp_small_kernel<., ., true>), 1 bp_edge_rp_kernel /
@@ -718,60 +675,39 @@ __global__ void edge_mem_table_kernel(const double *ag, int n, const int32_t *sc
 }
 
 template <class ARGS>
-static int launch_edge_mem(ldpc_hip_bp *h, void (*kern)(const ARGS), int rounds, int waves_per_simd, int64_t batch, ARGS &ma) {
+static int launch_edge_mem(ldpc_hip_bp *h, void (*kern)(const ARGS), int rounds, int waves_per_simd, ARGS &ma, const EdgeIo &io) {
     if (!kern) return fail(LDPC_HIP_ERR_UNSUPPORTED, "memory min-sum: no lane = edge kernel was built for %d rounds", rounds);
     int rc;
     const int slots = rounds * 64;
     if ((rc = h->e_mem.ensure(sizeof(double) * 2 * (size_t)slots))) return rc;
-    const dim3 gt((unsigned)((slots + 255) / 256));
-    LDPC_LAUNCH(edge_prior_kernel, gt, dim3(256), 0, h->stream, h->d_llr0, (const int32_t *)h->e_scol.p, (const uint8_t *)h->e_kind.p, slots, (double *)h->e_prior.p);
-    LDPC_LAUNCH(edge_mem_table_kernel, gt, dim3(256), 0, h->stream, (const double *)h->mem_ag.p, h->n, (const int32_t *)h->e_scol.p, (const uint8_t *)h->e_kind.p,
-                slots, (double *)h->e_mem.p);
+    launch_edge_prior(h, slots);
+    LDPC_LAUNCH(edge_mem_table_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, h->stream, (const double *)h->mem_ag.p, h->n, (const int32_t *)h->e_scol.p,
+                (const uint8_t *)h->e_kind.p, slots, (double *)h->e_mem.p);
     HIPCHK(hipGetLastError());
     ma.a_s = (const double *)h->e_mem.p;
     ma.g_s = (const double *)h->e_mem.p + slots;
-    auto &a = ma.e;
-    a.m = h->m; a.n = h->n; a.max_iter = h->max_iter;
-    a.ms_scaling_factor = h->ms_scaling_factor;
-    a.batch = batch;
-    a.prior_s = (const double *)h->e_prior.p;
-    a.kind = (const uint8_t *)h->e_kind.p; a.scol = (const int32_t *)h->e_scol.p;
-    const size_t dyn = edge_lds_bytes(rounds);
-    int64_t per_cu = (int64_t)((160u * 1024u) / (dyn + 64));
-    if (per_cu > 4 * waves_per_simd) per_cu = 4 * waves_per_simd;  // (edge_mem_waves / edge8_mem_waves: what the instantiation was compiled for)
-    const int64_t groups = batch < 256 * per_cu ? batch : 256 * per_cu;
-    if ((rc = edge_work_split(h, rounds, batch, groups, a))) return rc;
-    h->accumulated_ms = 0.f;
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    LDPC_LAUNCH(kern, dim3((unsigned)groups), dim3(64), (unsigned)dyn, h->stream, ma);
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    HIPCHK(hipGetLastError());
-    return LDPC_HIP_OK;
+    ma.e.prior_s = (const double *)h->e_prior.p;
+    return launch_edge(h, kern, ma, ma.e, rounds, edge_lds_bytes(rounds), waves_per_simd, io);  // (edge_mem_waves / edge8_mem_waves)
 }
 
-static int decode_edge_mem(ldpc_hip_bp *h, const EdgePlan &p, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr,
-                           int32_t *iters, uint8_t *conv) {
+static int decode_edge_mem(ldpc_hip_bp *h, const EdgePlan &p, const EdgeIo &io) {
     int rc;
     if ((rc = ensure_edge_tables(h, p))) return rc;
     EdgeMemArgs ma = {};
     ma.e.partner = (const uint16_t *)h->e_partner.p;
-    ma.e.synd = synd; ma.e.decoding = decoding; ma.e.llr = llr; ma.e.iters = iters; ma.e.conv = conv;
-    return launch_edge_mem(h, edge_mem_kernel(p.rounds), p.rounds, edge_mem_waves(p.rounds), batch, ma);
+    return launch_edge_mem(h, edge_mem_kernel(p.rounds), p.rounds, edge_mem_waves(p.rounds), ma, io);
 }
 
-static int decode_edge8_mem(ldpc_hip_bp *h, const Edge8Plan &p, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr,
-                            int32_t *iters, uint8_t *conv) {
+static int decode_edge8_mem(ldpc_hip_bp *h, const Edge8Plan &p, const EdgeIo &io) {
     int rc;
     if ((rc = ensure_edge8_tables(h, p))) return rc;
     Edge8MemArgs ma = {};
     ma.e.cpos = (const uint16_t *)h->e_partner.p;
-    ma.e.synd = synd; ma.e.decoding = decoding; ma.e.llr = llr; ma.e.iters = iters; ma.e.conv = conv;
-    return launch_edge_mem(h, edge8_mem_kernel(p.rounds, p.dc), p.rounds, edge8_mem_waves(p.rounds, p.dc), batch, ma);
+    return launch_edge_mem(h, edge8_mem_kernel(p.rounds, p.dc), p.rounds, edge8_mem_waves(p.rounds, p.dc), ma, io);
 }
 
 // ---- the same two families as Relay-BP (bp_edge_relay_kernel.h; instantiated in tu_onchip_relay.hip): ldpc_hip_bp_set_relay on the codes of plan_edge / plan_edge8 ----
-// Everything is launch_edge_mem's -- the shared slot tables, e_prior, the work pools, the grid sizing (by the wavefronts per SIMD the instantiation
+// Everything is launch_edge_mem's and, through it, launch_edge's -- the shared slot tables, e_prior, the work pools, the grid sizing (by the wavefronts per SIMD the instantiation
 // was compiled for), the clock probe, the timing events -- except that the slot tables of a and gamma are per leg: relay_ag [legs][2][n]
 // (upload_relay) -> e_relay [legs][2][R * 64], before every launch.
 __global__ void edge_relay_table_kernel(const double *ag, int n, int legs, const int32_t *scol, const uint8_t *kind, int slots, double *out) {
@@ -786,38 +722,21 @@ __global__ void edge_relay_table_kernel(const double *ag, int n, int legs, const
 }
 
 template <class ARGS>
-static int launch_edge_relay(ldpc_hip_bp *h, void (*kern)(const ARGS), int rounds, int waves_per_simd, int64_t batch, ARGS &ma) {
+static int launch_edge_relay(ldpc_hip_bp *h, void (*kern)(const ARGS), int rounds, int waves_per_simd, ARGS &ma, const EdgeIo &io) {
     if (!kern) return fail(LDPC_HIP_ERR_UNSUPPORTED, "Relay-BP: no lane = edge kernel was built for %d rounds", rounds);
     int rc;
     const int slots = rounds * 64;
     if ((rc = h->e_relay.ensure(sizeof(double) * 2 * (size_t)slots * (size_t)h->relay_legs))) return rc;
-    const dim3 gt((unsigned)((slots + 255) / 256));
-    LDPC_LAUNCH(edge_prior_kernel, gt, dim3(256), 0, h->stream, h->d_llr0, (const int32_t *)h->e_scol.p, (const uint8_t *)h->e_kind.p, slots, (double *)h->e_prior.p);
-    LDPC_LAUNCH(edge_relay_table_kernel, gt, dim3(256), 0, h->stream, (const double *)h->relay_ag.p, h->n, h->relay_legs, (const int32_t *)h->e_scol.p,
-                (const uint8_t *)h->e_kind.p, slots, (double *)h->e_relay.p);
+    launch_edge_prior(h, slots);
+    LDPC_LAUNCH(edge_relay_table_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, h->stream, (const double *)h->relay_ag.p, h->n, h->relay_legs,
+                (const int32_t *)h->e_scol.p, (const uint8_t *)h->e_kind.p, slots, (double *)h->e_relay.p);
     HIPCHK(hipGetLastError());
     ma.ag_s = (const double *)h->e_relay.p;
     ma.leg_iters = (const int32_t *)h->relay_it.p;
     ma.llr0 = h->d_llr0;
     ma.legs = h->relay_legs; ma.stop_after = h->relay_stop;
-    auto &a = ma.e;
-    a.m = h->m; a.n = h->n; a.max_iter = h->max_iter;  // (not read: leg_iters takes its place)
-    a.ms_scaling_factor = h->ms_scaling_factor;
-    a.batch = batch;
-    a.prior_s = (const double *)h->e_prior.p;
-    a.kind = (const uint8_t *)h->e_kind.p; a.scol = (const int32_t *)h->e_scol.p;
-    const size_t dyn = edge_lds_bytes(rounds);
-    int64_t per_cu = (int64_t)((160u * 1024u) / (dyn + 64));
-    if (per_cu > 4 * waves_per_simd) per_cu = 4 * waves_per_simd;  // (edge_relay_waves / edge8_relay_waves: what the instantiation was compiled for)
-    const int64_t groups = batch < 256 * per_cu ? batch : 256 * per_cu;
-    if ((rc = edge_work_split(h, rounds, batch, groups, a))) return rc;
-    h->accumulated_ms = 0.f;
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
-    LDPC_LAUNCH(kern, dim3((unsigned)groups), dim3(64), (unsigned)dyn, h->stream, ma);
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
-    h->timed = true;
-    HIPCHK(hipGetLastError());
-    return LDPC_HIP_OK;
+    ma.e.prior_s = (const double *)h->e_prior.p;
+    return launch_edge(h, kern, ma, ma.e, rounds, edge_lds_bytes(rounds), waves_per_simd, io);  // (edge_relay_waves / edge8_relay_waves; e.max_iter is not read: leg_iters takes its place)
 }
 
 // ---- Relay-BP and memory min-sum on the lane = node kernel (bp_wave_relay_kernel.h; instantiated in tu_onchip_wave_relay.hip): the codes beyond both lane = edge ladders ----
@@ -962,6 +881,7 @@ int ldpc_hip_bp_relay_route(const ldpc_hip_bp *h, int64_t batch, int32_t *route)
 // Relay-BP on chip: plan_edge, plan_edge8, plan_wave_relay in that order (plan_relay_route).  *took = false: the per-pass leg loop (host_stream.h: decode_relay).
 int decode_onchip_relay(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv, bool *took) {
     *took = false;
+    const EdgeIo io = {synd, batch, decoding, llr, iters, conv};
     const RelayRoute r = plan_relay_route(h, batch);
     int rc;
     if (r.route == 1) {
@@ -969,16 +889,14 @@ int decode_onchip_relay(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint
         if ((rc = ensure_edge_tables(h, r.ep))) return rc;
         EdgeRelayArgs ma = {};
         ma.e.partner = (const uint16_t *)h->e_partner.p;
-        ma.e.synd = synd; ma.e.decoding = decoding; ma.e.llr = llr; ma.e.iters = iters; ma.e.conv = conv;
-        return launch_edge_relay(h, edge_relay_kernel(r.ep.rounds), r.ep.rounds, edge_relay_waves(r.ep.rounds), batch, ma);
+        return launch_edge_relay(h, edge_relay_kernel(r.ep.rounds), r.ep.rounds, edge_relay_waves(r.ep.rounds), ma, io);
     }
     if (r.route == 2) {
         *took = true;
         if ((rc = ensure_edge8_tables(h, r.e8))) return rc;
         Edge8RelayArgs ma = {};
         ma.e.cpos = (const uint16_t *)h->e_partner.p;
-        ma.e.synd = synd; ma.e.decoding = decoding; ma.e.llr = llr; ma.e.iters = iters; ma.e.conv = conv;
-        return launch_edge_relay(h, edge8_relay_kernel(r.e8.rounds, r.e8.dc), r.e8.rounds, edge8_relay_waves(r.e8.rounds, r.e8.dc), batch, ma);
+        return launch_edge_relay(h, edge8_relay_kernel(r.e8.rounds, r.e8.dc), r.e8.rounds, edge8_relay_waves(r.e8.rounds, r.e8.dc), ma, io);
     }
     if (r.route >= 3) {
         *took = true;
@@ -992,12 +910,13 @@ int decode_onchip_relay(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint
 // float32 nothing ever goes to bp_wave_kernel, bp_small_kernel or any FP64 kernel).
 int decode_onchip_f32(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv, bool *took) {
     *took = false;
+    const EdgeIo io = {synd, batch, decoding, llr, iters, conv};
     if (!(h->small_mode == -1 || h->small_mode == 1 || h->small_mode == 6)) return LDPC_HIP_OK;
     if (!(h->m > 0 && h->n > 0 && h->nnz > 0 && (int64_t)h->nnz * 16 < (1 << 22) && batch < (1ll << 30))) return LDPC_HIP_OK;  // (32-bit syndrome indices in the work pools)
     const EdgePlan ep = plan_edge(h);
-    if (ep.rounds) { *took = true; return decode_edge_f32(h, ep, synd, batch, decoding, llr, iters, conv); }
+    if (ep.rounds) { *took = true; return decode_edge_f32(h, ep, io); }
     const Edge8Plan e8 = plan_edge8(h);
-    if (e8.rounds) { *took = true; return decode_edge8_f32(h, e8, synd, batch, decoding, llr, iters, conv); }
+    if (e8.rounds) { *took = true; return decode_edge8_f32(h, e8, io); }
     return LDPC_HIP_OK;
 }
 
@@ -1007,6 +926,7 @@ int decode_onchip_f32(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_
 // own priors too (bp_small_kernel<., ., RP>) -- with as many slots as fit -- and to the per-pass kernels (took = false) if not even one slot fits.
 int decode_onchip(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv, bool *took) {
     *took = false;
+    const EdgeIo io = {synd, batch, decoding, llr, iters, conv};
     const bool rp = h->row_probs != nullptr;
     if (h->mem_on) {
         // Memory min-sum (ldpc_hip_bp_set_memory), by plan_relay_route: a code that plan_edge or plan_edge8 takes runs on their memory forms, a code
@@ -1014,8 +934,8 @@ int decode_onchip(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
         // every other code -- and every code under mode 0 -- goes to the per-pass memory kernels (took = false).  The persistent ring kernel,
         // bp_wave_kernel, the slot kernel and the resident workgroup know nothing of the memory and never see such a decode.
         const RelayRoute r = plan_relay_route(h, batch);
-        if (r.route == 1) { *took = true; return decode_edge_mem(h, r.ep, synd, batch, decoding, llr, iters, conv); }
-        if (r.route == 2) { *took = true; return decode_edge8_mem(h, r.e8, synd, batch, decoding, llr, iters, conv); }
+        if (r.route == 1) { *took = true; return decode_edge_mem(h, r.ep, io); }
+        if (r.route == 2) { *took = true; return decode_edge8_mem(h, r.e8, io); }
         if (r.route >= 3) { *took = true; return decode_wave_relay(h, r.wp, (const double *)h->mem_ag.p, 1, nullptr, 1, synd, batch, decoding, llr, iters, conv); }
         return LDPC_HIP_OK;
     }
@@ -1031,14 +951,14 @@ int decode_onchip(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
             const EdgePlan ep = plan_edge(h);
             if (ep.rounds) {
                 *took = true;
-                if (!rp) return decode_edge(h, ep, synd, batch, decoding, llr, iters, conv);
-                if (edge_rp_route(h)) return decode_edge_rp(h, ep, synd, batch, decoding, llr, iters, conv);
+                if (!rp) return decode_edge(h, ep, io);
+                if (edge_rp_route(h)) return decode_edge_rp(h, ep, io);
             }
             const Edge8Plan e8 = plan_edge8(h);  // heavier nodes (rows <= 8, columns <= 4): rows in 8-lane groups
             if (!*took && e8.rounds) {
                 *took = true;
-                if (!rp) return decode_edge8(h, e8, synd, batch, decoding, llr, iters, conv);
-                if (edge_rp_route(h)) return decode_edge8_rp(h, e8, synd, batch, decoding, llr, iters, conv);
+                if (!rp) return decode_edge8(h, e8, io);
+                if (edge_rp_route(h)) return decode_edge8_rp(h, e8, io);
             }
         }
         if (!*took && h->small_mode != 2) {

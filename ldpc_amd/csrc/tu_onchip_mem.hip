@@ -1,20 +1,19 @@
 // tu_onchip_mem.hip -- libldpc_hip.so, translation unit of the lane = edge kernels with memory (bp_edge_mem_kernel.h): the 16
-// instantiations of bp_edge_mem_kernel and the 18 of bp_edge8_mem_kernel -- the ladders of plan_edge and plan_edge8 (host_onchip.h) -- and
+// instantiations of bp_edge_mem_kernel and the 18 of bp_edge8_mem_kernel -- the ladders LDPC_EDGE_LADDER and LDPC_EDGE8_LADDER (bp_edge_kernel.h), from which plan_edge and plan_edge8 (host_onchip.h) pick -- and
 // the two functions that hand them to the host side in tu_onchip.hip (decode_onchip).
 #include "bp_device_common.h"
 #include "bp_edge_mem_kernel.h"
 
 EdgeMemKernel edge_mem_kernel(int rounds) {
-    static const EdgeMemKernel kerns[17] = {nullptr, bp_edge_mem_kernel<1>, bp_edge_mem_kernel<2>, bp_edge_mem_kernel<3>, bp_edge_mem_kernel<4>, bp_edge_mem_kernel<5>,
-        bp_edge_mem_kernel<6>, bp_edge_mem_kernel<7>, bp_edge_mem_kernel<8>, bp_edge_mem_kernel<9>, bp_edge_mem_kernel<10>, bp_edge_mem_kernel<11>,
-        bp_edge_mem_kernel<12>, bp_edge_mem_kernel<13>, bp_edge_mem_kernel<14>, bp_edge_mem_kernel<15>, bp_edge_mem_kernel<16>};
+#define LDPC_E4(R) bp_edge_mem_kernel<R>,
+    static const EdgeMemKernel kerns[17] = {nullptr, LDPC_EDGE_LADDER(LDPC_E4)};
+#undef LDPC_E4
     return rounds < 1 || rounds > 16 ? nullptr : kerns[rounds];
 }
 
 Edge8MemKernel edge8_mem_kernel(int rounds, int dc) {
 #define LDPC_E8(R, C) if (rounds == R && dc == C) return bp_edge8_mem_kernel<R, C>;
-    LDPC_E8(2, 3) LDPC_E8(3, 3) LDPC_E8(4, 3) LDPC_E8(5, 3) LDPC_E8(6, 3) LDPC_E8(7, 3) LDPC_E8(8, 3) LDPC_E8(9, 3) LDPC_E8(10, 3) LDPC_E8(12, 3)
-    LDPC_E8(2, 4) LDPC_E8(3, 4) LDPC_E8(4, 4) LDPC_E8(5, 4) LDPC_E8(6, 4) LDPC_E8(7, 4) LDPC_E8(8, 4) LDPC_E8(9, 4)
+    LDPC_EDGE8_LADDER(LDPC_E8)
 #undef LDPC_E8
     return nullptr;
 }
