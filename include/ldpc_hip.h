@@ -574,6 +574,16 @@ int64_t ldpc_hip_debug_device_buf_bytes(void);
 void ldpc_hip_debug_launch_log(int32_t enable);
 int64_t ldpc_hip_debug_launch_log_read(char *buf, int64_t capacity);
 
+/* Math probe (a test aid; no counterpart in the reference): out[i] = f(in[i]) with f one of the inline routines of csrc/bp_math.h, evaluated
+ * ON THE DEVICE by one small kernel that calls the routines the decode kernels call -- so the device compile of them (the hand-rolled division,
+ * the inline-assembly fma, the wavefront ballot in front of every rare tail) can be compared with the host compile argument by argument.
+ *   which  0 tanh_half_libm   1 log_libm   2 ps_log_ratio_libm   3 log_near_one(q) ? log_libm_near_one(q) : log_libm_general(q, table)
+ *          4 div_cr: out[i] = div_cr(in[2 i], in[2 i + 1]) (`in` holds 2 count doubles)   5 tanh_half   6 ps_log_ratio
+ * Fixed layout: elements 64 w .. 64 w + 63 are the 64 lanes of ONE wavefront (256-thread blocks, a grid step that is a multiple of 64), so a
+ * caller chooses which arguments share a ballot.  Device pointers only, as for ldpc_hip_pack_b8; needs no handle: the kernel is queued on the
+ * null stream of the current device without synchronisation. */
+int ldpc_hip_debug_math_eval(int32_t which, const double *in, int64_t count, double *out);
+
 /* Page-locked host memory for a caller's result arrays (no counterpart in the reference: its arrays never leave the host).  A host
  * pointer into such a block -- or into memory the caller registered with hipHostRegister -- handed to ldpc_hip_bp_decode_batch as `llr`
  * is written by the device-to-host copies themselves: the pipelined host path (above) skips its pinned staging buffer and the

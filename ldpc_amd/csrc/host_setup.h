@@ -460,6 +460,43 @@ __attribute__((destructor)) static void launch_log_to_file() {
     }
 }
 
+// ldpc_hip_debug_math_eval: the routines of bp_math.h themselves, as the DEVICE compile evaluates them (div_cr's reciprocal sequence, fma_kk's
+// instruction, LDPC_ANY's ballot), one argument per lane.  Element 64 w + l is lane l of wavefront w: the block is four wavefronts and the grid's
+// step a multiple of 64, so the 64 arguments of one aligned group always share a ballot.  The log table is staged into LDS as the decode kernels do.
+__global__ void __launch_bounds__(256) debug_math_eval_kernel(int which, const double *__restrict__ in, int64_t count, double *__restrict__ out) {
+    __shared__ __attribute__((aligned(16))) double log_tab[256];
+    log_tab[threadIdx.x] = ldpc_math::k_log_tab[threadIdx.x];
+    __syncthreads();
+    const int64_t step = (int64_t)gridDim.x * 256;
+    const int64_t padded = (count + 63) & ~(int64_t)63;  // whole wavefronts enter every iteration: the routines' ballots see all 64 lanes
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < padded; i += step) {
+        const bool inside = i < count;
+        const double x = inside ? (which == 4 ? in[2 * i] : in[i]) : 1.0;
+        const double d = inside && which == 4 ? in[2 * i + 1] : 1.0;
+        double y;
+        switch (which) {
+        case 0: y = ldpc_math::tanh_half_libm(x); break;
+        case 1: y = ldpc_math::log_libm(x, log_tab); break;
+        case 2: y = ldpc_math::ps_log_ratio_libm(inside ? x : 0.0, log_tab); break;
+        case 3: y = ldpc_math::log_near_one(x) ? ldpc_math::log_libm_near_one(x) : ldpc_math::log_libm_general(x, log_tab); break;
+        case 4: y = ldpc_math::div_cr(x, d); break;
+        case 5: y = ldpc_math::tanh_half(x); break;
+        default: y = ldpc_math::ps_log_ratio(inside ? x : 0.0); break;
+        }
+        if (inside) out[i] = y;
+    }
+}
+
+int ldpc_hip_debug_math_eval(int32_t which, const double *in, int64_t count, double *out) {
+    if (which < 0 || which > 6) return fail(LDPC_HIP_ERR_INVALID, "math eval: which in 0 .. 6");
+    if (count < 0 || (count > 0 && (!in || !out))) return fail(LDPC_HIP_ERR_INVALID, "math eval: null argument");
+    if (count == 0) return LDPC_HIP_OK;
+    const int64_t blocks = std::min<int64_t>((count + 255) / 256, 4096);
+    LDPC_LAUNCH(debug_math_eval_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t) nullptr, (int)which, in, count, out);
+    HIPCHK(hipGetLastError());
+    return LDPC_HIP_OK;
+}
+
 void *ldpc_hip_host_alloc(size_t bytes) {
     void *p = nullptr;
     if (hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault) != hipSuccess) {

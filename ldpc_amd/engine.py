@@ -38,6 +38,27 @@ def launch_log():
             counts[name] = int(count)
 
 
+MATH_ROUTINES = ("tanh_half_libm", "log_libm", "ps_log_ratio_libm", "log_split", "div_cr", "tanh_half", "ps_log_ratio")
+
+
+def debug_math_eval(which, values):
+    """``ldpc_hip_debug_math_eval``: a routine of csrc/bp_math.h evaluated on the device, element by element.  ``which``: an index into
+    ``MATH_ROUTINES`` or one of its names; ``values``: a float64 torch tensor on the GPU -- for ``div_cr`` of shape ``[count, 2]``
+    (numerator, denominator).  Elements ``64 w .. 64 w + 63`` are the lanes of one wavefront.  Returns a new tensor of ``count`` doubles."""
+    import torch
+    which = MATH_ROUTINES.index(which) if isinstance(which, str) else int(which)
+    t = values.contiguous()
+    if t.dtype != torch.float64 or not t.is_cuda:
+        raise ValueError("debug_math_eval takes a float64 tensor on the GPU")
+    count = t.numel() // 2 if which == 4 else t.numel()
+    if which == 4 and (t.dim() != 2 or t.shape[1] != 2):
+        raise ValueError("div_cr takes a [count, 2] tensor of (numerator, denominator) pairs")
+    out = torch.empty(count, dtype=torch.float64, device=t.device)
+    with torch.cuda.device(t.device):
+        _lib.check(_lib.load().ldpc_hip_debug_math_eval(which, t.data_ptr(), count, out.data_ptr()))
+    return out
+
+
 def _is_torch(x) -> bool:
     return type(x).__module__.startswith("torch")
 

@@ -23,6 +23,8 @@ void dx_log_split_v(long n, const double *in, double *out) {
     for (long i = 0; i < n; i++)
         out[i] = ldpc_math::log_near_one(in[i]) ? ldpc_math::log_libm_near_one(in[i]) : ldpc_math::log_libm_general(in[i], ldpc_math::k_log_tab);
 }
+// plain IEEE division on (numerator, denominator) pairs: what div_cr is on the host, and what its device sequence must reproduce
+void dx_div_v(long n, const double *in, double *out) { for (long i = 0; i < n; i++) out[i] = ldpc_math::div_cr(in[2 * i], in[2 * i + 1]); }
 void libm_log_ratio_v(long n, const double *in, double *out) { for (long i = 0; i < n; i++) out[i] = std::log((1 + in[i]) / (1 - in[i])); }
 void *dx_tanh_half_ptr() { return (void *)&dx_tanh_half; }
 void *dx_log_ratio_ptr() { return (void *)&dx_log_ratio; }
