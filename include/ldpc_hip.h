@@ -544,6 +544,37 @@ int ldpc_hip_bp_get_relay(const ldpc_hip_bp *h, int32_t *legs, int32_t *stop_aft
  * LDPC_HIP_ERR_INVALID: NULL argument, negative batch, or neither ldpc_hip_bp_set_relay nor ldpc_hip_bp_set_memory is on. */
 int ldpc_hip_bp_relay_route(const ldpc_hip_bp *h, int64_t batch, int32_t *route);
 
+/*
+ * BP with guided decimation, BPGD (opt-in; no counterpart in the reference): minimum-sum, parallel schedule, FP64 messages, in up to max_rounds
+ * rounds of up to round_iters iterations per syndrome -- the two take the place of the handle's max_iter.  With L0[j] = log((1 - p[j]) / p[j]),
+ * P = L0 and frozen[j] = !isfinite(L0[j]) to start with, every iteration is the plain decode's with P for the prior; the iteration count runs on
+ * across the rounds (a scaling factor of 0 takes alpha = 1 - 2^-it of the row's TOTAL it), and the first iteration whose decisions reproduce the
+ * syndrome ends the row: converge = 1, iterations = it.  A round that ends without that, and is not the last, decimates: with M the posteriors of
+ * its last bit pass, j* = the column with frozen[j] false and M[j] not NaN whose |M[j]| is largest (the smallest j among equal ones) gets
+ * v = M[j*] <= 0 ? -freeze_llr : +freeze_llr for its prior P[j*] and for every one of its bit-to-check messages, and is frozen; every other
+ * message stays.  With nothing left to freeze the rounds still run.  A row that never converges: the last bit pass, converge = 0, iterations =
+ * max_rounds * round_iters.  A syndrome byte > 1 never converges.  max_rounds = 1 is the plain decode with max_iter = round_iters, bit for bit.
+ * The results are those of the NumPy restatement tests/bpgd_util.py, bit for bit.
+ *   ldpc_hip_bp_set_decimation(h, round_iters, max_rounds, freeze_llr): round_iters >= 1, max_rounds >= 1, their product within int32,
+ *       freeze_llr > 0 and finite or +inf (else LDPC_HIP_ERR_INVALID, the message names the value, and what the handle held stays).
+ *       round_iters = 0: off.  Decimation, ldpc_hip_bp_set_relay and ldpc_hip_bp_set_memory exclude one another: setting one while another is on
+ *       is LDPC_HIP_ERR_UNSUPPORTED.  ldpc_hip_bp_set_channel afterwards is followed.
+ *   ldpc_hip_bp_get_decimation(h, &round_iters, &max_rounds, &freeze_llr): 1 if it is on (the three set unless NULL), 0 if off (all three 0),
+ *       LDPC_HIP_ERR_INVALID for a NULL handle.
+ *   ldpc_hip_bp_decimation_route(h, batch, &route): which kernels decode `batch` syndromes with it on this handle as it is set now -- 0 none,
+ *       1 bp_edge (lane = edge, rows <= 4, columns <= 2), 2 bp_edge8 (rows <= 8, columns <= 4).  Launches nothing.  LDPC_HIP_ERR_INVALID: NULL
+ *       argument, negative batch, or the decimation is off.
+ * The lane = edge kernels (bp_edge_gd_kernel.h: one wavefront per syndrome, all rounds in one launch, nothing leaves the chip between rounds) are
+ * the only route so far: the lane = node route for the codes beyond their ladders and a per-pass route are not built.  With the decimation on,
+ * ldpc_hip_bp_decode_batch[_async], the BP + OSD-0 entry points (OSD sees the rows left unsolved, with the last posteriors), ldpc_hip_bp_decode_b8
+ * and ldpc_hip_bp_simulate_b8 decode with it.  Refused with LDPC_HIP_ERR_UNSUPPORTED before anything is staged or launched: a code neither lane =
+ * edge family takes or a small-code kernel mode other than -1, 1, 6 (route 0), product-sum, any serial schedule, LDPC_HIP_MSG_F32, the *_priors
+ * entry points, soft-syndrome decoding, several GPUs, OSD-E / OSD-CS.
+ */
+int ldpc_hip_bp_set_decimation(ldpc_hip_bp *h, int32_t round_iters, int32_t max_rounds, double freeze_llr);
+int ldpc_hip_bp_get_decimation(const ldpc_hip_bp *h, int32_t *round_iters, int32_t *max_rounds, double *freeze_llr);
+int ldpc_hip_bp_decimation_route(const ldpc_hip_bp *h, int64_t batch, int32_t *route);
+
 /* The shader clock the BP kernels actually ran at (a measurement aid; no counterpart in the reference).  Every workgroup of the
  * long-running BP kernels (bp_decode_kernel, bp_wave_kernel, bp_wave_ps_kernel, bp_edge_kernel, bp_edge8_kernel) adds the shader cycles
  * (s_memtime) and the constant-rate ticks (s_memrealtime) of its lifetime to two 64-bit words of the handle; the words only grow.

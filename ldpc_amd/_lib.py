@@ -28,6 +28,7 @@ SYMBOLS = (
     "ldpc_hip_bp_set_sampler", "ldpc_hip_bp_sample_b8", "ldpc_hip_count_mismatch_b8", "ldpc_hip_bp_simulate_b8",
     "ldpc_hip_bp_set_memory", "ldpc_hip_bp_get_memory",
     "ldpc_hip_bp_set_relay", "ldpc_hip_bp_get_relay", "ldpc_hip_bp_relay_route",
+    "ldpc_hip_bp_set_decimation", "ldpc_hip_bp_get_decimation", "ldpc_hip_bp_decimation_route",
 )
 
 
@@ -141,6 +142,10 @@ def load():
         lib.ldpc_hip_bp_get_relay.argtypes = [vp, vp, vp, vp, vp]
     if not os.environ.get("LDPC_HIP_LIB") or hasattr(lib, "ldpc_hip_bp_relay_route"):
         lib.ldpc_hip_bp_relay_route.argtypes = [vp, i64, vp]
+    if not os.environ.get("LDPC_HIP_LIB") or hasattr(lib, "ldpc_hip_bp_set_decimation"):
+        lib.ldpc_hip_bp_set_decimation.argtypes = [vp, i32, i32, dbl]
+        lib.ldpc_hip_bp_get_decimation.argtypes = [vp, vp, vp, vp]
+        lib.ldpc_hip_bp_decimation_route.argtypes = [vp, i64, vp]
     lib.ldpc_hip_bp_set_small_code_kernel.argtypes = [vp, i32]
     lib.ldpc_hip_bp_set_debug_switch.argtypes = [vp, C.c_char_p, i32]
     lib.ldpc_hip_bp_set_handoff.argtypes = [vp, i32]

@@ -147,6 +147,8 @@ class BpDecoderBase:
         self._engine_memory = None      # what the engine's handle is set to (a new handle starts with memory off)
         self._relay = None              # relay: None (off) or (strengths (legs, n), leg_iters (legs,), stop_after)
         self._engine_relay = None       # ... what the engine's handle is set to
+        self._decimation = None         # decimation: None (off) or (round_iters, max_rounds, freeze_llr)
+        self._engine_decimation = None  # ... what the engine's handle is set to
 
         self._h = _ingest(pcm)
         self.m, self.n = int(pcm.shape[0]), int(pcm.shape[1])
@@ -502,9 +504,72 @@ class BpDecoderBase:
             raise NotImplementedError(f"relay: bit {int(bad[0])} has a nonzero memory strength and a channel probability of {p[bad[0]]!r}; "
                                       "Relay-BP needs probabilities strictly between 0 and 1 there (or strength 0 on that bit in every leg).")
 
+    # ---- BP with guided decimation (additive; not a constructor keyword either) -----------------------------------
+    @property
+    def decimation(self):
+        """``None`` (default): off.  Set to a dict of ``ldpc_amd.bpgd_decoder.decimation_schedule`` keywords (``round_iters=5``,
+        ``max_rounds=None`` -- n --, ``freeze_llr=25.0``): every decode then runs BP with guided decimation (``ldpc_hip_bp_set_decimation``;
+        DESIGN.md section 7e) -- rounds of ``round_iters`` min-sum iterations, the most reliable bit frozen at ``+-freeze_llr`` after every
+        round that ends unsolved, the messages kept; ``round_iters`` and ``max_rounds`` take the place of ``max_iter``.  Read back as such a
+        dict.  Minimum-sum, parallel schedule, float64 messages, one GPU, OSD_0 at most, and a code the lane = edge kernels take
+        (``decimation_route``); not together with ``memory_strength``, ``relay``, ``channel_probs=`` or soft syndromes --
+        ``NotImplementedError`` at decode time."""
+        if self._decimation is None:
+            return None
+        return dict(round_iters=self._decimation[0], max_rounds=self._decimation[1], freeze_llr=self._decimation[2])
+
+    @decimation.setter
+    def decimation(self, value) -> None:
+        if value is None:
+            self._decimation = None
+            return
+        if not isinstance(value, dict):
+            raise ValueError(f"decimation must be None or a dict of decimation_schedule keywords, not {value!r}.")
+        from ldpc_amd.bpgd_decoder import decimation_schedule
+        self._decimation = decimation_schedule(self.n, **value)
+
+    @property
+    def decimation_route(self) -> str:
+        """Which kernels decode with guided decimation on this decoder as it is set now: ``HipBpEngine.decimation_route`` -- ``"bp_edge"``,
+        ``"bp_edge8"`` or ``"unavailable"`` (a code neither family takes).  ``ValueError`` when ``decimation`` is not set; where the decoder is
+        set to something decimation cannot serve at all (product-sum, a serial schedule, float32 messages, several GPUs, ``memory_strength``
+        or ``relay``) there is no route to name and the ``NotImplementedError`` of a decode is raised instead, with its reason."""
+        if self._decimation is None:
+            raise ValueError("decimation_route: decimation is not set.")
+        from ldpc_amd.bpgd_decoder import lane_edge_route
+        if lane_edge_route(self._h) == "unavailable":  # (no handle needed to say so)
+            return "unavailable"
+        self._require_decimation()
+        return self._get_engine().decimation_route(getattr(self, "_relay_batch", 1))
+
+    def _require_decimation(self, what=None):
+        if self._decimation is None:
+            return
+        if what is not None:
+            raise NotImplementedError(f"decimation with {what.replace('without memory only', 'without decimation only')}; set decimation=None.")
+        if self._memory is not None:
+            raise NotImplementedError("decimation with memory_strength: the two exclude each other; set memory_strength=None or decimation=None.")
+        if self._relay is not None:
+            raise NotImplementedError("decimation with relay: the two exclude each other; set relay=None or decimation=None.")
+        if self._bp_method != MINIMUM_SUM:
+            raise NotImplementedError("decimation with bp_method='product_sum': guided decimation is built on the minimum-sum kernels only.")
+        if self._schedule != PARALLEL or self._random_serial_schedule:
+            raise NotImplementedError(f"decimation with schedule='{self.schedule}'"
+                                      f"{' and random_serial_schedule' if self._random_serial_schedule else ''}: guided decimation needs schedule='parallel'.")
+        if self._message_dtype != "float64":
+            raise NotImplementedError("decimation with message_dtype='float32': guided decimation is decoded with float64 messages only.")
+        if self._device_ids is not None:
+            raise NotImplementedError("decimation with device_ids=[...]: guided decimation is not sharded over several GPUs; decode on one GPU.")
+        from ldpc_amd.bpgd_decoder import lane_edge_route
+        if lane_edge_route(self._h) == "unavailable":
+            raise NotImplementedError("decimation: neither lane = edge kernel family takes this code (rows of at most 4 entries and columns of at most 2 "
+                                      "within 1024 slots, or rows of at most 8 and columns of at most 4 within the kernels' ladder; every column used); "
+                                      "the lane = node route for larger codes and a per-pass route are not built yet.")
+
     def _require_memory(self, what=None):
         """What memory min-sum cannot do is refused here, at decode time, with its reason (``what``: the call's own addition) -- and what
-        Relay-BP cannot (``_require_relay``)."""
+        Relay-BP (``_require_relay``) and guided decimation (``_require_decimation``) cannot."""
+        self._require_decimation(what)
         self._require_relay(what)
         if self._memory is None:
             return
@@ -558,6 +623,10 @@ class BpDecoderBase:
         if self._message_dtype != self._engine_dtype:
             self._engine.set_message_dtype(self._message_dtype)
             self._engine_dtype = self._message_dtype
+        decimation_changed = self._decimation != self._engine_decimation
+        if decimation_changed and self._engine_decimation is not None:  # (off before the memory or the relay may go on: the three exclude one another on the handle)
+            self._engine.set_decimation(None)
+            self._engine_decimation = None
         relay_changed = self._relay is not self._engine_relay
         if relay_changed and self._relay is None:  # (off before the memory may go on: the two exclude each other on the handle)
             self._engine.set_relay(None)
@@ -569,6 +638,9 @@ class BpDecoderBase:
         if relay_changed and self._relay is not None:
             self._engine.set_relay(*self._relay)
             self._engine_relay = self._relay
+        if self._decimation is not None and self._engine_decimation is None:
+            self._engine.set_decimation(*self._decimation)
+            self._engine_decimation = self._decimation
         rnd = (bool(self._random_serial_schedule), self._random_schedule_seed, self._seed_epoch)
         if rnd != getattr(self, "_engine_random", (False, 0, 0)):
             self._engine.set_random_serial(rnd[0], rnd[1])  # re-seeds, as bpd.set_random_schedule_seed does (pyx:553-554)
@@ -605,7 +677,7 @@ class BpDecoderBase:
         """(B, m) uint8 NumPy -> (decoding, llr, iterations, converge) through the active backend.  ``llr_out``: a (B, n) float64
         C-contiguous array to receive the log-ratios instead of a new one.  ``channel_probs``: checked (B, n) row priors or None."""
         # (the schedule setters and the memory strengths live on the ctypes engine)
-        cy = self._get_cy() if self._schedule == PARALLEL and self._memory is None and self._relay is None else None
+        cy = self._get_cy() if self._schedule == PARALLEL and self._memory is None and self._relay is None and self._decimation is None else None
         if cy is None:
             self._relay_batch = max(1, len(synd2d))  # (relay_route)
         if cy is not None and channel_probs is not None:

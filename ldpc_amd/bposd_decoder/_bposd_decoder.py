@@ -103,6 +103,9 @@ class BpOsdDecoder(BpDecoderBase):
         self._require_memory()  # (memory_strength: BP with memory, OSD unchanged on its posteriors)
         if self._relay is not None and self._osd_method in (EXHAUSTIVE, COMBINATION_SWEEP):
             raise NotImplementedError(f"relay with osd_method='{self.osd_method}': Relay-BP is followed by OSD_0 only; set osd_method='osd_0' or relay=None.")
+        if self._decimation is not None and self._osd_method in (EXHAUSTIVE, COMBINATION_SWEEP):
+            raise NotImplementedError(f"decimation with osd_method='{self.osd_method}': guided decimation is followed by OSD_0 only; "
+                                      "set osd_method='osd_0' or decimation=None.")
         if self._osd_method == OSD_OFF:
             raise NotImplementedError("osd_method='OSD_OFF': the reference dereferences an unset LU object here (osd.hpp:63, 110); "
                                       "choose OSD_0, OSD_E or OSD_CS.")
@@ -115,7 +118,7 @@ class BpOsdDecoder(BpDecoderBase):
         """BP + OSD through the active backend with this decoder's osd_method / osd_order (``channel_probs``: checked row priors, OSD_0)."""
         method, order = (OSD_0, 0) if force_osd0 else (self._osd_method, self._osd_order)
         # (the schedule setters and the memory strengths live on the ctypes engine)
-        cy = self._get_cy() if self._schedule == PARALLEL and self._memory is None and self._relay is None else None
+        cy = self._get_cy() if self._schedule == PARALLEL and self._memory is None and self._relay is None and self._decimation is None else None
         if cy is not None:
             cy.osd_method, cy.osd_order = method, order
             if channel_probs is not None:

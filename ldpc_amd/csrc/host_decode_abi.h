@@ -385,7 +385,7 @@ static int decode_batch_staged(ldpc_hip_bp *h, int osd, const uint8_t *synd, int
             double *p_llr = (llr || osd >= 0) ? (double *)(dv + o_llr) : nullptr;
             uint8_t *p_cv = (conv || osd >= 0) ? (uint8_t *)(dv + o_cv) : nullptr;
             int32_t *p_it = iters ? (int32_t *)(dv + o_it) : nullptr;
-            if (batch == 1 && osd < 0 && h->msg_dtype == LDPC_HIP_MSG_F64 && !h->mem_on && !h->relay_on && !h->on("TIME_SMALL_CALLS")) {  // ONE syndrome: the resident workgroup, where one applies
+            if (batch == 1 && osd < 0 && h->msg_dtype == LDPC_HIP_MSG_F64 && !h->mem_on && !h->relay_on && !h->gd_on && !h->on("TIME_SMALL_CALLS")) {  // ONE syndrome: the resident workgroup, where one applies
                 bool took = false;
                 if ((rc = decode_onchip_resident(h, llr != nullptr, &took))) return rc;
                 if (took) {

@@ -1,5 +1,5 @@
 // host_handle.h -- the handle (struct ldpc_hip_bp), error reporting, device buffers, measurement switches
-// Part of libldpc_hip.so: included by every translation unit (bp_hip.hip = the C ABI; tu_stream / tu_serial / tu_onchip / tu_onchip_f32 / tu_onchip_rp / tu_onchip_mem / tu_onchip_relay / tu_onchip_wave_relay / tu_osd / tu_f32.hip = one kernel
+// Part of libldpc_hip.so: included by every translation unit (bp_hip.hip = the C ABI; tu_stream / tu_serial / tu_onchip / tu_onchip_f32 / tu_onchip_rp / tu_onchip_mem / tu_onchip_relay / tu_onchip_wave_relay / tu_onchip_gd / tu_osd / tu_f32.hip = one kernel
 // family each with its host side).  What one unit calls in another is declared at the end of this header.
 #pragma once
 
@@ -346,6 +346,14 @@ struct ldpc_hip_bp {
     DeviceBuf e_relay;                  // [legs][2][R * 64]: a and gamma of every slot, per leg (edge_relay_table_kernel, before every launch)
     DeviceBuf w_relay;                  // bp_wave_relay_kernel: [np + 2] the padded priors, then [legs][2][np] a and gamma of every column padded to np, per leg -- the relay's, or the memory's as one leg (before every launch)
     DeviceBuf relay_dec, relay_llr, relay_li, relay_cv, relay_state;  // the leg loop: a leg's outputs [batch][n] / [batch]; {best weight f64, solutions i32, iterations i32} per row
+    // BP with guided decimation (ldpc_hip_bp_set_decimation): up to gd_max_rounds rounds of gd_round_iters min-sum iterations per
+    // syndrome; a round that ends unsolved freezes the most reliable column at +-gd_freeze and keeps the messages.  gd_round_iters and gd_max_rounds
+    // take max_iter's place.  decode_device looks at gd_on and sends the batch to decode_onchip_gd (host_onchip.h: the lane = edge kernels of
+    // bp_edge_gd_kernel.h, nothing else).  Decimation, relay and memory exclude one another.  No device buffer of its own: the slot tables and e_prior are the plain decode's.
+    bool gd_on = false;
+    int32_t gd_round_iters = 0, gd_max_rounds = 0;
+    double gd_freeze = 0.0;
+    mutable int gd_route_known = -1, gd_route_method = 0, gd_route_mode = 0;  // gd_route's answer for this code under (bp_method, small_mode), -1: not asked yet (the plans scan the matrix: once, not at every refusal check)
 };
 
 // h->counter: work_pool_bytes() of work counters for the on-chip BP kernels, then OSD_COUNTER_BYTES for BP + OSD -- {listed, next} of the first
@@ -413,10 +421,33 @@ static int relay_refusal(const ldpc_hip_bp *h, const char *what) {
     return LDPC_HIP_OK;
 }
 
+// tu_onchip.hip (host_onchip.h): which lane = edge family decodes this handle's code with guided decimation -- 0 neither, 1 bp_edge, 2 bp_edge8.
+// It looks at the matrix, the BP method and the small-code kernel mode only, and launches nothing.
+int gd_route(const ldpc_hip_bp *h, int64_t batch);
+
+// What the handle is set up for that a decode with guided decimation cannot do (`what` as for the memory decode below).  The lane = edge kernels
+// are its only route: a code neither family takes is refused here, before anything is staged, not decoded some other way.
+static int gd_refusal(const ldpc_hip_bp *h, const char *what) {
+    if (!h->gd_on) return LDPC_HIP_OK;
+    if (what) return fail(LDPC_HIP_ERR_UNSUPPORTED, "guided decimation: %s not available (switch the decimation off: ldpc_hip_bp_set_decimation(h, 0, 0, 0))", what);
+    if (h->bp_method != LDPC_HIP_MINIMUM_SUM)
+        return fail(LDPC_HIP_ERR_UNSUPPORTED, "guided decimation: product-sum is not available (it is built on the minimum-sum lane = edge kernels only)");
+    if (h->schedule != 1 || h->random_serial)
+        return fail(LDPC_HIP_ERR_UNSUPPORTED, "guided decimation: the serial schedules are not available (parallel schedule required)");
+    if (h->msg_dtype != LDPC_HIP_MSG_F64)
+        return fail(LDPC_HIP_ERR_UNSUPPORTED, "guided decimation: float32 messages are not available (set the message dtype to float64)");
+    if (gd_route(h, 0) == 0)
+        return fail(LDPC_HIP_ERR_UNSUPPORTED, "guided decimation: neither lane = edge kernel family takes this code under small-code kernel mode %d "
+                    "(ldpc_hip_bp_decimation_route answers 0: it needs rows of at most 8 and columns of at most 4 entries within the kernels' ladders, and mode -1, 1 or 6); "
+                    "the lane = node route for larger codes and a per-pass route are not built yet", (int)h->small_mode);
+    return LDPC_HIP_OK;
+}
+
 // What the handle is set up for that a memory decode cannot do; `what`: the call's own addition (row priors, soft syndromes, several GPUs) or
 // nullptr.  LDPC_HIP_OK when memory is off.  Called beside f32_refusal by every decode entry point, before anything is staged or launched.
-// (With Relay-BP on instead -- the two exclude each other -- it answers for the relay: relay_refusal.)
+// (With Relay-BP or guided decimation on instead -- the three exclude one another -- it answers for them: relay_refusal, gd_refusal.)
 static int mem_refusal(const ldpc_hip_bp *h, const char *what) {
+    if (h->gd_on) return gd_refusal(h, what);
     if (h->relay_on) return relay_refusal(h, what);
     if (!h->mem_on) return LDPC_HIP_OK;
     if (what) return fail(LDPC_HIP_ERR_UNSUPPORTED, "memory min-sum: %s not available (switch the memory off: ldpc_hip_bp_set_memory(h, NULL))", what);
@@ -437,6 +468,8 @@ static int mem_refusal(const ldpc_hip_bp *h, const char *what) {
 static int relay_osd_refusal(const ldpc_hip_bp *h, bool with_osd) {
     if (h->relay_on && with_osd && h->osd_method >= 2 && h->osd_order > 0)
         return fail(LDPC_HIP_ERR_UNSUPPORTED, "Relay-BP: OSD-E and OSD-CS are not available (OSD-0 only: ldpc_hip_bp_set_osd(h, 1, 0), or switch the relay off)");
+    if (h->gd_on && with_osd && h->osd_method >= 2 && h->osd_order > 0)  // (guided decimation: the same rule)
+        return fail(LDPC_HIP_ERR_UNSUPPORTED, "guided decimation: OSD-E and OSD-CS are not available (OSD-0 only: ldpc_hip_bp_set_osd(h, 1, 0), or switch the decimation off)");
     return LDPC_HIP_OK;
 }
 
@@ -653,6 +686,9 @@ int decode_onchip(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
 // plan_edge / plan_edge8 take, the lane = node kernel (bp_wave_relay_kernel.h, tu_onchip_wave_relay.hip) for those plan_wave_relay takes, by the small-code
 // kernel mode (plan_relay_route); *took = false: decode_relay (host_stream.h) runs its leg loop
 int decode_onchip_relay(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv, bool *took);
+// tu_onchip.hip: BP with guided decimation, all rounds in one launch -- the lane = edge decimation kernels (bp_edge_gd_kernel.h, tu_onchip_gd.hip) for the
+// codes plan_edge / plan_edge8 take (gd_route); any other code: LDPC_HIP_ERR_UNSUPPORTED, nothing launched
+int decode_onchip_gd(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv);
 // tu_serial.hip: serial / serial_relative / random serial schedules, soft-syndrome decoding
 int decode_serial(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv);
 int soft_info_device(ldpc_hip_bp *h, const double *soft, int64_t batch, double cutoff, double sigma, uint8_t *decoding, double *llr,

@@ -905,6 +905,75 @@ int decode_onchip_relay(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint
     return LDPC_HIP_OK;
 }
 
+// ---- the same two families with guided decimation (bp_edge_gd_kernel.h; instantiated in tu_onchip_gd.hip): ldpc_hip_bp_set_decimation on the codes of plan_edge / plan_edge8 ----
+// Everything is decode_edge's / decode_edge8's and, through launch_edge, shared with every other variant -- the slot tables, e_prior (L0 per slot: every
+// syndrome's priors, initial messages and frozen slots start from it), the work pools, the grid sizing (by the wavefronts per SIMD the instantiation was
+// compiled for), the clock probe, the timing events.  The kernels read round_iters and max_rounds where the others read max_iter.
+// The route: decode_onchip's predicate for the lane = edge families (modes -1, 1, 6; the work pools' 32-bit syndrome indices) and their two plans, unchanged.
+// There is no other: the lane = node route for the codes beyond the ladders (bp_wave_relay_kernel's territory) and a per-pass route are not built.
+struct GdRoute { int route = 0; EdgePlan ep; Edge8Plan e8; };
+static GdRoute plan_gd_route(const ldpc_hip_bp *h, int64_t batch) {
+    GdRoute r;
+    if (!(h->small_mode == -1 || h->small_mode == 1 || h->small_mode == 6)) return r;
+    if (!(h->m > 0 && h->n > 0 && h->nnz > 0 && (int64_t)h->nnz * 16 < (1 << 22) && batch < (1ll << 30))) return r;
+    r.ep = plan_edge(h);
+    if (r.ep.rounds) { r.route = 1; return r; }
+    r.e8 = plan_edge8(h);
+    if (r.e8.rounds) r.route = 2;
+    return r;
+}
+
+// The route alone, for the refusal checks of every entry point and for ldpc_hip_bp_decimation_route: the plans' answer for the handle's code, kept per
+// (bp_method, small-code kernel mode) -- nothing else it depends on can change on a handle -- and the batch bound.  (decode_onchip_gd plans once per decode,
+// as decode_onchip does: it needs the plans' kernels.)
+int gd_route(const ldpc_hip_bp *h, int64_t batch) {
+    if (h->gd_route_known < 0 || h->gd_route_method != h->bp_method || h->gd_route_mode != h->small_mode) {
+        h->gd_route_known = plan_gd_route(h, 0).route;
+        h->gd_route_method = h->bp_method;
+        h->gd_route_mode = h->small_mode;
+    }
+    return batch < (1ll << 30) ? h->gd_route_known : 0;
+}
+
+int ldpc_hip_bp_decimation_route(const ldpc_hip_bp *h, int64_t batch, int32_t *route) {
+    if (!h || !route) return fail(LDPC_HIP_ERR_INVALID, "null argument");
+    if (batch < 0) return fail(LDPC_HIP_ERR_INVALID, "negative batch");
+    if (!h->gd_on) return fail(LDPC_HIP_ERR_INVALID, "guided decimation is not on (ldpc_hip_bp_set_decimation)");
+    *route = gd_route(h, batch);
+    return LDPC_HIP_OK;
+}
+
+template <class ARGS>
+static int launch_edge_gd(ldpc_hip_bp *h, void (*kern)(const ARGS), int rounds, int waves_per_simd, ARGS &ga, const EdgeIo &io) {
+    if (!kern) return fail(LDPC_HIP_ERR_UNSUPPORTED, "guided decimation: no lane = edge kernel was built for %d rounds", rounds);
+    launch_edge_prior(h, rounds * 64);
+    ga.e.prior_s = (const double *)h->e_prior.p;
+    ga.freeze_llr = h->gd_freeze;
+    ga.round_iters = h->gd_round_iters; ga.max_rounds = h->gd_max_rounds;
+    return launch_edge(h, kern, ga, ga.e, rounds, edge_lds_bytes(rounds), waves_per_simd, io);  // (edge_gd_waves / edge8_gd_waves; e.max_iter is not read: the rounds take its place)
+}
+
+int decode_onchip_gd(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv) {
+    const EdgeIo io = {synd, batch, decoding, llr, iters, conv};
+    const GdRoute r = plan_gd_route(h, batch);
+    int rc;
+    if (r.route == 1) {
+        if ((rc = ensure_edge_tables(h, r.ep))) return rc;
+        EdgeGdArgs ga = {};
+        ga.e.partner = (const uint16_t *)h->e_partner.p;
+        return launch_edge_gd(h, edge_gd_kernel(r.ep.rounds), r.ep.rounds, edge_gd_waves(r.ep.rounds), ga, io);
+    }
+    if (r.route == 2) {
+        if ((rc = ensure_edge8_tables(h, r.e8))) return rc;
+        Edge8GdArgs ga = {};
+        ga.e.cpos = (const uint16_t *)h->e_partner.p;
+        return launch_edge_gd(h, edge8_gd_kernel(r.e8.rounds, r.e8.dc), r.e8.rounds, edge8_gd_waves(r.e8.rounds, r.e8.dc), ga, io);
+    }
+    // (gd_refusal has said so for the code and the mode; what is left is the batch)
+    return fail(LDPC_HIP_ERR_UNSUPPORTED, "guided decimation: no lane = edge kernel takes a batch of %lld syndromes of this code (ldpc_hip_bp_decimation_route answers 0); "
+                "the lane = node route and a per-pass route are not built yet", (long long)batch);
+}
+
 // The float32 message mode's on-chip planner, called by decode_f32 (host_f32.h) after its refusals: decode_onchip's predicate for the lane =
 // edge families and their two plans, unchanged.  *took = false: neither takes the code -- decode_f32 goes on with its per-pass kernels (in
 // float32 nothing ever goes to bp_wave_kernel, bp_small_kernel or any FP64 kernel).

@@ -327,6 +327,8 @@ int ldpc_hip_bp_set_memory(ldpc_hip_bp *h, const double *gamma) {
     }
     if (h->relay_on)
         return fail(LDPC_HIP_ERR_UNSUPPORTED, "memory min-sum and Relay-BP exclude each other: switch the relay off first (ldpc_hip_bp_set_relay(h, 0, NULL, NULL, 0))");
+    if (h->gd_on)
+        return fail(LDPC_HIP_ERR_UNSUPPORTED, "memory min-sum and guided decimation exclude each other: switch the decimation off first (ldpc_hip_bp_set_decimation(h, 0, 0, 0))");
     const int bad = mem_gamma_first_invalid(gamma, h->n);
     if (bad >= 0) return fail(LDPC_HIP_ERR_INVALID, "memory strength %d is %g: every strength must be finite and in [-1, 1)", bad, gamma[bad]);
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -357,6 +359,8 @@ int ldpc_hip_bp_set_relay(ldpc_hip_bp *h, int32_t legs, const double *gamma, con
     }
     if (h->mem_on)
         return fail(LDPC_HIP_ERR_UNSUPPORTED, "Relay-BP and memory min-sum exclude each other: switch the memory off first (ldpc_hip_bp_set_memory(h, NULL))");
+    if (h->gd_on)
+        return fail(LDPC_HIP_ERR_UNSUPPORTED, "Relay-BP and guided decimation exclude each other: switch the decimation off first (ldpc_hip_bp_set_decimation(h, 0, 0, 0))");
     if (legs < 0 || legs > (1 << 20)) return fail(LDPC_HIP_ERR_INVALID, "Relay-BP: %d legs", (int)legs);
     if (!leg_iters) return fail(LDPC_HIP_ERR_INVALID, "Relay-BP: leg_iters must not be NULL");
     if (stop_after < 1) return fail(LDPC_HIP_ERR_INVALID, "Relay-BP: stop_after is %d: it must be at least 1", (int)stop_after);
@@ -384,6 +388,38 @@ int ldpc_hip_bp_get_relay(const ldpc_hip_bp *h, int32_t *legs, int32_t *stop_aft
     if (gamma_out) std::copy(h->relay_gamma.begin(), h->relay_gamma.end(), gamma_out);
     if (leg_iters_out) std::copy(h->relay_iters.begin(), h->relay_iters.end(), leg_iters_out);
     return 1;
+}
+
+int ldpc_hip_bp_set_decimation(ldpc_hip_bp *h, int32_t round_iters, int32_t max_rounds, double freeze_llr) {
+    if (!h) return fail(LDPC_HIP_ERR_INVALID, "null handle");
+    if (round_iters == 0) {  // off: the plain decode and its kernels again (nothing on the device is the decimation's own)
+        h->gd_on = false;
+        h->gd_round_iters = h->gd_max_rounds = 0;
+        h->gd_freeze = 0.0;
+        return LDPC_HIP_OK;
+    }
+    if (h->mem_on)
+        return fail(LDPC_HIP_ERR_UNSUPPORTED, "guided decimation and memory min-sum exclude each other: switch the memory off first (ldpc_hip_bp_set_memory(h, NULL))");
+    if (h->relay_on)
+        return fail(LDPC_HIP_ERR_UNSUPPORTED, "guided decimation and Relay-BP exclude each other: switch the relay off first (ldpc_hip_bp_set_relay(h, 0, NULL, NULL, 0))");
+    if (round_iters < 0) return fail(LDPC_HIP_ERR_INVALID, "guided decimation: round_iters is %d: it must be at least 1 (0 switches the decimation off)", (int)round_iters);
+    if (max_rounds < 1) return fail(LDPC_HIP_ERR_INVALID, "guided decimation: max_rounds is %d: it must be at least 1", (int)max_rounds);
+    if ((int64_t)round_iters * (int64_t)max_rounds > INT32_MAX)
+        return fail(LDPC_HIP_ERR_INVALID, "guided decimation: round_iters %d x max_rounds %d does not fit the 32-bit iteration count", (int)round_iters, (int)max_rounds);
+    if (!(freeze_llr > 0.0)) return fail(LDPC_HIP_ERR_INVALID, "guided decimation: freeze_llr is %g: it must be positive (finite or +inf)", freeze_llr);
+    h->gd_round_iters = round_iters;
+    h->gd_max_rounds = max_rounds;
+    h->gd_freeze = freeze_llr;
+    h->gd_on = true;
+    return LDPC_HIP_OK;
+}
+
+int ldpc_hip_bp_get_decimation(const ldpc_hip_bp *h, int32_t *round_iters, int32_t *max_rounds, double *freeze_llr) {
+    if (!h) return fail(LDPC_HIP_ERR_INVALID, "null handle");
+    if (round_iters) *round_iters = h->gd_on ? h->gd_round_iters : 0;
+    if (max_rounds) *max_rounds = h->gd_on ? h->gd_max_rounds : 0;
+    if (freeze_llr) *freeze_llr = h->gd_on ? h->gd_freeze : 0.0;
+    return h->gd_on ? 1 : 0;
 }
 
 int64_t ldpc_hip_bp_workspace_bytes(const ldpc_hip_bp *h, int64_t batch) {

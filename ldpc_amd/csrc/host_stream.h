@@ -484,10 +484,11 @@ int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
     h->timed_prev = h->timed_prev_mid = false;  // (what a two-pass decode before this one left)
     // Row priors (ldpc_hip_*_decode_batch_priors): every row is decoded with its own channel probabilities, h->row_probs [batch][n].  Two kernel
     // families read them: the slot kernel (decode_onchip sends there whatever an on-chip kernel would take) and the per-pass kernels (StreamPlan::rp).
-    if (h->mem_on || h->relay_on) {  // (the entry points have said so already, before staging anything: nothing wrong is ever decoded from here either)
+    if (h->mem_on || h->relay_on || h->gd_on) {  // (the entry points have said so already, before staging anything: nothing wrong is ever decoded from here either)
         const int refused = mem_refusal(h, h->row_probs ? "per-row channel probabilities are" : nullptr);
         if (refused) return refused;
     }
+    if (h->gd_on) return decode_onchip_gd(h, synd, batch, decoding, llr, iters, conv);  // guided decimation: the lane = edge kernels or a refusal, never another family
     if (h->relay_on) return decode_relay(h, synd, batch, decoding, llr, iters, conv);
     if (h->msg_dtype == LDPC_HIP_MSG_F32) return decode_f32(h, synd, batch, decoding, llr, iters, conv);  // (never an FP64 kernel: what the mode cannot do is refused there)
     const bool rp = h->row_probs != nullptr;

@@ -237,6 +237,46 @@ class HipBpEngine:
         _lib.check(rc)
         return self.RELAY_ROUTES[route.value]
 
+    def set_decimation(self, round_iters, max_rounds=None, freeze_llr=25.0):
+        """BP with guided decimation (``ldpc_hip_bp_set_decimation``): up to ``max_rounds`` rounds (``None``: n) of up to
+        ``round_iters`` min-sum iterations per syndrome -- together they take the place of ``max_iter``; a round that ends unsolved freezes the
+        most reliable bit at ``+-freeze_llr`` (positive, finite or ``inf``) and keeps the messages -- or ``round_iters=None``: off.
+        Minimum-sum, parallel schedule, float64 messages, the lane = edge kernels only (``decimation_route``); it excludes ``set_memory`` and
+        ``set_relay``; what it cannot do is refused when decoding."""
+        if round_iters is None:
+            _lib.check(self._lib.ldpc_hip_bp_set_decimation(self._h, 0, 0, 0.0))
+            return
+        if int(round_iters) == 0:
+            raise ValueError("round_iters is 0: it must be at least 1 (None switches the decimation off).")
+        rounds = self.n if max_rounds is None else int(max_rounds)
+        if not -2 ** 31 <= int(round_iters) < 2 ** 31 or not -2 ** 31 <= rounds < 2 ** 31:
+            raise ValueError(f"round_iters {round_iters} and max_rounds {rounds} must fit 32 bits.")
+        rc = self._lib.ldpc_hip_bp_set_decimation(self._h, int(round_iters), rounds, float(freeze_llr))
+        if rc == -1:  # LDPC_HIP_ERR_INVALID: the message names the value
+            raise ValueError(self._lib.ldpc_hip_last_error().decode("utf-8", "replace"))
+        _lib.check(rc)
+
+    @property
+    def decimation(self):
+        """``None`` when the decimation is off, else ``(round_iters, max_rounds, freeze_llr)``."""
+        t, r, c = C.c_int32(0), C.c_int32(0), C.c_double(0.0)
+        rc = int(self._lib.ldpc_hip_bp_get_decimation(self._h, C.byref(t), C.byref(r), C.byref(c)))
+        if rc < 0:
+            _lib.check(rc)
+        return (int(t.value), int(r.value), float(c.value)) if rc == 1 else None
+
+    DECIMATION_ROUTES = ("unavailable", "bp_edge", "bp_edge8")
+
+    def decimation_route(self, batch=1) -> str:
+        """Which kernels decode ``batch`` syndromes with guided decimation on this engine as it is set now (``ldpc_hip_bp_decimation_route``;
+        nothing is launched): ``"bp_edge"``, ``"bp_edge8"`` or ``"unavailable"`` (such a decode is refused).  ``ValueError`` when it is off."""
+        route = C.c_int32(-1)
+        rc = int(self._lib.ldpc_hip_bp_decimation_route(self._h, int(batch), C.byref(route)))
+        if rc == -1:
+            raise ValueError(self._lib.ldpc_hip_last_error().decode("utf-8", "replace"))
+        _lib.check(rc)
+        return self.DECIMATION_ROUTES[route.value]
+
     def set_ring(self, depth):
         """LDS-DMA ring for regular-degree matrices: False/0 = off, True/1 = default depth, 2 or 3 = slots per wave."""
         _lib.check(self._lib.ldpc_hip_bp_set_ring(self._h, int(depth)))

@@ -56,6 +56,9 @@ class MonteCarloDemSimulation:
     float64 messages only, and not together with a ``window_decoder``.  ``relay`` (a dict of ``ldpc_amd.relay_decoder.relay_schedule``
     keywords -- ``gamma0``, ``pre_iter``, ``num_sets``, ``set_max_iter``, ``gamma_dist_interval``, ``stop_nconv``, ``strengths``, ``seed``):
     Relay-BP, whose legs take the place of ``max_iter``; with ``osd_method`` OSD_0 only, and not together with ``memory_strength`` or a
+    ``window_decoder``.  ``decimation`` (a dict of ``ldpc_amd.bpgd_decoder.decimation_schedule`` keywords -- ``round_iters``, ``max_rounds``,
+    ``freeze_llr``): BP with guided decimation, whose rounds take the place of ``max_iter``; on models the lane = edge kernels take only
+    (others are refused at ``run()``), with ``osd_method`` OSD_0 only, and not together with ``relay``, ``memory_strength`` or a
     ``window_decoder``.
 
     One GPU (``device``; -1: the current one).  For several, run one simulation per device over disjoint shot ranges.
@@ -63,7 +66,7 @@ class MonteCarloDemSimulation:
 
     def __init__(self, model, *, target_run_count, batch_size: int = 65536, seed: int = 0, max_iter: int = 0, bp_method="ms",
                  ms_scaling_factor: float = 0.625, osd_method="osd0", osd_order: int = 0, message_dtype="float64", window_decoder=None,
-                 device: int = -1, memory_strength=None, relay=None) -> None:
+                 device: int = -1, memory_strength=None, relay=None, decimation=None) -> None:
         from ldpc_amd.bp_decoder._bp_decoder import _bp_method_code
         from ldpc_amd.noise_models.dem import check_dem_probabilities
         from ldpc_amd.sinter_decoders.sinter_bposd_decoder import _osd_code
@@ -129,6 +132,21 @@ class MonteCarloDemSimulation:
             from ldpc_amd.relay_decoder import relay_schedule
             relay = relay_schedule(self.check_matrix.shape[1], **relay)
         self.relay = relay
+        # BP with guided decimation (BpgdDecoder's keywords): (round_iters, max_rounds, freeze_llr) or None
+        if decimation is not None:
+            if relay is not None:
+                raise NotImplementedError("decimation with relay: the two exclude each other; leave one at None.")
+            if memory_strength is not None:
+                raise NotImplementedError("decimation with memory_strength: the two exclude each other; leave one at None.")
+            if window_decoder is not None:
+                raise NotImplementedError("decimation with a window_decoder: the windows decode with their own decoders; leave decimation at None.")
+            if self._osd_code in (2, 3) and self.osd_order > 0:
+                raise NotImplementedError("decimation with osd_method OSD_E / OSD_CS: guided decimation is followed by OSD_0 only.")
+            if not isinstance(decimation, dict):
+                raise ValueError("Invalid decimation provided. It must be None or a dict of decimation_schedule keywords.")
+            from ldpc_amd.bpgd_decoder import decimation_schedule
+            decimation = decimation_schedule(self.check_matrix.shape[1], **decimation)
+        self.decimation = decimation
         if not isinstance(device, int) or isinstance(device, bool):
             raise ValueError("Invalid device provided.")
         self.device = device
@@ -157,6 +175,8 @@ class MonteCarloDemSimulation:
             eng.set_memory(self.memory_strength)  # (what memory min-sum cannot do -- product-sum, float32 -- is refused at run(), by the library)
             if self.relay is not None:
                 eng.set_relay(*self.relay)  # (likewise)
+            if self.decimation is not None:
+                eng.set_decimation(*self.decimation)  # (likewise -- a model beyond the lane = edge kernels included)
             eng.set_observables(self.observables_matrix)
             eng.set_sampler(self.priors)
             self._engine = eng
