@@ -408,20 +408,6 @@ class BpDecoderBase:
             raise ValueError(f"message_dtype must be 'float64', 'float32', np.float64 or np.float32, not {value!r}.")
         self._message_dtype = key
 
-    def _require_message_dtype(self, what=None):
-        """What ``message_dtype='float32'`` cannot do is refused here, at decode time, with its reason (``what``: the call's own addition)."""
-        if self._message_dtype != "float32":
-            return
-        if what is not None:
-            raise NotImplementedError(f"message_dtype='float32' with {what}; set message_dtype='float64'.")
-        if self._bp_method != MINIMUM_SUM:
-            raise NotImplementedError("message_dtype='float32' with bp_method='product_sum': its tanh / log have no bit-exact float32 form here; "
-                                      "float32 messages are available for bp_method='minimum_sum' only.")
-        if self._schedule != PARALLEL:
-            raise NotImplementedError(f"message_dtype='float32' with schedule='{self.schedule}': float32 messages need schedule='parallel'.")
-        if self._device_ids is not None:
-            raise NotImplementedError("message_dtype='float32' with device_ids=[...]: float32 messages are not sharded over several GPUs; decode on one GPU.")
-
     # ---- memory min-sum BP (additive; not a constructor keyword either) ----------------------------------------
     @property
     def memory_strength(self):
@@ -479,30 +465,8 @@ class BpDecoderBase:
         ``ValueError`` when neither ``relay`` nor ``memory_strength`` is set."""
         if self._relay is None and self._memory is None:
             raise ValueError("relay_route: neither relay nor memory_strength is set.")
-        self._require_memory()
+        self._require_modes(message_dtype=False)
         return self._get_engine().relay_route(getattr(self, "_relay_batch", 1))
-
-    def _require_relay(self, what=None):
-        if self._relay is None:
-            return
-        if what is not None:
-            raise NotImplementedError(f"relay with {what.replace('without memory only', 'without the relay only')}; set relay=None.")
-        if self._memory is not None:
-            raise NotImplementedError("relay with memory_strength: the relay's legs carry their own strengths; set memory_strength=None.")
-        if self._bp_method != MINIMUM_SUM:
-            raise NotImplementedError("relay with bp_method='product_sum': the memory strengths are defined for bp_method='minimum_sum' only.")
-        if self._schedule != PARALLEL or self._random_serial_schedule:
-            raise NotImplementedError(f"relay with schedule='{self.schedule}'"
-                                      f"{' and random_serial_schedule' if self._random_serial_schedule else ''}: Relay-BP needs schedule='parallel'.")
-        if self._message_dtype != "float64":
-            raise NotImplementedError("relay with message_dtype='float32': Relay-BP is decoded with float64 messages only.")
-        if self._device_ids is not None:
-            raise NotImplementedError("relay with device_ids=[...]: Relay-BP is not sharded over several GPUs; decode on one GPU.")
-        p = self._channel_probs
-        bad = np.flatnonzero((self._relay[0] != 0.0).any(axis=0) & ~((p > 0.0) & (p < 1.0)))
-        if len(bad):
-            raise NotImplementedError(f"relay: bit {int(bad[0])} has a nonzero memory strength and a channel probability of {p[bad[0]]!r}; "
-                                      "Relay-BP needs probabilities strictly between 0 and 1 there (or strength 0 on that bit in every leg).")
 
     # ---- BP with guided decimation (additive; not a constructor keyword either) -----------------------------------
     @property
@@ -539,57 +503,68 @@ class BpDecoderBase:
         from ldpc_amd.bpgd_decoder import lane_edge_route
         if lane_edge_route(self._h) == "unavailable":  # (no handle needed to say so)
             return "unavailable"
-        self._require_decimation()
+        self._require_modes(message_dtype=False)
         return self._get_engine().decimation_route(getattr(self, "_relay_batch", 1))
 
-    def _require_decimation(self, what=None):
-        if self._decimation is None:
-            return
-        if what is not None:
-            raise NotImplementedError(f"decimation with {what.replace('without memory only', 'without decimation only')}; set decimation=None.")
-        if self._memory is not None:
-            raise NotImplementedError("decimation with memory_strength: the two exclude each other; set memory_strength=None or decimation=None.")
-        if self._relay is not None:
-            raise NotImplementedError("decimation with relay: the two exclude each other; set relay=None or decimation=None.")
-        if self._bp_method != MINIMUM_SUM:
-            raise NotImplementedError("decimation with bp_method='product_sum': guided decimation is built on the minimum-sum kernels only.")
-        if self._schedule != PARALLEL or self._random_serial_schedule:
-            raise NotImplementedError(f"decimation with schedule='{self.schedule}'"
-                                      f"{' and random_serial_schedule' if self._random_serial_schedule else ''}: guided decimation needs schedule='parallel'.")
-        if self._message_dtype != "float64":
-            raise NotImplementedError("decimation with message_dtype='float32': guided decimation is decoded with float64 messages only.")
-        if self._device_ids is not None:
-            raise NotImplementedError("decimation with device_ids=[...]: guided decimation is not sharded over several GPUs; decode on one GPU.")
-        from ldpc_amd.bpgd_decoder import lane_edge_route
-        if lane_edge_route(self._h) == "unavailable":
-            raise NotImplementedError("decimation: neither lane = edge kernel family takes this code (rows of at most 4 entries and columns of at most 2 "
-                                      "within 1024 slots, or rows of at most 8 and columns of at most 4 within the kernels' ladder; every column used); "
-                                      "the lane = node route for larger codes and a per-pass route are not built yet.")
+    # ---- what the four modes refuse, stated once (the C side's twin: ldpc_amd/csrc/mode_host.h) ---------------------------------------------
+    # One row per mode, asked in this order; within a row the rules are asked in the order of _require_modes.  Where the modes differ the row
+    # says so: ``random_serial`` -- whether random_serial_schedule alone breaks the schedule rule (float32 messages look at ``schedule`` only);
+    # ``excludes`` -- the modes that must be off, each with its own sentence; ``strengths`` -- where a nonzero strength needs a probability
+    # strictly between 0 and 1 (None: no such rule); ``route`` -- the mode needs a code the lane = edge kernels take.  ``only``: the mode's own
+    # wording for the ``{only}`` of a caller's ``what``.  A new mode is a new row.
+    _MODES = (
+        dict(key="message_dtype='float32'", on=lambda d: d._message_dtype == "float32", off="message_dtype='float64'", name="float32 messages", plural=True,
+             only="with float64 messages only", excludes=(), random_serial=False, float64_only=False, strengths=None, route=False,
+             product_sum="its tanh / log have no bit-exact float32 form here; float32 messages are available for bp_method='minimum_sum' only."),
+        dict(key="decimation", on=lambda d: d._decimation is not None, off="decimation=None", name="guided decimation", plural=False,
+             only="without decimation only", random_serial=True, float64_only=True, strengths=None, route=True,
+             excludes=(("memory_strength", lambda d: d._memory is not None, "the two exclude each other; set memory_strength=None or decimation=None."),
+                       ("relay", lambda d: d._relay is not None, "the two exclude each other; set relay=None or decimation=None.")),
+             product_sum="guided decimation is built on the minimum-sum kernels only."),
+        dict(key="relay", on=lambda d: d._relay is not None, off="relay=None", name="Relay-BP", plural=False,
+             only="without the relay only", random_serial=True, float64_only=True, strengths=lambda d: (d._relay[0] != 0.0).any(axis=0), every_leg=" in every leg", route=False,
+             excludes=(("memory_strength", lambda d: d._memory is not None, "the relay's legs carry their own strengths; set memory_strength=None."),),
+             product_sum="the memory strengths are defined for bp_method='minimum_sum' only."),
+        dict(key="memory_strength", on=lambda d: d._memory is not None, off="memory_strength=None", name="memory min-sum", plural=False,
+             only="without memory only", excludes=(), random_serial=True, float64_only=True, strengths=lambda d: d._memory != 0.0, every_leg="", route=False,
+             product_sum="the memory strengths are defined for bp_method='minimum_sum' only."),
+    )
 
-    def _require_memory(self, what=None):
-        """What memory min-sum cannot do is refused here, at decode time, with its reason (``what``: the call's own addition) -- and what
-        Relay-BP (``_require_relay``) and guided decimation (``_require_decimation``) cannot."""
-        self._require_decimation(what)
-        self._require_relay(what)
-        if self._memory is None:
-            return
-        if what is not None:
-            raise NotImplementedError(f"memory_strength with {what}; set memory_strength=None.")
-        if self._bp_method != MINIMUM_SUM:
-            raise NotImplementedError("memory_strength with bp_method='product_sum': the memory strengths are defined for "
-                                      "bp_method='minimum_sum' only.")
-        if self._schedule != PARALLEL or self._random_serial_schedule:
-            raise NotImplementedError(f"memory_strength with schedule='{self.schedule}'"
-                                      f"{' and random_serial_schedule' if self._random_serial_schedule else ''}: memory min-sum needs schedule='parallel'.")
-        if self._message_dtype != "float64":
-            raise NotImplementedError("memory_strength with message_dtype='float32': memory min-sum is decoded with float64 messages only.")
-        if self._device_ids is not None:
-            raise NotImplementedError("memory_strength with device_ids=[...]: memory min-sum is not sharded over several GPUs; decode on one GPU.")
-        p = self._channel_probs
-        bad = np.flatnonzero((self._memory != 0.0) & ~((p > 0.0) & (p < 1.0)))
-        if len(bad):
-            raise NotImplementedError(f"memory_strength: bit {int(bad[0])} has a nonzero memory strength and a channel probability of {p[bad[0]]!r}; "
-                                      "memory min-sum needs probabilities strictly between 0 and 1 there (or strength 0 on that bit).")
+    def _require_modes(self, what=None, message_dtype=True):
+        """What the modes that are on cannot do is refused here, at decode time and before any handle is made, with its reason.  ``what``: the
+        call's own addition, which no mode does -- its ``{only}`` takes each mode's own wording.  ``message_dtype=False``: the three variants
+        alone (the route properties, which name no float32 route)."""
+        for mode in self._MODES:
+            if not mode["on"](self) or (mode is self._MODES[0] and not message_dtype):
+                continue
+            key, name = mode["key"], mode["name"]
+            if what is not None:
+                raise NotImplementedError(f"{key} with {what.format(only=mode['only'])}; set {mode['off']}.")
+            for other, other_on, why in mode["excludes"]:
+                if other_on(self):
+                    raise NotImplementedError(f"{key} with {other}: {why}")
+            if self._bp_method != MINIMUM_SUM:
+                raise NotImplementedError(f"{key} with bp_method='product_sum': {mode['product_sum']}")
+            random_serial = mode["random_serial"] and self._random_serial_schedule
+            if self._schedule != PARALLEL or random_serial:
+                raise NotImplementedError(f"{key} with schedule='{self.schedule}'{' and random_serial_schedule' if random_serial else ''}: "
+                                          f"{name} need{'' if mode['plural'] else 's'} schedule='parallel'.")
+            if mode["float64_only"] and self._message_dtype != "float64":
+                raise NotImplementedError(f"{key} with message_dtype='float32': {name} is decoded with float64 messages only.")
+            if self._device_ids is not None:
+                raise NotImplementedError(f"{key} with device_ids=[...]: {name} {'are' if mode['plural'] else 'is'} not sharded over several GPUs; decode on one GPU.")
+            if mode["strengths"] is not None:
+                p = self._channel_probs
+                bad = np.flatnonzero(mode["strengths"](self) & ~((p > 0.0) & (p < 1.0)))
+                if len(bad):
+                    raise NotImplementedError(f"{key}: bit {int(bad[0])} has a nonzero memory strength and a channel probability of {p[bad[0]]!r}; "
+                                              f"{name} needs probabilities strictly between 0 and 1 there (or strength 0 on that bit{mode['every_leg']}).")
+            if mode["route"]:
+                from ldpc_amd.bpgd_decoder import lane_edge_route
+                if lane_edge_route(self._h) == "unavailable":
+                    raise NotImplementedError(f"{key}: neither lane = edge kernel family takes this code (rows of at most 4 entries and columns of at most 2 "
+                                              "within 1024 slots, or rows of at most 8 and columns of at most 4 within the kernels' ladder; every column used); "
+                                              "the lane = node route for larger codes and a per-pass route are not built yet.")
 
     # ---- device engine --------------------------------------------------------------------------
     def _get_engine(self):
@@ -623,24 +598,18 @@ class BpDecoderBase:
         if self._message_dtype != self._engine_dtype:
             self._engine.set_message_dtype(self._message_dtype)
             self._engine_dtype = self._message_dtype
-        decimation_changed = self._decimation != self._engine_decimation
-        if decimation_changed and self._engine_decimation is not None:  # (off before the memory or the relay may go on: the three exclude one another on the handle)
-            self._engine.set_decimation(None)
-            self._engine_decimation = None
-        relay_changed = self._relay is not self._engine_relay
-        if relay_changed and self._relay is None:  # (off before the memory may go on: the two exclude each other on the handle)
-            self._engine.set_relay(None)
-            self._engine_relay = None
-        if not (self._memory is self._engine_memory or (self._memory is not None and self._engine_memory is not None
-                                                         and np.array_equal(self._memory, self._engine_memory))):
-            self._engine.set_memory(self._memory)
-            self._engine_memory = None if self._memory is None else self._memory.copy()
-        if relay_changed and self._relay is not None:
-            self._engine.set_relay(*self._relay)
-            self._engine_relay = self._relay
-        if self._decimation is not None and self._engine_decimation is None:
-            self._engine.set_decimation(*self._decimation)
-            self._engine_decimation = self._decimation
+        # memory min-sum, Relay-BP, guided decimation: the handle holds at most one -- first off what it holds that is no longer wanted, then on what is
+        variants = (("_memory", "_engine_memory", "set_memory"), ("_relay", "_engine_relay", "set_relay"), ("_decimation", "_engine_decimation", "set_decimation"))
+        stale = [v for v in variants if not _same_setting(getattr(self, v[0]), getattr(self, v[1]))]
+        for wanted, held, setter in stale:
+            if getattr(self, wanted) is None:
+                getattr(self._engine, setter)(None)
+                setattr(self, held, None)
+        for wanted, held, setter in stale:
+            value = getattr(self, wanted)
+            if value is not None:
+                getattr(self._engine, setter)(*(value if isinstance(value, tuple) else (value,)))
+                setattr(self, held, value if isinstance(value, tuple) else value.copy())
         rnd = (bool(self._random_serial_schedule), self._random_schedule_seed, self._seed_epoch)
         if rnd != getattr(self, "_engine_random", (False, 0, 0)):
             self._engine.set_random_serial(rnd[0], rnd[1])  # re-seeds, as bpd.set_random_schedule_seed does (pyx:553-554)
@@ -692,8 +661,7 @@ class BpDecoderBase:
         """``channel_probs`` of ``decode_batch``: what cannot be done is refused with its reason, then the array is checked
         (``HipBpEngine._row_probs``) -- without a GPU: shape, dtype, range and place need none."""
         from ldpc_amd.engine import HipBpEngine
-        self._require_message_dtype("channel_probs: per-row channel probabilities are decoded with float64 messages only")
-        self._require_memory("channel_probs: per-row channel probabilities are decoded without memory only")
+        self._require_modes("channel_probs: per-row channel probabilities are decoded {only}")
         if self._schedule != PARALLEL:
             raise NotImplementedError(f"channel_probs with schedule='{self.schedule}': the serial schedules decode with the decoder's own "
                                       "channel probabilities only; per-row probabilities need schedule='parallel'.")
@@ -753,6 +721,11 @@ class BpDecoderBase:
         if self._schedule_keeps_state() and self._engine is not None and hasattr(self._engine, "schedule_order"):
             self._serial_schedule_order = self._engine.schedule_order().astype(np.int64)
             self._engine_sched = (self._schedule, tuple(int(v) for v in self._serial_schedule_order))
+
+
+def _same_setting(a, b) -> bool:
+    """A variant's setting on the decoder and the one its handle holds: the same object, or equal arrays (memory strengths)."""
+    return a is b or (isinstance(a, np.ndarray) and isinstance(b, np.ndarray) and np.array_equal(a, b))
 
 
 def _zero_rows(vec: np.ndarray) -> np.ndarray:
@@ -819,8 +792,7 @@ class BpDecoder(BpDecoderBase):
             self._converge = True
             return np.zeros(self.n, dtype=dtype)
         self._require_parallel()
-        self._require_message_dtype()  # (float32: the one row goes through the batch kernels; the resident single-decode path is float64 only)
-        self._require_memory()  # (likewise)
+        self._require_modes()  # (float32, memory: the one row goes through the batch kernels; the resident single-decode path is plain float64 only)
         as_syndrome = self._bp_input_type == SYNDROME or (self._bp_input_type == AUTO and ln == self.m)
         if as_syndrome:
             dec, llr, it, cv = self._decode_numpy(vec[None, :])
@@ -872,8 +844,7 @@ class BpDecoder(BpDecoderBase):
         elif self._bp_input_type == AUTO and not (ln == self.m or ln == self.n):
             raise ValueError(f"The input_vector must have length {self.m} (for syndrome decoding) or length {self.n} (for received vector decoding). Not length {ln}.")
         self._require_parallel()
-        self._require_message_dtype()
-        self._require_memory()
+        self._require_modes()
         as_syndrome = self._bp_input_type == SYNDROME or (self._bp_input_type == AUTO and ln == self.m)
         if channel_probs is not None:
             channel_probs = self._row_probs(input_vectors, channel_probs, as_syndrome)
@@ -984,8 +955,7 @@ class SoftInfoBpDecoder(BpDecoderBase):
         """With random_serial_schedule the routine rearranges the order the object carries at the top of every iteration it runs
         (bp.hpp:573-577: ``shuffle(order, std::default_random_engine(random_schedule_seed))``, a new engine each time); the engine
         does the same draws, every row of a batch from the order at the time of the call, and leaves its last row's order."""
-        self._require_message_dtype("soft-syndrome decoding: it is a serial schedule (bp.hpp:547-660)")
-        self._require_memory("soft-syndrome decoding: it is a serial schedule (bp.hpp:547-660)")
+        self._require_modes("soft-syndrome decoding: it is a serial schedule (bp.hpp:547-660)")
         out = self._get_engine().soft_info_decode_batch(soft2d, self.cutoff, self.sigma)
         self._pull_schedule_state()
         return out

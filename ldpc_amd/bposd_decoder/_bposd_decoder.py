@@ -99,8 +99,7 @@ class BpOsdDecoder(BpDecoderBase):
 
     def _require_supported(self):
         self._require_parallel()
-        self._require_message_dtype()  # (float32: BP in FP32, OSD unchanged on the widened posteriors)
-        self._require_memory()  # (memory_strength: BP with memory, OSD unchanged on its posteriors)
+        self._require_modes()  # (float32: BP in FP32; memory_strength: BP with memory -- OSD unchanged on the posteriors either way)
         if self._relay is not None and self._osd_method in (EXHAUSTIVE, COMBINATION_SWEEP):
             raise NotImplementedError(f"relay with osd_method='{self.osd_method}': Relay-BP is followed by OSD_0 only; set osd_method='osd_0' or relay=None.")
         if self._decimation is not None and self._osd_method in (EXHAUSTIVE, COMBINATION_SWEEP):

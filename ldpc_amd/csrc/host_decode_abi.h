@@ -10,8 +10,7 @@ int ldpc_hip_bposd0_decode_batch_async(ldpc_hip_bp *h, const uint8_t *synd, int6
     if (batch < 0) return fail(LDPC_HIP_ERR_INVALID, "negative batch");
     if (batch == 0) return LDPC_HIP_OK;
     if (!synd || !decoding) return fail(LDPC_HIP_ERR_INVALID, "syndromes and decoding must not be NULL");
-    { const int refused = f32_refusal(h, nullptr); if (refused) return refused; }
-    { const int refused = mem_refusal(h, nullptr); if (refused) return refused; }
+    { const int refused = decode_gate(h, nullptr, false); if (refused) return refused; }
     HIPCHK(hipSetDevice(h->device));
     return mark_queued(h, bposd_device(h, 1, 0, synd, batch, decoding, llr, iters, conv));
 }
@@ -60,9 +59,7 @@ int ldpc_hip_bposd_decode_batch_async(ldpc_hip_bp *h, const uint8_t *synd, int64
     if (batch < 0) return fail(LDPC_HIP_ERR_INVALID, "negative batch");
     if (batch == 0) return LDPC_HIP_OK;
     if (!synd || !decoding) return fail(LDPC_HIP_ERR_INVALID, "syndromes and decoding must not be NULL");
-    { const int refused = f32_refusal(h, nullptr); if (refused) return refused; }
-    { const int refused = mem_refusal(h, nullptr); if (refused) return refused; }
-    { const int refused = relay_osd_refusal(h, true); if (refused) return refused; }
+    { const int refused = decode_gate(h, nullptr, true); if (refused) return refused; }
     HIPCHK(hipSetDevice(h->device));
     return mark_queued(h, bposd_device(h, h->osd_method, h->osd_order, synd, batch, decoding, llr, iters, conv));
 }
@@ -74,8 +71,7 @@ int ldpc_hip_bp_decode_batch_async(ldpc_hip_bp *h, const uint8_t *synd, int64_t 
     if (batch == 0) return LDPC_HIP_OK;
     if (!synd || !decoding) return fail(LDPC_HIP_ERR_INVALID, "syndromes and decoding must not be NULL");
     if (batch > (1ll << 40)) return fail(LDPC_HIP_ERR_INVALID, "batch too large");
-    { const int refused = f32_refusal(h, nullptr); if (refused) return refused; }
-    { const int refused = mem_refusal(h, nullptr); if (refused) return refused; }
+    { const int refused = decode_gate(h, nullptr, false); if (refused) return refused; }
     HIPCHK(hipSetDevice(h->device));
     return mark_queued(h, decode_device(h, synd, batch, decoding, llr, iters, conv));
 }
@@ -85,12 +81,12 @@ static int decode_batch_staged(ldpc_hip_bp *h, int osd, const uint8_t *synd, int
                                double *llr, int32_t *iters, uint8_t *conv, const double *probs = nullptr);
 
 // ---- row priors: every syndrome decoded with its own channel probabilities ---------------------------------------------------------
-// what the handle is set up for that such a decode cannot do (decode_device would refuse the schedule too: this says so before anything is staged)
+// what the handle is set up for that such a decode cannot do (decode_device would refuse the schedule too: this says so before anything is staged).
+// The serial-schedule sentence is the call's own and speaks between the gate's two: after float32 messages (which refuse every such call), before the variant.
 static int row_priors_refusal(const ldpc_hip_bp *h) {
-    { const int refused = f32_refusal(h, "per-row channel probabilities are"); if (refused) return refused; }
-    if (h->schedule != 1 || h->random_serial)
+    if (h->msg_dtype != LDPC_HIP_MSG_F32 && (h->schedule != 1 || h->random_serial))
         return fail(LDPC_HIP_ERR_UNSUPPORTED, "per-row channel probabilities: the serial schedules read the handle's priors only (parallel schedule required)");
-    return mem_refusal(h, "per-row channel probabilities are");
+    return decode_gate(h, "per-row channel probabilities are", false);
 }
 
 int ldpc_hip_bp_decode_batch_priors(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr,
@@ -349,9 +345,7 @@ static int decode_batch_staged(ldpc_hip_bp *h, int osd, const uint8_t *synd, int
     if (batch == 0) return LDPC_HIP_OK;
     if (!synd || !decoding) return fail(LDPC_HIP_ERR_INVALID, "syndromes and decoding must not be NULL");
     if (probs) { const int refused = row_priors_refusal(h); if (refused) return refused; }
-    { const int refused = f32_refusal(h, nullptr); if (refused) return refused; }
-    { const int refused = mem_refusal(h, nullptr); if (refused) return refused; }
-    { const int refused = relay_osd_refusal(h, osd == 1); if (refused) return refused; }
+    { const int refused = decode_gate(h, nullptr, osd == 1); if (refused) return refused; }
     HIPCHK(hipSetDevice(h->device));
     const size_t B = (size_t)batch, m = (size_t)h->m, n = (size_t)h->n;
     const uint8_t *d_synd = synd;
@@ -385,7 +379,7 @@ static int decode_batch_staged(ldpc_hip_bp *h, int osd, const uint8_t *synd, int
             double *p_llr = (llr || osd >= 0) ? (double *)(dv + o_llr) : nullptr;
             uint8_t *p_cv = (conv || osd >= 0) ? (uint8_t *)(dv + o_cv) : nullptr;
             int32_t *p_it = iters ? (int32_t *)(dv + o_it) : nullptr;
-            if (batch == 1 && osd < 0 && h->msg_dtype == LDPC_HIP_MSG_F64 && !h->mem_on && !h->relay_on && !h->gd_on && !h->on("TIME_SMALL_CALLS")) {  // ONE syndrome: the resident workgroup, where one applies
+            if (batch == 1 && osd < 0 && h->msg_dtype == LDPC_HIP_MSG_F64 && h->variant == Variant::Plain && !h->on("TIME_SMALL_CALLS")) {  // ONE syndrome: the resident workgroup, where one applies
                 bool took = false;
                 if ((rc = decode_onchip_resident(h, llr != nullptr, &took))) return rc;
                 if (took) {
@@ -492,8 +486,7 @@ int ldpc_hip_bp_soft_info_decode_batch(ldpc_hip_bp *h, const double *soft_syndro
     if (batch == 0) return LDPC_HIP_OK;
     if (!soft_syndromes || !decoding) return fail(LDPC_HIP_ERR_INVALID, "soft syndromes and decoding must not be NULL");
     if (!(sigma > 0)) return fail(LDPC_HIP_ERR_INVALID, "The sigma value must be a float greater than 0.");  // _bp_decoder.pyx:748-749
-    { const int refused = f32_refusal(h, "soft-syndrome decoding is"); if (refused) return refused; }
-    { const int refused = mem_refusal(h, "soft-syndrome decoding is"); if (refused) return refused; }
+    { const int refused = decode_gate(h, "soft-syndrome decoding is", false); if (refused) return refused; }
     HIPCHK(hipSetDevice(h->device));
     const size_t B = (size_t)batch, m = (size_t)h->m, n = (size_t)h->n;
     int rc;
@@ -585,9 +578,7 @@ int ldpc_hip_bp_decode_b8(ldpc_hip_bp *h, const uint8_t *dets_b8, int64_t batch,
     if (!dets_b8) return fail(LDPC_HIP_ERR_INVALID, "null detection-event buffer");
     if (!obs_b8 && !decoding_b8) return fail(LDPC_HIP_ERR_INVALID, "neither obs_b8 nor decoding_b8 requested");
     if (obs_b8 && h->obs_k < 0) return fail(LDPC_HIP_ERR_INVALID, "obs_b8 requested but ldpc_hip_bp_set_observables was never called");
-    { const int refused = f32_refusal(h, nullptr); if (refused) return refused; }
-    { const int refused = mem_refusal(h, nullptr); if (refused) return refused; }
-    { const int refused = relay_osd_refusal(h, with_osd != 0); if (refused) return refused; }
+    { const int refused = decode_gate(h, nullptr, with_osd != 0); if (refused) return refused; }
     HIPCHK(hipSetDevice(h->device));
     const size_t B = (size_t)batch, m = (size_t)h->m, n = (size_t)h->n;
     const size_t mb = (m + 7) / 8, nb = (n + 7) / 8, kb = obs_b8 ? ((size_t)h->obs_k + 7) / 8 : 0;

@@ -159,9 +159,7 @@ int ldpc_hip_bp_simulate_b8(ldpc_hip_bp *h, uint64_t seed, int64_t shot0, int64_
     if (!out) return fail(LDPC_HIP_ERR_INVALID, "null output");
     if (!h->sampler_set) return fail(LDPC_HIP_ERR_INVALID, "ldpc_hip_bp_set_sampler was never called");
     if (h->obs_k < 0) return fail(LDPC_HIP_ERR_INVALID, "ldpc_hip_bp_set_observables was never called");
-    { const int refused = f32_refusal(h, nullptr); if (refused) return refused; }
-    { const int refused = mem_refusal(h, nullptr); if (refused) return refused; }
-    { const int refused = relay_osd_refusal(h, with_osd != 0); if (refused) return refused; }
+    { const int refused = decode_gate(h, nullptr, with_osd != 0); if (refused) return refused; }
     out[0] = out[1] = 0;
     if (shots == 0) return LDPC_HIP_OK;
     int words = 0, rc;

@@ -1,18 +1,7 @@
-// host_f32.h -- host side of the float32 message mode (bp_f32_kernels.h): what it refuses, its workspace, a chunk's rounds queued
+// host_f32.h -- host side of the float32 message mode (bp_f32_kernels.h): its workspace, a chunk's rounds queued
 // Part of libldpc_hip.so: included by tu_f32.hip.  Modelled on the per-pass route of host_stream.h (StreamPlan::rp): per-pass kernels
 // from the first iteration for any batch size, every round queued without waiting for the device.
 #pragma once
-
-// What the handle is set up for that the float32 mode cannot do; *what: the caller's own addition (row priors, soft syndromes) or nullptr.
-int f32_refusal(const ldpc_hip_bp *h, const char *what) {
-    if (h->msg_dtype != LDPC_HIP_MSG_F32) return LDPC_HIP_OK;
-    if (what) return fail(LDPC_HIP_ERR_UNSUPPORTED, "float32 messages: %s not available (set the message dtype to float64)", what);
-    if (h->bp_method != LDPC_HIP_MINIMUM_SUM)
-        return fail(LDPC_HIP_ERR_UNSUPPORTED, "float32 messages: product-sum is not available (its tanh / log have no bit-exact FP32 form here); use minimum-sum or float64");
-    if (h->schedule != 1 || h->random_serial)
-        return fail(LDPC_HIP_ERR_UNSUPPORTED, "float32 messages: the serial schedules are not available (parallel schedule required)");
-    return LDPC_HIP_OK;
-}
 
 // bytes of a 64-syndrome tile: both message arrays, the posteriors if wanted, packed syndromes and decisions
 static size_t f32_tile_bytes(const ldpc_hip_bp *h, bool want_llr) {
@@ -221,7 +210,7 @@ static int decode_f32_repacked(ldpc_hip_bp *h, const uint8_t *synd, int64_t batc
 // The float32 decode of a batch: device pointers, on h->stream; `llr` receives FP64 values, each an FP32 posterior widened.
 int decode_f32(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv) {
     int rc;
-    if ((rc = f32_refusal(h, h->row_probs ? "per-row channel probabilities are" : nullptr))) return rc;
+    if ((rc = decode_gate(h, h->row_probs ? "per-row channel probabilities are" : nullptr, false))) return rc;  // (the entry points have said so already)
     // Small codes of the lane = edge families stay on chip (host_onchip.h: decode_onchip_f32 -- one launch, messages in registers).  Off:
     // small_mode 0 (never an on-chip kernel), the switch F32_ONCHIP 0, and any switch that names the per-pass kernels below (F32_NT,
     // F32_GRID_ROWS, SPREAD_NODES: who sets one wants those kernels, on whatever code).

@@ -20,6 +20,7 @@
 #include <sys/mman.h>
 
 #include "mem_host.h"
+#include "mode_host.h"
 
 // ------------------------------------------------------------------------------------------------
 // host side
@@ -323,20 +324,20 @@ struct ldpc_hip_bp {
     const double *row_probs = nullptr;
     DeviceBuf rowp_llr;  // their log-ratios: in tile layout [tiles of a chunk][n][64] (io_kernels.h: row_priors_kernel), or row-major [batch][n] for the lane = edge kernels (row_priors_rowmajor_kernel)
     DeviceBuf st_probs;  // staging for a host pointer
+    // Which of memory min-sum, Relay-BP and guided decimation is on -- at most one: the three setters switch it and refuse a second (mode_host.h: mode_exclusion)
+    Variant variant = Variant::Plain;
     // Memory min-sum BP (ldpc_hip_bp_set_memory): every iteration's bit pass takes a[j] + gamma[j] * (the column's previous
-    // posterior) for the prior.  decode_device looks at mem_on and sends the batch to the memory kernels (bp_edge_mem_kernel.h, the bp_spread_mem_* kernels of
+    // posterior) for the prior.  decode_device looks at `variant` and sends the batch to the memory kernels (bp_edge_mem_kernel.h, the bp_spread_mem_* kernels of
     // bp_spread_kernels.h); with it off nothing below is read.  The per-pass route keeps the posteriors M [tiles of a chunk][n][64] in rowp_llr
     // (row priors and memory exclude each other).
-    bool mem_on = false;
     std::vector<double> mem_gamma;  // [n] the strengths as given
     int mem_bad_col = -1;           // first column with gamma != 0 whose prior is not finite, for the priors the handle holds NOW (-1: none)
     DeviceBuf mem_ag;               // [2][n]: a[] = (1 - gamma) * log((1 - p) / p) (mem_host.h), then gamma[]; rewritten by upload_memory
     DeviceBuf e_mem;                // [2][R * 64]: a and gamma of every slot of the lane = edge tables (edge_mem_table_kernel, before every launch)
     // Relay-BP (ldpc_hip_bp_set_relay): relay_legs memory legs chained per syndrome -- leg l runs up to relay_iters[l] iterations
     // with the strengths relay_gamma[l][.] and starts from the posteriors the leg before it ended with; the lightest of the first relay_stop
-    // solutions is the result.  decode_device looks at relay_on and sends the batch to decode_relay (host_stream.h): the lane = edge relay kernels
+    // solutions is the result.  decode_device looks at `variant` and sends the batch to decode_relay (host_stream.h): the lane = edge relay kernels
     // (bp_edge_relay_kernel.h), the lane = node kernel (bp_wave_relay_kernel.h), or a loop of per-pass memory decodes with relay_select_kernel after each.  Relay and memory exclude each other.
-    bool relay_on = false;
     int32_t relay_legs = 0, relay_stop = 0;
     std::vector<double> relay_gamma;    // [legs][n] the strengths as given
     std::vector<int32_t> relay_iters;   // [legs]
@@ -348,9 +349,8 @@ struct ldpc_hip_bp {
     DeviceBuf relay_dec, relay_llr, relay_li, relay_cv, relay_state;  // the leg loop: a leg's outputs [batch][n] / [batch]; {best weight f64, solutions i32, iterations i32} per row
     // BP with guided decimation (ldpc_hip_bp_set_decimation): up to gd_max_rounds rounds of gd_round_iters min-sum iterations per
     // syndrome; a round that ends unsolved freezes the most reliable column at +-gd_freeze and keeps the messages.  gd_round_iters and gd_max_rounds
-    // take max_iter's place.  decode_device looks at gd_on and sends the batch to decode_onchip_gd (host_onchip.h: the lane = edge kernels of
+    // take max_iter's place.  decode_device looks at `variant` and sends the batch to decode_onchip_gd (host_onchip.h: the lane = edge kernels of
     // bp_edge_gd_kernel.h, nothing else).  Decimation, relay and memory exclude one another.  No device buffer of its own: the slot tables and e_prior are the plain decode's.
-    bool gd_on = false;
     int32_t gd_round_iters = 0, gd_max_rounds = 0;
     double gd_freeze = 0.0;
     mutable int gd_route_known = -1, gd_route_method = 0, gd_route_mode = 0;  // gd_route's answer for this code under (bp_method, small_mode), -1: not asked yet (the plans scan the matrix: once, not at every refusal check)
@@ -374,7 +374,7 @@ static auto with_method_math(const ldpc_hip_bp *h, Fn &&f) {
 }
 
 // Memory min-sum: a[] and gamma[] of the priors and strengths the handle holds now -> mem_ag (the stream is idle: ldpc_hip_bp_set_memory and
-// ldpc_hip_bp_set_channel wait for it first).  mem_bad_col: what a decode has to refuse (mem_refusal).
+// ldpc_hip_bp_set_channel wait for it first).  mem_bad_col: what a decode has to refuse (decode_gate).
 static int upload_memory(ldpc_hip_bp *h) {
     const size_t n = (size_t)h->n;
     std::vector<double> ag(2 * (n ? n : 1), 0.0);
@@ -404,79 +404,28 @@ static int upload_relay(ldpc_hip_bp *h) {
     return LDPC_HIP_OK;
 }
 
-// What the handle is set up for that Relay-BP cannot do: the memory decode's list (`what` as there).  OSD of a higher order than OSD-0 is
-// refused by the BP + OSD entry points themselves.
-static int relay_refusal(const ldpc_hip_bp *h, const char *what) {
-    if (!h->relay_on) return LDPC_HIP_OK;
-    if (what) return fail(LDPC_HIP_ERR_UNSUPPORTED, "Relay-BP: %s not available (switch the relay off: ldpc_hip_bp_set_relay(h, 0, NULL, NULL, 0))", what);
-    if (h->bp_method != LDPC_HIP_MINIMUM_SUM)
-        return fail(LDPC_HIP_ERR_UNSUPPORTED, "Relay-BP: product-sum is not available (the memory strengths are defined for minimum-sum only)");
-    if (h->schedule != 1 || h->random_serial)
-        return fail(LDPC_HIP_ERR_UNSUPPORTED, "Relay-BP: the serial schedules are not available (parallel schedule required)");
-    if (h->msg_dtype != LDPC_HIP_MSG_F64)
-        return fail(LDPC_HIP_ERR_UNSUPPORTED, "Relay-BP: float32 messages are not available (set the message dtype to float64)");
-    if (h->relay_bad_col >= 0)
-        return fail(LDPC_HIP_ERR_UNSUPPORTED, "Relay-BP: column %d has a nonzero memory strength and a channel probability of 0 or 1 -- "
-                    "it needs probabilities strictly between 0 and 1 (or strength 0 on that column in every leg)", h->relay_bad_col);
-    return LDPC_HIP_OK;
-}
-
 // tu_onchip.hip (host_onchip.h): which lane = edge family decodes this handle's code with guided decimation -- 0 neither, 1 bp_edge, 2 bp_edge8.
 // It looks at the matrix, the BP method and the small-code kernel mode only, and launches nothing.
 int gd_route(const ldpc_hip_bp *h, int64_t batch);
 
-// What the handle is set up for that a decode with guided decimation cannot do (`what` as for the memory decode below).  The lane = edge kernels
-// are its only route: a code neither family takes is refused here, before anything is staged, not decoded some other way.
-static int gd_refusal(const ldpc_hip_bp *h, const char *what) {
-    if (!h->gd_on) return LDPC_HIP_OK;
-    if (what) return fail(LDPC_HIP_ERR_UNSUPPORTED, "guided decimation: %s not available (switch the decimation off: ldpc_hip_bp_set_decimation(h, 0, 0, 0))", what);
-    if (h->bp_method != LDPC_HIP_MINIMUM_SUM)
-        return fail(LDPC_HIP_ERR_UNSUPPORTED, "guided decimation: product-sum is not available (it is built on the minimum-sum lane = edge kernels only)");
-    if (h->schedule != 1 || h->random_serial)
-        return fail(LDPC_HIP_ERR_UNSUPPORTED, "guided decimation: the serial schedules are not available (parallel schedule required)");
-    if (h->msg_dtype != LDPC_HIP_MSG_F64)
-        return fail(LDPC_HIP_ERR_UNSUPPORTED, "guided decimation: float32 messages are not available (set the message dtype to float64)");
-    if (gd_route(h, 0) == 0)
-        return fail(LDPC_HIP_ERR_UNSUPPORTED, "guided decimation: neither lane = edge kernel family takes this code under small-code kernel mode %d "
-                    "(ldpc_hip_bp_decimation_route answers 0: it needs rows of at most 8 and columns of at most 4 entries within the kernels' ladders, and mode -1, 1 or 6); "
-                    "the lane = node route for larger codes and a per-pass route are not built yet", (int)h->small_mode);
-    return LDPC_HIP_OK;
-}
-
-// What the handle is set up for that a memory decode cannot do; `what`: the call's own addition (row priors, soft syndromes, several GPUs) or
-// nullptr.  LDPC_HIP_OK when memory is off.  Called beside f32_refusal by every decode entry point, before anything is staged or launched.
-// (With Relay-BP or guided decimation on instead -- the three exclude one another -- it answers for them: relay_refusal, gd_refusal.)
-static int mem_refusal(const ldpc_hip_bp *h, const char *what) {
-    if (h->gd_on) return gd_refusal(h, what);
-    if (h->relay_on) return relay_refusal(h, what);
-    if (!h->mem_on) return LDPC_HIP_OK;
-    if (what) return fail(LDPC_HIP_ERR_UNSUPPORTED, "memory min-sum: %s not available (switch the memory off: ldpc_hip_bp_set_memory(h, NULL))", what);
-    if (h->bp_method != LDPC_HIP_MINIMUM_SUM)
-        return fail(LDPC_HIP_ERR_UNSUPPORTED, "memory min-sum: product-sum is not available (the memory strengths are defined for minimum-sum only)");
-    if (h->schedule != 1 || h->random_serial)
-        return fail(LDPC_HIP_ERR_UNSUPPORTED, "memory min-sum: the serial schedules are not available (parallel schedule required)");
-    if (h->msg_dtype != LDPC_HIP_MSG_F64)
-        return fail(LDPC_HIP_ERR_UNSUPPORTED, "memory min-sum: float32 messages are not available (set the message dtype to float64)");
-    if (h->mem_bad_col >= 0)
-        return fail(LDPC_HIP_ERR_UNSUPPORTED, "memory min-sum: column %d has a nonzero memory strength and a channel probability of 0 or 1 -- "
-                    "it needs probabilities strictly between 0 and 1 (or strength 0 on that column)", h->mem_bad_col);
-    return LDPC_HIP_OK;
-}
-
-// Relay-BP with ordered-statistics post-processing: OSD-0 only (osd_order 0 takes the OSD-0 branch whatever the method).  `with_osd`: the call
-// runs the handle's osd_method / osd_order.
-static int relay_osd_refusal(const ldpc_hip_bp *h, bool with_osd) {
-    if (h->relay_on && with_osd && h->osd_method >= 2 && h->osd_order > 0)
-        return fail(LDPC_HIP_ERR_UNSUPPORTED, "Relay-BP: OSD-E and OSD-CS are not available (OSD-0 only: ldpc_hip_bp_set_osd(h, 1, 0), or switch the relay off)");
-    if (h->gd_on && with_osd && h->osd_method >= 2 && h->osd_order > 0)  // (guided decimation: the same rule)
-        return fail(LDPC_HIP_ERR_UNSUPPORTED, "guided decimation: OSD-E and OSD-CS are not available (OSD-0 only: ldpc_hip_bp_set_osd(h, 1, 0), or switch the decimation off)");
-    return LDPC_HIP_OK;
+// THE gate of every decode entry point, before anything is staged or launched: what the handle is set up for that its modes -- float32 messages,
+// and whichever of memory min-sum, Relay-BP and guided decimation is on -- cannot do (the rules and their texts: mode_host.h).  `what`: the call's own
+// addition (row priors, soft syndromes, several GPUs) or nullptr; with_osd: the call runs the handle's osd_method / osd_order.  The lane = edge
+// kernels are guided decimation's only route: a code neither family takes is refused here, not decoded some other way.
+static int decode_gate(const ldpc_hip_bp *h, const char *what, bool with_osd) {
+    const Variant v = h->variant;
+    const ModeState s = {h->bp_method, h->schedule == 1 && !h->random_serial, h->msg_dtype, v,
+                         v == Variant::Memory ? h->mem_bad_col : v == Variant::Relay ? h->relay_bad_col : -1,
+                         v != Variant::Decimation || gd_route(h, 0) != 0, h->small_mode, h->osd_method, h->osd_order};
+    char msg[512];
+    const int refused = mode_refusal(s, DecodeCall{what, with_osd}, msg, sizeof msg);
+    return refused ? fail(refused, "%s", msg) : LDPC_HIP_OK;
 }
 
 static int upload_priors(ldpc_hip_bp *h) {
     ++h->priors_version;
-    if (h->mem_on) { const int rc = upload_memory(h); if (rc) return rc; }  // a[] follows the priors
-    if (h->relay_on) { const int rc = upload_relay(h); if (rc) return rc; }  // ... of every leg
+    if (h->variant == Variant::Memory) { const int rc = upload_memory(h); if (rc) return rc; }  // a[] follows the priors
+    if (h->variant == Variant::Relay) { const int rc = upload_relay(h); if (rc) return rc; }  // ... of every leg
     // bp.hpp:150-151, evaluated by the host libm so that priors are bit-identical to the reference's
     std::vector<double> llr0((size_t)h->n);
     for (int j = 0; j < h->n; ++j)
@@ -693,9 +642,7 @@ int decode_onchip_gd(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t
 int decode_serial(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv);
 int soft_info_device(ldpc_hip_bp *h, const double *soft, int64_t batch, double cutoff, double sigma, uint8_t *decoding, double *llr,
                      int32_t *iters, uint8_t *conv, double *soft_out);
-// tu_f32.hip: the float32 message mode (min-sum, parallel schedule).  f32_refusal: what the handle is set up for that the mode cannot do
-// (`what`: the call's own addition -- row priors, soft syndromes -- or nullptr); LDPC_HIP_OK when the mode is off
-int f32_refusal(const ldpc_hip_bp *h, const char *what);
+// tu_f32.hip: the float32 message mode (min-sum, parallel schedule)
 int decode_f32(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv);
 // tu_onchip.hip: the float32 mode's on-chip route (bp_edge_f32_kernel, bp_edge8_f32_kernel, instantiated in tu_onchip_f32.hip) for the codes
 // plan_edge / plan_edge8 take; *took = false: neither does (decode_f32 then runs its per-pass kernels)

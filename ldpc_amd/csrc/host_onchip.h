@@ -873,7 +873,7 @@ static RelayRoute plan_relay_route(const ldpc_hip_bp *h, int64_t batch) {
 int ldpc_hip_bp_relay_route(const ldpc_hip_bp *h, int64_t batch, int32_t *route) {
     if (!h || !route) return fail(LDPC_HIP_ERR_INVALID, "null argument");
     if (batch < 0) return fail(LDPC_HIP_ERR_INVALID, "negative batch");
-    if (!h->relay_on && !h->mem_on) return fail(LDPC_HIP_ERR_INVALID, "neither Relay-BP nor memory min-sum is on (ldpc_hip_bp_set_relay, ldpc_hip_bp_set_memory)");
+    if (h->variant != Variant::Relay && h->variant != Variant::Memory) return fail(LDPC_HIP_ERR_INVALID, "neither Relay-BP nor memory min-sum is on (ldpc_hip_bp_set_relay, ldpc_hip_bp_set_memory)");
     *route = plan_relay_route(h, batch).route;
     return LDPC_HIP_OK;
 }
@@ -938,7 +938,7 @@ int gd_route(const ldpc_hip_bp *h, int64_t batch) {
 int ldpc_hip_bp_decimation_route(const ldpc_hip_bp *h, int64_t batch, int32_t *route) {
     if (!h || !route) return fail(LDPC_HIP_ERR_INVALID, "null argument");
     if (batch < 0) return fail(LDPC_HIP_ERR_INVALID, "negative batch");
-    if (!h->gd_on) return fail(LDPC_HIP_ERR_INVALID, "guided decimation is not on (ldpc_hip_bp_set_decimation)");
+    if (h->variant != Variant::Decimation) return fail(LDPC_HIP_ERR_INVALID, "guided decimation is not on (ldpc_hip_bp_set_decimation)");
     *route = gd_route(h, batch);
     return LDPC_HIP_OK;
 }
@@ -969,7 +969,7 @@ int decode_onchip_gd(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t
         ga.e.cpos = (const uint16_t *)h->e_partner.p;
         return launch_edge_gd(h, edge8_gd_kernel(r.e8.rounds, r.e8.dc), r.e8.rounds, edge8_gd_waves(r.e8.rounds, r.e8.dc), ga, io);
     }
-    // (gd_refusal has said so for the code and the mode; what is left is the batch)
+    // (decode_gate has said so for the code and the mode; what is left is the batch)
     return fail(LDPC_HIP_ERR_UNSUPPORTED, "guided decimation: no lane = edge kernel takes a batch of %lld syndromes of this code (ldpc_hip_bp_decimation_route answers 0); "
                 "the lane = node route and a per-pass route are not built yet", (long long)batch);
 }
@@ -997,7 +997,7 @@ int decode_onchip(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
     *took = false;
     const EdgeIo io = {synd, batch, decoding, llr, iters, conv};
     const bool rp = h->row_probs != nullptr;
-    if (h->mem_on) {
+    if (h->variant == Variant::Memory) {
         // Memory min-sum (ldpc_hip_bp_set_memory), by plan_relay_route: a code that plan_edge or plan_edge8 takes runs on their memory forms, a code
         // plan_wave_relay takes on bp_wave_relay_kernel as ONE relay leg of max_iter iterations that stops at its first solution -- that decode's bits;
         // every other code -- and every code under mode 0 -- goes to the per-pass memory kernels (took = false).  The persistent ring kernel,

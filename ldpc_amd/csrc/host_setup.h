@@ -317,7 +317,7 @@ int ldpc_hip_bp_set_memory(ldpc_hip_bp *h, const double *gamma) {
     HIPCHK(hipSetDevice(h->device));
     if (!gamma) {  // off: the plain decode and its kernels again
         HIPCHK(hipStreamSynchronize(h->stream));  // (a memory decode still queued reads the tables)
-        h->mem_on = false;
+        if (h->variant == Variant::Memory) h->variant = Variant::Plain;
         h->mem_gamma.clear();
         h->mem_bad_col = -1;
         h->mem_ag.release();
@@ -325,21 +325,18 @@ int ldpc_hip_bp_set_memory(ldpc_hip_bp *h, const double *gamma) {
         h->w_relay.release();
         return LDPC_HIP_OK;
     }
-    if (h->relay_on)
-        return fail(LDPC_HIP_ERR_UNSUPPORTED, "memory min-sum and Relay-BP exclude each other: switch the relay off first (ldpc_hip_bp_set_relay(h, 0, NULL, NULL, 0))");
-    if (h->gd_on)
-        return fail(LDPC_HIP_ERR_UNSUPPORTED, "memory min-sum and guided decimation exclude each other: switch the decimation off first (ldpc_hip_bp_set_decimation(h, 0, 0, 0))");
+    { char msg[512]; if (mode_exclusion(Variant::Memory, h->variant, msg, sizeof msg)) return fail(LDPC_HIP_ERR_UNSUPPORTED, "%s", msg); }  // (the handle holds another of the three)
     const int bad = mem_gamma_first_invalid(gamma, h->n);
     if (bad >= 0) return fail(LDPC_HIP_ERR_INVALID, "memory strength %d is %g: every strength must be finite and in [-1, 1)", bad, gamma[bad]);
     HIPCHK(hipStreamSynchronize(h->stream));
     h->mem_gamma.assign(gamma, gamma + h->n);
-    h->mem_on = true;
+    h->variant = Variant::Memory;
     return upload_memory(h);
 }
 
 int ldpc_hip_bp_get_memory(const ldpc_hip_bp *h, double *out) {
     if (!h) return fail(LDPC_HIP_ERR_INVALID, "null handle");
-    if (!h->mem_on) return 0;
+    if (h->variant != Variant::Memory) return 0;
     if (out) std::copy(h->mem_gamma.begin(), h->mem_gamma.end(), out);
     return 1;
 }
@@ -349,7 +346,7 @@ int ldpc_hip_bp_set_relay(ldpc_hip_bp *h, int32_t legs, const double *gamma, con
     HIPCHK(hipSetDevice(h->device));
     if (legs == 0 || !gamma) {  // off: the plain decode and its kernels again
         HIPCHK(hipStreamSynchronize(h->stream));  // (a relay decode still queued reads the tables)
-        h->relay_on = false;
+        if (h->variant == Variant::Relay) h->variant = Variant::Plain;
         h->relay_legs = h->relay_stop = 0;
         h->relay_gamma.clear();
         h->relay_iters.clear();
@@ -357,10 +354,7 @@ int ldpc_hip_bp_set_relay(ldpc_hip_bp *h, int32_t legs, const double *gamma, con
         for (DeviceBuf *b : {&h->relay_ag, &h->relay_it, &h->e_relay, &h->w_relay, &h->relay_dec, &h->relay_llr, &h->relay_li, &h->relay_cv, &h->relay_state}) b->release();
         return LDPC_HIP_OK;
     }
-    if (h->mem_on)
-        return fail(LDPC_HIP_ERR_UNSUPPORTED, "Relay-BP and memory min-sum exclude each other: switch the memory off first (ldpc_hip_bp_set_memory(h, NULL))");
-    if (h->gd_on)
-        return fail(LDPC_HIP_ERR_UNSUPPORTED, "Relay-BP and guided decimation exclude each other: switch the decimation off first (ldpc_hip_bp_set_decimation(h, 0, 0, 0))");
+    { char msg[512]; if (mode_exclusion(Variant::Relay, h->variant, msg, sizeof msg)) return fail(LDPC_HIP_ERR_UNSUPPORTED, "%s", msg); }  // (the handle holds another of the three)
     if (legs < 0 || legs > (1 << 20)) return fail(LDPC_HIP_ERR_INVALID, "Relay-BP: %d legs", (int)legs);
     if (!leg_iters) return fail(LDPC_HIP_ERR_INVALID, "Relay-BP: leg_iters must not be NULL");
     if (stop_after < 1) return fail(LDPC_HIP_ERR_INVALID, "Relay-BP: stop_after is %d: it must be at least 1", (int)stop_after);
@@ -376,15 +370,15 @@ int ldpc_hip_bp_set_relay(ldpc_hip_bp *h, int32_t legs, const double *gamma, con
     h->relay_iters.assign(leg_iters, leg_iters + legs);
     h->relay_legs = legs;
     h->relay_stop = stop_after;
-    h->relay_on = true;
+    h->variant = Variant::Relay;
     return upload_relay(h);
 }
 
 int ldpc_hip_bp_get_relay(const ldpc_hip_bp *h, int32_t *legs, int32_t *stop_after, double *gamma_out, int32_t *leg_iters_out) {
     if (!h) return fail(LDPC_HIP_ERR_INVALID, "null handle");
-    if (legs) *legs = h->relay_on ? h->relay_legs : 0;
-    if (stop_after) *stop_after = h->relay_on ? h->relay_stop : 0;
-    if (!h->relay_on) return 0;
+    if (legs) *legs = h->variant == Variant::Relay ? h->relay_legs : 0;
+    if (stop_after) *stop_after = h->variant == Variant::Relay ? h->relay_stop : 0;
+    if (h->variant != Variant::Relay) return 0;
     if (gamma_out) std::copy(h->relay_gamma.begin(), h->relay_gamma.end(), gamma_out);
     if (leg_iters_out) std::copy(h->relay_iters.begin(), h->relay_iters.end(), leg_iters_out);
     return 1;
@@ -393,15 +387,12 @@ int ldpc_hip_bp_get_relay(const ldpc_hip_bp *h, int32_t *legs, int32_t *stop_aft
 int ldpc_hip_bp_set_decimation(ldpc_hip_bp *h, int32_t round_iters, int32_t max_rounds, double freeze_llr) {
     if (!h) return fail(LDPC_HIP_ERR_INVALID, "null handle");
     if (round_iters == 0) {  // off: the plain decode and its kernels again (nothing on the device is the decimation's own)
-        h->gd_on = false;
+        if (h->variant == Variant::Decimation) h->variant = Variant::Plain;
         h->gd_round_iters = h->gd_max_rounds = 0;
         h->gd_freeze = 0.0;
         return LDPC_HIP_OK;
     }
-    if (h->mem_on)
-        return fail(LDPC_HIP_ERR_UNSUPPORTED, "guided decimation and memory min-sum exclude each other: switch the memory off first (ldpc_hip_bp_set_memory(h, NULL))");
-    if (h->relay_on)
-        return fail(LDPC_HIP_ERR_UNSUPPORTED, "guided decimation and Relay-BP exclude each other: switch the relay off first (ldpc_hip_bp_set_relay(h, 0, NULL, NULL, 0))");
+    { char msg[512]; if (mode_exclusion(Variant::Decimation, h->variant, msg, sizeof msg)) return fail(LDPC_HIP_ERR_UNSUPPORTED, "%s", msg); }  // (the handle holds another of the three)
     if (round_iters < 0) return fail(LDPC_HIP_ERR_INVALID, "guided decimation: round_iters is %d: it must be at least 1 (0 switches the decimation off)", (int)round_iters);
     if (max_rounds < 1) return fail(LDPC_HIP_ERR_INVALID, "guided decimation: max_rounds is %d: it must be at least 1", (int)max_rounds);
     if ((int64_t)round_iters * (int64_t)max_rounds > INT32_MAX)
@@ -410,16 +401,16 @@ int ldpc_hip_bp_set_decimation(ldpc_hip_bp *h, int32_t round_iters, int32_t max_
     h->gd_round_iters = round_iters;
     h->gd_max_rounds = max_rounds;
     h->gd_freeze = freeze_llr;
-    h->gd_on = true;
+    h->variant = Variant::Decimation;
     return LDPC_HIP_OK;
 }
 
 int ldpc_hip_bp_get_decimation(const ldpc_hip_bp *h, int32_t *round_iters, int32_t *max_rounds, double *freeze_llr) {
     if (!h) return fail(LDPC_HIP_ERR_INVALID, "null handle");
-    if (round_iters) *round_iters = h->gd_on ? h->gd_round_iters : 0;
-    if (max_rounds) *max_rounds = h->gd_on ? h->gd_max_rounds : 0;
-    if (freeze_llr) *freeze_llr = h->gd_on ? h->gd_freeze : 0.0;
-    return h->gd_on ? 1 : 0;
+    if (round_iters) *round_iters = h->variant == Variant::Decimation ? h->gd_round_iters : 0;
+    if (max_rounds) *max_rounds = h->variant == Variant::Decimation ? h->gd_max_rounds : 0;
+    if (freeze_llr) *freeze_llr = h->variant == Variant::Decimation ? h->gd_freeze : 0.0;
+    return h->variant == Variant::Decimation ? 1 : 0;
 }
 
 int64_t ldpc_hip_bp_workspace_bytes(const ldpc_hip_bp *h, int64_t batch) {

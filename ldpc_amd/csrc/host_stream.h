@@ -9,7 +9,7 @@ struct SpreadKernels { spread_kernel_t check = nullptr, bit = nullptr, check_loo
 static SpreadKernels pick_spread(const ldpc_hip_bp *h, bool nt, bool rp, bool mem) {
     SpreadKernels k;
     const int dr = h->max_row_deg, dc = h->max_col_deg;
-    if (mem) {  // memory min-sum (mem_refusal: minimum-sum only); no LOOP forms either -- such a decode is not cut in two passes
+    if (mem) {  // memory min-sum (decode_gate: minimum-sum only); no LOOP forms either -- such a decode is not cut in two passes
         pick_spread_mem(dr, dc, nt, k.check, k.bit);
         k.finish = bp_spread_mem_finish_kernel;
         return k;
@@ -92,7 +92,7 @@ static int stream_chunk_tiles(const ldpc_hip_bp *h, int64_t tiles_total, bool wa
 // What a pass decides once, before its first chunk.
 struct StreamPlan {
     int max_iter = 0;     // the pass's iteration limit
-    bool mem = false;     // memory min-sum (h->mem_on): as rp -- the per-pass kernels from the first iteration, bp_spread_mem_*; M lives where the row priors would
+    bool mem = false;     // memory min-sum (h->variant): as rp -- the per-pass kernels from the first iteration, bp_spread_mem_*; M lives where the row priors would
     bool rp = false;      // row priors (h->row_probs [batch][n]): the per-pass kernels from the first iteration whatever the batch size -- no persistent kernel, no edge0, no hand-off
     int64_t chunk = 0;    // tiles per chunk
     size_t per_tile_msg = 0, per_tile_llr = 0;  // bytes of one message array / of the log-ratios (0: not wanted) per tile
@@ -105,7 +105,7 @@ struct StreamPlan {
 static int plan_stream(const ldpc_hip_bp *h, int64_t tiles_total, bool want_llr, const StreamPass &pass, StreamPlan &p) {
     p.max_iter = pass.max_iter < 0 ? h->max_iter : pass.max_iter;
     p.rp = h->row_probs != nullptr;
-    p.mem = h->mem_on || pass.relay_ag != nullptr;
+    p.mem = h->variant == Variant::Memory || pass.relay_ag != nullptr;
     p.per_tile_msg = sizeof(double) * (size_t)(h->nnz ? h->nnz : 1) * LDPC_WAVE;
     p.per_tile_llr = want_llr ? sizeof(double) * (size_t)(h->n ? h->n : 1) * LDPC_WAVE : 0;
     int rc;
@@ -484,12 +484,10 @@ int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
     h->timed_prev = h->timed_prev_mid = false;  // (what a two-pass decode before this one left)
     // Row priors (ldpc_hip_*_decode_batch_priors): every row is decoded with its own channel probabilities, h->row_probs [batch][n].  Two kernel
     // families read them: the slot kernel (decode_onchip sends there whatever an on-chip kernel would take) and the per-pass kernels (StreamPlan::rp).
-    if (h->mem_on || h->relay_on || h->gd_on) {  // (the entry points have said so already, before staging anything: nothing wrong is ever decoded from here either)
-        const int refused = mem_refusal(h, h->row_probs ? "per-row channel probabilities are" : nullptr);
-        if (refused) return refused;
-    }
-    if (h->gd_on) return decode_onchip_gd(h, synd, batch, decoding, llr, iters, conv);  // guided decimation: the lane = edge kernels or a refusal, never another family
-    if (h->relay_on) return decode_relay(h, synd, batch, decoding, llr, iters, conv);
+    // (the entry points have said so already, before staging anything: nothing wrong is ever decoded from here either)
+    { const int refused = decode_gate(h, h->row_probs ? "per-row channel probabilities are" : nullptr, false); if (refused) return refused; }
+    if (h->variant == Variant::Decimation) return decode_onchip_gd(h, synd, batch, decoding, llr, iters, conv);  // guided decimation: the lane = edge kernels or a refusal, never another family
+    if (h->variant == Variant::Relay) return decode_relay(h, synd, batch, decoding, llr, iters, conv);
     if (h->msg_dtype == LDPC_HIP_MSG_F32) return decode_f32(h, synd, batch, decoding, llr, iters, conv);  // (never an FP64 kernel: what the mode cannot do is refused there)
     const bool rp = h->row_probs != nullptr;
     if (rp && h->schedule != 1) return fail(LDPC_HIP_ERR_UNSUPPORTED, "per-row channel probabilities: the serial schedules read the handle's priors only (parallel schedule required)");
@@ -504,7 +502,7 @@ int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
     // (switch REPACK_MIN_TILES t > 0: t instead of the 512 tiles -- the tests cut batches of a few dozen tiles with it)
     const int64_t min_tiles = h->sw("REPACK_MIN_TILES") > 0 ? h->sw("REPACK_MIN_TILES") : 512;
     // (memory min-sum is not cut in two passes: the compaction would have to gather M too -- DESIGN.md section 7c)
-    if (!rp && !h->mem_on && h->repack_iters != 0 && h->max_iter >= 8 && tiles_total >= min_tiles && h->m > 0 && h->n > 0)
+    if (!rp && h->variant != Variant::Memory && h->repack_iters != 0 && h->max_iter >= 8 && tiles_total >= min_tiles && h->m > 0 && h->n > 0)
         return decode_stream_repacked(h, synd, batch, decoding, llr, iters, conv);
     return decode_streamed(h, synd, batch, decoding, llr, iters, conv, StreamPass());
 }

@@ -224,10 +224,8 @@ extern "C" int ldpc_hip_bp_multi_decode_batch(ldpc_hip_bp_multi *mh, int32_t wit
     if (batch == 0) return LDPC_HIP_OK;
     if (!synd || !decoding) return fail(LDPC_HIP_ERR_INVALID, "syndromes and decoding must not be NULL");
     for (const MultiDev &md : mh->devs) {
-        const int refused = f32_refusal(md.h, "decoding over several GPUs (ldpc_hip_bp_multi) is");
+        const int refused = decode_gate(md.h, "decoding over several GPUs (ldpc_hip_bp_multi) is", false);
         if (refused) return refused;
-        const int refused_mem = mem_refusal(md.h, "decoding over several GPUs (ldpc_hip_bp_multi) is");
-        if (refused_mem) return refused_mem;
     }
     // where the caller's arrays live: all in host memory, or all on ONE GPU
     const int pd = pointer_device(synd);

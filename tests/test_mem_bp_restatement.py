@@ -166,7 +166,7 @@ def test_python_refusals():
 def test_python_refuses_a_nonzero_strength_on_a_probability_of_0_or_1():
     d = _decoder(error_rate=None, error_channel=[0.0, 0.05, 1.0, 0.05, 0.5, 0.05, 0.05])
     d.memory_strength = [0.0, 0.3, 0.0, -0.2, 0.4, 0.0, 0.1]  # strength 0 on the p = 0 and p = 1 bits: nothing to refuse here
-    d._require_memory()
+    d._require_modes()
     d.memory_strength = [0.0, 0.3, 0.2, -0.2, 0.4, 0.0, 0.1]
     _refused(d, "bit 2 has a nonzero memory strength.*strictly between 0 and 1")
     d.memory_strength = 0.3
