@@ -562,18 +562,28 @@ int ldpc_hip_bp_relay_route(const ldpc_hip_bp *h, int64_t batch, int32_t *route)
  *   ldpc_hip_bp_get_decimation(h, &round_iters, &max_rounds, &freeze_llr): 1 if it is on (the three set unless NULL), 0 if off (all three 0),
  *       LDPC_HIP_ERR_INVALID for a NULL handle.
  *   ldpc_hip_bp_decimation_route(h, batch, &route): which kernels decode `batch` syndromes with it on this handle as it is set now -- 0 none,
- *       1 bp_edge (lane = edge, rows <= 4, columns <= 2), 2 bp_edge8 (rows <= 8, columns <= 4).  Launches nothing.  LDPC_HIP_ERR_INVALID: NULL
- *       argument, negative batch, or the decimation is off.
+ *       1 bp_edge (lane = edge, rows <= 4, columns <= 2), 2 bp_edge8 (rows <= 8, columns <= 4), and with the lane = node switch on 3 bp_wave_gd
+ *       with one wavefront per syndrome, 4 with a team (the workgroup) per syndrome.  Launches nothing.  LDPC_HIP_ERR_INVALID: NULL argument,
+ *       negative batch, or the decimation is off.
+ *   ldpc_hip_bp_set_decimation_lane_node(h, on): on = 1 adds the lane = node kernel (bp_wave_gd_kernel.h: a syndrome's messages, posteriors and
+ *       frozen columns in LDS, one wavefront or a team per syndrome, all rounds in one launch) for the codes beyond both lane = edge ladders:
+ *       rows <= 16, columns <= 8, a syndrome's state within LDS.  Off (0) by default.  A setting of the handle, independent of whether the
+ *       decimation is on and read only while it is.  With it on the route follows ldpc_hip_bp_relay_route's order: any small-code kernel mode
+ *       but 0 asks the lane = edge families first, mode 6 stops there, modes -1, 1 and 3 take the lane = node kernel's own choice between one
+ *       wavefront and a team, 4 and 5 force either.  LDPC_HIP_ERR_INVALID: NULL handle, or a value other than 0 and 1.
+ *   ldpc_hip_bp_get_decimation_lane_node(h, &on): LDPC_HIP_ERR_INVALID for a NULL argument.
  * The lane = edge kernels (bp_edge_gd_kernel.h: one wavefront per syndrome, all rounds in one launch, nothing leaves the chip between rounds) are
- * the only route so far: the lane = node route for the codes beyond their ladders and a per-pass route are not built.  With the decimation on,
+ * the only route unless the lane = node switch is on; a per-pass route is not built.  With the decimation on,
  * ldpc_hip_bp_decode_batch[_async], the BP + OSD-0 entry points (OSD sees the rows left unsolved, with the last posteriors), ldpc_hip_bp_decode_b8
- * and ldpc_hip_bp_simulate_b8 decode with it.  Refused with LDPC_HIP_ERR_UNSUPPORTED before anything is staged or launched: a code neither lane =
- * edge family takes or a small-code kernel mode other than -1, 1, 6 (route 0), product-sum, any serial schedule, LDPC_HIP_MSG_F32, the *_priors
- * entry points, soft-syndrome decoding, several GPUs, OSD-E / OSD-CS.
+ * and ldpc_hip_bp_simulate_b8 decode with it.  Refused with LDPC_HIP_ERR_UNSUPPORTED before anything is staged or launched: a code no route
+ * takes under the small-code kernel mode (route 0: with the switch off, a code neither lane = edge family takes or a mode other than -1, 1, 6),
+ * product-sum, any serial schedule, LDPC_HIP_MSG_F32, the *_priors entry points, soft-syndrome decoding, several GPUs, OSD-E / OSD-CS.
  */
 int ldpc_hip_bp_set_decimation(ldpc_hip_bp *h, int32_t round_iters, int32_t max_rounds, double freeze_llr);
 int ldpc_hip_bp_get_decimation(const ldpc_hip_bp *h, int32_t *round_iters, int32_t *max_rounds, double *freeze_llr);
 int ldpc_hip_bp_decimation_route(const ldpc_hip_bp *h, int64_t batch, int32_t *route);
+int ldpc_hip_bp_set_decimation_lane_node(ldpc_hip_bp *h, int32_t on);
+int ldpc_hip_bp_get_decimation_lane_node(const ldpc_hip_bp *h, int32_t *on);
 
 /* The shader clock the BP kernels actually ran at (a measurement aid; no counterpart in the reference).  Every workgroup of the
  * long-running BP kernels (bp_decode_kernel, bp_wave_kernel, bp_wave_ps_kernel, bp_edge_kernel, bp_edge8_kernel) adds the shader cycles

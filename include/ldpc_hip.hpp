@@ -209,6 +209,33 @@ public:
         return true;
     }
 
+    // BP with guided decimation (ldpc_hip.h: ldpc_hip_bp_set_decimation): up to max_rounds >= 1 rounds of round_iters >= 1 min-sum iterations (they take
+    // the place of max_iter), the most reliable bit frozen at +-freeze_llr (> 0, finite or +inf) after every round that ends unsolved.
+    // round_iters = 0 switches it off.  It excludes set_memory and set_relay; what it cannot decode is refused when decoding, with its reason in last_error.
+    bool set_decimation(int32_t round_iters, int32_t max_rounds, double freeze_llr) {
+        if (mh_) { fail_(LDPC_HIP_ERR_UNSUPPORTED, "guided decimation is not sharded over several GPUs; decode on one GPU"); return false; }
+        last_status = ldpc_hip_bp_set_decimation(h_, round_iters, max_rounds, freeze_llr);
+        if (last_status != LDPC_HIP_OK) { last_error = ldpc_hip_last_error(); return false; }
+        return true;
+    }
+    // The lane = node route of guided decimation (ldpc_hip.h: ldpc_hip_bp_set_decimation_lane_node), opt-in and off by default: codes beyond the lane =
+    // edge kernels -- rows <= 16, columns <= 8, a syndrome's state within LDS -- are decoded instead of refused.  Read only while the decimation is on.
+    bool set_decimation_lane_node(bool on) {
+        if (mh_) { fail_(LDPC_HIP_ERR_UNSUPPORTED, "guided decimation is not sharded over several GPUs; decode on one GPU"); return false; }
+        last_status = ldpc_hip_bp_set_decimation_lane_node(h_, on ? 1 : 0);
+        if (last_status != LDPC_HIP_OK) { last_error = ldpc_hip_last_error(); return false; }
+        return true;
+    }
+    bool decimation_lane_node() const {
+        int32_t on = 0;
+        return h_ && ldpc_hip_bp_get_decimation_lane_node(h_, &on) == LDPC_HIP_OK && on != 0;
+    }
+    // 0 no kernel takes the code (such a decode is refused), 1 bp_edge, 2 bp_edge8, 3 / 4 bp_wave_gd with one wavefront / a team per syndrome; -1: the decimation is off
+    int32_t decimation_route(int64_t batch) const {
+        int32_t route = -1;
+        return h_ && ldpc_hip_bp_decimation_route(h_, batch, &route) == LDPC_HIP_OK ? route : -1;
+    }
+
     ldpc_hip_bp *handle() { return h_; }
     ldpc_hip_bp_multi *multi_handle() { return mh_; }  // null unless constructed with device_ids
     int device_count() const { return mh_ ? (int)ldpc_hip_bp_multi_devices(mh_) : 1; }

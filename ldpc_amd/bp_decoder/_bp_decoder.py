@@ -149,6 +149,8 @@ class BpDecoderBase:
         self._engine_relay = None       # ... what the engine's handle is set to
         self._decimation = None         # decimation: None (off) or (round_iters, max_rounds, freeze_llr)
         self._engine_decimation = None  # ... what the engine's handle is set to
+        self._decimation_lane_node = False         # decimation_lane_node: the lane = node route of guided decimation, opt-in
+        self._engine_decimation_lane_node = False  # ... what the engine's handle is set to
 
         self._h = _ingest(pcm)
         self.m, self.n = int(pcm.shape[0]), int(pcm.shape[1])
@@ -475,8 +477,8 @@ class BpDecoderBase:
         ``max_rounds=None`` -- n --, ``freeze_llr=25.0``): every decode then runs BP with guided decimation (``ldpc_hip_bp_set_decimation``;
         DESIGN.md section 7e) -- rounds of ``round_iters`` min-sum iterations, the most reliable bit frozen at ``+-freeze_llr`` after every
         round that ends unsolved, the messages kept; ``round_iters`` and ``max_rounds`` take the place of ``max_iter``.  Read back as such a
-        dict.  Minimum-sum, parallel schedule, float64 messages, one GPU, OSD_0 at most, and a code the lane = edge kernels take
-        (``decimation_route``); not together with ``memory_strength``, ``relay``, ``channel_probs=`` or soft syndromes --
+        dict.  Minimum-sum, parallel schedule, float64 messages, one GPU, OSD_0 at most, and a code the lane = edge kernels take -- or, with
+        ``decimation_lane_node``, the lane = node kernel -- (``decimation_route``); not together with ``memory_strength``, ``relay``, ``channel_probs=`` or soft syndromes --
         ``NotImplementedError`` at decode time."""
         if self._decimation is None:
             return None
@@ -493,15 +495,33 @@ class BpDecoderBase:
         self._decimation = decimation_schedule(self.n, **value)
 
     @property
+    def decimation_lane_node(self) -> bool:
+        """``False`` (default): guided decimation runs on the lane = edge kernels only and refuses every other code.  ``True``: a code beyond
+        them -- rows of at most 16, columns of at most 8 entries, a syndrome's state within LDS (``ldpc_amd.bpgd_decoder.lane_node_takes``)
+        -- is decoded by the lane = node kernel (``ldpc_hip_bp_set_decimation_lane_node``).  Read only while ``decimation`` is set."""
+        return self._decimation_lane_node
+
+    @decimation_lane_node.setter
+    def decimation_lane_node(self, value) -> None:
+        if not isinstance(value, (bool, np.bool_)):
+            raise ValueError(f"decimation_lane_node must be a bool, not {value!r}.")
+        self._decimation_lane_node = bool(value)
+
+    def _no_decimation_kernel(self) -> bool:
+        """No handle is needed to say that no kernel takes the code: neither lane = edge family, nor -- where asked for -- the lane = node kernel."""
+        from ldpc_amd.bpgd_decoder import lane_edge_route, lane_node_takes
+        return lane_edge_route(self._h) == "unavailable" and not (self._decimation_lane_node and lane_node_takes(self._h))
+
+    @property
     def decimation_route(self) -> str:
         """Which kernels decode with guided decimation on this decoder as it is set now: ``HipBpEngine.decimation_route`` -- ``"bp_edge"``,
-        ``"bp_edge8"`` or ``"unavailable"`` (a code neither family takes).  ``ValueError`` when ``decimation`` is not set; where the decoder is
+        ``"bp_edge8"``, with ``decimation_lane_node`` also ``"bp_wave"`` / ``"bp_wave_team"``, or ``"unavailable"`` (a code none of them
+        takes).  ``ValueError`` when ``decimation`` is not set; where the decoder is
         set to something decimation cannot serve at all (product-sum, a serial schedule, float32 messages, several GPUs, ``memory_strength``
         or ``relay``) there is no route to name and the ``NotImplementedError`` of a decode is raised instead, with its reason."""
         if self._decimation is None:
             raise ValueError("decimation_route: decimation is not set.")
-        from ldpc_amd.bpgd_decoder import lane_edge_route
-        if lane_edge_route(self._h) == "unavailable":  # (no handle needed to say so)
+        if self._no_decimation_kernel():
             return "unavailable"
         self._require_modes(message_dtype=False)
         return self._get_engine().decimation_route(getattr(self, "_relay_batch", 1))
@@ -559,12 +579,13 @@ class BpDecoderBase:
                 if len(bad):
                     raise NotImplementedError(f"{key}: bit {int(bad[0])} has a nonzero memory strength and a channel probability of {p[bad[0]]!r}; "
                                               f"{name} needs probabilities strictly between 0 and 1 there (or strength 0 on that bit{mode['every_leg']}).")
-            if mode["route"]:
-                from ldpc_amd.bpgd_decoder import lane_edge_route
-                if lane_edge_route(self._h) == "unavailable":
-                    raise NotImplementedError(f"{key}: neither lane = edge kernel family takes this code (rows of at most 4 entries and columns of at most 2 "
-                                              "within 1024 slots, or rows of at most 8 and columns of at most 4 within the kernels' ladder; every column used); "
-                                              "the lane = node route for larger codes and a per-pass route are not built yet.")
+            if mode["route"] and self._no_decimation_kernel():
+                if self._decimation_lane_node:
+                    raise NotImplementedError(f"{key}: neither lane = edge kernel family nor the lane = node kernel takes this code (rows of at most 16 entries and "
+                                              "columns of at most 8, a syndrome's state within LDS); a per-pass route is not built.")
+                raise NotImplementedError(f"{key}: neither lane = edge kernel family takes this code (rows of at most 4 entries and columns of at most 2 "
+                                          "within 1024 slots, or rows of at most 8 and columns of at most 4 within the kernels' ladder; every column used); "
+                                          "the lane = node route for larger codes and a per-pass route are not built yet.")
 
     # ---- device engine --------------------------------------------------------------------------
     def _get_engine(self):
@@ -610,6 +631,10 @@ class BpDecoderBase:
             if value is not None:
                 getattr(self._engine, setter)(*(value if isinstance(value, tuple) else (value,)))
                 setattr(self, held, value if isinstance(value, tuple) else value.copy())
+        # (read only while the decimation is on -- which is never the case on several GPUs: _require_modes -- so only then is it pushed)
+        if self._decimation is not None and self._decimation_lane_node != self._engine_decimation_lane_node:
+            self._engine.set_decimation_lane_node(self._decimation_lane_node)
+            self._engine_decimation_lane_node = self._decimation_lane_node
         rnd = (bool(self._random_serial_schedule), self._random_schedule_seed, self._seed_epoch)
         if rnd != getattr(self, "_engine_random", (False, 0, 0)):
             self._engine.set_random_serial(rnd[0], rnd[1])  # re-seeds, as bpd.set_random_schedule_seed does (pyx:553-554)

@@ -48,6 +48,7 @@
 //   bp_edge_relay_kernel.h bp_edge_relay_kernel, bp_edge8_relay_kernel   Relay-BP on the lane = edge families: chained memory legs in one launch (tu_onchip_relay.hip)
 //   bp_wave_relay_kernel.h bp_wave_relay_kernel             Relay-BP and memory min-sum beyond the lane = edge families: lane = node, messages and memory in LDS (tu_onchip_wave_relay.hip)
 //   bp_edge_gd_kernel.h  bp_edge_gd_kernel, bp_edge8_gd_kernel     BP with guided decimation on the lane = edge families: all rounds in one launch (tu_onchip_gd.hip)
+//   bp_wave_gd_kernel.h  bp_wave_gd_kernel                         BP with guided decimation beyond the lane = edge families: lane = node, messages, posteriors and frozen columns in LDS (tu_onchip_wave_gd.hip)
 //   relay_common.h       relay_weight                      Relay-BP: a solution's weight, shared by the relay kernels and relay_select_kernel (bp_spread_kernels.h)
 //   osd_kernels.h        osd0[_reg]_kernel, osdw[_reg]_kernel, osd_big_kernel   OSD-0 / OSD-E / OSD-CS post-processing
 //   io_kernels.h         pack / unpack / transpose, H v, b8 shot data, synthetic BSC shots

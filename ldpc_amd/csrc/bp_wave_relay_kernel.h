@@ -48,6 +48,8 @@ __host__ __device__ inline size_t wave_relay_lds_shared(int mp, int np, int DR, 
     return (b + 15) & ~(size_t)15;
 }
 __host__ __device__ inline size_t wave_relay_lds_private(int mp, int np, int DR) { return wave_lds_private(mp, np, DR, true); }
+// ... and what the host leaves free of the 160 KiB for the kernel's static __shared__ variables (plan_wave_relay; the kernel asserts that they fit)
+constexpr size_t WAVE_RELAY_LDS_STATIC = 64;
 
 template <int DR, int DC, bool TEAM>
 __global__ void __launch_bounds__(64 * wave_relay_waves(DR, DC, TEAM)) bp_wave_relay_kernel(const WaveRelayArgs ra) {
@@ -64,6 +66,7 @@ __global__ void __launch_bounds__(64 * wave_relay_waves(DR, DC, TEAM)) bp_wave_r
     __shared__ long long team_b;
     __shared__ double team_w;
     __shared__ unsigned long long clk_stamp[2];
+    static_assert(sizeof(team_unsat) + sizeof(team_b) + sizeof(team_w) + sizeof(clk_stamp) <= WAVE_RELAY_LDS_STATIC, "the host plans the dynamic LDS with this much left for the static part");
     if (threadIdx.x == 0) clock_probe_begin(clk_stamp);
     auto team_sync = [&]() { if (TEAM) __syncthreads(); else __builtin_amdgcn_wave_barrier(); };
     const int m = a.m, n = a.n, mp = a.mp, np = a.np, rm = DR * mp, cn = DC * np;

@@ -1,5 +1,5 @@
 // host_handle.h -- the handle (struct ldpc_hip_bp), error reporting, device buffers, measurement switches
-// Part of libldpc_hip.so: included by every translation unit (bp_hip.hip = the C ABI; tu_stream / tu_serial / tu_onchip / tu_onchip_f32 / tu_onchip_rp / tu_onchip_mem / tu_onchip_relay / tu_onchip_wave_relay / tu_onchip_gd / tu_osd / tu_f32.hip = one kernel
+// Part of libldpc_hip.so: included by every translation unit (bp_hip.hip = the C ABI; tu_stream / tu_serial / tu_onchip / tu_onchip_f32 / tu_onchip_rp / tu_onchip_mem / tu_onchip_relay / tu_onchip_wave_relay / tu_onchip_gd / tu_onchip_wave_gd / tu_osd / tu_f32.hip = one kernel
 // family each with its host side).  What one unit calls in another is declared at the end of this header.
 #pragma once
 
@@ -350,10 +350,13 @@ struct ldpc_hip_bp {
     // BP with guided decimation (ldpc_hip_bp_set_decimation): up to gd_max_rounds rounds of gd_round_iters min-sum iterations per
     // syndrome; a round that ends unsolved freezes the most reliable column at +-gd_freeze and keeps the messages.  gd_round_iters and gd_max_rounds
     // take max_iter's place.  decode_device looks at `variant` and sends the batch to decode_onchip_gd (host_onchip.h: the lane = edge kernels of
-    // bp_edge_gd_kernel.h, nothing else).  Decimation, relay and memory exclude one another.  No device buffer of its own: the slot tables and e_prior are the plain decode's.
+    // bp_edge_gd_kernel.h; with gd_lane_node also the lane = node kernel of bp_wave_gd_kernel.h; nothing else).  Decimation, relay and memory exclude one
+    // another.  On the lane = edge kernels no device buffer of its own: the slot tables and e_prior are the plain decode's.
     int32_t gd_round_iters = 0, gd_max_rounds = 0;
     double gd_freeze = 0.0;
-    mutable int gd_route_known = -1, gd_route_method = 0, gd_route_mode = 0;  // gd_route's answer for this code under (bp_method, small_mode), -1: not asked yet (the plans scan the matrix: once, not at every refusal check)
+    bool gd_lane_node = false;  // ldpc_hip_bp_set_decimation_lane_node: codes beyond both lane = edge ladders go to bp_wave_gd_kernel (opt-in; a handle setting like small_mode, read only while the decimation is on)
+    DeviceBuf w_gd;             // bp_wave_gd_kernel: [np + 2] the padded priors (before every launch; released when the decimation or the lane = node route is switched off)
+    mutable int gd_route_known = -1, gd_route_method = 0, gd_route_mode = 0;  // gd_route's answer for this code under (bp_method, small_mode, gd_lane_node -- its setter forgets the answer), -1: not asked yet (the plans scan the matrix: once, not at every refusal check)
 };
 
 // h->counter: work_pool_bytes() of work counters for the on-chip BP kernels, then OSD_COUNTER_BYTES for BP + OSD -- {listed, next} of the first
@@ -404,19 +407,20 @@ static int upload_relay(ldpc_hip_bp *h) {
     return LDPC_HIP_OK;
 }
 
-// tu_onchip.hip (host_onchip.h): which lane = edge family decodes this handle's code with guided decimation -- 0 neither, 1 bp_edge, 2 bp_edge8.
-// It looks at the matrix, the BP method and the small-code kernel mode only, and launches nothing.
+// tu_onchip.hip (host_onchip.h): which kernel decodes this handle's code with guided decimation -- 0 none, 1 bp_edge, 2 bp_edge8, and with
+// gd_lane_node 3 / 4 bp_wave_gd with one wavefront / a team per syndrome.
+// It looks at the matrix, the BP method, the small-code kernel mode and gd_lane_node only, and launches nothing.
 int gd_route(const ldpc_hip_bp *h, int64_t batch);
 
 // THE gate of every decode entry point, before anything is staged or launched: what the handle is set up for that its modes -- float32 messages,
 // and whichever of memory min-sum, Relay-BP and guided decimation is on -- cannot do (the rules and their texts: mode_host.h).  `what`: the call's own
-// addition (row priors, soft syndromes, several GPUs) or nullptr; with_osd: the call runs the handle's osd_method / osd_order.  The lane = edge
-// kernels are guided decimation's only route: a code neither family takes is refused here, not decoded some other way.
+// addition (row priors, soft syndromes, several GPUs) or nullptr; with_osd: the call runs the handle's osd_method / osd_order.  The on-chip
+// kernels of gd_route are guided decimation's only routes: a code none of them takes is refused here, not decoded some other way.
 static int decode_gate(const ldpc_hip_bp *h, const char *what, bool with_osd) {
     const Variant v = h->variant;
     const ModeState s = {h->bp_method, h->schedule == 1 && !h->random_serial, h->msg_dtype, v,
                          v == Variant::Memory ? h->mem_bad_col : v == Variant::Relay ? h->relay_bad_col : -1,
-                         v != Variant::Decimation || gd_route(h, 0) != 0, h->small_mode, h->osd_method, h->osd_order};
+                         v != Variant::Decimation || gd_route(h, 0) != 0, h->small_mode, h->osd_method, h->osd_order, h->gd_lane_node};
     char msg[512];
     const int refused = mode_refusal(s, DecodeCall{what, with_osd}, msg, sizeof msg);
     return refused ? fail(refused, "%s", msg) : LDPC_HIP_OK;
@@ -636,7 +640,8 @@ int decode_onchip(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
 // kernel mode (plan_relay_route); *took = false: decode_relay (host_stream.h) runs its leg loop
 int decode_onchip_relay(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv, bool *took);
 // tu_onchip.hip: BP with guided decimation, all rounds in one launch -- the lane = edge decimation kernels (bp_edge_gd_kernel.h, tu_onchip_gd.hip) for the
-// codes plan_edge / plan_edge8 take (gd_route); any other code: LDPC_HIP_ERR_UNSUPPORTED, nothing launched
+// codes plan_edge / plan_edge8 take, with gd_lane_node the lane = node kernel (bp_wave_gd_kernel.h, tu_onchip_wave_gd.hip) for those plan_wave_gd takes
+// (gd_route); any other code: LDPC_HIP_ERR_UNSUPPORTED, nothing launched
 int decode_onchip_gd(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv);
 // tu_serial.hip: serial / serial_relative / random serial schedules, soft-syndrome decoding
 int decode_serial(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv);

@@ -1,4 +1,4 @@
-// host_onchip.h -- host side of the on-chip kernels: plans (LDS / occupancy), tables and launches of bp_small / bp_wave / bp_wave_ps / bp_edge / bp_wave_relay
+// host_onchip.h -- host side of the on-chip kernels: plans (LDS / occupancy), tables and launches of bp_small / bp_wave / bp_wave_ps / bp_edge / bp_wave_relay / bp_wave_gd
 // Part of libldpc_hip.so: included by bp_hip.hip (one translation unit), in the order given there.
 #pragma once
 
@@ -743,7 +743,10 @@ static int launch_edge_relay(ldpc_hip_bp *h, void (*kern)(const ARGS), int round
 // plan_wave with the posterior copy forced into LDS (it IS the memory), min-sum only, the priors always read from the padded device array: the
 // rungs of pick_wave, the same 16-bit table limits, the same padding rule, the same choice between one wavefront and a team per syndrome (modes 4
 // and 5 force either), capped by the wavefronts the instantiation was compiled for (wave_relay_waves).  waves == 0: not applicable.
-static WavePlan plan_wave_relay(const ldpc_hip_bp *h, bool forced, int64_t batch) {
+// plan_wave_lds states the rules once, for this kernel and for bp_wave_gd_kernel (plan_wave_gd): the size of a syndrome's private region
+// (`lds_private`), the wavefront caps (`waves_of`) and the bytes left free for the kernel's static LDS (`lds_static`) are all that differ --
+// the shared tables are the same (wave_relay_lds_shared).
+static WavePlan plan_wave_lds(const ldpc_hip_bp *h, bool forced, int64_t batch, size_t (*lds_private)(int, int, int), int (*waves_of)(int, int, bool), size_t lds_static) {
     WavePlan p;
     if (h->bp_method != LDPC_HIP_MINIMUM_SUM || h->m <= 0 || h->n <= 0 || h->nnz <= 0 || h->max_row_deg > 16 || h->max_col_deg > 8) return p;
     static const int rungs[6][2] = {{4, 2}, {4, 4}, {6, 3}, {8, 4}, {8, 8}, {16, 8}};  // pick_wave's
@@ -756,18 +759,18 @@ static WavePlan plan_wave_relay(const ldpc_hip_bp *h, bool forced, int64_t batch
     if (rm + 2 >= 65536 || p.np + 1 >= 65536) return p;               // positions and column numbers are 16 bits
     if (!forced && rm > 2 * (size_t)h->nnz + 1024) return p;          // a few heavy rows would pad every row
     p.shared = wave_relay_lds_shared(p.mp, p.np, p.dr, p.dc);
-    p.per_wave = wave_relay_lds_private(p.mp, p.np, p.dr);
+    p.per_wave = lds_private(p.mp, p.np, p.dr);
     p.prior_global = true;
-    const size_t lds = 160u * 1024u - 64u;  // (the kernel's few bytes of static LDS come on top of the dynamic part)
+    const size_t lds = 160u * 1024u - lds_static;  // (the kernel's static LDS comes on top of the dynamic part: WAVE_RELAY_LDS_STATIC / WAVE_GD_LDS_STATIC, which each kernel asserts it keeps to)
     if (p.shared + p.per_wave > lds) return p;
     size_t w = (lds - p.shared) / p.per_wave;
-    if (w > (size_t)wave_relay_waves(p.dr, p.dc, false)) w = (size_t)wave_relay_waves(p.dr, p.dc, false);
+    if (w > (size_t)waves_of(p.dr, p.dc, false)) w = (size_t)waves_of(p.dr, p.dc, false);
     const int u = p.dr <= 4 ? 4 : p.dr <= 8 ? 2 : 1;  // (plan_wave's rule, min-sum)
     const bool team = h->small_mode == 5 || (h->small_mode != 4 && (w < 6 || 2 * p.np > 3 * 64 * u || batch <= 256 * (int64_t)w));
     if (team) {
         int tw = (p.np + 64 * u - 1) / (64 * u);
         if (tw < 2) tw = 2;
-        if (tw > wave_relay_waves(p.dr, p.dc, true)) tw = wave_relay_waves(p.dr, p.dc, true);
+        if (tw > waves_of(p.dr, p.dc, true)) tw = waves_of(p.dr, p.dc, true);
         p.team = true;
         p.waves = tw;
         p.groups_per_cu = (int)(lds / (p.shared + p.per_wave));
@@ -783,6 +786,15 @@ static WavePlan plan_wave_relay(const ldpc_hip_bp *h, bool forced, int64_t batch
     if (p.groups_per_cu < 1) p.groups_per_cu = 1;
     return p;
 }
+static WavePlan plan_wave_relay(const ldpc_hip_bp *h, bool forced, int64_t batch) {
+    return plan_wave_lds(h, forced, batch, [](int mp, int np, int dr) { return wave_relay_lds_private(mp, np, dr); }, [](int dr, int dc, bool team) { return wave_relay_waves(dr, dc, team); },
+                         WAVE_RELAY_LDS_STATIC);
+}
+// Guided decimation on bp_wave_gd_kernel (bp_wave_gd_kernel.h): the shared tables are the relay kernel's, the private region carries the two masks
+static WavePlan plan_wave_gd(const ldpc_hip_bp *h, bool forced, int64_t batch) {
+    return plan_wave_lds(h, forced, batch, [](int mp, int np, int dr) { return wave_gd_lds_private(mp, np, dr); }, [](int dr, int dc, bool team) { return wave_gd_waves(dr, dc, team); },
+                         WAVE_GD_LDS_STATIC);
+}
 
 // a and gamma of every leg as the kernel reads them: [legs][2][np], beyond n a = 1.0 and gamma = 0 (the padding columns form the finite prior 1.0)
 __global__ void wave_relay_table_kernel(const double *ag, int n, int np, int legs, double *out) {
@@ -797,27 +809,21 @@ __global__ void wave_relay_table_kernel(const double *ag, int n, int np, int leg
 // The launch: decode_wave's -- the shared position tables, the padded priors, the static share for a handful of syndromes and work_pool_next beyond,
 // the grid sizing, the clock probe, the timing events on the dispatch.  ag [legs][2][n]: relay_ag, or mem_ag as one leg (leg_iters == nullptr: to
 // h->max_iter).  The OSD hook is left alone: bposd_device lists the unsolved rows itself, as after the lane = edge relay kernels.
-static int decode_wave_relay(ldpc_hip_bp *h, const WavePlan &p, const double *ag, int legs, const int32_t *leg_iters, int stop_after, const uint8_t *synd,
-                             int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv) {
-    const WaveRelayKernel kern = wave_relay_kernel(p.dr, p.dc, p.team);
-    if (!kern) return fail(LDPC_HIP_ERR_UNSUPPORTED, "Relay-BP / memory min-sum: no lane = node kernel was built for rows of %d, columns of %d", p.dr, p.dc);
+// wave_lds_begin and launch_wave_lds are what decode_wave_relay shares with decode_wave_gd: everything but the kernel's own tables and arguments.
+static bool wave_static_teams(const WavePlan &p, int64_t batch) { return p.team && batch <= 256 * (int64_t)p.groups_per_cu; }
+// before the kernel's own tables are written: the position tables, the work counters
+static int wave_lds_begin(ldpc_hip_bp *h, const WavePlan &p, int64_t batch) {
     int rc;
     if ((rc = ensure_wave_tables(h, p))) return rc;
-    const bool static_teams = p.team && batch <= 256 * (int64_t)p.groups_per_cu;
     if ((rc = h->counter.ensure(counter_bytes()))) return rc;
-    if (!static_teams) HIPCHK(hipMemsetAsync(h->counter.p, 0, work_pool_bytes(), h->stream));
-    // w_relay: [np + 2] the padded priors, then [legs][2][np] the padded tables (its own buffer: it goes when the relay or the memory is switched off)
-    if ((rc = h->w_relay.ensure(sizeof(double) * ((size_t)(p.np + 2) + 2 * (size_t)p.np * (size_t)legs)))) return rc;
-    double *const prior_p = (double *)h->w_relay.p, *const ag_p = prior_p + p.np + 2;
-    // (the priors, the strengths or the legs may have changed since the last call)
-    LDPC_LAUNCH(wave_prior_pad_kernel, dim3((unsigned)((p.np + 2 + 255) / 256)), dim3(256), 0, h->stream, h->d_llr0, h->n, p.np, prior_p);
-    LDPC_LAUNCH(wave_relay_table_kernel, dim3((unsigned)((p.np + 255) / 256)), dim3(256), 0, h->stream, ag, h->n, p.np, legs, ag_p);
-    HIPCHK(hipGetLastError());
-    WaveRelayArgs ra = {};
-    ra.ag_p = ag_p;
-    ra.leg_iters = leg_iters;
-    ra.legs = legs; ra.stop_after = stop_after;
-    WaveArgs &a = ra.w;
+    if (!wave_static_teams(p, batch)) HIPCHK(hipMemsetAsync(h->counter.p, 0, work_pool_bytes(), h->stream));
+    return LDPC_HIP_OK;
+}
+// ra: the kernel's argument block with its own fields set, a: the WaveArgs inside it; prior_p: [np + 2] the padded priors
+template <class ARGS>
+static int launch_wave_lds(ldpc_hip_bp *h, const WavePlan &p, void (*kern)(const ARGS), ARGS &ra, WaveArgs &a, const double *prior_p, const uint8_t *synd,
+                           int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv) {
+    const bool static_teams = wave_static_teams(p, batch);
     a.pool_per = work_pool_share(batch, 0);
     a.m = h->m; a.n = h->n; a.mp = p.mp; a.np = p.np; a.max_iter = h->max_iter;
     a.ms_scaling_factor = h->ms_scaling_factor;
@@ -843,6 +849,42 @@ static int decode_wave_relay(ldpc_hip_bp *h, const WavePlan &p, const double *ag
     h->timed = timed;
     HIPCHK(hipGetLastError());
     return LDPC_HIP_OK;
+}
+
+static int decode_wave_relay(ldpc_hip_bp *h, const WavePlan &p, const double *ag, int legs, const int32_t *leg_iters, int stop_after, const uint8_t *synd,
+                             int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv) {
+    const WaveRelayKernel kern = wave_relay_kernel(p.dr, p.dc, p.team);
+    if (!kern) return fail(LDPC_HIP_ERR_UNSUPPORTED, "Relay-BP / memory min-sum: no lane = node kernel was built for rows of %d, columns of %d", p.dr, p.dc);
+    int rc;
+    if ((rc = wave_lds_begin(h, p, batch))) return rc;
+    // w_relay: [np + 2] the padded priors, then [legs][2][np] the padded tables (its own buffer: it goes when the relay or the memory is switched off)
+    if ((rc = h->w_relay.ensure(sizeof(double) * ((size_t)(p.np + 2) + 2 * (size_t)p.np * (size_t)legs)))) return rc;
+    double *const prior_p = (double *)h->w_relay.p, *const ag_p = prior_p + p.np + 2;
+    // (the priors, the strengths or the legs may have changed since the last call)
+    LDPC_LAUNCH(wave_prior_pad_kernel, dim3((unsigned)((p.np + 2 + 255) / 256)), dim3(256), 0, h->stream, h->d_llr0, h->n, p.np, prior_p);
+    LDPC_LAUNCH(wave_relay_table_kernel, dim3((unsigned)((p.np + 255) / 256)), dim3(256), 0, h->stream, ag, h->n, p.np, legs, ag_p);
+    HIPCHK(hipGetLastError());
+    WaveRelayArgs ra = {};
+    ra.ag_p = ag_p;
+    ra.leg_iters = leg_iters;
+    ra.legs = legs; ra.stop_after = stop_after;
+    return launch_wave_lds(h, p, kern, ra, ra.w, prior_p, synd, batch, decoding, llr, iters, conv);
+}
+
+// Guided decimation on the lane = node kernel (bp_wave_gd_kernel.h; instantiated in tu_onchip_wave_gd.hip): decode_wave_relay's launch with the
+// padded priors alone in w_gd (written before every launch: the priors may have changed) and the rounds where the relay has its legs.
+static int decode_wave_gd(ldpc_hip_bp *h, const WavePlan &p, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv) {
+    const WaveGdKernel kern = wave_gd_kernel(p.dr, p.dc, p.team);
+    if (!kern) return fail(LDPC_HIP_ERR_UNSUPPORTED, "guided decimation: no lane = node kernel was built for rows of %d, columns of %d", p.dr, p.dc);
+    int rc;
+    if ((rc = wave_lds_begin(h, p, batch))) return rc;
+    if ((rc = h->w_gd.ensure(sizeof(double) * (size_t)(p.np + 2)))) return rc;
+    LDPC_LAUNCH(wave_prior_pad_kernel, dim3((unsigned)((p.np + 2 + 255) / 256)), dim3(256), 0, h->stream, h->d_llr0, h->n, p.np, (double *)h->w_gd.p);
+    HIPCHK(hipGetLastError());
+    WaveGdArgs ga = {};
+    ga.freeze_llr = h->gd_freeze;
+    ga.round_iters = h->gd_round_iters; ga.max_rounds = h->gd_max_rounds;
+    return launch_wave_lds(h, p, kern, ga, ga.w, (const double *)h->w_gd.p, synd, batch, decoding, llr, iters, conv);  // (w.max_iter is not read: the rounds take its place)
 }
 
 // Is the lane = node route what the default modes (-1, 1) take?  By the rule of DESIGN.md section 7d, stated there before the measurement: the
@@ -910,16 +952,21 @@ int decode_onchip_relay(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint
 // syndrome's priors, initial messages and frozen slots start from it), the work pools, the grid sizing (by the wavefronts per SIMD the instantiation was
 // compiled for), the clock probe, the timing events.  The kernels read round_iters and max_rounds where the others read max_iter.
 // The route: decode_onchip's predicate for the lane = edge families (modes -1, 1, 6; the work pools' 32-bit syndrome indices) and their two plans, unchanged.
-// There is no other: the lane = node route for the codes beyond the ladders (bp_wave_relay_kernel's territory) and a per-pass route are not built.
-struct GdRoute { int route = 0; EdgePlan ep; Edge8Plan e8; };
+// With ldpc_hip_bp_set_decimation_lane_node on (opt-in, off by default) the order is plan_relay_route's: any mode but 0 asks plan_edge and plan_edge8, mode
+// 6 stops there, and modes -1, 1, 3, 4, 5 go on to plan_wave_gd -- bp_wave_gd_kernel (bp_wave_gd_kernel.h) with one wavefront (3) or a team (4) per
+// syndrome, 4 and 5 forcing either.  A per-pass route is not built.
+struct GdRoute { int route = 0; EdgePlan ep; Edge8Plan e8; WavePlan wp; };
 static GdRoute plan_gd_route(const ldpc_hip_bp *h, int64_t batch) {
     GdRoute r;
-    if (!(h->small_mode == -1 || h->small_mode == 1 || h->small_mode == 6)) return r;
+    if (!(h->gd_lane_node ? h->small_mode != 0 : h->small_mode == -1 || h->small_mode == 1 || h->small_mode == 6)) return r;
     if (!(h->m > 0 && h->n > 0 && h->nnz > 0 && (int64_t)h->nnz * 16 < (1 << 22) && batch < (1ll << 30))) return r;
     r.ep = plan_edge(h);
     if (r.ep.rounds) { r.route = 1; return r; }
     r.e8 = plan_edge8(h);
-    if (r.e8.rounds) r.route = 2;
+    if (r.e8.rounds) { r.route = 2; return r; }
+    if (!h->gd_lane_node || h->small_mode == 6 || h->small_mode == 2) return r;
+    r.wp = plan_wave_gd(h, h->small_mode != -1, batch);  // (forced: as plan_relay_route, by modes 1, 3, 4, 5)
+    if (r.wp.waves) r.route = r.wp.team ? 4 : 3;
     return r;
 }
 
@@ -928,11 +975,13 @@ static GdRoute plan_gd_route(const ldpc_hip_bp *h, int64_t batch) {
 // as decode_onchip does: it needs the plans' kernels.)
 int gd_route(const ldpc_hip_bp *h, int64_t batch) {
     if (h->gd_route_known < 0 || h->gd_route_method != h->bp_method || h->gd_route_mode != h->small_mode) {
-        h->gd_route_known = plan_gd_route(h, 0).route;
+        h->gd_route_known = plan_gd_route(h, 0).route;  // (a batch of 0: whether the lane = node kernel takes the code at all does not depend on it, only 3 or 4 does)
         h->gd_route_method = h->bp_method;
         h->gd_route_mode = h->small_mode;
     }
-    return batch < (1ll << 30) ? h->gd_route_known : 0;
+    if (batch >= (1ll << 30)) return 0;
+    if (h->gd_route_known < 3 || batch == 0) return h->gd_route_known;
+    return plan_wave_gd(h, h->small_mode != -1, batch).team ? 4 : 3;  // (one wavefront or a team: by the batch; the plan does not scan the matrix)
 }
 
 int ldpc_hip_bp_decimation_route(const ldpc_hip_bp *h, int64_t batch, int32_t *route) {
@@ -969,7 +1018,11 @@ int decode_onchip_gd(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t
         ga.e.cpos = (const uint16_t *)h->e_partner.p;
         return launch_edge_gd(h, edge8_gd_kernel(r.e8.rounds, r.e8.dc), r.e8.rounds, edge8_gd_waves(r.e8.rounds, r.e8.dc), ga, io);
     }
+    if (r.route >= 3) return decode_wave_gd(h, r.wp, synd, batch, decoding, llr, iters, conv);
     // (decode_gate has said so for the code and the mode; what is left is the batch)
+    if (h->gd_lane_node)
+        return fail(LDPC_HIP_ERR_UNSUPPORTED, "guided decimation: no on-chip kernel takes a batch of %lld syndromes of this code (ldpc_hip_bp_decimation_route answers 0); "
+                    "a per-pass route is not built", (long long)batch);
     return fail(LDPC_HIP_ERR_UNSUPPORTED, "guided decimation: no lane = edge kernel takes a batch of %lld syndromes of this code (ldpc_hip_bp_decimation_route answers 0); "
                 "the lane = node route and a per-pass route are not built yet", (long long)batch);
 }

@@ -386,7 +386,12 @@ int ldpc_hip_bp_get_relay(const ldpc_hip_bp *h, int32_t *legs, int32_t *stop_aft
 
 int ldpc_hip_bp_set_decimation(ldpc_hip_bp *h, int32_t round_iters, int32_t max_rounds, double freeze_llr) {
     if (!h) return fail(LDPC_HIP_ERR_INVALID, "null handle");
-    if (round_iters == 0) {  // off: the plain decode and its kernels again (nothing on the device is the decimation's own)
+    if (round_iters == 0) {  // off: the plain decode and its kernels again (on the device only the lane = node route's padded priors are the decimation's own)
+        if (h->w_gd.p) {
+            HIPCHK(hipSetDevice(h->device));
+            HIPCHK(hipStreamSynchronize(h->stream));  // (a decimation decode still queued reads them)
+            h->w_gd.release();
+        }
         if (h->variant == Variant::Decimation) h->variant = Variant::Plain;
         h->gd_round_iters = h->gd_max_rounds = 0;
         h->gd_freeze = 0.0;
@@ -411,6 +416,25 @@ int ldpc_hip_bp_get_decimation(const ldpc_hip_bp *h, int32_t *round_iters, int32
     if (max_rounds) *max_rounds = h->variant == Variant::Decimation ? h->gd_max_rounds : 0;
     if (freeze_llr) *freeze_llr = h->variant == Variant::Decimation ? h->gd_freeze : 0.0;
     return h->variant == Variant::Decimation ? 1 : 0;
+}
+
+int ldpc_hip_bp_set_decimation_lane_node(ldpc_hip_bp *h, int32_t on) {
+    if (!h) return fail(LDPC_HIP_ERR_INVALID, "null handle");
+    if (on != 0 && on != 1) return fail(LDPC_HIP_ERR_INVALID, "guided decimation: the lane = node switch is %d: it must be 0 or 1", (int)on);
+    if (!on && h->w_gd.p) {  // off: its padded priors go (a decode still queued reads them)
+        HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        h->w_gd.release();
+    }
+    h->gd_lane_node = on != 0;
+    h->gd_route_known = -1;  // (gd_route asks the plans again)
+    return LDPC_HIP_OK;
+}
+
+int ldpc_hip_bp_get_decimation_lane_node(const ldpc_hip_bp *h, int32_t *on) {
+    if (!h || !on) return fail(LDPC_HIP_ERR_INVALID, "null argument");
+    *on = h->gd_lane_node ? 1 : 0;
+    return LDPC_HIP_OK;
 }
 
 int64_t ldpc_hip_bp_workspace_bytes(const ldpc_hip_bp *h, int64_t batch) {

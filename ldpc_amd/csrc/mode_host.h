@@ -21,6 +21,7 @@ struct ModeRules {
     const char *bad_column;  // %d: the column -- a nonzero memory strength on a channel probability of 0 or 1
     const char *no_route;    // %d: the small-code kernel mode -- no lane = edge family takes the code
     bool osd0_only;          // OSD-E and OSD-CS after it are refused
+    const char *no_route_node = nullptr;  // %d: the mode -- no_route's text where the lane = node route was asked for too (ModeState::lane_node)
 };
 
 #define LDPC_MODE_SERIAL "the serial schedules are not available (parallel schedule required)"
@@ -39,7 +40,10 @@ static const ModeRules k_mode_rules[4] = {
      "product-sum is not available (it is built on the minimum-sum lane = edge kernels only)", LDPC_MODE_SERIAL, LDPC_MODE_FLOAT32, nullptr,
      "neither lane = edge kernel family takes this code under small-code kernel mode %d "
      "(ldpc_hip_bp_decimation_route answers 0: it needs rows of at most 8 and columns of at most 4 entries within the kernels' ladders, and mode -1, 1 or 6); "
-     "the lane = node route for larger codes and a per-pass route are not built yet", true},
+     "the lane = node route for larger codes and a per-pass route are not built yet", true,
+     "neither lane = edge kernel family nor the lane = node kernel takes this code under small-code kernel mode %d "
+     "(ldpc_hip_bp_decimation_route answers 0: the lane = node kernel needs rows of at most 16 and columns of at most 8 entries, a syndrome's state "
+     "within LDS, and mode -1, 1, 3, 4 or 5); a per-pass route is not built"},
 };
 
 // What a handle is set up for, as far as the rules look at it.
@@ -49,8 +53,9 @@ struct ModeState {
     int msg_dtype;      // LDPC_HIP_MSG_F64 | LDPC_HIP_MSG_F32
     Variant variant;
     int bad_col;        // the variant's first column with a nonzero strength on a probability of 0 or 1 (-1: none)
-    bool route;         // a lane = edge family takes the code (asked of guided decimation only)
+    bool route;         // an on-chip kernel takes the code (asked of guided decimation only)
     int small_mode, osd_method, osd_order;  // the small-code kernel mode (no_route's message); the handle's OSD
+    bool lane_node = false;  // guided decimation: the lane = node route is switched on (ldpc_hip_bp_set_decimation_lane_node) -- which sentence a missing route gets
 };
 
 // What a decode entry point adds: `what` -- "per-row channel probabilities are", "soft-syndrome decoding is", ... -- is something no mode does
@@ -72,7 +77,7 @@ inline int mode_refusal(const ModeState &s, const DecodeCall &call, char *msg, s
         else if (r->serial && !s.parallel) snprintf(at, room, "%s", r->serial);
         else if (r->float32 && f32) snprintf(at, room, "%s", r->float32);
         else if (r->bad_column && s.bad_col >= 0) snprintf(at, room, r->bad_column, s.bad_col);
-        else if (r->no_route && !s.route) snprintf(at, room, r->no_route, s.small_mode);
+        else if (r->no_route && !s.route) snprintf(at, room, s.lane_node && r->no_route_node ? r->no_route_node : r->no_route, s.small_mode);
         else continue;
         return LDPC_HIP_ERR_UNSUPPORTED;
     }

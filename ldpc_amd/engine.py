@@ -241,8 +241,9 @@ class HipBpEngine:
         """BP with guided decimation (``ldpc_hip_bp_set_decimation``): up to ``max_rounds`` rounds (``None``: n) of up to
         ``round_iters`` min-sum iterations per syndrome -- together they take the place of ``max_iter``; a round that ends unsolved freezes the
         most reliable bit at ``+-freeze_llr`` (positive, finite or ``inf``) and keeps the messages -- or ``round_iters=None``: off.
-        Minimum-sum, parallel schedule, float64 messages, the lane = edge kernels only (``decimation_route``); it excludes ``set_memory`` and
-        ``set_relay``; what it cannot do is refused when decoding."""
+        Minimum-sum, parallel schedule, float64 messages, the lane = edge kernels only unless ``set_decimation_lane_node`` adds the lane = node
+        kernel for the codes beyond them (``decimation_route``); it excludes ``set_memory`` and ``set_relay``; what it cannot do is refused when
+        decoding."""
         if round_iters is None:
             _lib.check(self._lib.ldpc_hip_bp_set_decimation(self._h, 0, 0, 0.0))
             return
@@ -265,11 +266,24 @@ class HipBpEngine:
             _lib.check(rc)
         return (int(t.value), int(r.value), float(c.value)) if rc == 1 else None
 
-    DECIMATION_ROUTES = ("unavailable", "bp_edge", "bp_edge8")
+    def set_decimation_lane_node(self, on):
+        """Opt in to (or out of) the lane = node route of guided decimation (``ldpc_hip_bp_set_decimation_lane_node``; off by default): a code
+        neither lane = edge family takes -- rows of at most 16, columns of at most 8 entries, a syndrome's state within LDS -- is decoded by
+        ``bp_wave_gd_kernel`` instead of being refused.  A setting of the engine, read only while the decimation is on."""
+        _lib.check(self._lib.ldpc_hip_bp_set_decimation_lane_node(self._h, 1 if on else 0))
+
+    @property
+    def decimation_lane_node(self) -> bool:
+        on = C.c_int32(0)
+        _lib.check(self._lib.ldpc_hip_bp_get_decimation_lane_node(self._h, C.byref(on)))
+        return bool(on.value)
+
+    DECIMATION_ROUTES = ("unavailable", "bp_edge", "bp_edge8", "bp_wave", "bp_wave_team")
 
     def decimation_route(self, batch=1) -> str:
         """Which kernels decode ``batch`` syndromes with guided decimation on this engine as it is set now (``ldpc_hip_bp_decimation_route``;
-        nothing is launched): ``"bp_edge"``, ``"bp_edge8"`` or ``"unavailable"`` (such a decode is refused).  ``ValueError`` when it is off."""
+        nothing is launched): ``"bp_edge"``, ``"bp_edge8"``, with ``decimation_lane_node`` also ``"bp_wave"`` / ``"bp_wave_team"`` (the lane =
+        node kernel with one wavefront / a team per syndrome), or ``"unavailable"`` (such a decode is refused).  ``ValueError`` when it is off."""
         route = C.c_int32(-1)
         rc = int(self._lib.ldpc_hip_bp_decimation_route(self._h, int(batch), C.byref(route)))
         if rc == -1:

@@ -58,7 +58,8 @@ class MonteCarloDemSimulation:
     Relay-BP, whose legs take the place of ``max_iter``; with ``osd_method`` OSD_0 only, and not together with ``memory_strength`` or a
     ``window_decoder``.  ``decimation`` (a dict of ``ldpc_amd.bpgd_decoder.decimation_schedule`` keywords -- ``round_iters``, ``max_rounds``,
     ``freeze_llr``): BP with guided decimation, whose rounds take the place of ``max_iter``; on models the lane = edge kernels take only
-    (others are refused at ``run()``), with ``osd_method`` OSD_0 only, and not together with ``relay``, ``memory_strength`` or a
+    (others are refused at ``run()``) unless ``decimation_lane_node=True`` adds the lane = node kernel for the models beyond them
+    (``ldpc_hip_bp_set_decimation_lane_node``), with ``osd_method`` OSD_0 only, and not together with ``relay``, ``memory_strength`` or a
     ``window_decoder``.
 
     One GPU (``device``; -1: the current one).  For several, run one simulation per device over disjoint shot ranges.
@@ -66,7 +67,7 @@ class MonteCarloDemSimulation:
 
     def __init__(self, model, *, target_run_count, batch_size: int = 65536, seed: int = 0, max_iter: int = 0, bp_method="ms",
                  ms_scaling_factor: float = 0.625, osd_method="osd0", osd_order: int = 0, message_dtype="float64", window_decoder=None,
-                 device: int = -1, memory_strength=None, relay=None, decimation=None) -> None:
+                 device: int = -1, memory_strength=None, relay=None, decimation=None, decimation_lane_node: bool = False) -> None:
         from ldpc_amd.bp_decoder._bp_decoder import _bp_method_code
         from ldpc_amd.noise_models.dem import check_dem_probabilities
         from ldpc_amd.sinter_decoders.sinter_bposd_decoder import _osd_code
@@ -147,6 +148,9 @@ class MonteCarloDemSimulation:
             from ldpc_amd.bpgd_decoder import decimation_schedule
             decimation = decimation_schedule(self.check_matrix.shape[1], **decimation)
         self.decimation = decimation
+        if not isinstance(decimation_lane_node, bool):
+            raise ValueError("Invalid decimation_lane_node provided. It must be a bool.")
+        self.decimation_lane_node = decimation_lane_node
         if not isinstance(device, int) or isinstance(device, bool):
             raise ValueError("Invalid device provided.")
         self.device = device
@@ -176,7 +180,8 @@ class MonteCarloDemSimulation:
             if self.relay is not None:
                 eng.set_relay(*self.relay)  # (likewise)
             if self.decimation is not None:
-                eng.set_decimation(*self.decimation)  # (likewise -- a model beyond the lane = edge kernels included)
+                eng.set_decimation_lane_node(self.decimation_lane_node)
+                eng.set_decimation(*self.decimation)  # (likewise -- a model no decimation kernel takes included)
             eng.set_observables(self.observables_matrix)
             eng.set_sampler(self.priors)
             self._engine = eng
