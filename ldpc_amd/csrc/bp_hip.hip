@@ -47,6 +47,7 @@
 //   bp_edge_mem_kernel.h bp_edge_mem_kernel, bp_edge8_mem_kernel   memory min-sum on the lane = edge families: per-bit memory strengths (tu_onchip_mem.hip)
 //   bp_edge_relay_kernel.h bp_edge_relay_kernel, bp_edge8_relay_kernel   Relay-BP on the lane = edge families: chained memory legs in one launch (tu_onchip_relay.hip)
 //   bp_wave_relay_kernel.h bp_wave_relay_kernel             Relay-BP and memory min-sum beyond the lane = edge families: lane = node, messages and memory in LDS (tu_onchip_wave_relay.hip)
+//   bp_wave_ms_body.h    (a textual fragment)                       one min-sum iteration on the lane = node layout, the do-while body of bp_wave_relay_kernel and bp_wave_gd_kernel
 //   bp_edge_gd_kernel.h  bp_edge_gd_kernel, bp_edge8_gd_kernel     BP with guided decimation on the lane = edge families: all rounds in one launch (tu_onchip_gd.hip)
 //   bp_wave_gd_kernel.h  bp_wave_gd_kernel                         BP with guided decimation beyond the lane = edge families: lane = node, messages, posteriors and frozen columns in LDS (tu_onchip_wave_gd.hip)
 //   relay_common.h       relay_weight                      Relay-BP: a solution's weight, shared by the relay kernels and relay_select_kernel (bp_spread_kernels.h)

@@ -9,7 +9,7 @@
 // whatever fits LDS; the contract: tests/bpgd_util.py).  The skeleton is bp_wave_relay_kernel's (bp_wave_relay_kernel.h),
 // operation by operation: the min-sum check pass, bit pass and syndrome test of bp_wave_kernel, the structure-of-arrays M, the apos table,
 // phantom entries, the DUMMY / ZERO slots, one wavefront or (TEAM) the whole workgroup per syndrome, work_pool_next or the static team share,
-// the clock probe.  What differs:
+// the clock probe.  One iteration is the same text in both: the fragment bp_wave_ms_body.h, included below.  What differs:
 //   the rounds  in place of the legs: a round is up to round_iters iterations (stop = it + round_iters) and `it` is never reset -- the scaling
 //               factor 0 takes alpha = 1 - 2^-it of the row's TOTAL, and TEAM's two flags are indexed by that total.
 //   the prior   of column j in the bit pass is D[j] ? (S[j] ? -C : +C) : prior_g[j]: D (decimated) and S (the frozen sign) are two bit masks
@@ -36,11 +36,6 @@ typedef void (*WaveGdKernel)(const WaveGdArgs);
 // The instantiations live in tu_onchip_wave_gd.hip: the six rungs of pick_wave (host_onchip.h), each with and without TEAM; nullptr: no such rung
 WaveGdKernel wave_gd_kernel(int dr, int dc, bool team);
 
-// Wavefronts per workgroup the instantiations are compiled for (__launch_bounds__) -- the host launches no more (plan_wave_gd).  What each
-// instantiation compiles to is listed in DESIGN.md section 7e: the one-wavefront forms of (4,2) and (8,4) -- U rows AND U columns of a lane in
-// flight -- spill 18 / 13 VGPRs at sixteen (128 registers: 76 / 56 bytes of scratch a lane) and get twelve (168), as wave_relay_waves gives them.
-__host__ __device__ constexpr int wave_gd_waves(int dr, int dc, bool team) { return !team && ((dr == 4 && dc == 2) || (dr == 8 && dc == 4)) ? 12 : 16; }
-
 // LDS bytes of the private region of one syndrome (host and device agree through this; the shared tables are bp_wave_relay_kernel's:
 // wave_relay_lds_shared): bp_wave_kernel's with the posterior copy, and the two masks D and S behind the hard decisions.
 __host__ __device__ inline size_t wave_gd_lds_private(int mp, int np, int DR) {  // [M + 2][L][hardw, D, S][syndrome bytes]
@@ -53,15 +48,15 @@ __host__ __device__ inline size_t wave_gd_lds_private(int mp, int np, int DR) { 
 constexpr size_t WAVE_GD_LDS_STATIC = 256;
 
 template <int DR, int DC, bool TEAM>
-__global__ void __launch_bounds__(64 * wave_gd_waves(DR, DC, TEAM)) bp_wave_gd_kernel(const WaveGdArgs ga) {
+__global__ void __launch_bounds__(64 * wave_ms_waves(DR, DC, TEAM)) bp_wave_gd_kernel(const WaveGdArgs ga) {
     using edge_detail::GdPick;
     using edge_detail::gd_take;
     using edge_detail::gd_wave_best;
     const WaveArgs &a = ga.w;
-    constexpr int U = DR <= 4 ? (DC <= 2 ? 4 : 2) : DR <= 8 ? (DC <= 4 ? 2 : 1) : 1;  // nodes per lane in flight (bp_wave_kernel, min-sum)
+    constexpr int U = wave_ms_nodes_per_lane(DR, DC);
     constexpr int UC = TEAM ? 1 : U;
-    constexpr int MAXW = 16;  // (wave_gd_waves never gives a team more)
-    static_assert(wave_gd_waves(DR, DC, true) <= MAXW, "team_key / team_tag hold one winner per wavefront");
+    constexpr int MAXW = 16;  // (wave_ms_waves never gives a team more)
+    static_assert(wave_ms_waves(DR, DC, true) <= MAXW, "team_key / team_tag hold one winner per wavefront");
     extern __shared__ __attribute__((aligned(16))) unsigned char wv_lds[];
     const int tid = threadIdx.x, T = blockDim.x;
     const int lane = tid & 63;
@@ -136,112 +131,11 @@ __global__ void __launch_bounds__(64 * wave_gd_waves(DR, DC, TEAM)) bp_wave_gd_k
         bool unsat_any = true;
         for (int round = 0;; ++round) {
             const int stop = it + round_iters;
+            // one iteration: bp_wave_ms_body.h.  A frozen column's prior is +-C (the wavefront's 64 columns: one word of each mask); the flags by the row's total
+#define WAVE_MS_SET_PRIOR(pr, j, word) { const uint64_t dw = Dm[word], sw = Sm[word]; const double l0 = a.prior_g[j]; pr = ((dw >> lane) & 1ull) ? (((sw >> lane) & 1ull) ? -C : C) : l0; }
+#define WAVE_MS_ITERATIONS it
             do {
-                ++it;
-                const double alpha = (a.ms_scaling_factor == 0.0) ? 1.0 - ldexp(1.0, -it) : a.ms_scaling_factor;
-                // ---- check pass (bp.hpp:201-273), in place, UC rows per lane in flight: loads, arithmetic, stores ----
-                for (int i0 = wt * 64 * UC; i0 < mp; i0 += 64 * UC * W) {
-                    uint8_t sb[UC];
-                    int d[UC];
-                    double cur[UC][DR], out[UC][DR];
-#pragma unroll
-                    for (int u = 0; u < UC; ++u)
-                        if (i0 + u * 64 < mp) {  // wave-uniform
-                            const int i = i0 + u * 64 + lane;
-                            sb[u] = sy[i];
-                            d[u] = rdeg[i];
-#pragma unroll
-                            for (int k = 0; k < DR; ++k) cur[u][k] = M[k * mp + i];
-                        }
-#pragma unroll
-                    for (int u = 0; u < UC; ++u)
-                        if (i0 + u * 64 < mp) {
-                            int parity = sb[u] & 1;  // total_sgn = syndrome[i] + #{b2c <= 0}, parity only (bp.hpp:236-262)
-                            double temp = DBL_MAX;
-#pragma unroll
-                            for (int k = 0; k < DR; ++k) {
-                                if (cur[u][k] <= 0) parity ^= 1;
-                                out[u][k] = temp;
-                                const double ab = fabs(cur[u][k]);
-                                if (ab < temp) temp = ab;
-                            }
-                            temp = DBL_MAX;
-#pragma unroll
-                            for (int k = DR - 1; k >= 0; --k) {
-                                const int sgn = parity ^ (cur[u][k] <= 0 ? 1 : 0);
-                                double mag = out[u][k];
-                                if (temp < mag) mag = temp;
-                                out[u][k] = mag * (sgn ? -alpha : alpha);
-                                const double ab = fabs(cur[u][k]);
-                                if (ab < temp) temp = ab;
-                            }
-                        }
-#pragma unroll
-                    for (int u = 0; u < UC; ++u)
-                        if (i0 + u * 64 < mp) {
-                            const int i = i0 + u * 64 + lane;
-#pragma unroll
-                            for (int k = 0; k < DR; ++k) M[k < d[u] ? k * mp + i : DUMMY] = out[u][k];  // phantom entries keep their neutral value
-                        }
-                }
-                team_sync();
-                // ---- bit pass (bp.hpp:276-298, 311-318), in place through the position table, U bits per lane in flight; a frozen column's prior is +-C ----
-                for (int j0 = wt * 64 * U; j0 < np; j0 += 64 * U * W) {
-                    int pos[U][DC];
-                    double c[U][DC], pre[U][DC], pr[U];
-#pragma unroll
-                    for (int u = 0; u < U; ++u)
-                        if (j0 + u * 64 < np) {
-                            const int j = j0 + u * 64 + lane;
-                            const uint64_t dw = Dm[(j0 >> 6) + u], sw = Sm[(j0 >> 6) + u];  // the wavefront's 64 columns: one word of each mask
-                            const double l0 = a.prior_g[j];
-                            pr[u] = ((dw >> lane) & 1ull) ? (((sw >> lane) & 1ull) ? -C : C) : l0;
-#pragma unroll
-                            for (int k = 0; k < DC; ++k) { pos[u][k] = apos[k * np + j]; c[u][k] = M[pos[u][k]]; }  // phantom: the +0.0 slot
-                        }
-#pragma unroll
-                    for (int u = 0; u < U; ++u)
-                        if (j0 + u * 64 < np) {
-                            double temp = pr[u];
-#pragma unroll
-                            for (int k = 0; k < DC; ++k) { pre[u][k] = temp; temp += c[u][k]; }
-                            L[j0 + u * 64 + lane] = temp;  // the outputs, and what a decimation looks at
-                            const uint64_t word = __ballot(temp <= 0);  // padding bits: prior 1.0, no entries -> 0
-                            if (lane == 0) hardw[(j0 >> 6) + u] = word;
-                            double sfx = 0.0;
-#pragma unroll
-                            for (int k = DC - 1; k >= 0; --k) {
-                                pre[u][k] = pre[u][k] + sfx;
-                                sfx += c[u][k];
-                            }
-                        }
-#pragma unroll
-                    for (int u = 0; u < U; ++u)
-                        if (j0 + u * 64 < np) {
-#pragma unroll
-                            for (int k = 0; k < DC; ++k) M[pos[u][k] == ZERO ? DUMMY : pos[u][k]] = pre[u][k];
-                        }
-                }
-                team_sync();
-                // ---- syndrome test (bp.hpp:292-294, 300-302): candidate parity of every check vs its syndrome BYTE ----
-                bool unsat = false;
-                for (int i0 = wt * 64; i0 < mp; i0 += 64 * W) {
-                    const int i = i0 + lane;
-                    unsigned par = 0;
-#pragma unroll
-                    for (int k = 0; k < DR; ++k) {
-                        const int cj = col[k * mp + i];  // phantom: bit np, always zero
-                        par ^= (unsigned)(hardw[cj >> 6] >> (cj & 63)) & 1u;
-                    }
-                    unsat |= par != (unsigned)sy[i];
-                }
-                unsat_any = __ballot(unsat) != 0;
-                if (TEAM) {  // two flags, by the row's total: iteration g + 1 raises the one nobody has read since iteration g - 1
-                    if (unsat_any && lane == 0) team_unsat[it & 1] = 1;
-                    if (tid == 0) team_unsat[(it + 1) & 1] = 0;
-                    __syncthreads();
-                    unsat_any = team_unsat[it & 1] != 0;
-                }
+#include "bp_wave_ms_body.h"
             } while (unsat_any && it < stop);
             if (!unsat_any || round == max_rounds - 1) break;  // (unsat_any is the same in every thread of the team)
 

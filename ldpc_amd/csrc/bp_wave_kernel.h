@@ -61,6 +61,15 @@ __host__ __device__ inline size_t wave_lds_private(int mp, int np, int DR, bool 
     return (b + 15) & ~(size_t)15;
 }
 
+// Min-sum: nodes per lane in flight in a pass of the lane = node kernels (bp_wave_kernel, bp_wave_relay_kernel, bp_wave_gd_kernel) -- few live
+// values per node, heavier rows and columns take fewer nodes.  The host's team rules go by its row part (dc = 1: plan_wave_lds, host_onchip.h).
+__host__ __device__ constexpr int wave_ms_nodes_per_lane(int dr, int dc) { return dr <= 4 ? (dc <= 2 ? 4 : 2) : dr <= 8 ? (dc <= 4 ? 2 : 1) : 1; }
+// Wavefronts per workgroup bp_wave_relay_kernel and bp_wave_gd_kernel are compiled for (__launch_bounds__) -- the host launches no more
+// (plan_wave_lds).  What each instantiation compiles to is listed in DESIGN.md sections 7d and 7e: the one-wavefront forms of (4,2) and (8,4)
+// -- U rows AND U columns of a lane in flight, with the prior's terms beside them -- spill 13 - 20 VGPRs at sixteen (128 registers) and get
+// twelve (168).
+__host__ __device__ constexpr int wave_ms_waves(int dr, int dc, bool team) { return !team && ((dr == 4 && dc == 2) || (dr == 8 && dc == 4)) ? 12 : 16; }
+
 // TEAM: the whole workgroup decodes ONE syndrome at a time (its wavefronts share the rows of the check pass and the columns of
 // the bit pass; workgroup barriers between the passes, the syndrome test reduced through an LDS flag).  For the codes whose
 // message array leaves room for two or three wavefronts per compute unit (e.g. a 768 x 1600 hypergraph product: 49 KiB a
@@ -69,7 +78,7 @@ template <int METHOD, int MATH, int DR, int DC, bool TEAM = false>
 __global__ void __launch_bounds__(1024) bp_wave_kernel(const WaveArgs a) {
     // nodes per lane in flight: min-sum has few live values per node, the transcendental chains of product-sum many
     // (four nodes of four / two of eight entries each spilled 62 / 38 VGPRs in the bit pass: heavier columns take fewer nodes per lane)
-    constexpr int U = METHOD == LDPC_HIP_MINIMUM_SUM ? (DR <= 4 ? (DC <= 2 ? 4 : 2) : DR <= 8 ? (DC <= 4 ? 2 : 1) : 1) : (DR <= 6 ? 2 : 1);
+    constexpr int U = METHOD == LDPC_HIP_MINIMUM_SUM ? wave_ms_nodes_per_lane(DR, DC) : (DR <= 6 ? 2 : 1);
     // (a team has more wavefronts than the check pass has rounds of 64 U rows -- there are half as many rows as columns --: one row
     // per lane there, so that twice as many wavefronts take part)
     constexpr int UC = TEAM ? 1 : U;

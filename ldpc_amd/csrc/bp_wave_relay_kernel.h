@@ -8,7 +8,8 @@
 // ldpc_hip_bp_set_relay / ldpc_hip_bp_set_memory on a code beyond the lane = edge families (rows <= 16, columns <= 8, whatever fits LDS): the
 // min-sum check and bit passes of bp_wave_kernel (bp_wave_kernel.h), operation by operation -- the structure-of-arrays M, the apos table, phantom
 // entries, the reference's entry order and two sweeps; one wavefront, or (TEAM) the whole workgroup, per syndrome -- inside the leg loop of
-// bp_edge_relay_kernel (bp_edge_relay_kernel.h).  What differs from bp_wave_kernel:
+// bp_edge_relay_kernel (bp_edge_relay_kernel.h).  One iteration -- alpha, both passes, the syndrome test, TEAM's flags -- is written once for this
+// kernel and bp_wave_gd_kernel: the fragment bp_wave_ms_body.h, included below.  What differs from bp_wave_kernel:
 //   the memory  Mprev[np], the posteriors of the last bit pass, lives beside the messages in the syndrome's private LDS region (always: there is no
 //               llr_direct form).  The bit pass forms the prior of column j as mem_prior does (bp_spread_kernels.h): g == 0 ? a : a + g * Mprev[j],
 //               the product rounded, then the sum.  The lane (team thread) that owns column j is the same in every bit pass: it reads the old value
@@ -37,11 +38,6 @@ typedef void (*WaveRelayKernel)(const WaveRelayArgs);
 // The instantiations live in tu_onchip_wave_relay.hip: the six rungs of pick_wave (host_onchip.h), each with and without TEAM; nullptr: no such rung
 WaveRelayKernel wave_relay_kernel(int dr, int dc, bool team);
 
-// Wavefronts per workgroup the instantiations are compiled for (__launch_bounds__) -- the host launches no more (plan_wave_relay).  What each
-// instantiation compiles to is listed in DESIGN.md section 7d: the one-wavefront forms of (4,2) and (8,4) -- U rows AND U columns of a lane in
-// flight, with a, gamma and Mprev beside them -- spill 20 / 16 VGPRs at sixteen (128 registers) and get twelve (168).
-__host__ __device__ constexpr int wave_relay_waves(int dr, int dc, bool team) { return !team && ((dr == 4 && dc == 2) || (dr == 8 && dc == 4)) ? 12 : 16; }
-
 // LDS bytes: the tables a workgroup shares / the private region of one syndrome (host and device agree through these)
 __host__ __device__ inline size_t wave_relay_lds_shared(int mp, int np, int DR, int DC) {
     const size_t b = (size_t)DR * mp * 2 + (size_t)DC * np * 2 + (size_t)mp;
@@ -52,9 +48,9 @@ __host__ __device__ inline size_t wave_relay_lds_private(int mp, int np, int DR)
 constexpr size_t WAVE_RELAY_LDS_STATIC = 64;
 
 template <int DR, int DC, bool TEAM>
-__global__ void __launch_bounds__(64 * wave_relay_waves(DR, DC, TEAM)) bp_wave_relay_kernel(const WaveRelayArgs ra) {
+__global__ void __launch_bounds__(64 * wave_ms_waves(DR, DC, TEAM)) bp_wave_relay_kernel(const WaveRelayArgs ra) {
     const WaveArgs &a = ra.w;
-    constexpr int U = DR <= 4 ? (DC <= 2 ? 4 : 2) : DR <= 8 ? (DC <= 4 ? 2 : 1) : 1;  // nodes per lane in flight (bp_wave_kernel, min-sum)
+    constexpr int U = wave_ms_nodes_per_lane(DR, DC);
     constexpr int UC = TEAM ? 1 : U;
     extern __shared__ __attribute__((aligned(16))) unsigned char wv_lds[];
     const int tid = threadIdx.x, T = blockDim.x;
@@ -140,112 +136,11 @@ __global__ void __launch_bounds__(64 * wave_relay_waves(DR, DC, TEAM)) bp_wave_r
 
             int it = 0;
             bool unsat_any = true;
+            // one iteration: bp_wave_ms_body.h.  The prior of column j as mem_prior forms it (a select: a + 0 * inf would be NaN); the flags by all legs' iterations
+#define WAVE_MS_SET_PRIOR(pr, j, word) { const double as = a_t[j], gs = g_t[j], prev = L[j]; pr = gs == 0.0 ? as : as + gs * prev; }
+#define WAVE_MS_ITERATIONS (total + it)
             do {
-                ++it;
-                const double alpha = (a.ms_scaling_factor == 0.0) ? 1.0 - ldexp(1.0, -it) : a.ms_scaling_factor;
-                // ---- check pass (bp.hpp:201-273), in place, UC rows per lane in flight: loads, arithmetic, stores ----
-                for (int i0 = wt * 64 * UC; i0 < mp; i0 += 64 * UC * W) {
-                    uint8_t sb[UC];
-                    int d[UC];
-                    double cur[UC][DR], out[UC][DR];
-#pragma unroll
-                    for (int u = 0; u < UC; ++u)
-                        if (i0 + u * 64 < mp) {  // wave-uniform
-                            const int i = i0 + u * 64 + lane;
-                            sb[u] = sy[i];
-                            d[u] = rdeg[i];
-#pragma unroll
-                            for (int k = 0; k < DR; ++k) cur[u][k] = M[k * mp + i];
-                        }
-#pragma unroll
-                    for (int u = 0; u < UC; ++u)
-                        if (i0 + u * 64 < mp) {
-                            int parity = sb[u] & 1;  // total_sgn = syndrome[i] + #{b2c <= 0}, parity only (bp.hpp:236-262)
-                            double temp = DBL_MAX;
-#pragma unroll
-                            for (int k = 0; k < DR; ++k) {
-                                if (cur[u][k] <= 0) parity ^= 1;
-                                out[u][k] = temp;
-                                const double ab = fabs(cur[u][k]);
-                                if (ab < temp) temp = ab;
-                            }
-                            temp = DBL_MAX;
-#pragma unroll
-                            for (int k = DR - 1; k >= 0; --k) {
-                                const int sgn = parity ^ (cur[u][k] <= 0 ? 1 : 0);
-                                double mag = out[u][k];
-                                if (temp < mag) mag = temp;
-                                out[u][k] = mag * (sgn ? -alpha : alpha);
-                                const double ab = fabs(cur[u][k]);
-                                if (ab < temp) temp = ab;
-                            }
-                        }
-#pragma unroll
-                    for (int u = 0; u < UC; ++u)
-                        if (i0 + u * 64 < mp) {
-                            const int i = i0 + u * 64 + lane;
-#pragma unroll
-                            for (int k = 0; k < DR; ++k) M[k < d[u] ? k * mp + i : DUMMY] = out[u][k];  // phantom entries keep their neutral value
-                        }
-                }
-                team_sync();
-                // ---- bit pass (bp.hpp:276-298, 311-318), in place through the position table, U bits per lane in flight; the prior from Mprev ----
-                for (int j0 = wt * 64 * U; j0 < np; j0 += 64 * U * W) {
-                    int pos[U][DC];
-                    double c[U][DC], pre[U][DC], pr[U];
-#pragma unroll
-                    for (int u = 0; u < U; ++u)
-                        if (j0 + u * 64 < np) {
-                            const int j = j0 + u * 64 + lane;
-                            const double as = a_t[j], gs = g_t[j], prev = L[j];
-                            pr[u] = gs == 0.0 ? as : as + gs * prev;  // (a select: a + 0 * inf would be NaN)
-#pragma unroll
-                            for (int k = 0; k < DC; ++k) { pos[u][k] = apos[k * np + j]; c[u][k] = M[pos[u][k]]; }  // phantom: the +0.0 slot
-                        }
-#pragma unroll
-                    for (int u = 0; u < U; ++u)
-                        if (j0 + u * 64 < np) {
-                            double temp = pr[u];
-#pragma unroll
-                            for (int k = 0; k < DC; ++k) { pre[u][k] = temp; temp += c[u][k]; }
-                            L[j0 + u * 64 + lane] = temp;  // Mprev of the next iteration, and of the next leg
-                            const uint64_t word = __ballot(temp <= 0);  // padding bits: prior 1.0, no entries -> 0
-                            if (lane == 0) hardw[(j0 >> 6) + u] = word;
-                            double sfx = 0.0;
-#pragma unroll
-                            for (int k = DC - 1; k >= 0; --k) {
-                                pre[u][k] = pre[u][k] + sfx;
-                                sfx += c[u][k];
-                            }
-                        }
-#pragma unroll
-                    for (int u = 0; u < U; ++u)
-                        if (j0 + u * 64 < np) {
-#pragma unroll
-                            for (int k = 0; k < DC; ++k) M[pos[u][k] == ZERO ? DUMMY : pos[u][k]] = pre[u][k];
-                        }
-                }
-                team_sync();
-                // ---- syndrome test (bp.hpp:292-294, 300-302): candidate parity of every check vs its syndrome BYTE ----
-                bool unsat = false;
-                for (int i0 = wt * 64; i0 < mp; i0 += 64 * W) {
-                    const int i = i0 + lane;
-                    unsigned par = 0;
-#pragma unroll
-                    for (int k = 0; k < DR; ++k) {
-                        const int cj = col[k * mp + i];  // phantom: bit np, always zero
-                        par ^= (unsigned)(hardw[cj >> 6] >> (cj & 63)) & 1u;
-                    }
-                    unsat |= par != (unsigned)sy[i];
-                }
-                unsat_any = __ballot(unsat) != 0;
-                if (TEAM) {  // two flags, by the iterations of ALL legs so far: iteration g + 1 raises the one nobody has read since iteration g - 1
-                    const int g = total + it;
-                    if (unsat_any && lane == 0) team_unsat[g & 1] = 1;
-                    if (tid == 0) team_unsat[(g + 1) & 1] = 0;
-                    __syncthreads();
-                    unsat_any = team_unsat[g & 1] != 0;
-                }
+#include "bp_wave_ms_body.h"
             } while (unsat_any && it < leg_iters);
             total += it;
 

@@ -742,11 +742,11 @@ static int launch_edge_relay(ldpc_hip_bp *h, void (*kern)(const ARGS), int round
 // ---- Relay-BP and memory min-sum on the lane = node kernel (bp_wave_relay_kernel.h; instantiated in tu_onchip_wave_relay.hip): the codes beyond both lane = edge ladders ----
 // plan_wave with the posterior copy forced into LDS (it IS the memory), min-sum only, the priors always read from the padded device array: the
 // rungs of pick_wave, the same 16-bit table limits, the same padding rule, the same choice between one wavefront and a team per syndrome (modes 4
-// and 5 force either), capped by the wavefronts the instantiation was compiled for (wave_relay_waves).  waves == 0: not applicable.
+// and 5 force either), capped by the wavefronts the instantiation was compiled for (wave_ms_waves).  waves == 0: not applicable.
 // plan_wave_lds states the rules once, for this kernel and for bp_wave_gd_kernel (plan_wave_gd): the size of a syndrome's private region
-// (`lds_private`), the wavefront caps (`waves_of`) and the bytes left free for the kernel's static LDS (`lds_static`) are all that differ --
-// the shared tables are the same (wave_relay_lds_shared).
-static WavePlan plan_wave_lds(const ldpc_hip_bp *h, bool forced, int64_t batch, size_t (*lds_private)(int, int, int), int (*waves_of)(int, int, bool), size_t lds_static) {
+// (`lds_private`) and the bytes left free for the kernel's static LDS (`lds_static`) are all that differ -- the shared tables
+// (wave_relay_lds_shared) and the wavefront caps (wave_ms_waves) are the same.
+static WavePlan plan_wave_lds(const ldpc_hip_bp *h, bool forced, int64_t batch, size_t (*lds_private)(int, int, int), size_t lds_static) {
     WavePlan p;
     if (h->bp_method != LDPC_HIP_MINIMUM_SUM || h->m <= 0 || h->n <= 0 || h->nnz <= 0 || h->max_row_deg > 16 || h->max_col_deg > 8) return p;
     static const int rungs[6][2] = {{4, 2}, {4, 4}, {6, 3}, {8, 4}, {8, 8}, {16, 8}};  // pick_wave's
@@ -764,13 +764,13 @@ static WavePlan plan_wave_lds(const ldpc_hip_bp *h, bool forced, int64_t batch, 
     const size_t lds = 160u * 1024u - lds_static;  // (the kernel's static LDS comes on top of the dynamic part: WAVE_RELAY_LDS_STATIC / WAVE_GD_LDS_STATIC, which each kernel asserts it keeps to)
     if (p.shared + p.per_wave > lds) return p;
     size_t w = (lds - p.shared) / p.per_wave;
-    if (w > (size_t)waves_of(p.dr, p.dc, false)) w = (size_t)waves_of(p.dr, p.dc, false);
-    const int u = p.dr <= 4 ? 4 : p.dr <= 8 ? 2 : 1;  // (plan_wave's rule, min-sum)
+    if (w > (size_t)wave_ms_waves(p.dr, p.dc, false)) w = (size_t)wave_ms_waves(p.dr, p.dc, false);
+    const int u = wave_ms_nodes_per_lane(p.dr, 1);  // (plan_wave's rule, min-sum: the row part)
     const bool team = h->small_mode == 5 || (h->small_mode != 4 && (w < 6 || 2 * p.np > 3 * 64 * u || batch <= 256 * (int64_t)w));
     if (team) {
         int tw = (p.np + 64 * u - 1) / (64 * u);
         if (tw < 2) tw = 2;
-        if (tw > waves_of(p.dr, p.dc, true)) tw = waves_of(p.dr, p.dc, true);
+        if (tw > wave_ms_waves(p.dr, p.dc, true)) tw = wave_ms_waves(p.dr, p.dc, true);
         p.team = true;
         p.waves = tw;
         p.groups_per_cu = (int)(lds / (p.shared + p.per_wave));
@@ -787,13 +787,11 @@ static WavePlan plan_wave_lds(const ldpc_hip_bp *h, bool forced, int64_t batch, 
     return p;
 }
 static WavePlan plan_wave_relay(const ldpc_hip_bp *h, bool forced, int64_t batch) {
-    return plan_wave_lds(h, forced, batch, [](int mp, int np, int dr) { return wave_relay_lds_private(mp, np, dr); }, [](int dr, int dc, bool team) { return wave_relay_waves(dr, dc, team); },
-                         WAVE_RELAY_LDS_STATIC);
+    return plan_wave_lds(h, forced, batch, [](int mp, int np, int dr) { return wave_relay_lds_private(mp, np, dr); }, WAVE_RELAY_LDS_STATIC);
 }
 // Guided decimation on bp_wave_gd_kernel (bp_wave_gd_kernel.h): the shared tables are the relay kernel's, the private region carries the two masks
 static WavePlan plan_wave_gd(const ldpc_hip_bp *h, bool forced, int64_t batch) {
-    return plan_wave_lds(h, forced, batch, [](int mp, int np, int dr) { return wave_gd_lds_private(mp, np, dr); }, [](int dr, int dc, bool team) { return wave_gd_waves(dr, dc, team); },
-                         WAVE_GD_LDS_STATIC);
+    return plan_wave_lds(h, forced, batch, [](int mp, int np, int dr) { return wave_gd_lds_private(mp, np, dr); }, WAVE_GD_LDS_STATIC);
 }
 
 // a and gamma of every leg as the kernel reads them: [legs][2][np], beyond n a = 1.0 and gamma = 0 (the padding columns form the finite prior 1.0)
