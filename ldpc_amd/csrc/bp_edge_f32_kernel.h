@@ -9,7 +9,9 @@
 // not touched and not parametrised by the type.
 //
 // Reused as they are: the slot tables (partner / cpos, kind, scol: ensure_edge_tables, ensure_edge8_tables), the LDS slot convention
-// (R * 64 slots, then +0.0, then +inf, then a dummy), work_pool_next, the clock probe, the lane-mask helpers of namespace edge_detail.
+// (R * 64 slots, then +0.0, then +inf, then a dummy), work_pool_next, the clock probe, the lane-mask helpers of namespace edge_detail, and
+// the two fragments of the FP64 kernels that touch no message: bp_edge_synd.h (a syndrome's bytes as lane masks) and bp_edge_out_status.h
+// (`iters`, `conv`, the wave_barrier).  The passes have their own types throughout and stay written out here.
 //
 // Arithmetic: that of bp_f32_kernels.h and of tests/f32_util.py: min_sum_restatement(..., np.float32), which binds; per edge
 //   priors       the handle's FP64 log((1 - p) / p) rounded ONCE to FP32, round-to-nearest-even (per slot: edge_prior_f32_kernel,
@@ -112,6 +114,8 @@ __host__ __device__ constexpr int edge8_f32_waves(int rounds, int dc, bool unifo
                    : (rounds <= 4 ? 8 : rounds == 5 ? (uniform ? 8 : 7) : rounds == 6 ? 6 : rounds == 7 ? 5 : rounds == 8 ? (uniform ? 5 : 4) : 4);
 }
 
+#define LDPC_EDGE_ARG(field) LDPC_KERNARG(ARGS_T, field)  // (bp_edge_kernel.h: the block is the arguments)
+
 namespace edge_f32_detail {
 using edge_detail::select_by_mask;
 __device__ __forceinline__ int f2i(float x) { return __builtin_bit_cast(int, x); }
@@ -168,6 +172,7 @@ __global__ void __launch_bounds__(64, edge_f32_waves(R)) bp_edge_f32_kernel(cons
     if (lane == 0) clock_probe_begin(clk_stamp);
     const int m = a.m, n = a.n;
     constexpr int ZERO = R * 64;
+    constexpr int LG = 2;
     constexpr uint64_t LOW = 0x1111111111111111ull;
 
     // per lane and round, for the whole kernel: prior, partner address; per round: which lanes are first / second entries
@@ -187,22 +192,11 @@ __global__ void __launch_bounds__(64, edge_f32_waves(R)) bp_edge_f32_kernel(cons
     if (lane == 0) { X[ZERO] = 0.0f; X[ZERO + 1] = __builtin_inff(); }
 
     // Work: the static share, then chunks from the pooled work counters (work_pool_next, bp_device_common.h)
-    int b0 = (int)blockIdx.x * LDPC_KERNARG(ARGS_T, static_per), b1 = b0 + LDPC_KERNARG(ARGS_T, static_per);
+    int b0 = (int)blockIdx.x * LDPC_EDGE_ARG(static_per), b1 = b0 + LDPC_EDGE_ARG(static_per);
     int pool = (int)(blockIdx.x & (WORK_POOLS - 1));
     for (;;) {
       for (int b = b0; b < b1; ++b) {
-        // this syndrome's bytes as lane masks: bit 4 q of sy[r] = (byte & 1) of the row that lanes 4 q .. 4 q + 3 serve in round r;
-        // a byte above 1 can never be matched
-        uint64_t sy[R];
-        bool never = false;
-        const auto sb = global_ptr(LDPC_KERNARG(ARGS_T, synd)) + (int64_t)b * m;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int row = r * 16 + (lane >> 2);
-            const int byte = row < m ? (int)sb[row] : 0;
-            sy[r] = __ballot((byte & 1) != 0) & LOW;  // (kept in bit 0 of every nibble only: one set of masks for both passes)
-            never = never || __ballot(byte > 1) != 0;
-        }
+#include "bp_edge_synd.h"  // sy[r], never
 #pragma unroll
         for (int r = 0; r < R; ++r) msg[r] = UNIFORM ? (paddr[r] == ZERO + 1 ? __builtin_inff() : pu) : prv[r];  // every edge starts with its column's prior
 
@@ -223,7 +217,7 @@ __global__ void __launch_bounds__(64, edge_f32_waves(R)) bp_edge_f32_kernel(cons
                 const float mag = NOCLAMP ? f::min_abs(x1, other) : f::fmin_pos(f::min_abs(x1, other), flt_max);  // over the three other entries, from FLT_MAX down
                 int sa;  // bits of +-alpha: sign = row parity (syndrome included) + own
                 if (r < (NOCLAMP ? EDGE_F32_V1N : EDGE_F32_V1)) {
-                    // the vector unit spreads the row's parity (see bp_edge_kernel): 2 vector instructions more, 5 scalar ones fewer
+                    // the vector unit spreads the row's parity (see bp_edge_check4.h): 2 vector instructions more, 5 scalar ones fewer
                     const uint64_t par = nibble_parity_low(neg ^ sy[r]);
                     const int own = select_by_mask(ab, nb, neg);
                     const int rowbit = select_by_mask(0, (int)0x80000000, par);
@@ -274,15 +268,15 @@ __global__ void __launch_bounds__(64, edge_f32_waves(R)) bp_edge_f32_kernel(cons
         //      syndrome's first check pass rewrites every slot), then leave in whole rows, widened to FP64 on the way ----
 #pragma unroll
         for (int r = 0; r < R; ++r) msg[r] = (LDPC_EDGE_PRIOR(r) + X[r * 64 + lane]) + X[paddr[r]];
-        const auto scol_t = global_ptr(LDPC_KERNARG(ARGS_T, scol));
+        const auto scol_t = global_ptr(LDPC_EDGE_ARG(scol));
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int j = scol_t[r * 64 + lane];
             if ((k0[r] >> lane) & 1ull) X[j] = msg[r];
         }
         {
-            const auto dp = global_ptr(LDPC_KERNARG(ARGS_T, decoding)) + (int64_t)b * n;
-            auto lp = global_ptr(LDPC_KERNARG(ARGS_T, llr));
+            const auto dp = global_ptr(LDPC_EDGE_ARG(decoding)) + (int64_t)b * n;
+            auto lp = global_ptr(LDPC_EDGE_ARG(llr));
             if (lp) lp += (int64_t)b * n;
             for (int j = lane; j < n; j += 64) {
                 const float l0 = X[j];
@@ -290,20 +284,12 @@ __global__ void __launch_bounds__(64, edge_f32_waves(R)) bp_edge_f32_kernel(cons
                 if (lp) lp[j] = (double)l0;
             }
         }
-        {
-            const auto ip = global_ptr(LDPC_KERNARG(ARGS_T, iters));
-            const auto cp = global_ptr(LDPC_KERNARG(ARGS_T, conv));
-            if (lane == 0) {
-                if (ip) ip[b] = it;
-                if (cp) cp[b] = unsat ? 0 : 1;
-            }
-        }
-        __builtin_amdgcn_wave_barrier();  // (the wavefront must be whole again before lane 0 pulls the next syndrome: see bp_edge_kernel)
+#include "bp_edge_out_status.h"
       }
-        if (!work_pool_next(LDPC_KERNARG(ARGS_T, next), LDPC_KERNARG(ARGS_T, dyn_base), LDPC_KERNARG(ARGS_T, pool_per), LDPC_KERNARG(ARGS_T, chunk),
-                            (int)LDPC_KERNARG(ARGS_T, batch), lane, pool, b0, b1)) break;
+        if (!work_pool_next(LDPC_EDGE_ARG(next), LDPC_EDGE_ARG(dyn_base), LDPC_EDGE_ARG(pool_per), LDPC_EDGE_ARG(chunk),
+                            (int)LDPC_EDGE_ARG(batch), lane, pool, b0, b1)) break;
     }
-    if (lane == 0) clock_probe_end(LDPC_KERNARG(ARGS_T, clk), clk_stamp);
+    if (lane == 0) clock_probe_end(LDPC_EDGE_ARG(clk), clk_stamp);
 #undef LDPC_EDGE_PRIOR
 }
 
@@ -329,6 +315,7 @@ __global__ void __launch_bounds__(64, edge8_f32_waves(R, DC, UNIFORM)) bp_edge8_
     if (lane == 0) clock_probe_begin(clk_stamp);
     const int m = a.m, n = a.n;
     constexpr int ZERO = R * 64;
+    constexpr int LG = 3;
     constexpr uint64_t LOW = 0x0101010101010101ull;
 
     float prv[UNIFORM ? 1 : R], msg[R];
@@ -352,20 +339,11 @@ __global__ void __launch_bounds__(64, edge8_f32_waves(R, DC, UNIFORM)) bp_edge8_
     if (lane == 0) { X[ZERO] = 0.0f; X[ZERO + 1] = __builtin_inff(); }
 
     // Work: the static share, then chunks from the pooled work counters (work_pool_next, bp_device_common.h)
-    int b0 = (int)blockIdx.x * LDPC_KERNARG(ARGS_T, static_per), b1 = b0 + LDPC_KERNARG(ARGS_T, static_per);
+    int b0 = (int)blockIdx.x * LDPC_EDGE_ARG(static_per), b1 = b0 + LDPC_EDGE_ARG(static_per);
     int pool = (int)(blockIdx.x & (WORK_POOLS - 1));
     for (;;) {
       for (int b = b0; b < b1; ++b) {
-        uint64_t sy[R];
-        bool never = false;
-        const auto sb = global_ptr(LDPC_KERNARG(ARGS_T, synd)) + (int64_t)b * m;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int row = r * 8 + (lane >> 3);
-            const int byte = row < m ? (int)sb[row] : 0;
-            sy[r] = __ballot((byte & 1) != 0) & LOW;
-            never = never || __ballot(byte > 1) != 0;
-        }
+#include "bp_edge_synd.h"  // sy[r], never
 #pragma unroll
         for (int r = 0; r < R; ++r) msg[r] = phantom_lane[r] ? __builtin_inff() : LDPC_EDGE_PRIOR(r);  // every edge starts with its column's prior
 
@@ -431,12 +409,12 @@ __global__ void __launch_bounds__(64, edge8_f32_waves(R, DC, UNIFORM)) bp_edge8_
             for (int j = 0; j < DC; ++j) t += X[caddr[r][j]];
             msg[r] = t;
         }
-        const auto scol_t = global_ptr(LDPC_KERNARG(ARGS_T, scol));
+        const auto scol_t = global_ptr(LDPC_EDGE_ARG(scol));
 #pragma unroll
         for (int r = 0; r < R; ++r) X[scol_t[r * 64 + lane]] = msg[r];
         {
-            const auto dp = global_ptr(LDPC_KERNARG(ARGS_T, decoding)) + (int64_t)b * n;
-            auto lp = global_ptr(LDPC_KERNARG(ARGS_T, llr));
+            const auto dp = global_ptr(LDPC_EDGE_ARG(decoding)) + (int64_t)b * n;
+            auto lp = global_ptr(LDPC_EDGE_ARG(llr));
             if (lp) lp += (int64_t)b * n;
             for (int j = lane; j < n; j += 64) {
                 const float t = X[j];
@@ -444,19 +422,12 @@ __global__ void __launch_bounds__(64, edge8_f32_waves(R, DC, UNIFORM)) bp_edge8_
                 if (lp) lp[j] = (double)t;
             }
         }
-        {
-            const auto ip = global_ptr(LDPC_KERNARG(ARGS_T, iters));
-            const auto cp = global_ptr(LDPC_KERNARG(ARGS_T, conv));
-            if (lane == 0) {
-                if (ip) ip[b] = it;
-                if (cp) cp[b] = unsat ? 0 : 1;
-            }
-        }
-        __builtin_amdgcn_wave_barrier();  // (see bp_edge_kernel)
+#include "bp_edge_out_status.h"
       }
-        if (!work_pool_next(LDPC_KERNARG(ARGS_T, next), LDPC_KERNARG(ARGS_T, dyn_base), LDPC_KERNARG(ARGS_T, pool_per), LDPC_KERNARG(ARGS_T, chunk),
-                            (int)LDPC_KERNARG(ARGS_T, batch), lane, pool, b0, b1)) break;
+        if (!work_pool_next(LDPC_EDGE_ARG(next), LDPC_EDGE_ARG(dyn_base), LDPC_EDGE_ARG(pool_per), LDPC_EDGE_ARG(chunk),
+                            (int)LDPC_EDGE_ARG(batch), lane, pool, b0, b1)) break;
     }
-    if (lane == 0) clock_probe_end(LDPC_KERNARG(ARGS_T, clk), clk_stamp);
+    if (lane == 0) clock_probe_end(LDPC_EDGE_ARG(clk), clk_stamp);
 #undef LDPC_EDGE_PRIOR
 }
+#undef LDPC_EDGE_ARG

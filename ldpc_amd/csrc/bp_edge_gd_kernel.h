@@ -5,8 +5,8 @@
 #include "bp_edge_kernel.h"
 
 // ldpc_hip_bp_set_decimation on a code of the lane = edge families (the contract: tests/bpgd_util.py).  The check and bit
-// passes are those of the general forms of bp_edge_kernel / bp_edge8_kernel (per-column prior, the clamp to DBL_MAX stays), operation by
-// operation, as bp_edge_rp_kernel.h restates them with a prior register per lane and round -- inside a loop over the ROUNDS: one wavefront per
+// passes are those of the general forms of bp_edge_kernel / bp_edge8_kernel (per-column prior, the clamp to DBL_MAX stays): the same
+// fragments (bp_edge_kernel.h), with a prior register per lane and round as in bp_edge_rp_kernel.h -- inside a loop over the ROUNDS: one wavefront per
 // syndrome, nothing leaves the chip between rounds.  A round is up to round_iters iterations; the iteration count runs on across the rounds
 // (the scaling factor 0 takes alpha = 1 - 2^-it of the row's TOTAL it).  A round that ends without the syndrome reproduced, and is not the
 // last, DECIMATES: the posteriors M of its last bit pass are formed from the check-to-bit messages that pass left in LDS (the outputs'
@@ -59,6 +59,10 @@ __device__ __forceinline__ GdPick gd_wave_best(GdPick p) {
 }
 }  // namespace edge_detail
 
+// (LDPC_EDGE_ARG: bp_edge_kernel.h -- here the EdgeArgs / Edge8Args block is the member `e`)
+#define LDPC_EDGE_ARG(field) LDPC_KERNARG(ARGS_T, e.field)
+#define LDPC_EDGE_PRIOR(r) prv[r]  // the prior of the bit-pass fragments: a register per lane and round
+
 template <int R>
 __global__ void __launch_bounds__(64, edge_gd_waves(R)) bp_edge_gd_kernel(const EdgeGdArgs ga) {
     using namespace edge_detail;
@@ -72,7 +76,9 @@ __global__ void __launch_bounds__(64, edge_gd_waves(R)) bp_edge_gd_kernel(const 
     if (lane == 0) clock_probe_begin(clk_stamp);
     const int m = a.m, n = a.n;
     constexpr int ZERO = R * 64;
+    constexpr int LG = 2;
     constexpr uint64_t LOW = 0x1111111111111111ull;
+    constexpr bool NOCLAMP = false;  // (bp_edge_check4.h: the clamp to DBL_MAX stays)
 
     // per lane and round, for the whole kernel: partner address; per round: which lanes are first entries.  prv[r], frz: per SYNDROME, rewritten by a decimation
     double prv[R], msg[R];
@@ -88,14 +94,14 @@ __global__ void __launch_bounds__(64, edge_gd_waves(R)) bp_edge_gd_kernel(const 
     if (lane == 0) { X[ZERO] = 0.0; X[ZERO + 1] = __builtin_inf(); }
 
     // Work: the static share, then chunks from the pooled work counters (work_pool_next, bp_device_common.h)
-    int b0 = (int)blockIdx.x * LDPC_EDGE_VARIANT_ARG(static_per), b1 = b0 + LDPC_EDGE_VARIANT_ARG(static_per);
+    int b0 = (int)blockIdx.x * LDPC_EDGE_ARG(static_per), b1 = b0 + LDPC_EDGE_ARG(static_per);
     int pool = (int)(blockIdx.x & (WORK_POOLS - 1));
     for (;;) {
       for (int b = b0; b < b1; ++b) {
         // L0 again for THIS syndrome (whichever row the wavefront pulled): priors, initial messages (initialise_log_domain_bp, bp.hpp:147-157), frozen slots
         unsigned frz = 0;
         {
-            const auto l0_t = global_ptr(LDPC_EDGE_VARIANT_ARG(prior_s));
+            const auto l0_t = global_ptr(LDPC_EDGE_ARG(prior_s));
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 prv[r] = l0_t[r * 64 + lane];  // (phantom lanes: +inf)
@@ -103,19 +109,10 @@ __global__ void __launch_bounds__(64, edge_gd_waves(R)) bp_edge_gd_kernel(const 
                 if (paddr[r] == ZERO + 1 || !__builtin_isfinite(prv[r])) frz |= 1u << r;
             }
         }
-        uint64_t sy[R];
-        bool never = false;
-        const auto sb = global_ptr(LDPC_EDGE_VARIANT_ARG(synd)) + (int64_t)b * m;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int row = r * 16 + (lane >> 2);
-            const int byte = row < m ? (int)sb[row] : 0;
-            sy[r] = __ballot((byte & 1) != 0) & LOW;
-            never = never || __ballot(byte > 1) != 0;
-        }
+#include "bp_edge_synd.h"  // sy[r], never
 
         const int round_iters = LDPC_KERNARG(ARGS_T, round_iters), max_rounds = LDPC_KERNARG(ARGS_T, max_rounds);
-        const auto scol_t = global_ptr(LDPC_EDGE_VARIANT_ARG(scol));
+        const auto scol_t = global_ptr(LDPC_EDGE_ARG(scol));
         int it = 0;
         bool unsat = true;
         for (int round = 0;; ++round) {
@@ -124,59 +121,10 @@ __global__ void __launch_bounds__(64, edge_gd_waves(R)) bp_edge_gd_kernel(const 
                 ++it;
                 const AlphaWords al = alpha_words(a.ms_scaling_factor, it);
                 // ---- check pass: msg[r] (bit_to_check) -> msg[r] (check_to_bit), stored at the slot ----
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const double cur = msg[r];
-                    const uint64_t neg = __ballot(cur <= 0.0);
-                    const double x1 = quad_perm<0xB1>(cur);               // lane ^ 1
-                    const double pairmin = min_abs(cur, x1);
-                    const double other = quad_perm<0x4E>(pairmin);        // the other pair's minimum (lane ^ 2)
-                    const double mag = fmin_pos(min_abs(x1, other), dbl_max);  // over the three other entries, from DBL_MAX down
-                    int shi;  // high word of +-alpha: sign = row parity (syndrome included) + own
-                    if (r < EDGE_V1) {
-                        const uint64_t par = nibble_parity_low(neg ^ sy[r]);
-                        const int own = select_by_mask(al.hi, al.nhi, neg);
-                        const int rowbit = select_by_mask(0, (int)0x80000000, par);
-                        shi = own ^ __builtin_amdgcn_mov_dpp(rowbit, 0x00, 0xf, 0xf, true);  // quad_perm [0, 0, 0, 0]
-                    } else {
-                        const uint64_t flip = spread_nibble(nibble_parity_low(neg ^ sy[r])) ^ neg;
-                        shi = select_by_mask(al.hi, al.nhi, flip);
-                    }
-                    const double c = mag * __hiloint2double(shi, al.lo);
-                    msg[r] = c;
-                    X[r * 64 + lane] = c;
-                }
+#include "bp_edge_check4.h"
                 // ---- bit pass: the partner's message; log-ratio, decision, new bit_to_check ----
                 uint64_t bad = 0;
-#pragma unroll
-                for (int r0 = 0; r0 < R; r0 += EDGE_G) {
-                    double cpv[EDGE_G];
-#pragma unroll
-                    for (int g = 0; g < EDGE_G; ++g)
-                        if (r0 + g < R) cpv[g] = X[paddr[r0 + g]];
-                    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                    for (int g = 0; g < EDGE_G; ++g) {
-                        const int r = r0 + g;
-                        if (r >= R) break;
-                        const double cp = cpv[g];
-                        const double c = msg[r];
-                        const double b2c = prv[r] + cp;
-                        const double l1 = b2c + c;             // second entry of its column: (prior + c0) + c1 with c0 = the partner's
-                        const double l0 = (prv[r] + c) + cp;   // first entry: c0 = its own
-                        uint64_t d;
-                        if (r < EDGE_V2) {
-                            const double l = __hiloint2double(select_by_mask(__double2hiint(l1), __double2hiint(l0), k0[r]),
-                                                              select_by_mask(__double2loint(l1), __double2loint(l0), k0[r]));
-                            d = __ballot(l <= 0.0);
-                        } else {
-                            const uint64_t d1 = __ballot(l1 <= 0.0);
-                            d = d1 ^ ((__ballot(l0 <= 0.0) ^ d1) & k0[r]);  // (phantom lanes: neither)
-                        }
-                        bad |= nibble_parity_low(d) ^ sy[r];  // candidate syndrome vs syndrome (bp.hpp:292-302), bit 0 of every nibble
-                        msg[r] = b2c;
-                    }
-                }
+#include "bp_edge_bit4.h"
                 unsat = never || (bad & LOW) != 0;
             } while (unsat && it < stop);
             if (!unsat || round == max_rounds - 1) break;
@@ -211,29 +159,12 @@ __global__ void __launch_bounds__(64, edge_gd_waves(R)) bp_edge_gd_kernel(const 
             const int j = scol_t[r * 64 + lane];
             if ((k0[r] >> lane) & 1ull) X[j] = msg[r];
         }
-        {
-            const auto dp = global_ptr(LDPC_EDGE_VARIANT_ARG(decoding)) + (int64_t)b * n;
-            auto lp = global_ptr(LDPC_EDGE_VARIANT_ARG(llr));
-            if (lp) lp += (int64_t)b * n;
-            for (int j = lane; j < n; j += 64) {
-                const double l0 = X[j];
-                dp[j] = l0 <= 0.0 ? 1 : 0;
-                if (lp) lp[j] = l0;
-            }
-        }
-        {
-            const auto ip = global_ptr(LDPC_EDGE_VARIANT_ARG(iters));
-            const auto cp = global_ptr(LDPC_EDGE_VARIANT_ARG(conv));
-            if (lane == 0) {
-                if (ip) ip[b] = it;
-                if (cp) cp[b] = unsat ? 0 : 1;
-            }
-        }
-        __builtin_amdgcn_wave_barrier();  // (see bp_edge_kernel: the wavefront is whole before lane 0 pulls the next syndrome)
+#include "bp_edge_out_rows.h"
+#include "bp_edge_out_status.h"
       }
-        if (!work_pool_next(LDPC_EDGE_VARIANT_ARG(next), LDPC_EDGE_VARIANT_ARG(dyn_base), LDPC_EDGE_VARIANT_ARG(pool_per), LDPC_EDGE_VARIANT_ARG(chunk), (int)LDPC_EDGE_VARIANT_ARG(batch), lane, pool, b0, b1)) break;
+        if (!work_pool_next(LDPC_EDGE_ARG(next), LDPC_EDGE_ARG(dyn_base), LDPC_EDGE_ARG(pool_per), LDPC_EDGE_ARG(chunk), (int)LDPC_EDGE_ARG(batch), lane, pool, b0, b1)) break;
     }
-    if (lane == 0) clock_probe_end(LDPC_EDGE_VARIANT_ARG(clk), clk_stamp);
+    if (lane == 0) clock_probe_end(LDPC_EDGE_ARG(clk), clk_stamp);
 }
 
 template <int R, int DC>
@@ -250,6 +181,7 @@ __global__ void __launch_bounds__(64, edge8_gd_waves(R, DC)) bp_edge8_gd_kernel(
     if (lane == 0) clock_probe_begin(clk_stamp);
     const int m = a.m, n = a.n;
     constexpr int ZERO = R * 64;
+    constexpr int LG = 3;
     constexpr uint64_t LOW = 0x0101010101010101ull;
 
     double prv[R], msg[R];
@@ -267,14 +199,14 @@ __global__ void __launch_bounds__(64, edge8_gd_waves(R, DC)) bp_edge8_gd_kernel(
     const double dbl_max = uniform_f64(DBL_MAX);
     if (lane == 0) { X[ZERO] = 0.0; X[ZERO + 1] = __builtin_inf(); }
 
-    int b0 = (int)blockIdx.x * LDPC_EDGE_VARIANT_ARG(static_per), b1 = b0 + LDPC_EDGE_VARIANT_ARG(static_per);
+    int b0 = (int)blockIdx.x * LDPC_EDGE_ARG(static_per), b1 = b0 + LDPC_EDGE_ARG(static_per);
     int pool = (int)(blockIdx.x & (WORK_POOLS - 1));
     for (;;) {
       for (int b = b0; b < b1; ++b) {
         // L0 again for THIS syndrome (see bp_edge_gd_kernel); phantom lanes: the first address is the +inf slot
         unsigned frz = 0;
         {
-            const auto l0_t = global_ptr(LDPC_EDGE_VARIANT_ARG(prior_s));
+            const auto l0_t = global_ptr(LDPC_EDGE_ARG(prior_s));
 #pragma unroll
             for (int r = 0; r < R; ++r) {
                 prv[r] = l0_t[r * 64 + lane];  // (phantom lanes: +inf)
@@ -282,19 +214,10 @@ __global__ void __launch_bounds__(64, edge8_gd_waves(R, DC)) bp_edge8_gd_kernel(
                 if (caddr[r][0] == ZERO + 1 || !__builtin_isfinite(prv[r])) frz |= 1u << r;
             }
         }
-        uint64_t sy[R];
-        bool never = false;
-        const auto sb = global_ptr(LDPC_EDGE_VARIANT_ARG(synd)) + (int64_t)b * m;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int row = r * 8 + (lane >> 3);
-            const int byte = row < m ? (int)sb[row] : 0;
-            sy[r] = __ballot((byte & 1) != 0) & LOW;
-            never = never || __ballot(byte > 1) != 0;
-        }
+#include "bp_edge_synd.h"  // sy[r], never
 
         const int round_iters = LDPC_KERNARG(ARGS_T, round_iters), max_rounds = LDPC_KERNARG(ARGS_T, max_rounds);
-        const auto scol_t = global_ptr(LDPC_EDGE_VARIANT_ARG(scol));
+        const auto scol_t = global_ptr(LDPC_EDGE_ARG(scol));
         int it = 0;
         bool unsat = true;
         for (int round = 0;; ++round) {
@@ -303,47 +226,10 @@ __global__ void __launch_bounds__(64, edge8_gd_waves(R, DC)) bp_edge8_gd_kernel(
                 ++it;
                 const AlphaWords al = alpha_words(a.ms_scaling_factor, it);
                 // ---- check pass (bp.hpp:220-273): minimum over the seven other lanes of the group, sign by the group's parity ----
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const double cur = msg[r];
-                    const uint64_t neg = __ballot(cur <= 0.0);
-                    const double x1 = quad_perm<0xB1>(cur);                // lane ^ 1
-                    const double pairmin = min_abs(cur, x1);
-                    const double otherpair = quad_perm<0x4E>(pairmin);     // lane ^ 2: the other pair of the quad
-                    const double inquad = min_abs(x1, otherpair);          // the three others of the quad
-                    const double quadmin = min_abs(pairmin, otherpair);    // ... and the whole quad, for the other quad
-                    const double otherquad = xor4(quadmin);
-                    const double mag = fmin_pos(min_abs(inquad, otherquad), dbl_max);  // the seven other entries, from DBL_MAX down
-                    const uint64_t flip = spread_byte(byte_parity_low(neg ^ sy[r])) ^ neg;
-                    const double c = mag * __hiloint2double(select_by_mask(al.hi, al.nhi, flip), al.lo);
-                    msg[r] = c;
-                    X[r * 64 + lane] = c;
-                }
+#include "bp_edge_check8.h"
                 // ---- bit pass (bp.hpp:276-318): the column's entries in order; log-ratio, decision, the lane's own bit_to_check ----
                 uint64_t bad = 0;
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    double c[DC];
-#pragma unroll
-                    for (int j = 0; j < DC; ++j) c[j] = X[caddr[r][j]];
-                    const double pr = prv[r];
-                    double pre[DC];  // pre[k] = prior + c0 + ... + c_{k-1}
-                    double t = pr;
-#pragma unroll
-                    for (int j = 0; j < DC; ++j) { pre[j] = t; t += c[j]; }
-                    const uint64_t d = __ballot(t <= 0.0);  // (phantom lanes: +inf or NaN, never <= 0)
-                    bad |= byte_parity_low(d) ^ sy[r];
-                    double cand[DC];
-                    double sfx = c[DC - 1];
-                    cand[DC - 1] = pre[DC - 1];
-                    cand[DC - 2] = pre[DC - 2] + sfx;
-#pragma unroll
-                    for (int k = DC - 3; k >= 0; --k) { sfx += c[k + 1]; cand[k] = pre[k] + sfx; }
-                    double b2c = cand[0];
-#pragma unroll
-                    for (int k = 1; k < DC; ++k) b2c = select_f64(b2c, cand[k], kmask[r][k - 1]);
-                    msg[r] = b2c;
-                }
+#include "bp_edge_bit8.h"
                 unsat = never || (bad & LOW) != 0;
             } while (unsat && it < stop);
             if (!unsat || round == max_rounds - 1) break;
@@ -382,27 +268,12 @@ __global__ void __launch_bounds__(64, edge8_gd_waves(R, DC)) bp_edge8_gd_kernel(
         }
 #pragma unroll
         for (int r = 0; r < R; ++r) X[scol_t[r * 64 + lane]] = msg[r];
-        {
-            const auto dp = global_ptr(LDPC_EDGE_VARIANT_ARG(decoding)) + (int64_t)b * n;
-            auto lp = global_ptr(LDPC_EDGE_VARIANT_ARG(llr));
-            if (lp) lp += (int64_t)b * n;
-            for (int j = lane; j < n; j += 64) {
-                const double t = X[j];
-                dp[j] = t <= 0.0 ? 1 : 0;
-                if (lp) lp[j] = t;
-            }
-        }
-        {
-            const auto ip = global_ptr(LDPC_EDGE_VARIANT_ARG(iters));
-            const auto cp = global_ptr(LDPC_EDGE_VARIANT_ARG(conv));
-            if (lane == 0) {
-                if (ip) ip[b] = it;
-                if (cp) cp[b] = unsat ? 0 : 1;
-            }
-        }
-        __builtin_amdgcn_wave_barrier();  // (see bp_edge_kernel)
+#include "bp_edge_out_rows.h"
+#include "bp_edge_out_status.h"
       }
-        if (!work_pool_next(LDPC_EDGE_VARIANT_ARG(next), LDPC_EDGE_VARIANT_ARG(dyn_base), LDPC_EDGE_VARIANT_ARG(pool_per), LDPC_EDGE_VARIANT_ARG(chunk), (int)LDPC_EDGE_VARIANT_ARG(batch), lane, pool, b0, b1)) break;
+        if (!work_pool_next(LDPC_EDGE_ARG(next), LDPC_EDGE_ARG(dyn_base), LDPC_EDGE_ARG(pool_per), LDPC_EDGE_ARG(chunk), (int)LDPC_EDGE_ARG(batch), lane, pool, b0, b1)) break;
     }
-    if (lane == 0) clock_probe_end(LDPC_EDGE_VARIANT_ARG(clk), clk_stamp);
+    if (lane == 0) clock_probe_end(LDPC_EDGE_ARG(clk), clk_stamp);
 }
+#undef LDPC_EDGE_PRIOR
+#undef LDPC_EDGE_ARG

@@ -22,22 +22,21 @@
 //                returns the other operand for a quiet NaN); sign = parity(syndrome byte + #{entries <= 0}) + own
 //                (bp.hpp:236-262); message = magnitude * (+-alpha) (bp.hpp:264-266).
 //   bit pass     column entries c0 (lower row), c1:  log-ratio = (prior + c0) + c1 (bp.hpp:278-281);
-//                bit_to_check_0 = prior + (0.0 + c1), bit_to_check_1 = (prior + c0) + 0.0 (bp.hpp:279, :313-316).
-//                Both equal prior + (the other entry) EXACTLY: x + 0.0 differs from x only for x = -0.0, and neither
-//                0.0 + c1 feeding a sum with the prior nor prior + c0 can be a -0.0 that matters -- the prior is
-//                log((1 - p) / p), never -0.0, and a sum is -0.0 only if both terms are.  A column of weight one reads
-//                a slot that holds +0.0 for good: prior + 0.0.
-// The reference's minimum starts from DBL_MAX and replaces it only by something SMALLER (bp.hpp:240-247): an infinite
-// |bit_to_check| never enters it.  Hence the clamp min(., DBL_MAX) after the butterfly -- and hence phantom lanes (a row
-// lighter than four, the padding behind the last row) may hold +inf for good (prior +inf, partner = a slot that holds +inf): clamped
-// to DBL_MAX in the minimum, positive in the sign ballot, and their "log-ratio" is +inf or, at worst, inf - inf = NaN:
-// never <= 0, so they drop out of the decision ballots by themselves.
+//                bit_to_check = prior + (the other entry), which is the reference's sum EXACTLY.
 // Results are bit-identical to bp_wave_kernel and to the reference (tests/test_gpu_parity.py, test_gpu_fuzz.py).
-// The variants (bp_edge_rp_kernel.h: row priors, bp_edge_mem_kernel.h: memory, bp_edge_relay_kernel.h: Relay-BP) restate these passes operation
-// by operation, deliberately for now: as __forceinline__ function templates -- whole passes on the register arrays, or one round on values --
-// they compile to other instruction streams in many instantiations (profiles/edge_passes_isa.txt).  Shared as code: edge_detail below, the two
-// ladders, and ONE launch on the host (launch_edge, host_onchip.h).  The arguments about -0.0, phantom lanes, the clamp and the wave_barrier
-// are kept with bp_edge_kernel; the copies point here.
+// The variants (bp_edge_rp_kernel.h: row priors, bp_edge_mem_kernel.h: memory, bp_edge_relay_kernel.h: Relay-BP, bp_edge_gd_kernel.h: guided
+// decimation) run the SAME passes, and every pass is written once, in a textual fragment that the kernels #include where the pass stands:
+//   bp_edge_check4.h, bp_edge_check8.h   the check pass, rows in four / eight lanes (the clamp to DBL_MAX, the phantom lanes, the DPP parity spread)
+//   bp_edge_bit4.h, bp_edge_bit4_mem.h   the bit pass for columns of weight <= 2, plain / memory form (-0.0, the grouped LDS reads)
+//   bp_edge_bit8.h                       the bit pass for columns of weight <= DC, both forms
+//   bp_edge_synd.h                       a syndrome's bytes as lane masks
+//   bp_edge_out_rows.h, bp_edge_out_status.h   the outputs leave; the wave_barrier at the end of a syndrome's turn
+// Each fragment's header lists the names it takes from the kernel, and carries the argument for its code, once.  Textual because a fragment
+// gives every kernel the token stream it had with the pass written out, hence the same code (profiles/edge_fragments_isa.txt); as
+// __forceinline__ function templates -- whole passes on the register arrays, or one round on values -- the passes compiled to other
+// instruction streams in many instantiations (profiles/edge_passes_isa.txt).  Still written out in each kernel: the table set-up and the
+// work loop (two halves that bracket the kernel; edge_fragments_isa.txt says why).  Shared as code: edge_detail below, the two ladders, and
+// ONE launch on the host (launch_edge, host_onchip.h).
 struct EdgeArgs {
     int32_t m, n, max_iter;
     double ms_scaling_factor;
@@ -85,8 +84,10 @@ __host__ __device__ inline size_t edge_f32_lds_bytes(int rounds) { return ((size
 #ifndef EDGE_G
 #define EDGE_G 4
 #endif
-// a cold field (LDPC_KERNARG, bp_device_common.h) of the EdgeArgs / Edge8Args block `e` inside a variant kernel's arguments ARGS_T
-#define LDPC_EDGE_VARIANT_ARG(field) LDPC_KERNARG(ARGS_T, e.field)
+// LDPC_EDGE_ARG(field): a cold field (LDPC_KERNARG, bp_device_common.h) of the EdgeArgs / Edge8Args block in a kernel's arguments ARGS_T -- the
+// one spelling the kernels and the fragments use.  Every kernel header defines it for its own kernels and undefines it at its end: here the
+// block IS the arguments; in a variant it is their member `e`, and the variant's own fields are LDPC_KERNARG(ARGS_T, field).
+#define LDPC_EDGE_ARG(field) LDPC_KERNARG(ARGS_T, field)
 namespace edge_detail {
 typedef __attribute__((address_space(3))) double lds_f64;         // the wave-private LDS array of messages
 typedef __attribute__((address_space(1))) const double *gtab_t;  // a slot table of doubles in global memory
@@ -156,6 +157,7 @@ __global__ void __launch_bounds__(64, UNIFORM ? 5 : 4) bp_edge_kernel(const Edge
     if (lane == 0) clock_probe_begin(clk_stamp);
     const int m = a.m, n = a.n;
     constexpr int ZERO = R * 64;
+    constexpr int LG = 2;  // a row sits in 1 << LG neighbouring lanes; LOW: bit 0 of every such group
     constexpr uint64_t LOW = 0x1111111111111111ull;
 
     // per lane and round, for the whole kernel: prior, partner address; per round: which lanes are first / second entries
@@ -175,22 +177,11 @@ __global__ void __launch_bounds__(64, UNIFORM ? 5 : 4) bp_edge_kernel(const Edge
     if (lane == 0) { X[ZERO] = 0.0; X[ZERO + 1] = __builtin_inf(); }
 
     // Work: the static share, then chunks from the pooled work counters (work_pool_next, bp_device_common.h)
-    int b0 = (int)blockIdx.x * LDPC_KERNARG(ARGS_T, static_per), b1 = b0 + LDPC_KERNARG(ARGS_T, static_per);
+    int b0 = (int)blockIdx.x * LDPC_EDGE_ARG(static_per), b1 = b0 + LDPC_EDGE_ARG(static_per);
     int pool = (int)(blockIdx.x & (WORK_POOLS - 1));
     for (;;) {
       for (int b = b0; b < b1; ++b) {
-        // this syndrome's bytes as lane masks: bit 4 q of sy[r] = (byte & 1) of the row that lanes 4 q .. 4 q + 3 serve in round r;
-        // a byte above 1 can never be matched (bp.hpp:300)
-        uint64_t sy[R];
-        bool never = false;
-        const auto sb = global_ptr(LDPC_KERNARG(ARGS_T, synd)) + (int64_t)b * m;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int row = r * 16 + (lane >> 2);
-            const int byte = row < m ? (int)sb[row] : 0;
-            sy[r] = __ballot((byte & 1) != 0) & LOW;  // (kept in bit 0 of every nibble only: one set of masks for both passes)
-            never = never || __ballot(byte > 1) != 0;
-        }
+#include "bp_edge_synd.h"  // sy[r], never
 #pragma unroll
         for (int r = 0; r < R; ++r) msg[r] = UNIFORM ? (paddr[r] == ZERO + 1 ? __builtin_inf() : pu) : prv[r];  // initialise_log_domain_bp (bp.hpp:147-157)
 
@@ -200,118 +191,40 @@ __global__ void __launch_bounds__(64, UNIFORM ? 5 : 4) bp_edge_kernel(const Edge
             ++it;
             const AlphaWords al = alpha_words(a.ms_scaling_factor, it);
             // ---- check pass: msg[r] (bit_to_check) -> msg[r] (check_to_bit), stored at the slot ----
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const double cur = msg[r];
-                const uint64_t neg = __ballot(cur <= 0.0);
-                const double x1 = quad_perm<0xB1>(cur);               // lane ^ 1
-                const double pairmin = min_abs(cur, x1);
-                const double other = quad_perm<0x4E>(pairmin);        // the other pair's minimum (lane ^ 2)
-                const double mag = NOCLAMP ? min_abs(x1, other) : fmin_pos(min_abs(x1, other), dbl_max);  // over the three other entries, from DBL_MAX down
-                int shi;  // high word of +-alpha: sign = row parity (syndrome included) + own
-                if (r < (NOCLAMP ? EDGE_V1N : EDGE_V1)) {
-                    // the vector unit spreads the row's parity: lane 0 of the quad picks it up from the (unspread) scalar mask, a DPP
-                    // broadcast inside the quad XORs it onto everyone's own sign -- 2 vector instructions more, 5 scalar ones fewer
-                    const uint64_t par = nibble_parity_low(neg ^ sy[r]);
-                    const int own = select_by_mask(al.hi, al.nhi, neg);
-                    const int rowbit = select_by_mask(0, (int)0x80000000, par);
-                    shi = own ^ __builtin_amdgcn_mov_dpp(rowbit, 0x00, 0xf, 0xf, true);  // quad_perm [0, 0, 0, 0]
-                } else {
-                    const uint64_t flip = spread_nibble(nibble_parity_low(neg ^ sy[r])) ^ neg;  // row parity incl. the syndrome, own sign out
-                    shi = select_by_mask(al.hi, al.nhi, flip);
-                }
-                const double c = mag * __hiloint2double(shi, al.lo);
-                msg[r] = c;
-                X[r * 64 + lane] = c;
-            }
+#include "bp_edge_check4.h"
             // ---- bit pass: the partner's message; log-ratio, decision, new bit_to_check ----
             uint64_t bad = 0;
-            // (groups of EDGE_G rounds: their LDS reads are issued together, then consumed -- one round trip per group, not per round)
-#pragma unroll
-            for (int r0 = 0; r0 < R; r0 += EDGE_G) {
-                double cpv[EDGE_G];
-#pragma unroll
-                for (int g = 0; g < EDGE_G; ++g)
-                    if (r0 + g < R) cpv[g] = X[paddr[r0 + g]];
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int g = 0; g < EDGE_G; ++g) {
-                    const int r = r0 + g;
-                    if (r >= R) break;
-                    const double cp = cpv[g];
-                    const double c = msg[r];
-                    const double b2c = LDPC_EDGE_PRIOR(r) + cp;
-                    const double l1 = b2c + c;                       // second entry of its column: (prior + c0) + c1 with c0 = the partner's
-                    const double l0 = (LDPC_EDGE_PRIOR(r) + c) + cp; // first entry: c0 = its own
-                    uint64_t d;
-                    if (r < EDGE_V2) {  // the vector unit picks the lane's own log-ratio: 1 vector instruction more, 3 scalar ones fewer
-                        const double l = __hiloint2double(select_by_mask(__double2hiint(l1), __double2hiint(l0), k0[r]),
-                                                          select_by_mask(__double2loint(l1), __double2loint(l0), k0[r]));
-                        d = __ballot(l <= 0.0);
-                    } else {
-                        const uint64_t d1 = __ballot(l1 <= 0.0);
-                        d = d1 ^ ((__ballot(l0 <= 0.0) ^ d1) & k0[r]);  // (phantom lanes: neither)
-                    }
-                    bad |= nibble_parity_low(d) ^ sy[r];  // candidate syndrome vs syndrome (bp.hpp:292-302), bit 0 of every nibble
-                    msg[r] = b2c;
-                }
-            }
+#include "bp_edge_bit4.h"
             unsat = never || (bad & LOW) != 0;
         } while (unsat && it < a.max_iter);
 
         // ---- outputs (bp.hpp:62,65,69,71): the log-ratios, formed from the last iteration's messages by the lanes that own the first entry
-        //      of a column, change places with the messages (X[j] = log-ratio of column j; n <= R * 64: every column has an entry, and
-        //      the next syndrome's first check pass rewrites every slot), then leave in whole 512- / 64-byte rows ----
+        //      of a column, change places with the messages (X[j] = log-ratio of column j), then leave in whole rows ----
 #pragma unroll
         for (int r = 0; r < R; ++r) msg[r] = (LDPC_EDGE_PRIOR(r) + X[r * 64 + lane]) + X[paddr[r]];
-        const auto scol_t = global_ptr(LDPC_KERNARG(ARGS_T, scol));
+        const auto scol_t = global_ptr(LDPC_EDGE_ARG(scol));
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int j = scol_t[r * 64 + lane];
             if ((k0[r] >> lane) & 1ull) X[j] = msg[r];
         }
-        {
-            const auto dp = global_ptr(LDPC_KERNARG(ARGS_T, decoding)) + (int64_t)b * n;
-            auto lp = global_ptr(LDPC_KERNARG(ARGS_T, llr));
-            if (lp) lp += (int64_t)b * n;
-            for (int j = lane; j < n; j += 64) {
-                const double l0 = X[j];
-                dp[j] = l0 <= 0.0 ? 1 : 0;
-                if (lp) lp[j] = l0;
-            }
-        }
-        {
-            const auto ip = global_ptr(LDPC_KERNARG(ARGS_T, iters));
-            const auto cp = global_ptr(LDPC_KERNARG(ARGS_T, conv));
-            if (lane == 0) {
-                if (ip) ip[b] = it;
-                if (cp) cp[b] = unsat ? 0 : 1;
-            }
-        }
-        // The wavefront must be whole again before lane 0 pulls the next syndrome: without this (convergent) barrier the
-        // compiler threads this `lane == 0` block into the one at the top of the loop and the readfirstlane there runs with
-        // lane 0 masked off -- every other lane's `pulled` is 0, i.e. syndrome 0 for ever (seen with R = 1).
-        __builtin_amdgcn_wave_barrier();
+#include "bp_edge_out_rows.h"
+#include "bp_edge_out_status.h"
       }
-        if (!work_pool_next(LDPC_KERNARG(ARGS_T, next), LDPC_KERNARG(ARGS_T, dyn_base), LDPC_KERNARG(ARGS_T, pool_per), LDPC_KERNARG(ARGS_T, chunk),
-                            (int)LDPC_KERNARG(ARGS_T, batch), lane, pool, b0, b1)) break;
+        if (!work_pool_next(LDPC_EDGE_ARG(next), LDPC_EDGE_ARG(dyn_base), LDPC_EDGE_ARG(pool_per), LDPC_EDGE_ARG(chunk),
+                            (int)LDPC_EDGE_ARG(batch), lane, pool, b0, b1)) break;
     }
-    if (lane == 0) clock_probe_end(LDPC_KERNARG(ARGS_T, clk), clk_stamp);
+    if (lane == 0) clock_probe_end(LDPC_EDGE_ARG(clk), clk_stamp);
 #undef LDPC_EDGE_PRIOR
 }
 
 // ---- the same idea for heavier nodes: rows of weight <= 8 in EIGHT neighbouring lanes, columns of weight <= DC (<= 4) ----------
 // Bivariate-bicycle codes (rows of 6, columns of 3: BB [[72,12,6]] ... [[144,12,12]]), small hypergraph products.  Differences to
 // bp_edge_kernel:
-//   * the butterfly over the other entries of a row has a third step across the two quads of the 8-lane group (row_shl:4 / row_shr:4
-//     DPP moves, each writing the banks it is meant for), the sign parity is a BYTE parity of the lane mask;
-//   * a column has up to DC entries, so a lane reads ALL of them from the wave-private LDS array in column order (its own
-//     included; lighter columns: the +0.0 slot behind their entries) and forms the reference's sums with them:
-//         log-ratio            (((prior + c0) + c1) + c2) + c3                                   (bp.hpp:278-281), the same in every lane of a column,
-//         bit_to_check of k    ((prior + c0) + ... + c_{k-1})  +  (((0 + c_{DC-1}) + ...) + c_{k+1})  (bp.hpp:279, 311-318)
-//     (0.0 + x and x + 0.0 are dropped where x + a prior follows or the sum contains the prior: they can only turn -0.0 into +0.0,
-//     which a sum with a prior log((1-p)/p) -- never -0.0 -- does not see); the lane's own k picks its bit_to_check by two or three
-//     v_cndmask pairs reading per-round lane masks from SGPRs.
+//   * the butterfly over the other entries of a row has a third step across the two quads of the 8-lane group, the sign parity is a
+//     BYTE parity of the lane mask (bp_edge_check8.h);
+//   * a column has up to DC entries, so a lane reads ALL of them from the wave-private LDS array in column order and forms the
+//     reference's sums with them; the lane's own k picks its bit_to_check (bp_edge_bit8.h).
 struct Edge8Args {
     int32_t m, n, max_iter;
     double ms_scaling_factor;
@@ -369,6 +282,7 @@ __global__ void __launch_bounds__(64, UNIFORM ? 5 : 4) bp_edge8_kernel(const Edg
     if (lane == 0) clock_probe_begin(clk_stamp);
     const int m = a.m, n = a.n;
     constexpr int ZERO = R * 64;
+    constexpr int LG = 3;
     constexpr uint64_t LOW = 0x0101010101010101ull;
 
     double prv[UNIFORM ? 1 : R], msg[R];
@@ -392,20 +306,11 @@ __global__ void __launch_bounds__(64, UNIFORM ? 5 : 4) bp_edge8_kernel(const Edg
     if (lane == 0) { X[ZERO] = 0.0; X[ZERO + 1] = __builtin_inf(); }
 
     // Work: the static share, then chunks from the pooled work counters (work_pool_next, bp_device_common.h)
-    int b0 = (int)blockIdx.x * LDPC_KERNARG(ARGS_T, static_per), b1 = b0 + LDPC_KERNARG(ARGS_T, static_per);
+    int b0 = (int)blockIdx.x * LDPC_EDGE_ARG(static_per), b1 = b0 + LDPC_EDGE_ARG(static_per);
     int pool = (int)(blockIdx.x & (WORK_POOLS - 1));
     for (;;) {
       for (int b = b0; b < b1; ++b) {
-        uint64_t sy[R];
-        bool never = false;
-        const auto sb = global_ptr(LDPC_KERNARG(ARGS_T, synd)) + (int64_t)b * m;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const int row = r * 8 + (lane >> 3);
-            const int byte = row < m ? (int)sb[row] : 0;
-            sy[r] = __ballot((byte & 1) != 0) & LOW;
-            never = never || __ballot(byte > 1) != 0;
-        }
+#include "bp_edge_synd.h"  // sy[r], never
 #pragma unroll
         for (int r = 0; r < R; ++r) msg[r] = phantom_lane[r] ? __builtin_inf() : LDPC_EDGE_PRIOR(r);  // initialise_log_domain_bp (bp.hpp:147-157)
 
@@ -415,49 +320,10 @@ __global__ void __launch_bounds__(64, UNIFORM ? 5 : 4) bp_edge8_kernel(const Edg
             ++it;
             const AlphaWords al = alpha_words(a.ms_scaling_factor, it);
             // ---- check pass (bp.hpp:220-273): minimum over the seven other lanes of the group, sign by the group's parity ----
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                const double cur = msg[r];
-                const uint64_t neg = __ballot(cur <= 0.0);
-                const double x1 = quad_perm<0xB1>(cur);                // lane ^ 1
-                const double pairmin = min_abs(cur, x1);
-                const double otherpair = quad_perm<0x4E>(pairmin);     // lane ^ 2: the other pair of the quad
-                const double inquad = min_abs(x1, otherpair);          // the three others of the quad
-                const double quadmin = min_abs(pairmin, otherpair);    // ... and the whole quad, for the other quad (values >= 0: |.| is idle)
-                const double otherquad = xor4(quadmin);
-                const double mag = fmin_pos(min_abs(inquad, otherquad), dbl_max);  // the seven other entries, from DBL_MAX down
-                const uint64_t flip = spread_byte(byte_parity_low(neg ^ sy[r])) ^ neg;
-                const double c = mag * __hiloint2double(select_by_mask(al.hi, al.nhi, flip), al.lo);
-                msg[r] = c;
-                X[r * 64 + lane] = c;
-            }
+#include "bp_edge_check8.h"
             // ---- bit pass (bp.hpp:276-318): the column's entries in order; log-ratio, decision, the lane's own bit_to_check ----
             uint64_t bad = 0;
-#pragma unroll
-            for (int r = 0; r < R; ++r) {
-                double c[DC];
-#pragma unroll
-                for (int j = 0; j < DC; ++j) c[j] = X[caddr[r][j]];
-                const double pr = LDPC_EDGE_PRIOR(r);
-                double pre[DC];  // pre[k] = prior + c0 + ... + c_{k-1}
-                double t = pr;
-#pragma unroll
-                for (int j = 0; j < DC; ++j) { pre[j] = t; t += c[j]; }
-                const uint64_t d = __ballot(t <= 0.0);  // (phantom lanes: +inf or NaN, never <= 0)
-                bad |= byte_parity_low(d) ^ sy[r];
-                // the lane's own bit_to_check: cand[k] = pre[k] + (((0 + c_{DC-1}) + ...) + c_{k+1}), accumulated downwards as the reference
-                // does (bp.hpp:311-318); the k-th entry of its column takes cand[k]
-                double cand[DC];
-                double sfx = c[DC - 1];
-                cand[DC - 1] = pre[DC - 1];
-                cand[DC - 2] = pre[DC - 2] + sfx;
-#pragma unroll
-                for (int k = DC - 3; k >= 0; --k) { sfx += c[k + 1]; cand[k] = pre[k] + sfx; }
-                double b2c = cand[0];
-#pragma unroll
-                for (int k = 1; k < DC; ++k) b2c = select_f64(b2c, cand[k], kmask[r][k - 1]);
-                msg[r] = b2c;
-            }
+#include "bp_edge_bit8.h"
             unsat = never || (bad & LOW) != 0;
         } while (unsat && it < a.max_iter);
 
@@ -470,32 +336,16 @@ __global__ void __launch_bounds__(64, UNIFORM ? 5 : 4) bp_edge8_kernel(const Edg
             for (int j = 0; j < DC; ++j) t += X[caddr[r][j]];
             msg[r] = t;
         }
-        const auto scol_t = global_ptr(LDPC_KERNARG(ARGS_T, scol));
+        const auto scol_t = global_ptr(LDPC_EDGE_ARG(scol));
 #pragma unroll
         for (int r = 0; r < R; ++r) X[scol_t[r * 64 + lane]] = msg[r];
-        {
-            const auto dp = global_ptr(LDPC_KERNARG(ARGS_T, decoding)) + (int64_t)b * n;
-            auto lp = global_ptr(LDPC_KERNARG(ARGS_T, llr));
-            if (lp) lp += (int64_t)b * n;
-            for (int j = lane; j < n; j += 64) {
-                const double t = X[j];
-                dp[j] = t <= 0.0 ? 1 : 0;
-                if (lp) lp[j] = t;
-            }
-        }
-        {
-            const auto ip = global_ptr(LDPC_KERNARG(ARGS_T, iters));
-            const auto cp = global_ptr(LDPC_KERNARG(ARGS_T, conv));
-            if (lane == 0) {
-                if (ip) ip[b] = it;
-                if (cp) cp[b] = unsat ? 0 : 1;
-            }
-        }
-        __builtin_amdgcn_wave_barrier();  // (see bp_edge_kernel)
+#include "bp_edge_out_rows.h"
+#include "bp_edge_out_status.h"
       }
-        if (!work_pool_next(LDPC_KERNARG(ARGS_T, next), LDPC_KERNARG(ARGS_T, dyn_base), LDPC_KERNARG(ARGS_T, pool_per), LDPC_KERNARG(ARGS_T, chunk),
-                            (int)LDPC_KERNARG(ARGS_T, batch), lane, pool, b0, b1)) break;
+        if (!work_pool_next(LDPC_EDGE_ARG(next), LDPC_EDGE_ARG(dyn_base), LDPC_EDGE_ARG(pool_per), LDPC_EDGE_ARG(chunk),
+                            (int)LDPC_EDGE_ARG(batch), lane, pool, b0, b1)) break;
     }
-    if (lane == 0) clock_probe_end(LDPC_KERNARG(ARGS_T, clk), clk_stamp);
+    if (lane == 0) clock_probe_end(LDPC_EDGE_ARG(clk), clk_stamp);
 #undef LDPC_EDGE_PRIOR
 }
+#undef LDPC_EDGE_ARG

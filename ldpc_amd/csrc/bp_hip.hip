@@ -49,6 +49,8 @@
 //   bp_wave_relay_kernel.h bp_wave_relay_kernel             Relay-BP and memory min-sum beyond the lane = edge families: lane = node, messages and memory in LDS (tu_onchip_wave_relay.hip)
 //   bp_wave_ms_body.h    (a textual fragment)                       one min-sum iteration on the lane = node layout, the do-while body of bp_wave_relay_kernel and bp_wave_gd_kernel
 //   bp_edge_gd_kernel.h  bp_edge_gd_kernel, bp_edge8_gd_kernel     BP with guided decimation on the lane = edge families: all rounds in one launch (tu_onchip_gd.hip)
+//   bp_edge_check4.h, bp_edge_check8.h, bp_edge_bit4.h, bp_edge_bit4_mem.h, bp_edge_bit8.h, bp_edge_synd.h, bp_edge_out_rows.h, bp_edge_out_status.h,
+//   bp_edge_relay_take.h (textual fragments)                        the passes of the lane = edge kernels, each written once and included by the kernels above (bp_edge_kernel.h lists them)
 //   bp_wave_gd_kernel.h  bp_wave_gd_kernel                         BP with guided decimation beyond the lane = edge families: lane = node, messages, posteriors and frozen columns in LDS (tu_onchip_wave_gd.hip)
 //   relay_common.h       relay_weight                      Relay-BP: a solution's weight, shared by the relay kernels and relay_select_kernel (bp_spread_kernels.h)
 //   osd_kernels.h        osd0[_reg]_kernel, osdw[_reg]_kernel, osd_big_kernel   OSD-0 / OSD-E / OSD-CS post-processing
