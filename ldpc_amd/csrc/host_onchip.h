@@ -3,6 +3,22 @@
 #pragma once
 
 
+// what a decode is given (decode_onchip and its kin hand it on): device pointers, on h->stream
+struct DecodeIo {
+    const uint8_t *synd;
+    int64_t batch;
+    uint8_t *decoding;
+    double *llr;
+    int32_t *iters;
+    uint8_t *conv;
+};
+
+// What every on-chip route asks before any plan: a code, small enough for the plans' tables, and a batch whose syndrome indices fit the work
+// pools' 32 bits.  Each caller's own small-mode rule stands beside its call.
+static bool onchip_bound(const ldpc_hip_bp *h, int64_t batch) {
+    return h->m > 0 && h->n > 0 && h->nnz > 0 && (int64_t)h->nnz * 16 < (1 << 22) && batch < (1ll << 30);
+}
+
 // LDS bytes of the on-chip kernel for `slots` resident syndromes; 0 if the code is too large for it
 static size_t small_lds_bytes(const ldpc_hip_bp *h, int slots, bool rp = false) {
     size_t fixed = 256 * 8 + (size_t)h->n * 8 + ((size_t)h->m + 1 + h->nnz + h->n + 1 + h->nnz) * 4;
@@ -68,18 +84,54 @@ struct WavePlan {
     void (*kern)(const WaveArgs) = nullptr, (*kern_team)(const WaveArgs) = nullptr;
 };
 
+// The rungs (rows <=, columns <=) of the lane = node and lane = entry kernels, ascending: a code takes the first that holds it.  The first four are
+// bp_wave_ps_kernel's too (pick_wave_ps, which goes on with rungs of its own); all six are bp_wave_kernel's, bp_wave_relay_kernel's and bp_wave_gd_kernel's.
+#define LDPC_WAVE_LADDER4(X) X(4, 2) X(4, 4) X(6, 3) X(8, 4)
+#define LDPC_WAVE_LADDER(X) LDPC_WAVE_LADDER4(X) X(8, 8) X(16, 8)
+
 template <int METHOD, int MATH>
 static void pick_wave(int max_row, int max_col, WavePlan &p) {
-#define LDPC_PICK_WAVE(R, C) { p.dr = R; p.dc = C; p.kern = bp_wave_kernel<METHOD, MATH, R, C, false>; p.kern_team = bp_wave_kernel<METHOD, MATH, R, C, true>; return; }
-    if (max_row <= 4 && max_col <= 2) LDPC_PICK_WAVE(4, 2)
-    if (max_row <= 4 && max_col <= 4) LDPC_PICK_WAVE(4, 4)
-    if (max_row <= 6 && max_col <= 3) LDPC_PICK_WAVE(6, 3)
-    if (max_row <= 8 && max_col <= 4) LDPC_PICK_WAVE(8, 4)
-    if (max_row <= 8) LDPC_PICK_WAVE(8, 8)
     // rows of up to 16 entries (hamming(5) as a full parity-check matrix): min-sum only -- product-sum takes the lane = entry kernel there
     // (bp_wave_ps_kernel<., 16 | 32, 8>), and its lane = node form would need more registers than a 16-wavefront workgroup has
-    if constexpr (METHOD == LDPC_HIP_MINIMUM_SUM) LDPC_PICK_WAVE(16, 8)
-#undef LDPC_PICK_WAVE
+#define LDPC_RUNG(R, C) \
+    if constexpr (R <= 8 || METHOD == LDPC_HIP_MINIMUM_SUM) \
+        if (!p.kern && max_row <= R && max_col <= C) { p.dr = R; p.dc = C; p.kern = bp_wave_kernel<METHOD, MATH, R, C, false>; p.kern_team = bp_wave_kernel<METHOD, MATH, R, C, true>; }
+    LDPC_WAVE_LADDER(LDPC_RUNG)
+#undef LDPC_RUNG
+}
+
+// ---- the rules plan_wave and plan_wave_lds share, each stated once ----
+// rows and columns padded to whole wavefronts; false: a table entry would not fit (positions and column numbers are 16 bits)
+static bool wave_pad(const ldpc_hip_bp *h, WavePlan &p) {
+    p.mp = (h->m + 63) / 64 * 64;
+    p.np = (h->n + 63) / 64 * 64;
+    return !((size_t)p.dr * p.mp + 2 >= 65536 || p.np + 1 >= 65536);
+}
+// a few heavy rows would pad every row (a plan that was not forced refuses)
+static bool wave_padding_dominates(const ldpc_hip_bp *h, const WavePlan &p) { return (size_t)p.dr * p.mp > 2 * (size_t)h->nnz + 1024; }
+// Do the workgroup's wavefronts share ONE syndrome?  w: the wavefronts LDS has room for, one syndrome each; u: the kernel's nodes per lane in flight.
+// small_mode 5 forces, 4 forbids it; the reasons and the measurements stand in plan_wave.
+static bool wave_team_rule(const ldpc_hip_bp *h, const WavePlan &p, size_t w, int u, int64_t batch) {
+    return h->small_mode == 5 || (h->small_mode != 4 && (w < 6 || 2 * p.np > 3 * 64 * u || batch <= 256 * (int64_t)w));
+}
+// a team: as many wavefronts as its bit pass has rounds of 64 u columns for, two at least, `cap` at most
+static int wave_team_width(const WavePlan &p, int u, int cap) {
+    const int tw = (p.np + 64 * u - 1) / (64 * u);
+    return tw < 2 ? 2 : tw > cap ? cap : tw;
+}
+// teams per compute unit, sixteen wavefronts in all
+// (bp_wave_kernel's ~100 VGPRs allow 16 wavefronts per CU: two teams of eight beat one of thirteen -- 768 x 1600: 4.0 vs 4.8 ms)
+static void wave_team_groups(WavePlan &p, size_t lds) {
+    p.groups_per_cu = (int)(lds / (p.shared + p.per_wave));
+    if (p.groups_per_cu >= 2 && p.waves > 8) p.waves = 8;
+    if (p.groups_per_cu * p.waves > 16) p.groups_per_cu = 16 / p.waves;
+    if (p.groups_per_cu < 1) p.groups_per_cu = 1;
+}
+// workgroups of p.waves wavefronts, one syndrome each, per compute unit: `cap` wavefronts in all
+static void wave_solo_groups(WavePlan &p, size_t lds, int cap) {
+    p.groups_per_cu = (int)(lds / (p.shared + (size_t)p.waves * p.per_wave));
+    if (p.groups_per_cu * p.waves > cap) p.groups_per_cu = cap / p.waves;
+    if (p.groups_per_cu < 1) p.groups_per_cu = 1;
 }
 
 static WavePlan plan_wave(const ldpc_hip_bp *h, bool forced, bool want_llr, int64_t batch) {
@@ -87,14 +139,9 @@ static WavePlan plan_wave(const ldpc_hip_bp *h, bool forced, bool want_llr, int6
     if (h->m <= 0 || h->n <= 0 || h->nnz <= 0 || h->max_row_deg > 16 || h->max_col_deg > 8) return p;
     with_method_math(h, [&](auto M, auto F) { pick_wave<M, F>(h->max_row_deg, h->max_col_deg, p); });
     if (!p.kern) return p;
-    p.mp = (h->m + 63) / 64 * 64;
-    p.np = (h->n + 63) / 64 * 64;
-    const size_t rm = (size_t)p.dr * p.mp, cn = (size_t)p.dc * p.np;
-    if (rm + 2 >= 65536 || p.np + 1 >= 65536) return p;               // positions and column numbers are 16 bits
-    if (!forced && rm > 2 * (size_t)h->nnz + 1024) return p;          // a few heavy rows would pad every row
+    if (!wave_pad(h, p) || (!forced && wave_padding_dominates(h, p))) return p;
     p.shared = wave_lds_shared(p.mp, p.np, p.dr, p.dc, h->bp_method == LDPC_HIP_PRODUCT_SUM);
     p.per_wave = wave_lds_private(p.mp, p.np, p.dr, want_llr);
-    (void)cn;
     // one workgroup per compute unit with as many wavefronts as LDS (160 KiB) and the 16-wave workgroup limit allow;
     // small codes fit several such workgroups
     const size_t lds = 160u * 1024u - 64u;  // (the kernels' few bytes of static LDS come on top of the dynamic part)
@@ -120,33 +167,23 @@ static WavePlan plan_wave(const ldpc_hip_bp *h, bool forced, bool want_llr, int6
     // surface d = 41 / 31 / 21 25 -> 11 / 24 -> 12.6 / 11.0 -> 10.0 ms, 300 x 600 1.03 -> 0.79 ms; d = 13, 17 (the bit pass of one
     // wavefront is a single round of 64 U columns already) 7 % slower -- hence the second condition.
     const bool ms = h->bp_method == LDPC_HIP_MINIMUM_SUM;
-    const int u = ms ? (p.dr <= 4 ? 4 : p.dr <= 8 ? 2 : 1) : (p.dr <= 6 ? 2 : 1);  // the kernel's nodes per lane in flight
+    const int u = ms ? wave_ms_nodes_per_lane(p.dr, 1) : (p.dr <= 6 ? 2 : 1);  // the kernel's nodes per lane in flight (min-sum: the row part)
     // A batch of no more than one syndrome per wavefront slot is about latency: a team (two wavefronts at least) then too --
     // surface d = 9 .. 17, BB144 at 512 / 4 096 syndromes: 1.25 - 1.6x / 1.0 - 1.3x faster, at 65 536 up to 16 % slower.
-    const bool team = h->small_mode == 5 || (h->small_mode != 4 && (w < 6 || 2 * p.np > 3 * 64 * u || batch <= 256 * (int64_t)w));
-    if (team) {
-        int tw = (p.np + 64 * u - 1) / (64 * u);
-        if (tw < 2) tw = 2;
-        if (tw > 16) tw = 16;
+    if (wave_team_rule(h, p, w, u, batch)) {
         p.team = true;
-        p.waves = tw;
+        p.waves = wave_team_width(p, u, 16);
         p.kern = p.kern_team;
         if (ms) {  // the LDS copy of the priors, 8 (np + 2) bytes: worth reading them from memory where that fits another workgroup
             const size_t lean_shared = wave_lds_shared(p.mp, p.np, p.dr, p.dc, false, false);
             if (lds / (lean_shared + p.per_wave) > lds / (p.shared + p.per_wave)) { p.shared = lean_shared; p.prior_global = true; }
         }
-        // (the kernel's ~100 VGPRs allow 16 wavefronts per CU: two teams of eight beat one of thirteen -- 768 x 1600: 4.0 vs 4.8 ms)
-        p.groups_per_cu = (int)(lds / (p.shared + p.per_wave));
-        if (p.groups_per_cu >= 2 && p.waves > 8) p.waves = 8;
-        if (p.groups_per_cu * p.waves > 16) p.groups_per_cu = 16 / p.waves;
-        if (p.groups_per_cu < 1) p.groups_per_cu = 1;
+        wave_team_groups(p, lds);
         return p;
     }
-    if (!forced && w < (h->bp_method == LDPC_HIP_MINIMUM_SUM ? 2 : 3)) return p;
+    if (!forced && w < (ms ? 2 : 3)) return p;
     p.waves = (int)w;
-    p.groups_per_cu = (int)(lds / (p.shared + (size_t)p.waves * p.per_wave));
-    if (p.groups_per_cu * p.waves > 32) p.groups_per_cu = 32 / p.waves;  // 32 wavefronts per compute unit
-    if (p.groups_per_cu < 1) p.groups_per_cu = 1;
+    wave_solo_groups(p, lds, 32);  // 32 wavefronts per compute unit
     return p;
 }
 
@@ -191,16 +228,14 @@ struct WavePsPlan {
 
 template <int MATH>
 static void pick_wave_ps(int max_row, int max_col, WavePsPlan &p) {
-#define LDPC_PICK_WAVE_PS(R, C) { p.dr = R; p.dc = C; p.kern = bp_wave_ps_kernel<MATH, R, C, false>; p.kern_team = bp_wave_ps_kernel<MATH, R, C, true>; return; }
-    if (max_row <= 4 && max_col <= 2) LDPC_PICK_WAVE_PS(4, 2)
-    if (max_row <= 4 && max_col <= 4) LDPC_PICK_WAVE_PS(4, 4)
-    if (max_row <= 6 && max_col <= 3) LDPC_PICK_WAVE_PS(6, 3)
-    if (max_row <= 8 && max_col <= 4) LDPC_PICK_WAVE_PS(8, 4)
+#define LDPC_RUNG(R, C) \
+    if (!p.kern && max_row <= R && max_col <= C) { p.dr = R; p.dc = C; p.kern = bp_wave_ps_kernel<MATH, R, C, false>; p.kern_team = bp_wave_ps_kernel<MATH, R, C, true>; }
+    LDPC_WAVE_LADDER4(LDPC_RUNG)
     // heavier rows (classical codes given as full parity-check matrices: hamming(5) has rows of 16, hamming(6) of 32): until round 4 these
     // fell to the workgroup ("slot") kernel, ~11 us of barriers per iteration -- a single decode() of hamming(5) took 230 us
-    if (max_row <= 16) LDPC_PICK_WAVE_PS(16, 8)
-    LDPC_PICK_WAVE_PS(32, 8)
-#undef LDPC_PICK_WAVE_PS
+    LDPC_RUNG(16, 8)
+    LDPC_RUNG(32, 8)
+#undef LDPC_RUNG
 }
 
 static WavePsPlan plan_wave_ps(const ldpc_hip_bp *h, bool forced, bool want_llr, int64_t batch) {
@@ -274,51 +309,86 @@ static int ensure_wave_ps_tables(ldpc_hip_bp *h, const WavePsPlan &p) {
     return LDPC_HIP_OK;
 }
 
-static int decode_wave_ps(ldpc_hip_bp *h, const WavePsPlan &p, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr,
-                          int32_t *iters, uint8_t *conv) {
+// ---- what the launches of the lane = node and lane = entry kernels share (bp_wave_kernel, bp_wave_ps_kernel, bp_wave_relay_kernel, bp_wave_gd_kernel) ----
+// PLAN: WavePlan or WavePsPlan (team, waves, groups_per_cu, shared, per_wave, np); ARGS: WaveArgs or WavePsArgs, where their field names agree.
+
+// a team per syndrome and no more syndromes than resident teams -- e.g. ONE decode(): static assignment, no work counter to reset
+template <class PLAN>
+static bool wave_static_teams(const PLAN &p, int64_t batch) { return p.team && batch <= 256 * (int64_t)p.groups_per_cu; }
+// workgroups: a team per syndrome or a wavefront per syndrome, no more than are resident
+template <class PLAN>
+static int64_t wave_groups(const PLAN &p, int64_t batch) {
+    const int64_t groups = p.team ? batch : (batch + p.waves - 1) / p.waves, resident = 256 * (int64_t)p.groups_per_cu;
+    return groups > resident ? resident : groups;
+}
+
+// The work counters, zeroed unless the teams are static.  hook: the block that takes BP + OSD's hand-over where it is armed (the OSD counters sit
+// right behind the work pools and share the fill); nullptr: a kernel without one -- bposd_device then lists the unsolved rows itself.
+template <class ARGS = WaveArgs>
+static int wave_counters(ldpc_hip_bp *h, bool static_teams, ARGS *hook = nullptr) {
     int rc;
-    if ((rc = ensure_wave_ps_tables(h, p))) return rc;
-    // (a team per syndrome and no more syndromes than resident teams -- e.g. ONE decode(): static assignment, no work counter to reset)
-    const bool static_teams = p.team && batch <= 256 * (int64_t)p.groups_per_cu;
     if ((rc = h->counter.ensure(counter_bytes()))) return rc;
-    // (BP + OSD: the OSD counters sit right behind the work pools and share the fill)
-    const bool osd_hook = h->osd_hook.armed && h->osd_hook.count == osd_counter_ptr(h);
+    const bool osd_hook = hook && h->osd_hook.armed && h->osd_hook.count == osd_counter_ptr(h);
     if (osd_hook && static_teams) HIPCHK(hipMemsetAsync(osd_counter_ptr(h), 0, OSD_COUNTER_BYTES, h->stream));
     if (!static_teams) HIPCHK(hipMemsetAsync(h->counter.p, 0, osd_hook ? counter_bytes() : work_pool_bytes(), h->stream));
-    WavePsArgs a = {};
-    a.pool_per = work_pool_share(batch, 0);
-    a.m = h->m; a.n = h->n; a.np = p.np; a.max_iter = h->max_iter;
-    a.batch = batch;
+    if (osd_hook) { hook->osd_list = h->osd_hook.list; hook->osd_count = h->osd_hook.count; hook->osd_status = h->osd_hook.status; h->osd_hook.done = true; }
+    return LDPC_HIP_OK;
+}
+
+// what the argument blocks say of the position tables (ensure_wave_tables, ensure_wave_ps_tables) and what goes with them
+static void wave_table_fields(const ldpc_hip_bp *h, const WavePlan &p, WaveArgs &a) {
+    a.mp = p.mp;
+    a.ms_scaling_factor = h->ms_scaling_factor;
+    a.rdeg = (const uint8_t *)h->w_rdeg.p; a.cdeg = (const uint8_t *)h->w_cdeg.p;
+    a.col = (const uint16_t *)h->w_col.p; a.apos = (const uint16_t *)h->w_apos.p;
+}
+static void wave_table_fields(const ldpc_hip_bp *h, const WavePsPlan &, WavePsArgs &a) {
     a.rdeg = (const uint8_t *)h->wp_rdeg.p; a.col = (const uint16_t *)h->wp_col.p; a.epos = (const uint16_t *)h->wp_epos.p;
+    a.min_rdeg = h->m;
+    for (int i = 0; i < h->m; ++i) a.min_rdeg = std::min(a.min_rdeg, h->h_row_ptr[(size_t)i + 1] - h->h_row_ptr[(size_t)i]);
+}
+
+// The launch.  `args` is the kernel's argument block and `a` the WaveArgs / WavePsArgs in it (the plain kernels: args itself); the caller has ensured the
+// position tables, called wave_counters, set the fields that are its kernel's own and launched the kernels that fill its tables.  Here: the fields all
+// share, the static share for a handful of syndromes and work_pool_next beyond, the clock probe, LDS above 48 KiB, the grid, the timing events.
+template <class KARGS, class ARGS, class PLAN>
+static int launch_wave(ldpc_hip_bp *h, const PLAN &p, void (*kern)(const KARGS), KARGS &args, ARGS &a, const DecodeIo &io) {
+    const bool static_teams = wave_static_teams(p, io.batch);
+    a.pool_per = work_pool_share(io.batch, 0);
+    a.m = h->m; a.n = h->n; a.np = p.np; a.max_iter = h->max_iter;
+    a.batch = io.batch;
+    wave_table_fields(h, p, a);
     a.llr0 = h->d_llr0;
-    a.synd = synd; a.decoding = decoding; a.llr = llr; a.iters = iters; a.conv = conv;
-    if (osd_hook) { a.osd_list = h->osd_hook.list; a.osd_count = h->osd_hook.count; a.osd_status = h->osd_hook.status; h->osd_hook.done = true; }
+    a.synd = io.synd; a.decoding = io.decoding; a.llr = io.llr; a.iters = io.iters; a.conv = io.conv;
     a.next = static_teams ? nullptr : (unsigned long long *)h->counter.p;
     a.clk = h->d_clk;
     a.lds_shared = (int32_t)p.shared; a.lds_per_wave = (int32_t)p.per_wave;
-    a.min_rdeg = h->m;
-    for (int i = 0; i < h->m; ++i) a.min_rdeg = std::min(a.min_rdeg, h->h_row_ptr[(size_t)i + 1] - h->h_row_ptr[(size_t)i]);
     const size_t dyn = p.shared + (size_t)(p.team ? 1 : p.waves) * p.per_wave;
     if (dyn > 48u * 1024u)
-        HIPCHK(hipFuncSetAttribute((const void *)p.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-    int64_t groups = p.team ? batch : (batch + p.waves - 1) / p.waves;
-    const int64_t resident = 256 * (int64_t)p.groups_per_cu;
-    if (groups > resident) groups = resident;
+        HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
+    const int64_t groups = wave_groups(p, io.batch);
     h->accumulated_ms = 0.f;
     const bool timed = !(h->untimed_call && static_teams);
     // (the timing events ride on the dispatch itself -- hipExtLaunchKernelGGL attaches them to the kernel's own start and completion -- instead of
     // two hipEventRecord around it: those are a barrier packet each on the stream, 5.8 us of a 0.38 ms step, profiles/r6_c5_step_fusion.txt)
-    if (timed) LDPC_LAUNCH_TIMED(p.kern, dim3((unsigned)groups), dim3((unsigned)(p.waves * 64)), (unsigned)dyn, h->stream, h->ev0, h->ev1, 0, a);
-    else LDPC_LAUNCH(p.kern, dim3((unsigned)groups), dim3((unsigned)(p.waves * 64)), (unsigned)dyn, h->stream, a);
+    if (timed) LDPC_LAUNCH_TIMED(kern, dim3((unsigned)groups), dim3((unsigned)(p.waves * 64)), (unsigned)dyn, h->stream, h->ev0, h->ev1, 0, args);
+    else LDPC_LAUNCH(kern, dim3((unsigned)groups), dim3((unsigned)(p.waves * 64)), (unsigned)dyn, h->stream, args);
     h->timed = timed;
     HIPCHK(hipGetLastError());
+    return LDPC_HIP_OK;
+}
+
+static int decode_wave_ps(ldpc_hip_bp *h, const WavePsPlan &p, const DecodeIo &io) {
+    int rc;
+    WavePsArgs a = {};
+    if ((rc = ensure_wave_ps_tables(h, p)) || (rc = wave_counters(h, wave_static_teams(p, io.batch), &a)) || (rc = launch_wave(h, p, p.kern, a, a, io))) return rc;
 #ifdef LDPC_WPS_PROF  // measurement build: print and clear the kernel's cycle sums (tools/wave_ps_phases.py)
     {
         HIPCHK(hipStreamSynchronize(h->stream));
         unsigned long long v[12] = {};
         HIPCHK(hipMemcpyFromSymbol(v, HIP_SYMBOL(g_wps_prof), sizeof v));
         fprintf(stderr, "[wps_prof] team %d waves %d groups %lld batch %lld : checkA %llu checkB %llu bitA %llu bitB+synd %llu close %llu setup/out %llu pull %llu iterations %llu syndromes %llu\n",
-                (int)p.team, p.waves, (long long)groups, (long long)batch, v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8]);
+                (int)p.team, p.waves, (long long)wave_groups(p, io.batch), (long long)io.batch, v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], v[8]);
         unsigned long long z[12] = {};
         HIPCHK(hipMemcpyToSymbol(HIP_SYMBOL(g_wps_prof), z, sizeof z));
     }
@@ -327,69 +397,51 @@ static int decode_wave_ps(ldpc_hip_bp *h, const WavePsPlan &p, const uint8_t *sy
 }
 
 // Wavefront-per-syndrome on-chip variant (bp_wave_kernel).  Device pointers, on h->stream.
-static int decode_wave(ldpc_hip_bp *h, const WavePlan &p, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr,
-                       int32_t *iters, uint8_t *conv) {
+static int decode_wave(ldpc_hip_bp *h, const WavePlan &p, const DecodeIo &io) {
     int rc;
-    if ((rc = ensure_wave_tables(h, p))) return rc;
-    const bool static_teams = p.team && batch <= 256 * (int64_t)p.groups_per_cu;  // (as decode_wave_ps: no work counter for a handful of syndromes)
-    if ((rc = h->counter.ensure(counter_bytes()))) return rc;
-    // (BP + OSD: the OSD counters sit right behind the work pools and share the fill)
-    const bool osd_hook = h->osd_hook.armed && h->osd_hook.count == osd_counter_ptr(h);
-    if (osd_hook && static_teams) HIPCHK(hipMemsetAsync(osd_counter_ptr(h), 0, OSD_COUNTER_BYTES, h->stream));
-    if (!static_teams) HIPCHK(hipMemsetAsync(h->counter.p, 0, osd_hook ? counter_bytes() : work_pool_bytes(), h->stream));
     WaveArgs a = {};
-    a.pool_per = work_pool_share(batch, 0);
-    a.m = h->m; a.n = h->n; a.mp = p.mp; a.np = p.np; a.max_iter = h->max_iter;
-    a.ms_scaling_factor = h->ms_scaling_factor;
-    a.batch = batch;
-    a.rdeg = (const uint8_t *)h->w_rdeg.p; a.cdeg = (const uint8_t *)h->w_cdeg.p;
-    a.col = (const uint16_t *)h->w_col.p; a.apos = (const uint16_t *)h->w_apos.p;
-    a.llr0 = h->d_llr0;
+    if ((rc = ensure_wave_tables(h, p)) || (rc = wave_counters(h, wave_static_teams(p, io.batch), &a))) return rc;
     if (p.prior_global) {
         if ((rc = h->w_prior.ensure(sizeof(double) * (size_t)(p.np + 2)))) return rc;
         LDPC_LAUNCH(wave_prior_pad_kernel, dim3((unsigned)((p.np + 2 + 255) / 256)), dim3(256), 0, h->stream, h->d_llr0, h->n, p.np, (double *)h->w_prior.p);
         a.prior_g = (const double *)h->w_prior.p;
     }
-    a.synd = synd; a.decoding = decoding; a.llr = llr; a.iters = iters; a.conv = conv;
-    if (osd_hook) { a.osd_list = h->osd_hook.list; a.osd_count = h->osd_hook.count; a.osd_status = h->osd_hook.status; h->osd_hook.done = true; }
     a.llr_direct = p.llr_direct ? 1 : 0;
-    a.next = static_teams ? nullptr : (unsigned long long *)h->counter.p;
-    a.clk = h->d_clk;
-    a.lds_shared = (int32_t)p.shared; a.lds_per_wave = (int32_t)p.per_wave;
-    const size_t dyn = p.shared + (size_t)(p.team ? 1 : p.waves) * p.per_wave;
-    if (dyn > 48u * 1024u)
-        HIPCHK(hipFuncSetAttribute((const void *)p.kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-    int64_t groups = p.team ? batch : (batch + p.waves - 1) / p.waves;
-    const int64_t resident = 256 * (int64_t)p.groups_per_cu;
-    if (groups > resident) groups = resident;
-    h->accumulated_ms = 0.f;
-    const bool timed = !(h->untimed_call && static_teams);
-    // (the timing events ride on the dispatch itself -- hipExtLaunchKernelGGL attaches them to the kernel's own start and completion -- instead of
-    // two hipEventRecord around it: those are a barrier packet each on the stream, 5.8 us of a 0.38 ms step, profiles/r6_c5_step_fusion.txt)
-    if (timed) LDPC_LAUNCH_TIMED(p.kern, dim3((unsigned)groups), dim3((unsigned)(p.waves * 64)), (unsigned)dyn, h->stream, h->ev0, h->ev1, 0, a);
-    else LDPC_LAUNCH(p.kern, dim3((unsigned)groups), dim3((unsigned)(p.waves * 64)), (unsigned)dyn, h->stream, a);
-    h->timed = timed;
-    HIPCHK(hipGetLastError());
-    return LDPC_HIP_OK;
+    return launch_wave(h, p, p.kern, a, a, io);
 }
 
-// ---- bp_edge_kernel (min-sum, lane = edge, messages in registers): rows <= 4, columns 1 .. 2 entries, 4 m <= 1024 slots ----
+// ---- the lane = edge kernels (min-sum, messages in registers) ----
+// One plan for the two families: family 1, bp_edge_kernel -- rows in four lanes: rows <= 4, columns 1 .. 2 entries, 4 m <= 1024 slots; family 2,
+// bp_edge8_kernel -- rows in eight lanes: rows <= 8, columns 1 .. 4 entries, 8 m <= 64 R slots.
 struct EdgePlan {
-    int rounds = 0;  // 0: not applicable
-    bool uniform = false;  // every column has the same prior: the form without prior registers (bp_edge_kernel<R, true>)
-    bool noclamp = false;  // ... and the clamp cannot bite (bp_edge_kernel<R, true, true>)
-    void (*kern)(const EdgeArgs) = nullptr;
+    int family = 0;  // 0: not applicable
+    int rounds = 0, dc = 0;  // (dc: family 2, the column weight its kernels are built for)
+    bool uniform = false;  // every column has the same prior: the form without prior registers (bp_edge_kernel<R, true>, bp_edge8_kernel<R, C, true>)
+    bool noclamp = false;  // family 1: ... and the clamp cannot bite (bp_edge_kernel<R, true, true>)
+    void (*kern)(const EdgeArgs) = nullptr;    // family 1
+    void (*kern8)(const Edge8Args) = nullptr;  // family 2
 };
+
+// a column without entries has no lane to write its outputs
+static bool every_column_has_an_entry(const ldpc_hip_bp *h) {
+    std::vector<char> seen((size_t)h->n, 0);
+    for (int32_t j : h->h_col_idx) seen[(size_t)j] = 1;
+    for (char c : seen) if (!c) return false;
+    return true;
+}
+// all priors bit-equal?
+static bool priors_uniform(const ldpc_hip_bp *h) {
+    for (int j = 1; j < h->n; ++j)
+        if (std::memcmp(&h->channel_probs[(size_t)j], &h->channel_probs[0], sizeof(double)) != 0) return false;
+    return true;
+}
 
 static EdgePlan plan_edge(const ldpc_hip_bp *h) {
     EdgePlan p;
     if (h->bp_method != LDPC_HIP_MINIMUM_SUM || h->m <= 0 || h->n <= 0 || h->nnz <= 0) return p;
     if (h->max_row_deg > 4 || h->max_col_deg > 2 || h->n > 65535) return p;
     const int rounds = (4 * h->m + 63) / 64;
-    if (rounds > 16) return p;
-    std::vector<char> seen((size_t)h->n, 0);  // a column without entries has no lane to write its outputs
-    for (int32_t j : h->h_col_idx) seen[(size_t)j] = 1;
-    for (char c : seen) if (!c) return p;
+    if (rounds > 16 || !every_column_has_an_entry(h)) return p;
 #define LDPC_GENERAL(R) bp_edge_kernel<R, false>,
 #define LDPC_UNIFORM(R) bp_edge_kernel<R, true>,
 #define LDPC_NOCLAMP(R) bp_edge_kernel<R, true, true>,
@@ -397,9 +449,8 @@ static EdgePlan plan_edge(const ldpc_hip_bp *h) {
 #undef LDPC_GENERAL
 #undef LDPC_UNIFORM
 #undef LDPC_NOCLAMP
-    p.uniform = true;
-    for (int j = 1; j < h->n && p.uniform; ++j)
-        p.uniform = std::memcmp(&h->channel_probs[(size_t)j], &h->channel_probs[0], sizeof(double)) == 0;
+    p.uniform = priors_uniform(h);
+    p.family = 1;
     p.rounds = rounds;
     // the form without the clamp to DBL_MAX (bp_edge_kernel.h, NOCLAMP): finite prior, |alpha| <= 1 (0 = the adaptive 1 - 2^-it), rows of two or more
     bool noclamp = p.uniform && std::isfinite(std::log((1 - h->channel_probs[0]) / h->channel_probs[0])) && std::fabs(h->ms_scaling_factor) <= 1.0 && !h->on("EDGE_CLAMP");
@@ -419,6 +470,20 @@ static void launch_edge_prior(ldpc_hip_bp *h, int slots) {
                 (const uint8_t *)h->e_kind.p, slots, (double *)h->e_prior.p);
 }
 
+// the slot tables of either family into e_partner (partner / cpos), e_kind, e_scol, with room for the priors per slot in e_prior; key: h->edge_rounds
+static int upload_edge_tables(ldpc_hip_bp *h, int key, const std::vector<uint16_t> &partner, const std::vector<uint8_t> &kind, const std::vector<int32_t> &scol) {
+    const size_t slots = kind.size();
+    int rc;
+    if ((rc = h->e_partner.ensure(partner.size() * 2)) || (rc = h->e_kind.ensure(slots)) || (rc = h->e_scol.ensure(slots * 4)) ||
+        (rc = h->e_prior.ensure(slots * 8))) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));  // a previous launch may still read the old tables
+    HIPCHK(hipMemcpy(h->e_partner.p, partner.data(), partner.size() * 2, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->e_kind.p, kind.data(), slots, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->e_scol.p, scol.data(), slots * 4, hipMemcpyHostToDevice));
+    h->edge_rounds = key;
+    return LDPC_HIP_OK;
+}
+
 // slot tables of bp_edge_kernel: entry k of row i sits in slot 4 i + k (see bp_edge_kernel.h)
 static int ensure_edge_tables(ldpc_hip_bp *h, const EdgePlan &p) {
     if (h->edge_rounds == p.rounds) return LDPC_HIP_OK;
@@ -433,15 +498,57 @@ static int ensure_edge_tables(ldpc_hip_bp *h, const EdgePlan &p) {
             if (first[(size_t)j] < 0) { first[(size_t)j] = s; kind[(size_t)s] = 1; partner[(size_t)s] = (uint16_t)slots; }  // rows ascend: the column's first entry (bp.hpp:278); alone so far: the +0.0 slot
             else { kind[(size_t)s] = 2; partner[(size_t)s] = (uint16_t)first[(size_t)j]; partner[(size_t)first[(size_t)j]] = (uint16_t)s; }
         }
-    int rc;
-    if ((rc = h->e_partner.ensure((size_t)slots * 2)) || (rc = h->e_kind.ensure((size_t)slots)) || (rc = h->e_scol.ensure((size_t)slots * 4)) ||
-        (rc = h->e_prior.ensure((size_t)slots * 8))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));  // a previous launch may still read the old tables
-    HIPCHK(hipMemcpy(h->e_partner.p, partner.data(), (size_t)slots * 2, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->e_kind.p, kind.data(), (size_t)slots, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->e_scol.p, scol.data(), (size_t)slots * 4, hipMemcpyHostToDevice));
-    h->edge_rounds = p.rounds;
-    return LDPC_HIP_OK;
+    return upload_edge_tables(h, p.rounds, partner, kind, scol);
+}
+
+static EdgePlan plan_edge8(const ldpc_hip_bp *h) {
+    EdgePlan p;
+    if (h->bp_method != LDPC_HIP_MINIMUM_SUM || h->m <= 0 || h->n <= 0 || h->nnz <= 0) return p;
+    if (h->max_row_deg > 8 || h->max_col_deg > 4 || h->n > 65535) return p;
+    const int dc = h->max_col_deg <= 3 ? 3 : 4;
+    const int need = (8 * h->m + 63) / 64;
+    int rounds = 0;  // the first rung of the column weight (they ascend) that holds the code
+#define LDPC_RUNG(R, C) if (dc == C && !rounds && R >= need) rounds = R;
+    LDPC_EDGE8_LADDER(LDPC_RUNG)
+#undef LDPC_RUNG
+    if (!rounds || !every_column_has_an_entry(h)) return p;
+    p.uniform = priors_uniform(h);
+#define LDPC_E8(R, C) if (rounds == R && dc == C) p.kern8 = p.uniform ? bp_edge8_kernel<R, C, true> : bp_edge8_kernel<R, C, false>;
+    LDPC_EDGE8_LADDER(LDPC_E8)
+#undef LDPC_E8
+    p.family = 2;
+    p.rounds = rounds;
+    p.dc = dc;
+    return p;
+}
+
+// slot tables of bp_edge8_kernel: entry k of row i sits in slot 8 i + k (see bp_edge_kernel.h)
+static int ensure_edge8_tables(ldpc_hip_bp *h, const EdgePlan &p) {
+    const int key = 1000 + p.rounds * 8 + p.dc;
+    if (h->edge_rounds == key) return LDPC_HIP_OK;
+    const int slots = p.rounds * 64, dc = p.dc;
+    std::vector<uint16_t> cpos((size_t)dc * slots, (uint16_t)(slots + 1));  // phantom lanes read the slot that holds +inf
+    std::vector<uint8_t> kind((size_t)slots, 0);
+    std::vector<int32_t> scol((size_t)slots, slots + 2);  // phantom lanes: the dummy slot
+    std::vector<std::vector<int>> col_slots((size_t)h->n);
+    for (int i = 0; i < h->m; ++i)
+        for (int e = h->h_row_ptr[(size_t)i]; e < h->h_row_ptr[(size_t)i + 1]; ++e) {
+            const int s = 8 * i + (e - h->h_row_ptr[(size_t)i]), j = h->h_col_idx[(size_t)e];
+            scol[(size_t)s] = j;
+            kind[(size_t)s] = (uint8_t)(1 + col_slots[(size_t)j].size());  // rows ascend: the column's order (bp.hpp:278)
+            col_slots[(size_t)j].push_back(s);
+        }
+    for (int j = 0; j < h->n; ++j)
+        for (int s : col_slots[(size_t)j])
+            for (int q = 0; q < dc; ++q)
+                cpos[(size_t)q * slots + s] = (uint16_t)(q < (int)col_slots[(size_t)j].size() ? col_slots[(size_t)j][(size_t)q] : slots);  // beyond the column: +0.0
+    return upload_edge_tables(h, key, cpos, kind, scol);
+}
+
+// Which lane = edge family takes the handle's code, with its plan: rows in four lanes first, rows in eight lanes (heavier nodes) if that does not
+static EdgePlan plan_edge_family(const ldpc_hip_bp *h) {
+    const EdgePlan p = plan_edge(h);
+    return p.family ? p : plan_edge8(h);
 }
 
 // How the lane = edge kernels share a batch among their wavefronts (work_pool_next, bp_device_common.h): one syndrome each to
@@ -465,23 +572,34 @@ static int edge_work_split(ldpc_hip_bp *h, int rounds, int64_t batch, int64_t gr
     return LDPC_HIP_OK;
 }
 
-// what a decode is given (decode_onchip and its kin hand it on): device pointers, on h->stream
-struct EdgeIo {
-    const uint8_t *synd;
-    int64_t batch;
-    uint8_t *decoding;
-    double *llr;
-    int32_t *iters;
-    uint8_t *conv;
-};
+// The two families differ for the host in two things, said here once: which slot tables a plan asks for, and which field of the inner argument block --
+// the EdgeArgs / Edge8Args / EdgeF32Args / Edge8F32Args, which the plain kernels take as it is and the variants carry as `e` -- points at e_partner.
+static EdgeArgs &edge_inner(EdgeArgs &a) { return a; }
+static Edge8Args &edge_inner(Edge8Args &a) { return a; }
+static EdgeF32Args &edge_inner(EdgeF32Args &a) { return a; }
+static Edge8F32Args &edge_inner(Edge8F32Args &a) { return a; }
+template <class KARGS> static auto edge_inner(KARGS &args) -> decltype((args.e)) { return args.e; }
+static const uint16_t *&edge_partner_field(EdgeArgs &e) { return e.partner; }
+static const uint16_t *&edge_partner_field(Edge8Args &e) { return e.cpos; }
+static const uint16_t *&edge_partner_field(EdgeF32Args &e) { return e.partner; }
+static const uint16_t *&edge_partner_field(Edge8F32Args &e) { return e.cpos; }
+// the first step of every lane = edge mode: the plan's slot tables, and `args` told where they are
+template <class KARGS>
+static int edge_tables(ldpc_hip_bp *h, const EdgePlan &p, KARGS &args) {
+    const int rc = p.family == 1 ? ensure_edge_tables(h, p) : ensure_edge8_tables(h, p);
+    if (rc) return rc;
+    edge_partner_field(edge_inner(args)) = (const uint16_t *)h->e_partner.p;
+    return LDPC_HIP_OK;
+}
 
-// The launch of EVERY lane = edge kernel -- FP64 and FP32, rows in four and in eight lanes, plain, row priors, memory, Relay-BP.  `args` is the
-// kernel's argument block and `a` the EdgeArgs / Edge8Args / EdgeF32Args / Edge8F32Args in it (the plain kernels: args itself); the caller has set
-// what is its own -- partner / cpos, the priors, a variant's tables -- and launched the kernels that fill them.  Here: the fields all share, one
-// wavefront per workgroup and as many of them resident as LDS (`dyn` bytes and the kernels' few static ones, of 160 KiB) and the registers (the
-// wavefronts per SIMD the instantiation was compiled for) allow, the work split, the launch between the two timing events.
-template <class KARGS, class EARGS>
-static int launch_edge(ldpc_hip_bp *h, void (*kern)(const KARGS), KARGS &args, EARGS &a, int rounds, size_t dyn, int waves_per_simd, const EdgeIo &io) {
+// The launch of EVERY lane = edge kernel -- FP64 and FP32, rows in four and in eight lanes, plain, row priors, memory, Relay-BP, decimation.  `args` is
+// the kernel's argument block; the mode has called edge_tables, set what is its own in it -- the priors, a variant's tables -- and launched the kernels
+// that fill them.  Here: the fields all share, one wavefront per workgroup and as many of them resident as LDS (`dyn` bytes and the kernels' few static
+// ones, of 160 KiB) and the registers (the wavefronts per SIMD the instantiation was compiled for) allow, the work split, the launch between the two
+// timing events.
+template <class KARGS>
+static int launch_edge(ldpc_hip_bp *h, void (*kern)(const KARGS), KARGS &args, int rounds, size_t dyn, int waves_per_simd, const DecodeIo &io) {
+    auto &a = edge_inner(args);
     a.m = h->m; a.n = h->n; a.max_iter = h->max_iter;
     a.ms_scaling_factor = h->ms_scaling_factor;
     a.batch = io.batch;
@@ -501,87 +619,22 @@ static int launch_edge(ldpc_hip_bp *h, void (*kern)(const KARGS), KARGS &args, E
     return LDPC_HIP_OK;
 }
 
-static int decode_edge(ldpc_hip_bp *h, const EdgePlan &p, const EdgeIo &io) {
-    int rc;
-    if ((rc = ensure_edge_tables(h, p))) return rc;
-    launch_edge_prior(h, p.rounds * 64);
-    EdgeArgs a = {};
-    a.prior_s = (const double *)h->e_prior.p; a.partner = (const uint16_t *)h->e_partner.p;
-    a.prior_u = std::log((1 - h->channel_probs[0]) / h->channel_probs[0]);  // as upload_priors (bp.hpp:150-151); read by the uniform form only
-    return launch_edge(h, p.kern, a, a, p.rounds, edge_lds_bytes(p.rounds), p.uniform ? 5 : 4, io);  // (__launch_bounds__(64, UNIFORM ? 5 : 4))
-}
+// a zeroed argument block of the type `kern` takes
+template <class KARGS> static KARGS kernel_args(void (*)(const KARGS)) { return {}; }
 
-// ---- bp_edge8_kernel (min-sum, lane = edge, rows in 8-lane groups): rows <= 8, columns 1 .. 4 entries, 8 m <= 64 R slots ----
-struct Edge8Plan {
-    int rounds = 0, dc = 0;  // rounds == 0: not applicable
-    bool uniform = false;
-    void (*kern)(const Edge8Args) = nullptr;
-};
-
-static Edge8Plan plan_edge8(const ldpc_hip_bp *h) {
-    Edge8Plan p;
-    if (h->bp_method != LDPC_HIP_MINIMUM_SUM || h->m <= 0 || h->n <= 0 || h->nnz <= 0) return p;
-    if (h->max_row_deg > 8 || h->max_col_deg > 4 || h->n > 65535) return p;
-    const int dc = h->max_col_deg <= 3 ? 3 : 4;
-    const int need = (8 * h->m + 63) / 64;
-    int rounds = 0;  // the first rung of the column weight (they ascend) that holds the code
-#define LDPC_RUNG(R, C) if (dc == C && !rounds && R >= need) rounds = R;
-    LDPC_EDGE8_LADDER(LDPC_RUNG)
-#undef LDPC_RUNG
-    if (!rounds) return p;
-    std::vector<char> seen((size_t)h->n, 0);  // a column without entries has no lane to write its outputs
-    for (int32_t j : h->h_col_idx) seen[(size_t)j] = 1;
-    for (char c : seen) if (!c) return p;
-    p.uniform = true;
-    for (int j = 1; j < h->n && p.uniform; ++j)
-        p.uniform = std::memcmp(&h->channel_probs[(size_t)j], &h->channel_probs[0], sizeof(double)) == 0;
-#define LDPC_E8(R, C) if (rounds == R && dc == C) p.kern = p.uniform ? bp_edge8_kernel<R, C, true> : bp_edge8_kernel<R, C, false>;
-    LDPC_EDGE8_LADDER(LDPC_E8)
-#undef LDPC_E8
-    p.rounds = rounds;
-    p.dc = dc;
-    return p;
-}
-
-// slot tables of bp_edge8_kernel: entry k of row i sits in slot 8 i + k (see bp_edge_kernel.h)
-static int ensure_edge8_tables(ldpc_hip_bp *h, const Edge8Plan &p) {
-    const int key = 1000 + p.rounds * 8 + p.dc;
-    if (h->edge_rounds == key) return LDPC_HIP_OK;
-    const int slots = p.rounds * 64, dc = p.dc;
-    std::vector<uint16_t> cpos((size_t)dc * slots, (uint16_t)(slots + 1));  // phantom lanes read the slot that holds +inf
-    std::vector<uint8_t> kind((size_t)slots, 0);
-    std::vector<int32_t> scol((size_t)slots, slots + 2);  // phantom lanes: the dummy slot
-    std::vector<std::vector<int>> col_slots((size_t)h->n);
-    for (int i = 0; i < h->m; ++i)
-        for (int e = h->h_row_ptr[(size_t)i]; e < h->h_row_ptr[(size_t)i + 1]; ++e) {
-            const int s = 8 * i + (e - h->h_row_ptr[(size_t)i]), j = h->h_col_idx[(size_t)e];
-            scol[(size_t)s] = j;
-            kind[(size_t)s] = (uint8_t)(1 + col_slots[(size_t)j].size());  // rows ascend: the column's order (bp.hpp:278)
-            col_slots[(size_t)j].push_back(s);
-        }
-    for (int j = 0; j < h->n; ++j)
-        for (int s : col_slots[(size_t)j])
-            for (int q = 0; q < dc; ++q)
-                cpos[(size_t)q * slots + s] = (uint16_t)(q < (int)col_slots[(size_t)j].size() ? col_slots[(size_t)j][(size_t)q] : slots);  // beyond the column: +0.0
-    int rc;
-    if ((rc = h->e_partner.ensure(cpos.size() * 2)) || (rc = h->e_kind.ensure((size_t)slots)) || (rc = h->e_scol.ensure((size_t)slots * 4)) ||
-        (rc = h->e_prior.ensure((size_t)slots * 8))) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));  // a previous launch may still read the old tables
-    HIPCHK(hipMemcpy(h->e_partner.p, cpos.data(), cpos.size() * 2, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->e_kind.p, kind.data(), (size_t)slots, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->e_scol.p, scol.data(), (size_t)slots * 4, hipMemcpyHostToDevice));
-    h->edge_rounds = key;
-    return LDPC_HIP_OK;
-}
-
-static int decode_edge8(ldpc_hip_bp *h, const Edge8Plan &p, const EdgeIo &io) {
-    int rc;
-    if ((rc = ensure_edge8_tables(h, p))) return rc;
-    launch_edge_prior(h, p.rounds * 64);
-    Edge8Args a = {};
-    a.prior_s = (const double *)h->e_prior.p; a.cpos = (const uint16_t *)h->e_partner.p;
-    a.prior_u = std::log((1 - h->channel_probs[0]) / h->channel_probs[0]);
-    return launch_edge(h, p.kern, a, a, p.rounds, edge_lds_bytes(p.rounds), p.uniform ? 5 : 4, io);
+// Each mode below is one function: `launch` is its body, written once for the argument blocks of both families, and its last line hands `launch` the
+// family's kernel and the wavefronts per SIMD that kernel was compiled for.
+static int decode_edge(ldpc_hip_bp *h, const EdgePlan &p, const DecodeIo &io) {
+    const auto launch = [&](auto kern) -> int {
+        auto a = kernel_args(kern);
+        int rc;
+        if ((rc = edge_tables(h, p, a))) return rc;
+        launch_edge_prior(h, p.rounds * 64);
+        a.prior_s = (const double *)h->e_prior.p;
+        a.prior_u = std::log((1 - h->channel_probs[0]) / h->channel_probs[0]);  // as upload_priors (bp.hpp:150-151); read by the uniform form only
+        return launch_edge(h, kern, a, p.rounds, edge_lds_bytes(p.rounds), p.uniform ? 5 : 4, io);  // (__launch_bounds__(64, UNIFORM ? 5 : 4))
+    };
+    return p.family == 1 ? launch(p.kern) : launch(p.kern8);
 }
 
 // ---- the same two families with FP32 messages (bp_edge_f32_kernel.h; instantiated in tu_onchip_f32.hip): the float32 message mode's on-chip route ----
@@ -593,64 +646,40 @@ __global__ void edge_prior_f32_kernel(const double *llr0, const int32_t *scol, c
     if (s < slots) out[s] = kind[s] ? (float)llr0[scol[s]] : __builtin_inff();  // one rounding (v_cvt_f32_f64); phantom lanes: +inf
 }
 
-// what decode_edge_f32 and decode_edge8_f32 share: the per-slot priors as floats, then launch_edge
-template <class ARGS>
-static int launch_edge_f32(ldpc_hip_bp *h, void (*kern)(const ARGS), int rounds, int waves_per_simd, ARGS &a, const EdgeIo &io) {
-    if (!kern) return fail(LDPC_HIP_ERR_UNSUPPORTED, "float32 messages: no on-chip kernel was built for %d rounds", rounds);
-    const int slots = rounds * 64;
-    LDPC_LAUNCH(edge_prior_f32_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, h->stream, h->d_llr0, (const int32_t *)h->e_scol.p,
-                       (const uint8_t *)h->e_kind.p, slots, (float *)h->e_prior.p);
-    a.prior_s = (const float *)h->e_prior.p;
-    a.prior_u = (float)std::log((1 - h->channel_probs[0]) / h->channel_probs[0]);  // the FP64 prior of upload_priors, rounded once; read by the uniform form only
-    return launch_edge(h, kern, a, a, rounds, edge_f32_lds_bytes(rounds), waves_per_simd, io);  // (edge_f32_waves / edge8_f32_waves)
-}
-
-static int decode_edge_f32(ldpc_hip_bp *h, const EdgePlan &p, const EdgeIo &io) {
-    int rc;
-    if ((rc = ensure_edge_tables(h, p))) return rc;
-    EdgeF32Args a = {};
-    a.partner = (const uint16_t *)h->e_partner.p;
-    return launch_edge_f32(h, edge_f32_kernel(p.rounds, p.uniform, p.noclamp), p.rounds, edge_f32_waves(p.rounds), a, io);
-}
-
-static int decode_edge8_f32(ldpc_hip_bp *h, const Edge8Plan &p, const EdgeIo &io) {
-    int rc;
-    if ((rc = ensure_edge8_tables(h, p))) return rc;
-    Edge8F32Args a = {};
-    a.cpos = (const uint16_t *)h->e_partner.p;
-    return launch_edge_f32(h, edge8_f32_kernel(p.rounds, p.dc, p.uniform), p.rounds, edge8_f32_waves(p.rounds, p.dc, p.uniform), a, io);
+static int decode_edge_f32(ldpc_hip_bp *h, const EdgePlan &p, const DecodeIo &io) {
+    const auto launch = [&](auto kern, int waves_per_simd) -> int {
+        auto a = kernel_args(kern);
+        int rc;
+        if ((rc = edge_tables(h, p, a))) return rc;
+        if (!kern) return fail(LDPC_HIP_ERR_UNSUPPORTED, "float32 messages: no on-chip kernel was built for %d rounds", p.rounds);
+        const int slots = p.rounds * 64;
+        LDPC_LAUNCH(edge_prior_f32_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, h->stream, h->d_llr0, (const int32_t *)h->e_scol.p,
+                    (const uint8_t *)h->e_kind.p, slots, (float *)h->e_prior.p);
+        a.prior_s = (const float *)h->e_prior.p;
+        a.prior_u = (float)std::log((1 - h->channel_probs[0]) / h->channel_probs[0]);  // the FP64 prior of upload_priors, rounded once; read by the uniform form only
+        return launch_edge(h, kern, a, p.rounds, edge_f32_lds_bytes(p.rounds), waves_per_simd, io);
+    };
+    return p.family == 1 ? launch(edge_f32_kernel(p.rounds, p.uniform, p.noclamp), edge_f32_waves(p.rounds))
+                         : launch(edge8_f32_kernel(p.rounds, p.dc, p.uniform), edge8_f32_waves(p.rounds, p.dc, p.uniform));
 }
 
 // ---- the same two families with row priors (bp_edge_rp_kernel.h; instantiated in tu_onchip_rp.hip): ldpc_hip_*_decode_batch_priors on the codes of plan_edge / plan_edge8 ----
-// Everything but the priors is decode_edge's / decode_edge8's: the shared slot tables, the work split, the grid of the general form (4 wavefronts per
-// SIMD), the timing events.  The priors: h->row_probs [batch][n] -> h->rowp_llr [batch][n] log-ratios, whole batch (row_priors_rowmajor_kernel,
-// io_kernels.h); e_prior is neither written nor read, so the next plain call finds it as its own last launch left it (and rewrites it anyway).
-template <class ARGS>
-static int launch_edge_rp(ldpc_hip_bp *h, void (*kern)(const ARGS), int rounds, ARGS &ra, const EdgeIo &io) {
-    if (!kern) return fail(LDPC_HIP_ERR_UNSUPPORTED, "row priors: no lane = edge kernel was built for %d rounds", rounds);
-    int rc;
-    const size_t items = (size_t)io.batch * (size_t)h->n;
-    if ((rc = h->rowp_llr.ensure(sizeof(double) * items))) return rc;
-    LDPC_LAUNCH(row_priors_rowmajor_kernel, flat_grid(items), dim3(256), 0, h->stream, h->row_probs, (int64_t)items, (double *)h->rowp_llr.p);
-    HIPCHK(hipGetLastError());
-    ra.rowp = (const double *)h->rowp_llr.p;
-    return launch_edge(h, kern, ra, ra.e, rounds, edge_lds_bytes(rounds), 4, io);  // (__launch_bounds__(64, 4): the general form's four wavefronts per SIMD)
-}
-
-static int decode_edge_rp(ldpc_hip_bp *h, const EdgePlan &p, const EdgeIo &io) {
-    int rc;
-    if ((rc = ensure_edge_tables(h, p))) return rc;
-    EdgeRpArgs ra = {};
-    ra.e.partner = (const uint16_t *)h->e_partner.p;
-    return launch_edge_rp(h, edge_rp_kernel(p.rounds), p.rounds, ra, io);
-}
-
-static int decode_edge8_rp(ldpc_hip_bp *h, const Edge8Plan &p, const EdgeIo &io) {
-    int rc;
-    if ((rc = ensure_edge8_tables(h, p))) return rc;
-    Edge8RpArgs ra = {};
-    ra.e.cpos = (const uint16_t *)h->e_partner.p;
-    return launch_edge_rp(h, edge8_rp_kernel(p.rounds, p.dc), p.rounds, ra, io);
+// The priors: h->row_probs [batch][n] -> h->rowp_llr [batch][n] log-ratios, whole batch (row_priors_rowmajor_kernel, io_kernels.h); e_prior is neither
+// written nor read, so the next plain call finds it as its own last launch left it (and rewrites it anyway).
+static int decode_edge_rp(ldpc_hip_bp *h, const EdgePlan &p, const DecodeIo &io) {
+    const auto launch = [&](auto kern) -> int {
+        auto ra = kernel_args(kern);
+        int rc;
+        if ((rc = edge_tables(h, p, ra))) return rc;
+        if (!kern) return fail(LDPC_HIP_ERR_UNSUPPORTED, "row priors: no lane = edge kernel was built for %d rounds", p.rounds);
+        const size_t items = (size_t)io.batch * (size_t)h->n;
+        if ((rc = h->rowp_llr.ensure(sizeof(double) * items))) return rc;
+        LDPC_LAUNCH(row_priors_rowmajor_kernel, flat_grid(items), dim3(256), 0, h->stream, h->row_probs, (int64_t)items, (double *)h->rowp_llr.p);
+        HIPCHK(hipGetLastError());
+        ra.rowp = (const double *)h->rowp_llr.p;
+        return launch_edge(h, kern, ra, p.rounds, edge_lds_bytes(p.rounds), 4, io);  // (__launch_bounds__(64, 4): the general form's four wavefronts per SIMD)
+    };
+    return p.family == 1 ? launch(edge_rp_kernel(p.rounds)) : launch(edge8_rp_kernel(p.rounds, p.dc));
 }
 
 // Row priors on the lane = edge kernels?  Debug switch EDGE_RP: 0 the slot kernel (bp_small_kernel<., ., true>), 1 bp_edge_rp_kernel /
@@ -664,8 +693,7 @@ static bool edge_rp_route(const ldpc_hip_bp *h) {
 }
 
 // ---- the same two families with memory (bp_edge_mem_kernel.h; instantiated in tu_onchip_mem.hip): ldpc_hip_bp_set_memory on the codes of plan_edge / plan_edge8 ----
-// Everything but the priors is decode_edge's / decode_edge8's: the shared slot tables, e_prior (the log-ratios per slot: the initial messages),
-// the work split, the grid of the general form (4 wavefronts per SIMD), the timing events.  The memory: a[] and gamma[] of the handle (mem_ag,
+// e_prior (the log-ratios per slot) holds the initial messages, as in the plain decode.  The memory: a[] and gamma[] of the handle (mem_ag,
 // upload_memory) per slot into e_mem, before every launch as e_prior is -- the priors or the strengths may have changed since the last one.
 __global__ void edge_mem_table_kernel(const double *ag, int n, const int32_t *scol, const uint8_t *kind, int slots, double *out) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
@@ -674,42 +702,29 @@ __global__ void edge_mem_table_kernel(const double *ag, int n, const int32_t *sc
     out[slots + s] = kind[s] ? ag[n + scol[s]] : 0.0;   // ... by strength 0 (bp_edge_mem_kernel.h)
 }
 
-template <class ARGS>
-static int launch_edge_mem(ldpc_hip_bp *h, void (*kern)(const ARGS), int rounds, int waves_per_simd, ARGS &ma, const EdgeIo &io) {
-    if (!kern) return fail(LDPC_HIP_ERR_UNSUPPORTED, "memory min-sum: no lane = edge kernel was built for %d rounds", rounds);
-    int rc;
-    const int slots = rounds * 64;
-    if ((rc = h->e_mem.ensure(sizeof(double) * 2 * (size_t)slots))) return rc;
-    launch_edge_prior(h, slots);
-    LDPC_LAUNCH(edge_mem_table_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, h->stream, (const double *)h->mem_ag.p, h->n, (const int32_t *)h->e_scol.p,
-                (const uint8_t *)h->e_kind.p, slots, (double *)h->e_mem.p);
-    HIPCHK(hipGetLastError());
-    ma.a_s = (const double *)h->e_mem.p;
-    ma.g_s = (const double *)h->e_mem.p + slots;
-    ma.e.prior_s = (const double *)h->e_prior.p;
-    return launch_edge(h, kern, ma, ma.e, rounds, edge_lds_bytes(rounds), waves_per_simd, io);  // (edge_mem_waves / edge8_mem_waves)
-}
-
-static int decode_edge_mem(ldpc_hip_bp *h, const EdgePlan &p, const EdgeIo &io) {
-    int rc;
-    if ((rc = ensure_edge_tables(h, p))) return rc;
-    EdgeMemArgs ma = {};
-    ma.e.partner = (const uint16_t *)h->e_partner.p;
-    return launch_edge_mem(h, edge_mem_kernel(p.rounds), p.rounds, edge_mem_waves(p.rounds), ma, io);
-}
-
-static int decode_edge8_mem(ldpc_hip_bp *h, const Edge8Plan &p, const EdgeIo &io) {
-    int rc;
-    if ((rc = ensure_edge8_tables(h, p))) return rc;
-    Edge8MemArgs ma = {};
-    ma.e.cpos = (const uint16_t *)h->e_partner.p;
-    return launch_edge_mem(h, edge8_mem_kernel(p.rounds, p.dc), p.rounds, edge8_mem_waves(p.rounds, p.dc), ma, io);
+static int decode_edge_mem(ldpc_hip_bp *h, const EdgePlan &p, const DecodeIo &io) {
+    const auto launch = [&](auto kern, int waves_per_simd) -> int {
+        auto ma = kernel_args(kern);
+        int rc;
+        if ((rc = edge_tables(h, p, ma))) return rc;
+        if (!kern) return fail(LDPC_HIP_ERR_UNSUPPORTED, "memory min-sum: no lane = edge kernel was built for %d rounds", p.rounds);
+        const int slots = p.rounds * 64;
+        if ((rc = h->e_mem.ensure(sizeof(double) * 2 * (size_t)slots))) return rc;
+        launch_edge_prior(h, slots);
+        LDPC_LAUNCH(edge_mem_table_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, h->stream, (const double *)h->mem_ag.p, h->n, (const int32_t *)h->e_scol.p,
+                    (const uint8_t *)h->e_kind.p, slots, (double *)h->e_mem.p);
+        HIPCHK(hipGetLastError());
+        ma.a_s = (const double *)h->e_mem.p;
+        ma.g_s = (const double *)h->e_mem.p + slots;
+        ma.e.prior_s = (const double *)h->e_prior.p;
+        return launch_edge(h, kern, ma, p.rounds, edge_lds_bytes(p.rounds), waves_per_simd, io);
+    };
+    return p.family == 1 ? launch(edge_mem_kernel(p.rounds), edge_mem_waves(p.rounds)) : launch(edge8_mem_kernel(p.rounds, p.dc), edge8_mem_waves(p.rounds, p.dc));
 }
 
 // ---- the same two families as Relay-BP (bp_edge_relay_kernel.h; instantiated in tu_onchip_relay.hip): ldpc_hip_bp_set_relay on the codes of plan_edge / plan_edge8 ----
-// Everything is launch_edge_mem's and, through it, launch_edge's -- the shared slot tables, e_prior, the work pools, the grid sizing (by the wavefronts per SIMD the instantiation
-// was compiled for), the clock probe, the timing events -- except that the slot tables of a and gamma are per leg: relay_ag [legs][2][n]
-// (upload_relay) -> e_relay [legs][2][R * 64], before every launch.
+// As the memory decode, except that the slot tables of a and gamma are per leg: relay_ag [legs][2][n] (upload_relay) -> e_relay [legs][2][R * 64],
+// before every launch.
 __global__ void edge_relay_table_kernel(const double *ag, int n, int legs, const int32_t *scol, const uint8_t *kind, int slots, double *out) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= slots) return;
@@ -721,43 +736,42 @@ __global__ void edge_relay_table_kernel(const double *ag, int n, int legs, const
     }
 }
 
-template <class ARGS>
-static int launch_edge_relay(ldpc_hip_bp *h, void (*kern)(const ARGS), int rounds, int waves_per_simd, ARGS &ma, const EdgeIo &io) {
-    if (!kern) return fail(LDPC_HIP_ERR_UNSUPPORTED, "Relay-BP: no lane = edge kernel was built for %d rounds", rounds);
-    int rc;
-    const int slots = rounds * 64;
-    if ((rc = h->e_relay.ensure(sizeof(double) * 2 * (size_t)slots * (size_t)h->relay_legs))) return rc;
-    launch_edge_prior(h, slots);
-    LDPC_LAUNCH(edge_relay_table_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, h->stream, (const double *)h->relay_ag.p, h->n, h->relay_legs,
-                (const int32_t *)h->e_scol.p, (const uint8_t *)h->e_kind.p, slots, (double *)h->e_relay.p);
-    HIPCHK(hipGetLastError());
-    ma.ag_s = (const double *)h->e_relay.p;
-    ma.leg_iters = (const int32_t *)h->relay_it.p;
-    ma.llr0 = h->d_llr0;
-    ma.legs = h->relay_legs; ma.stop_after = h->relay_stop;
-    ma.e.prior_s = (const double *)h->e_prior.p;
-    return launch_edge(h, kern, ma, ma.e, rounds, edge_lds_bytes(rounds), waves_per_simd, io);  // (edge_relay_waves / edge8_relay_waves; e.max_iter is not read: leg_iters takes its place)
+static int decode_edge_relay(ldpc_hip_bp *h, const EdgePlan &p, const DecodeIo &io) {
+    const auto launch = [&](auto kern, int waves_per_simd) -> int {
+        auto ma = kernel_args(kern);
+        int rc;
+        if ((rc = edge_tables(h, p, ma))) return rc;
+        if (!kern) return fail(LDPC_HIP_ERR_UNSUPPORTED, "Relay-BP: no lane = edge kernel was built for %d rounds", p.rounds);
+        const int slots = p.rounds * 64;
+        if ((rc = h->e_relay.ensure(sizeof(double) * 2 * (size_t)slots * (size_t)h->relay_legs))) return rc;
+        launch_edge_prior(h, slots);
+        LDPC_LAUNCH(edge_relay_table_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, h->stream, (const double *)h->relay_ag.p, h->n, h->relay_legs,
+                    (const int32_t *)h->e_scol.p, (const uint8_t *)h->e_kind.p, slots, (double *)h->e_relay.p);
+        HIPCHK(hipGetLastError());
+        ma.ag_s = (const double *)h->e_relay.p;
+        ma.leg_iters = (const int32_t *)h->relay_it.p;
+        ma.llr0 = h->d_llr0;
+        ma.legs = h->relay_legs; ma.stop_after = h->relay_stop;
+        ma.e.prior_s = (const double *)h->e_prior.p;
+        return launch_edge(h, kern, ma, p.rounds, edge_lds_bytes(p.rounds), waves_per_simd, io);  // (e.max_iter is not read: leg_iters takes its place)
+    };
+    return p.family == 1 ? launch(edge_relay_kernel(p.rounds), edge_relay_waves(p.rounds)) : launch(edge8_relay_kernel(p.rounds, p.dc), edge8_relay_waves(p.rounds, p.dc));
 }
 
 // ---- Relay-BP and memory min-sum on the lane = node kernel (bp_wave_relay_kernel.h; instantiated in tu_onchip_wave_relay.hip): the codes beyond both lane = edge ladders ----
-// plan_wave with the posterior copy forced into LDS (it IS the memory), min-sum only, the priors always read from the padded device array: the
-// rungs of pick_wave, the same 16-bit table limits, the same padding rule, the same choice between one wavefront and a team per syndrome (modes 4
-// and 5 force either), capped by the wavefronts the instantiation was compiled for (wave_ms_waves).  waves == 0: not applicable.
-// plan_wave_lds states the rules once, for this kernel and for bp_wave_gd_kernel (plan_wave_gd): the size of a syndrome's private region
-// (`lds_private`) and the bytes left free for the kernel's static LDS (`lds_static`) are all that differ -- the shared tables
-// (wave_relay_lds_shared) and the wavefront caps (wave_ms_waves) are the same.
+// plan_wave's shared rules (the ladder, wave_pad, wave_padding_dominates, wave_team_rule and what follows it) with the posterior copy forced into LDS (it
+// IS the memory), min-sum only, the priors always read from the padded device array, and the wavefronts capped by what the instantiation was compiled for
+// (wave_ms_waves).  waves == 0: not applicable.  One planner for this kernel and for bp_wave_gd_kernel (plan_wave_gd): the size of a syndrome's private
+// region (`lds_private`) and the bytes left free for the kernel's static LDS (`lds_static`) are all that differ between the two.
+// (It stays a planner of its own beside plan_wave: the two share the rules above, but plan_wave chooses its kernel, llr_direct and prior_global, and has
+// other caps and another refusal -- merged, every second line would ask which of the two it serves.)
 static WavePlan plan_wave_lds(const ldpc_hip_bp *h, bool forced, int64_t batch, size_t (*lds_private)(int, int, int), size_t lds_static) {
     WavePlan p;
     if (h->bp_method != LDPC_HIP_MINIMUM_SUM || h->m <= 0 || h->n <= 0 || h->nnz <= 0 || h->max_row_deg > 16 || h->max_col_deg > 8) return p;
-    static const int rungs[6][2] = {{4, 2}, {4, 4}, {6, 3}, {8, 4}, {8, 8}, {16, 8}};  // pick_wave's
-    for (const auto &r : rungs)
-        if (!p.dr && h->max_row_deg <= r[0] && h->max_col_deg <= r[1]) { p.dr = r[0]; p.dc = r[1]; }
-    if (!p.dr) { p.dr = 16; p.dc = 8; }
-    p.mp = (h->m + 63) / 64 * 64;
-    p.np = (h->n + 63) / 64 * 64;
-    const size_t rm = (size_t)p.dr * p.mp;
-    if (rm + 2 >= 65536 || p.np + 1 >= 65536) return p;               // positions and column numbers are 16 bits
-    if (!forced && rm > 2 * (size_t)h->nnz + 1024) return p;          // a few heavy rows would pad every row
+#define LDPC_RUNG(R, C) if (!p.dr && h->max_row_deg <= R && h->max_col_deg <= C) { p.dr = R; p.dc = C; }
+    LDPC_WAVE_LADDER(LDPC_RUNG)
+#undef LDPC_RUNG
+    if (!wave_pad(h, p) || (!forced && wave_padding_dominates(h, p))) return p;
     p.shared = wave_relay_lds_shared(p.mp, p.np, p.dr, p.dc);
     p.per_wave = lds_private(p.mp, p.np, p.dr);
     p.prior_global = true;
@@ -765,25 +779,16 @@ static WavePlan plan_wave_lds(const ldpc_hip_bp *h, bool forced, int64_t batch, 
     if (p.shared + p.per_wave > lds) return p;
     size_t w = (lds - p.shared) / p.per_wave;
     if (w > (size_t)wave_ms_waves(p.dr, p.dc, false)) w = (size_t)wave_ms_waves(p.dr, p.dc, false);
-    const int u = wave_ms_nodes_per_lane(p.dr, 1);  // (plan_wave's rule, min-sum: the row part)
-    const bool team = h->small_mode == 5 || (h->small_mode != 4 && (w < 6 || 2 * p.np > 3 * 64 * u || batch <= 256 * (int64_t)w));
-    if (team) {
-        int tw = (p.np + 64 * u - 1) / (64 * u);
-        if (tw < 2) tw = 2;
-        if (tw > wave_ms_waves(p.dr, p.dc, true)) tw = wave_ms_waves(p.dr, p.dc, true);
+    const int u = wave_ms_nodes_per_lane(p.dr, 1);  // (the row part, as plan_wave)
+    if (wave_team_rule(h, p, w, u, batch)) {
         p.team = true;
-        p.waves = tw;
-        p.groups_per_cu = (int)(lds / (p.shared + p.per_wave));
-        if (p.groups_per_cu >= 2 && p.waves > 8) p.waves = 8;
-        if (p.groups_per_cu * p.waves > 16) p.groups_per_cu = 16 / p.waves;
-        if (p.groups_per_cu < 1) p.groups_per_cu = 1;
+        p.waves = wave_team_width(p, u, wave_ms_waves(p.dr, p.dc, true));
+        wave_team_groups(p, lds);
         return p;
     }
     if (!forced && w < 2) return p;
     p.waves = (int)w;
-    p.groups_per_cu = (int)(lds / (p.shared + (size_t)p.waves * p.per_wave));
-    if (p.groups_per_cu * p.waves > 16) p.groups_per_cu = 16 / p.waves;  // (the kernel's 87 .. 150 VGPRs: 16 wavefronts per compute unit, 12 where compiled for 12)
-    if (p.groups_per_cu < 1) p.groups_per_cu = 1;
+    wave_solo_groups(p, lds, 16);  // (the kernel's 87 .. 150 VGPRs: 16 wavefronts per compute unit, 12 where compiled for 12)
     return p;
 }
 static WavePlan plan_wave_relay(const ldpc_hip_bp *h, bool forced, int64_t batch) {
@@ -804,57 +809,13 @@ __global__ void wave_relay_table_kernel(const double *ag, int n, int np, int leg
     }
 }
 
-// The launch: decode_wave's -- the shared position tables, the padded priors, the static share for a handful of syndromes and work_pool_next beyond,
-// the grid sizing, the clock probe, the timing events on the dispatch.  ag [legs][2][n]: relay_ag, or mem_ag as one leg (leg_iters == nullptr: to
-// h->max_iter).  The OSD hook is left alone: bposd_device lists the unsolved rows itself, as after the lane = edge relay kernels.
-// wave_lds_begin and launch_wave_lds are what decode_wave_relay shares with decode_wave_gd: everything but the kernel's own tables and arguments.
-static bool wave_static_teams(const WavePlan &p, int64_t batch) { return p.team && batch <= 256 * (int64_t)p.groups_per_cu; }
-// before the kernel's own tables are written: the position tables, the work counters
-static int wave_lds_begin(ldpc_hip_bp *h, const WavePlan &p, int64_t batch) {
-    int rc;
-    if ((rc = ensure_wave_tables(h, p))) return rc;
-    if ((rc = h->counter.ensure(counter_bytes()))) return rc;
-    if (!wave_static_teams(p, batch)) HIPCHK(hipMemsetAsync(h->counter.p, 0, work_pool_bytes(), h->stream));
-    return LDPC_HIP_OK;
-}
-// ra: the kernel's argument block with its own fields set, a: the WaveArgs inside it; prior_p: [np + 2] the padded priors
-template <class ARGS>
-static int launch_wave_lds(ldpc_hip_bp *h, const WavePlan &p, void (*kern)(const ARGS), ARGS &ra, WaveArgs &a, const double *prior_p, const uint8_t *synd,
-                           int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv) {
-    const bool static_teams = wave_static_teams(p, batch);
-    a.pool_per = work_pool_share(batch, 0);
-    a.m = h->m; a.n = h->n; a.mp = p.mp; a.np = p.np; a.max_iter = h->max_iter;
-    a.ms_scaling_factor = h->ms_scaling_factor;
-    a.batch = batch;
-    a.rdeg = (const uint8_t *)h->w_rdeg.p; a.cdeg = (const uint8_t *)h->w_cdeg.p;
-    a.col = (const uint16_t *)h->w_col.p; a.apos = (const uint16_t *)h->w_apos.p;
-    a.llr0 = h->d_llr0;
-    a.prior_g = prior_p;
-    a.synd = synd; a.decoding = decoding; a.llr = llr; a.iters = iters; a.conv = conv;
-    a.next = static_teams ? nullptr : (unsigned long long *)h->counter.p;
-    a.clk = h->d_clk;
-    a.lds_shared = (int32_t)p.shared; a.lds_per_wave = (int32_t)p.per_wave;
-    const size_t dyn = p.shared + (size_t)(p.team ? 1 : p.waves) * p.per_wave;
-    if (dyn > 48u * 1024u)
-        HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
-    int64_t groups = p.team ? batch : (batch + p.waves - 1) / p.waves;
-    const int64_t resident = 256 * (int64_t)p.groups_per_cu;
-    if (groups > resident) groups = resident;
-    h->accumulated_ms = 0.f;
-    const bool timed = !(h->untimed_call && static_teams);
-    if (timed) LDPC_LAUNCH_TIMED(kern, dim3((unsigned)groups), dim3((unsigned)(p.waves * 64)), (unsigned)dyn, h->stream, h->ev0, h->ev1, 0, ra);
-    else LDPC_LAUNCH(kern, dim3((unsigned)groups), dim3((unsigned)(p.waves * 64)), (unsigned)dyn, h->stream, ra);
-    h->timed = timed;
-    HIPCHK(hipGetLastError());
-    return LDPC_HIP_OK;
-}
-
-static int decode_wave_relay(ldpc_hip_bp *h, const WavePlan &p, const double *ag, int legs, const int32_t *leg_iters, int stop_after, const uint8_t *synd,
-                             int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv) {
+// ag [legs][2][n]: relay_ag, or mem_ag as one leg (leg_iters == nullptr: to h->max_iter).  No OSD hook: bposd_device lists the unsolved rows itself, as
+// after the lane = edge relay kernels.
+static int decode_wave_relay(ldpc_hip_bp *h, const WavePlan &p, const double *ag, int legs, const int32_t *leg_iters, int stop_after, const DecodeIo &io) {
     const WaveRelayKernel kern = wave_relay_kernel(p.dr, p.dc, p.team);
     if (!kern) return fail(LDPC_HIP_ERR_UNSUPPORTED, "Relay-BP / memory min-sum: no lane = node kernel was built for rows of %d, columns of %d", p.dr, p.dc);
     int rc;
-    if ((rc = wave_lds_begin(h, p, batch))) return rc;
+    if ((rc = ensure_wave_tables(h, p)) || (rc = wave_counters(h, wave_static_teams(p, io.batch)))) return rc;
     // w_relay: [np + 2] the padded priors, then [legs][2][np] the padded tables (its own buffer: it goes when the relay or the memory is switched off)
     if ((rc = h->w_relay.ensure(sizeof(double) * ((size_t)(p.np + 2) + 2 * (size_t)p.np * (size_t)legs)))) return rc;
     double *const prior_p = (double *)h->w_relay.p, *const ag_p = prior_p + p.np + 2;
@@ -863,26 +824,28 @@ static int decode_wave_relay(ldpc_hip_bp *h, const WavePlan &p, const double *ag
     LDPC_LAUNCH(wave_relay_table_kernel, dim3((unsigned)((p.np + 255) / 256)), dim3(256), 0, h->stream, ag, h->n, p.np, legs, ag_p);
     HIPCHK(hipGetLastError());
     WaveRelayArgs ra = {};
+    ra.w.prior_g = prior_p;
     ra.ag_p = ag_p;
     ra.leg_iters = leg_iters;
     ra.legs = legs; ra.stop_after = stop_after;
-    return launch_wave_lds(h, p, kern, ra, ra.w, prior_p, synd, batch, decoding, llr, iters, conv);
+    return launch_wave(h, p, kern, ra, ra.w, io);
 }
 
-// Guided decimation on the lane = node kernel (bp_wave_gd_kernel.h; instantiated in tu_onchip_wave_gd.hip): decode_wave_relay's launch with the
+// Guided decimation on the lane = node kernel (bp_wave_gd_kernel.h; instantiated in tu_onchip_wave_gd.hip): as decode_wave_relay, with the
 // padded priors alone in w_gd (written before every launch: the priors may have changed) and the rounds where the relay has its legs.
-static int decode_wave_gd(ldpc_hip_bp *h, const WavePlan &p, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv) {
+static int decode_wave_gd(ldpc_hip_bp *h, const WavePlan &p, const DecodeIo &io) {
     const WaveGdKernel kern = wave_gd_kernel(p.dr, p.dc, p.team);
     if (!kern) return fail(LDPC_HIP_ERR_UNSUPPORTED, "guided decimation: no lane = node kernel was built for rows of %d, columns of %d", p.dr, p.dc);
     int rc;
-    if ((rc = wave_lds_begin(h, p, batch))) return rc;
+    if ((rc = ensure_wave_tables(h, p)) || (rc = wave_counters(h, wave_static_teams(p, io.batch)))) return rc;
     if ((rc = h->w_gd.ensure(sizeof(double) * (size_t)(p.np + 2)))) return rc;
     LDPC_LAUNCH(wave_prior_pad_kernel, dim3((unsigned)((p.np + 2 + 255) / 256)), dim3(256), 0, h->stream, h->d_llr0, h->n, p.np, (double *)h->w_gd.p);
     HIPCHK(hipGetLastError());
     WaveGdArgs ga = {};
+    ga.w.prior_g = (const double *)h->w_gd.p;
     ga.freeze_llr = h->gd_freeze;
     ga.round_iters = h->gd_round_iters; ga.max_rounds = h->gd_max_rounds;
-    return launch_wave_lds(h, p, kern, ga, ga.w, (const double *)h->w_gd.p, synd, batch, decoding, llr, iters, conv);  // (w.max_iter is not read: the rounds take its place)
+    return launch_wave(h, p, kern, ga, ga.w, io);  // (w.max_iter is not read: the rounds take its place)
 }
 
 // Is the lane = node route what the default modes (-1, 1) take?  By the rule of DESIGN.md section 7d, stated there before the measurement: the
@@ -895,14 +858,14 @@ static constexpr bool k_wave_relay_default = true;
 // and ldpc_hip_bp_relay_route: 0 the per-pass kernels (the relay's leg loop), 1 bp_edge, 2 bp_edge8, 3 / 4 bp_wave_relay with one wavefront / a team
 // per syndrome.  small_mode: 0 everything per pass; 6 stops after the lane = edge families; 4 and 5 force the one-wavefront and the team form, 3 takes
 // the plan's own choice; -1 and 1 take it where k_wave_relay_default says so.
-struct RelayRoute { int route = 0; EdgePlan ep; Edge8Plan e8; WavePlan wp; };
-static RelayRoute plan_relay_route(const ldpc_hip_bp *h, int64_t batch) {
-    RelayRoute r;
-    if (!(h->small_mode != 0 && h->m > 0 && h->n > 0 && h->nnz > 0 && (int64_t)h->nnz * 16 < (1 << 22) && batch < (1ll << 30))) return r;
-    r.ep = plan_edge(h);
-    if (r.ep.rounds) { r.route = 1; return r; }
-    r.e8 = plan_edge8(h);
-    if (r.e8.rounds) { r.route = 2; return r; }
+// (OnchipRoute: this decision's and plan_gd_route's answer -- the route with the plan that goes with it: ep for 1 and 2, wp for 3 and 4.)
+struct OnchipRoute { int route = 0; EdgePlan ep; WavePlan wp; };
+static OnchipRoute plan_relay_route(const ldpc_hip_bp *h, int64_t batch) {
+    OnchipRoute r;
+    if (!(h->small_mode != 0 && onchip_bound(h, batch))) return r;
+    r.ep = plan_edge_family(h);
+    r.route = r.ep.family;
+    if (r.route) return r;
     const bool asked = h->small_mode >= 3 && h->small_mode <= 5;
     if (!asked && !(k_wave_relay_default && (h->small_mode == -1 || h->small_mode == 1))) return r;
     r.wp = plan_wave_relay(h, asked || h->small_mode == 1, batch);
@@ -921,47 +884,28 @@ int ldpc_hip_bp_relay_route(const ldpc_hip_bp *h, int64_t batch, int32_t *route)
 // Relay-BP on chip: plan_edge, plan_edge8, plan_wave_relay in that order (plan_relay_route).  *took = false: the per-pass leg loop (host_stream.h: decode_relay).
 int decode_onchip_relay(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv, bool *took) {
     *took = false;
-    const EdgeIo io = {synd, batch, decoding, llr, iters, conv};
-    const RelayRoute r = plan_relay_route(h, batch);
-    int rc;
-    if (r.route == 1) {
-        *took = true;
-        if ((rc = ensure_edge_tables(h, r.ep))) return rc;
-        EdgeRelayArgs ma = {};
-        ma.e.partner = (const uint16_t *)h->e_partner.p;
-        return launch_edge_relay(h, edge_relay_kernel(r.ep.rounds), r.ep.rounds, edge_relay_waves(r.ep.rounds), ma, io);
-    }
-    if (r.route == 2) {
-        *took = true;
-        if ((rc = ensure_edge8_tables(h, r.e8))) return rc;
-        Edge8RelayArgs ma = {};
-        ma.e.cpos = (const uint16_t *)h->e_partner.p;
-        return launch_edge_relay(h, edge8_relay_kernel(r.e8.rounds, r.e8.dc), r.e8.rounds, edge8_relay_waves(r.e8.rounds, r.e8.dc), ma, io);
-    }
-    if (r.route >= 3) {
-        *took = true;
-        return decode_wave_relay(h, r.wp, (const double *)h->relay_ag.p, h->relay_legs, (const int32_t *)h->relay_it.p, h->relay_stop, synd, batch, decoding, llr, iters, conv);
-    }
+    const DecodeIo io = {synd, batch, decoding, llr, iters, conv};
+    const OnchipRoute r = plan_relay_route(h, batch);
+    *took = r.route != 0;
+    if (r.route == 1 || r.route == 2) return decode_edge_relay(h, r.ep, io);
+    if (r.route >= 3) return decode_wave_relay(h, r.wp, (const double *)h->relay_ag.p, h->relay_legs, (const int32_t *)h->relay_it.p, h->relay_stop, io);
     return LDPC_HIP_OK;
 }
 
 // ---- the same two families with guided decimation (bp_edge_gd_kernel.h; instantiated in tu_onchip_gd.hip): ldpc_hip_bp_set_decimation on the codes of plan_edge / plan_edge8 ----
-// Everything is decode_edge's / decode_edge8's and, through launch_edge, shared with every other variant -- the slot tables, e_prior (L0 per slot: every
-// syndrome's priors, initial messages and frozen slots start from it), the work pools, the grid sizing (by the wavefronts per SIMD the instantiation was
-// compiled for), the clock probe, the timing events.  The kernels read round_iters and max_rounds where the others read max_iter.
-// The route: decode_onchip's predicate for the lane = edge families (modes -1, 1, 6; the work pools' 32-bit syndrome indices) and their two plans, unchanged.
+// e_prior (L0 per slot) is the plain decode's: every syndrome's priors, initial messages and frozen slots start from it.  The kernels read round_iters and
+// max_rounds where the others read max_iter.
+// The route: decode_onchip's small-mode rule for the lane = edge families (modes -1, 1, 6), onchip_bound and plan_edge_family.
 // With ldpc_hip_bp_set_decimation_lane_node on (opt-in, off by default) the order is plan_relay_route's: any mode but 0 asks plan_edge and plan_edge8, mode
 // 6 stops there, and modes -1, 1, 3, 4, 5 go on to plan_wave_gd -- bp_wave_gd_kernel (bp_wave_gd_kernel.h) with one wavefront (3) or a team (4) per
 // syndrome, 4 and 5 forcing either.  A per-pass route is not built.
-struct GdRoute { int route = 0; EdgePlan ep; Edge8Plan e8; WavePlan wp; };
-static GdRoute plan_gd_route(const ldpc_hip_bp *h, int64_t batch) {
-    GdRoute r;
+static OnchipRoute plan_gd_route(const ldpc_hip_bp *h, int64_t batch) {
+    OnchipRoute r;
     if (!(h->gd_lane_node ? h->small_mode != 0 : h->small_mode == -1 || h->small_mode == 1 || h->small_mode == 6)) return r;
-    if (!(h->m > 0 && h->n > 0 && h->nnz > 0 && (int64_t)h->nnz * 16 < (1 << 22) && batch < (1ll << 30))) return r;
-    r.ep = plan_edge(h);
-    if (r.ep.rounds) { r.route = 1; return r; }
-    r.e8 = plan_edge8(h);
-    if (r.e8.rounds) { r.route = 2; return r; }
+    if (!onchip_bound(h, batch)) return r;
+    r.ep = plan_edge_family(h);
+    r.route = r.ep.family;
+    if (r.route) return r;
     if (!h->gd_lane_node || h->small_mode == 6 || h->small_mode == 2) return r;
     r.wp = plan_wave_gd(h, h->small_mode != -1, batch);  // (forced: as plan_relay_route, by modes 1, 3, 4, 5)
     if (r.wp.waves) r.route = r.wp.team ? 4 : 3;
@@ -990,33 +934,26 @@ int ldpc_hip_bp_decimation_route(const ldpc_hip_bp *h, int64_t batch, int32_t *r
     return LDPC_HIP_OK;
 }
 
-template <class ARGS>
-static int launch_edge_gd(ldpc_hip_bp *h, void (*kern)(const ARGS), int rounds, int waves_per_simd, ARGS &ga, const EdgeIo &io) {
-    if (!kern) return fail(LDPC_HIP_ERR_UNSUPPORTED, "guided decimation: no lane = edge kernel was built for %d rounds", rounds);
-    launch_edge_prior(h, rounds * 64);
-    ga.e.prior_s = (const double *)h->e_prior.p;
-    ga.freeze_llr = h->gd_freeze;
-    ga.round_iters = h->gd_round_iters; ga.max_rounds = h->gd_max_rounds;
-    return launch_edge(h, kern, ga, ga.e, rounds, edge_lds_bytes(rounds), waves_per_simd, io);  // (edge_gd_waves / edge8_gd_waves; e.max_iter is not read: the rounds take its place)
+static int decode_edge_gd(ldpc_hip_bp *h, const EdgePlan &p, const DecodeIo &io) {
+    const auto launch = [&](auto kern, int waves_per_simd) -> int {
+        auto ga = kernel_args(kern);
+        int rc;
+        if ((rc = edge_tables(h, p, ga))) return rc;
+        if (!kern) return fail(LDPC_HIP_ERR_UNSUPPORTED, "guided decimation: no lane = edge kernel was built for %d rounds", p.rounds);
+        launch_edge_prior(h, p.rounds * 64);
+        ga.e.prior_s = (const double *)h->e_prior.p;
+        ga.freeze_llr = h->gd_freeze;
+        ga.round_iters = h->gd_round_iters; ga.max_rounds = h->gd_max_rounds;
+        return launch_edge(h, kern, ga, p.rounds, edge_lds_bytes(p.rounds), waves_per_simd, io);  // (e.max_iter is not read: the rounds take its place)
+    };
+    return p.family == 1 ? launch(edge_gd_kernel(p.rounds), edge_gd_waves(p.rounds)) : launch(edge8_gd_kernel(p.rounds, p.dc), edge8_gd_waves(p.rounds, p.dc));
 }
 
 int decode_onchip_gd(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv) {
-    const EdgeIo io = {synd, batch, decoding, llr, iters, conv};
-    const GdRoute r = plan_gd_route(h, batch);
-    int rc;
-    if (r.route == 1) {
-        if ((rc = ensure_edge_tables(h, r.ep))) return rc;
-        EdgeGdArgs ga = {};
-        ga.e.partner = (const uint16_t *)h->e_partner.p;
-        return launch_edge_gd(h, edge_gd_kernel(r.ep.rounds), r.ep.rounds, edge_gd_waves(r.ep.rounds), ga, io);
-    }
-    if (r.route == 2) {
-        if ((rc = ensure_edge8_tables(h, r.e8))) return rc;
-        Edge8GdArgs ga = {};
-        ga.e.cpos = (const uint16_t *)h->e_partner.p;
-        return launch_edge_gd(h, edge8_gd_kernel(r.e8.rounds, r.e8.dc), r.e8.rounds, edge8_gd_waves(r.e8.rounds, r.e8.dc), ga, io);
-    }
-    if (r.route >= 3) return decode_wave_gd(h, r.wp, synd, batch, decoding, llr, iters, conv);
+    const DecodeIo io = {synd, batch, decoding, llr, iters, conv};
+    const OnchipRoute r = plan_gd_route(h, batch);
+    if (r.route == 1 || r.route == 2) return decode_edge_gd(h, r.ep, io);
+    if (r.route >= 3) return decode_wave_gd(h, r.wp, io);
     // (decode_gate has said so for the code and the mode; what is left is the batch)
     if (h->gd_lane_node)
         return fail(LDPC_HIP_ERR_UNSUPPORTED, "guided decimation: no on-chip kernel takes a batch of %lld syndromes of this code (ldpc_hip_bp_decimation_route answers 0); "
@@ -1025,19 +962,17 @@ int decode_onchip_gd(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t
                 "the lane = node route and a per-pass route are not built yet", (long long)batch);
 }
 
-// The float32 message mode's on-chip planner, called by decode_f32 (host_f32.h) after its refusals: decode_onchip's predicate for the lane =
-// edge families and their two plans, unchanged.  *took = false: neither takes the code -- decode_f32 goes on with its per-pass kernels (in
+// The float32 message mode's on-chip planner, called by decode_f32 (host_f32.h) after its refusals: decode_onchip's small-mode rule for the lane =
+// edge families, onchip_bound and plan_edge_family.  *took = false: neither family takes the code -- decode_f32 goes on with its per-pass kernels (in
 // float32 nothing ever goes to bp_wave_kernel, bp_small_kernel or any FP64 kernel).
 int decode_onchip_f32(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv, bool *took) {
     *took = false;
-    const EdgeIo io = {synd, batch, decoding, llr, iters, conv};
     if (!(h->small_mode == -1 || h->small_mode == 1 || h->small_mode == 6)) return LDPC_HIP_OK;
-    if (!(h->m > 0 && h->n > 0 && h->nnz > 0 && (int64_t)h->nnz * 16 < (1 << 22) && batch < (1ll << 30))) return LDPC_HIP_OK;  // (32-bit syndrome indices in the work pools)
-    const EdgePlan ep = plan_edge(h);
-    if (ep.rounds) { *took = true; return decode_edge_f32(h, ep, io); }
-    const Edge8Plan e8 = plan_edge8(h);
-    if (e8.rounds) { *took = true; return decode_edge8_f32(h, e8, io); }
-    return LDPC_HIP_OK;
+    if (!onchip_bound(h, batch)) return LDPC_HIP_OK;
+    const EdgePlan ep = plan_edge_family(h);
+    if (!ep.family) return LDPC_HIP_OK;
+    *took = true;
+    return decode_edge_f32(h, ep, {synd, batch, decoding, llr, iters, conv});
 }
 
 // Which on-chip kernel (if any) takes this batch: called by decode_device (host_stream.h) before it falls back to the streamed tiles.
@@ -1046,44 +981,38 @@ int decode_onchip_f32(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_
 // own priors too (bp_small_kernel<., ., RP>) -- with as many slots as fit -- and to the per-pass kernels (took = false) if not even one slot fits.
 int decode_onchip(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv, bool *took) {
     *took = false;
-    const EdgeIo io = {synd, batch, decoding, llr, iters, conv};
+    const DecodeIo io = {synd, batch, decoding, llr, iters, conv};
     const bool rp = h->row_probs != nullptr;
     if (h->variant == Variant::Memory) {
         // Memory min-sum (ldpc_hip_bp_set_memory), by plan_relay_route: a code that plan_edge or plan_edge8 takes runs on their memory forms, a code
         // plan_wave_relay takes on bp_wave_relay_kernel as ONE relay leg of max_iter iterations that stops at its first solution -- that decode's bits;
         // every other code -- and every code under mode 0 -- goes to the per-pass memory kernels (took = false).  The persistent ring kernel,
         // bp_wave_kernel, the slot kernel and the resident workgroup know nothing of the memory and never see such a decode.
-        const RelayRoute r = plan_relay_route(h, batch);
-        if (r.route == 1) { *took = true; return decode_edge_mem(h, r.ep, io); }
-        if (r.route == 2) { *took = true; return decode_edge8_mem(h, r.e8, io); }
-        if (r.route >= 3) { *took = true; return decode_wave_relay(h, r.wp, (const double *)h->mem_ag.p, 1, nullptr, 1, synd, batch, decoding, llr, iters, conv); }
+        const OnchipRoute r = plan_relay_route(h, batch);
+        *took = r.route != 0;
+        if (r.route == 1 || r.route == 2) return decode_edge_mem(h, r.ep, io);
+        if (r.route >= 3) return decode_wave_relay(h, r.wp, (const double *)h->mem_ag.p, 1, nullptr, 1, io);
         return LDPC_HIP_OK;
     }
-    if (h->small_mode != 0 && h->m > 0 && h->n > 0 && h->nnz > 0 && (int64_t)h->nnz * 16 < (1 << 22) && batch < (1ll << 30)) {  // (32-bit syndrome indices in the work pools)
+    if (h->small_mode != 0 && onchip_bound(h, batch)) {
         // small code: keep the messages on chip.  Bounded degrees: one wavefront per syndrome (bp_wave_kernel).
         // Otherwise the slot kernel -- auto: the most resident syndromes (<= 4) per workgroup that still leave
         // four workgroups per CU (<= 39.5 KiB each); forced: whatever fits in 150 KiB
         if (h->small_mode < 2 || h->small_mode == 6) {  // (mode 6: as -1 wherever the lane = edge variants do not apply) product-sum: one lane per entry keeps the lanes busy with transcendentals
             const WavePsPlan pp = plan_wave_ps(h, h->small_mode == 1, llr != nullptr, batch);
-            if (pp.waves) { *took = true; if (!rp) return decode_wave_ps(h, pp, synd, batch, decoding, llr, iters, conv); }
+            if (pp.waves) { *took = true; if (!rp) return decode_wave_ps(h, pp, io); }
         }
         if (!*took && (h->small_mode == -1 || h->small_mode == 1 || h->small_mode == 6)) {  // min-sum on the surface-code family: lane = edge
-            const EdgePlan ep = plan_edge(h);
-            if (ep.rounds) {
+            const EdgePlan ep = plan_edge_family(h);
+            if (ep.family) {
                 *took = true;
                 if (!rp) return decode_edge(h, ep, io);
                 if (edge_rp_route(h)) return decode_edge_rp(h, ep, io);
             }
-            const Edge8Plan e8 = plan_edge8(h);  // heavier nodes (rows <= 8, columns <= 4): rows in 8-lane groups
-            if (!*took && e8.rounds) {
-                *took = true;
-                if (!rp) return decode_edge8(h, e8, io);
-                if (edge_rp_route(h)) return decode_edge8_rp(h, e8, io);
-            }
         }
         if (!*took && h->small_mode != 2) {
             const WavePlan wp = plan_wave(h, h->small_mode == 1 || (h->small_mode >= 3 && h->small_mode != 6), llr != nullptr, batch);
-            if (wp.waves) { *took = true; if (!rp) return decode_wave(h, wp, synd, batch, decoding, llr, iters, conv); }
+            if (wp.waves) { *took = true; if (!rp) return decode_wave(h, wp, io); }
         }
         int slots = 0;
         // (*took here: row priors, and another on-chip kernel would have taken the code -- whatever fits, as when the slot kernel is forced)
@@ -1122,7 +1051,7 @@ int decode_onchip_resident(ldpc_hip_bp *h, bool want_llr, bool *took) {
     (void)want_llr;
     // (the same predicate as decode_onchip's bp_wave_ps branch: a caller who FORCED another small-code kernel -- modes 3, 4, 5, 2 -- gets that kernel)
     if (h->sw("RESIDENT") == 0 || !h->pin_host || h->schedule != 1 || !(h->small_mode < 2 || h->small_mode == 6) || h->small_mode == 0) return LDPC_HIP_OK;
-    if (h->m <= 0 || h->n <= 0 || h->nnz <= 0 || (int64_t)h->nnz * 16 >= (1 << 22)) return LDPC_HIP_OK;
+    if (!onchip_bound(h, 1)) return LDPC_HIP_OK;
     const WavePsPlan p = plan_wave_ps(h, h->small_mode == 1, true, 1);  // (the posteriors are always formed: one plan whatever the caller asks for)
     if (!p.waves || !p.team) return LDPC_HIP_OK;
     auto &r = h->res;
@@ -1149,15 +1078,13 @@ int decode_onchip_resident(ldpc_hip_bp *h, bool want_llr, bool *took) {
         WavePsArgs a = {};
         a.m = h->m; a.n = h->n; a.np = p.np; a.max_iter = h->max_iter;
         a.batch = 1;
-        a.rdeg = (const uint8_t *)h->wp_rdeg.p; a.col = (const uint16_t *)h->wp_col.p; a.epos = (const uint16_t *)h->wp_epos.p;
+        wave_table_fields(h, p, a);
         a.llr0 = h->d_llr0;
         unsigned char *dv = h->pin_dev;
         a.synd = dv; a.decoding = dv + o_dec; a.llr = (double *)(dv + o_llr); a.iters = (int32_t *)(dv + o_it); a.conv = dv + o_cv;
         a.next = nullptr;
         a.clk = nullptr;
         a.lds_shared = (int32_t)p.shared; a.lds_per_wave = (int32_t)p.per_wave;
-        a.min_rdeg = h->m;
-        for (int i = 0; i < h->m; ++i) a.min_rdeg = std::min(a.min_rdeg, h->h_row_ptr[(size_t)i + 1] - h->h_row_ptr[(size_t)i]);
         a.mail = reinterpret_cast<unsigned *>(h->pin_dev + ldpc_hip_bp::PIN_MAIL);
         a.served0 = __atomic_load_n(mail + 1, __ATOMIC_ACQUIRE);
         const int linger_us = 100;
