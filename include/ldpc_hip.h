@@ -478,12 +478,29 @@ int ldpc_hip_bp_set_math(ldpc_hip_bp *h, int32_t math_mode);
  *       ldpc_hip_bposd_decode_batch[_async] route BP through the FP32 kernels (OSD runs unchanged on the widened posteriors).
  *       Refused with LDPC_HIP_ERR_UNSUPPORTED (ldpc_hip_last_error says why) before anything is staged: product-sum, any serial
  *       schedule, the *_priors entry points, soft-syndrome decoding, and ldpc_hip_bp_multi_decode_batch.
+ *       Small codes stay on chip, one launch per decode: the codes of the two lane = edge families (rows <= 4 / columns <= 2, rows <= 8 /
+ *       columns <= 4) with the messages in registers; with ldpc_hip_bp_set_f32_lane_node on also the codes beyond them (rows <= 16,
+ *       columns <= 8, a syndrome's state within LDS) with the messages in LDS.  Every other code, and every code under small-code kernel
+ *       mode 0 or 2, takes the per-pass kernels: four launches an iteration, the messages in HBM.  All routes give the same bits.
  * The setter returns LDPC_HIP_ERR_INVALID for any other value; the getter returns the current value, or LDPC_HIP_ERR_INVALID for NULL.
+ *   ldpc_hip_bp_set_f32_lane_node(h, on): on = 1 adds the lane = node kernel (bp_wave_f32_kernel.h: a syndrome's FP32 messages in LDS, one
+ *       wavefront or a team -- the workgroup -- per syndrome) to the LDPC_HIP_MSG_F32 routes, for the codes beyond both lane = edge ladders.
+ *       Off (0) by default.  A setting of the handle, independent of the message dtype and read only by float32 decodes.  With it on the
+ *       route follows ldpc_hip_bp_relay_route's order: small-code kernel modes -1, 1 and 6 ask the lane = edge families first, mode 6 stops
+ *       there, modes -1, 1 and 3 take the lane = node kernel's own choice between one wavefront and a team, 4 and 5 force either; modes 0
+ *       and 2 stay per-pass.  LDPC_HIP_ERR_INVALID: NULL handle, or a value other than 0 and 1.
+ *   ldpc_hip_bp_get_f32_lane_node(h, &on): LDPC_HIP_ERR_INVALID for a NULL argument.
+ *   ldpc_hip_bp_f32_route(h, batch, want_llr, &route): which kernels a float32 decode of `batch` syndromes takes on this handle as it is set
+ *       now (whatever its current message dtype), with or without log-ratios -- 0 the per-pass kernels, 1 bp_edge, 2 bp_edge8, 3 bp_wave_f32
+ *       with one wavefront per syndrome, 4 with a team per syndrome.  Launches nothing.  LDPC_HIP_ERR_INVALID: NULL argument or negative batch.
  */
 #define LDPC_HIP_MSG_F64 0
 #define LDPC_HIP_MSG_F32 1
 int ldpc_hip_bp_set_message_dtype(ldpc_hip_bp *h, int32_t dtype);
 int ldpc_hip_bp_get_message_dtype(const ldpc_hip_bp *h);
+int ldpc_hip_bp_set_f32_lane_node(ldpc_hip_bp *h, int32_t on);
+int ldpc_hip_bp_get_f32_lane_node(const ldpc_hip_bp *h, int32_t *on);
+int ldpc_hip_bp_f32_route(const ldpc_hip_bp *h, int64_t batch, int32_t want_llr, int32_t *route);
 
 /*
  * Memory min-sum BP (opt-in; no counterpart in the reference): per-bit memory strengths gamma[n] -- Mem-BP, or with strengths that differ

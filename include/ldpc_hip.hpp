@@ -37,6 +37,8 @@ public:
     double ms_scaling_factor = 1.0;
     int message_dtype = LDPC_HIP_MSG_F64;      // LDPC_HIP_MSG_F32: float32 messages (minimum-sum, parallel schedule, one GPU; ldpc_hip.h:
                                                // ldpc_hip_bp_set_message_dtype) -- results are then not the reference's bits
+    bool float32_lane_node = false;            // float32 decodes of codes beyond the lane = edge ladders stay on chip (bp_wave_f32_kernel; opt-in;
+                                               // ldpc_hip.h: ldpc_hip_bp_set_f32_lane_node) -- read only by float32 decodes
     std::vector<int> serial_schedule_order;    // empty: 0 .. n-1 (bp.hpp:120-124)
     std::vector<double> soft_syndrome;         // after soft_info_decode_serial (bp.hpp:65, 547-660)
     std::vector<uint8_t> decoding;
@@ -255,6 +257,11 @@ private:
             if (last_status != LDPC_HIP_OK) { last_error = ldpc_hip_last_error(); return false; }
             synced_dtype_ = message_dtype;
         }
+        if (float32_lane_node != synced_f32_lane_node_) {
+            last_status = each_([&](ldpc_hip_bp *h) { return ldpc_hip_bp_set_f32_lane_node(h, float32_lane_node ? 1 : 0); });
+            if (last_status != LDPC_HIP_OK) { last_error = ldpc_hip_last_error(); return false; }
+            synced_f32_lane_node_ = float32_lane_node;
+        }
         if ((int)schedule != synced_schedule_ || serial_schedule_order != synced_order_) {
             if (!serial_schedule_order.empty() && (int)serial_schedule_order.size() != bit_count) {
                 fail_(LDPC_HIP_ERR_INVALID, "serial_schedule_order must have n entries");
@@ -283,6 +290,7 @@ private:
     std::vector<double> synced_probs_;
     int synced_schedule_ = (int)PARALLEL;
     int synced_dtype_ = LDPC_HIP_MSG_F64;
+    bool synced_f32_lane_node_ = false;
     std::vector<int> synced_order_;
 };
 

@@ -30,6 +30,7 @@ SYMBOLS = (
     "ldpc_hip_bp_set_relay", "ldpc_hip_bp_get_relay", "ldpc_hip_bp_relay_route",
     "ldpc_hip_bp_set_decimation", "ldpc_hip_bp_get_decimation", "ldpc_hip_bp_decimation_route",
     "ldpc_hip_bp_set_decimation_lane_node", "ldpc_hip_bp_get_decimation_lane_node",
+    "ldpc_hip_bp_set_f32_lane_node", "ldpc_hip_bp_get_f32_lane_node", "ldpc_hip_bp_f32_route",
 )
 
 
@@ -150,6 +151,10 @@ def load():
     if not os.environ.get("LDPC_HIP_LIB") or hasattr(lib, "ldpc_hip_bp_set_decimation_lane_node"):
         lib.ldpc_hip_bp_set_decimation_lane_node.argtypes = [vp, i32]
         lib.ldpc_hip_bp_get_decimation_lane_node.argtypes = [vp, vp]
+    if not os.environ.get("LDPC_HIP_LIB") or hasattr(lib, "ldpc_hip_bp_set_f32_lane_node"):
+        lib.ldpc_hip_bp_set_f32_lane_node.argtypes = [vp, i32]
+        lib.ldpc_hip_bp_get_f32_lane_node.argtypes = [vp, vp]
+        lib.ldpc_hip_bp_f32_route.argtypes = [vp, i64, i32, vp]
     lib.ldpc_hip_bp_set_small_code_kernel.argtypes = [vp, i32]
     lib.ldpc_hip_bp_set_debug_switch.argtypes = [vp, C.c_char_p, i32]
     lib.ldpc_hip_bp_set_handoff.argtypes = [vp, i32]

@@ -30,6 +30,7 @@ cdef extern from "ldpc_hip.hpp" namespace "ldpc_hip":
         BpMethod bp_method
         double ms_scaling_factor
         int message_dtype
+        cbool float32_lane_node
         vector[uint8_t] decoding
         vector[double] log_prob_ratios
         int iterations
@@ -113,6 +114,15 @@ cdef class CyBpCore:
     @message_dtype.setter
     def message_dtype(self, int value):
         self.bpd.message_dtype = value
+
+    @property
+    def float32_lane_node(self):
+        """The lane = node route of the float32 message mode, opt-in (``ldpc_hip_bp_set_f32_lane_node``)."""
+        return self.bpd.float32_lane_node
+
+    @float32_lane_node.setter
+    def float32_lane_node(self, bint value):
+        self.bpd.float32_lane_node = value
 
     @property
     def converge(self):

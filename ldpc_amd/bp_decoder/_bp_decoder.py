@@ -47,6 +47,37 @@ def _bp_method_code(value) -> int:
                     'product_sum', 'minimum_sum'")
 
 
+_WAVE_RUNGS = ((4, 2), (4, 4), (6, 3), (8, 4), (8, 8), (16, 8))  # bp_wave_f32_kernel's instantiations (rows, columns): LDPC_WAVE_LADDER
+_WAVE_F32_LDS_STATIC = 64  # ldpc_amd/csrc/bp_wave_f32_kernel.h: what plan_wave_f32 leaves free of a workgroup's 160 KiB for the kernel's static LDS
+
+
+def float32_lane_node_takes(pcm, forced=False) -> bool:
+    """Whether the lane = node float32 kernel (``BpDecoder.float32_lane_node``) takes the code -- the refusals of plan_wave_f32
+    (ldpc_amd/csrc/host_onchip.h) restated without a GPU: rows of at most 16 entries and columns of at most 8; 16-bit positions and column
+    numbers; padding every row to the rung's weight costs at most twice the entries plus 1024 (the default small-code kernel mode only:
+    ``forced=True`` -- modes 1, 3, 4, 5 -- waives it); the shared tables and one syndrome's private region in its smaller form (FP32
+    messages, the hard-decision words, the syndrome bytes; the log-ratios stored straight to memory) within 160 KiB - 64 of LDS.  It says
+    nothing about the lane = edge families, which modes -1, 1 and 6 ask first."""
+    h = scipy.sparse.csr_matrix(pcm)
+    m, n = h.shape
+    if m <= 0 or n <= 0 or h.nnz <= 0 or h.nnz * 16 >= (1 << 22):
+        return False
+    rows = int(np.diff(h.indptr).max())
+    cmax = int(np.bincount(h.indices, minlength=n).max())
+    rung = next(((r, c) for r, c in _WAVE_RUNGS if rows <= r and cmax <= c), None)
+    if rung is None:
+        return False
+    dr, dc = rung
+    mp, np_ = (m + 63) // 64 * 64, (n + 63) // 64 * 64
+    rm = dr * mp
+    if rm + 2 >= 65536 or np_ + 1 >= 65536 or (not forced and rm > 2 * h.nnz + 1024):
+        return False
+    up16 = lambda b: (b + 15) & ~15  # noqa: E731
+    shared = up16(rm * 2 + dc * np_ * 2 + mp)
+    private = up16((rm + 2) * 4 + (np_ // 64 + 1) * 8 + mp)
+    return shared + private <= 160 * 1024 - _WAVE_F32_LDS_STATIC
+
+
 def _check_pcm_type(pcm, spaces=12):
     if not isinstance(pcm, (np.ndarray, scipy.sparse.spmatrix)):  # pyx:17-21, 113-117
         # (the reference's message carries the indentation of its source line across a backslash continuation: 12 spaces in
@@ -149,6 +180,8 @@ class BpDecoderBase:
         self._engine_relay = None       # ... what the engine's handle is set to
         self._decimation = None         # decimation: None (off) or (round_iters, max_rounds, freeze_llr)
         self._engine_decimation = None  # ... what the engine's handle is set to
+        self._float32_lane_node = False            # float32_lane_node: the lane = node route of the float32 message mode, opt-in
+        self._engine_float32_lane_node = False     # ... what the engine's handle is set to
         self._decimation_lane_node = False         # decimation_lane_node: the lane = node route of guided decimation, opt-in
         self._engine_decimation_lane_node = False  # ... what the engine's handle is set to
 
@@ -410,6 +443,30 @@ class BpDecoderBase:
             raise ValueError(f"message_dtype must be 'float64', 'float32', np.float64 or np.float32, not {value!r}.")
         self._message_dtype = key
 
+    @property
+    def float32_lane_node(self) -> bool:
+        """``False`` (default): with ``message_dtype='float32'`` only the codes of the two lane = edge kernel families are decoded on chip;
+        every other code takes the per-pass kernels (four launches an iteration, the messages in HBM).  ``True``: a code beyond them -- rows
+        of at most 16, columns of at most 8 entries, a syndrome's state within LDS (``ldpc_amd.bp_decoder.float32_lane_node_takes``) -- is
+        decoded on chip by the lane = node kernel (``ldpc_hip_bp_set_f32_lane_node``).  The results are the same bits either way.  Setting it
+        requires no particular ``message_dtype``; it is read only by float32 decodes."""
+        return self._float32_lane_node
+
+    @float32_lane_node.setter
+    def float32_lane_node(self, value) -> None:
+        if not isinstance(value, (bool, np.bool_)):
+            raise ValueError(f"float32_lane_node must be a bool, not {value!r}.")
+        self._float32_lane_node = bool(value)
+
+    @property
+    def float32_route(self) -> str:
+        """Which kernels a ``message_dtype='float32'`` decode takes on this decoder as it is set now, for a batch of the size last decoded
+        (1 before any): ``HipBpEngine.f32_route`` -- ``"per_pass"``, ``"bp_edge"``, ``"bp_edge8"``, and with ``float32_lane_node`` also
+        ``"bp_wave"`` / ``"bp_wave_team"`` (one wavefront / a team per syndrome).  It answers whatever ``message_dtype`` is."""
+        if self._device_ids is not None:
+            raise NotImplementedError("float32_route with device_ids=[...]: float32 messages are decoded on one GPU only.")
+        return self._get_engine().f32_route(getattr(self, "_last_batch", 1))
+
     # ---- memory min-sum BP (additive; not a constructor keyword either) ----------------------------------------
     @property
     def memory_strength(self):
@@ -619,6 +676,10 @@ class BpDecoderBase:
         if self._message_dtype != self._engine_dtype:
             self._engine.set_message_dtype(self._message_dtype)
             self._engine_dtype = self._message_dtype
+        # (read only by float32 decodes -- which several GPUs refuse: _require_modes -- so it is pushed to a single engine only)
+        if self._device_ids is None and self._float32_lane_node != self._engine_float32_lane_node:
+            self._engine.set_f32_lane_node(self._float32_lane_node)
+            self._engine_float32_lane_node = self._float32_lane_node
         # memory min-sum, Relay-BP, guided decimation: the handle holds at most one -- first off what it holds that is no longer wanted, then on what is
         variants = (("_memory", "_engine_memory", "set_memory"), ("_relay", "_engine_relay", "set_relay"), ("_decimation", "_engine_decimation", "set_decimation"))
         stale = [v for v in variants if not _same_setting(getattr(self, v[0]), getattr(self, v[1]))]
@@ -665,12 +726,14 @@ class BpDecoderBase:
         self._cy.bp_method = self._bp_method
         self._cy.ms_scaling_factor = self._ms_scaling_factor
         self._cy.message_dtype = 1 if self._message_dtype == "float32" else 0
+        self._cy.float32_lane_node = self._float32_lane_node
         return self._cy
 
     def _decode_numpy(self, synd2d, want_llr=True, osd0=False, llr_out=None, channel_probs=None):
         """(B, m) uint8 NumPy -> (decoding, llr, iterations, converge) through the active backend.  ``llr_out``: a (B, n) float64
         C-contiguous array to receive the log-ratios instead of a new one.  ``channel_probs``: checked (B, n) row priors or None."""
         # (the schedule setters and the memory strengths live on the ctypes engine)
+        self._last_batch = max(1, len(synd2d))  # (float32_route)
         cy = self._get_cy() if self._schedule == PARALLEL and self._memory is None and self._relay is None and self._decimation is None else None
         if cy is None:
             self._relay_batch = max(1, len(synd2d))  # (relay_route)

@@ -43,6 +43,7 @@
 //   bp_serial_kernels.h  bp_serial_kernel, bp_softinfo_kernel   serial schedule, soft-syndrome serial min-sum
 //   bp_f32_kernels.h     bp_f32_*_kernel                    float32 message mode: min-sum, parallel schedule, one launch per pass (host_f32.h)
 //   bp_edge_f32_kernel.h bp_edge_f32_kernel, bp_edge8_f32_kernel   float32 message mode on the lane = edge families: messages in registers (tu_onchip_f32.hip)
+//   bp_wave_f32_kernel.h bp_wave_f32_kernel                        float32 message mode beyond the lane = edge families, opt-in: lane = node, messages in LDS (tu_onchip_wave_f32.hip)
 //   bp_edge_rp_kernel.h  bp_edge_rp_kernel, bp_edge8_rp_kernel     row priors on the lane = edge families: every syndrome its own priors (tu_onchip_rp.hip)
 //   bp_edge_mem_kernel.h bp_edge_mem_kernel, bp_edge8_mem_kernel   memory min-sum on the lane = edge families: per-bit memory strengths (tu_onchip_mem.hip)
 //   bp_edge_relay_kernel.h bp_edge_relay_kernel, bp_edge8_relay_kernel   Relay-BP on the lane = edge families: chained memory legs in one launch (tu_onchip_relay.hip)

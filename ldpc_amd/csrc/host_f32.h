@@ -211,10 +211,10 @@ static int decode_f32_repacked(ldpc_hip_bp *h, const uint8_t *synd, int64_t batc
 int decode_f32(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv) {
     int rc;
     if ((rc = decode_gate(h, h->row_probs ? "per-row channel probabilities are" : nullptr, false))) return rc;  // (the entry points have said so already)
-    // Small codes of the lane = edge families stay on chip (host_onchip.h: decode_onchip_f32 -- one launch, messages in registers).  Off:
-    // small_mode 0 (never an on-chip kernel), the switch F32_ONCHIP 0, and any switch that names the per-pass kernels below (F32_NT,
-    // F32_GRID_ROWS, SPREAD_NODES: who sets one wants those kernels, on whatever code).
-    if (h->small_mode != 0 && h->sw("F32_ONCHIP") != 0 && h->sw("F32_NT") < 0 && h->sw("F32_GRID_ROWS") <= 0 && h->sw("SPREAD_NODES") <= 0) {
+    // Small codes stay on chip where plan_f32_route (host_onchip.h) says so -- one launch, messages in registers (the lane = edge families) or, with
+    // ldpc_hip_bp_set_f32_lane_node on, in LDS (the lane = node kernel).  Its answer is 0 under small_mode 0 and 2, the switch F32_ONCHIP 0, and any
+    // switch that names the per-pass kernels below (F32_NT, F32_GRID_ROWS, SPREAD_NODES).
+    {
         bool took = false;
         rc = decode_onchip_f32(h, synd, batch, decoding, llr, iters, conv, &took);
         if (took || rc) return rc;

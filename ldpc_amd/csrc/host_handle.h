@@ -1,5 +1,5 @@
 // host_handle.h -- the handle (struct ldpc_hip_bp), error reporting, device buffers, measurement switches
-// Part of libldpc_hip.so: included by every translation unit (bp_hip.hip = the C ABI; tu_stream / tu_serial / tu_onchip / tu_onchip_f32 / tu_onchip_rp / tu_onchip_mem / tu_onchip_relay / tu_onchip_wave_relay / tu_onchip_gd / tu_onchip_wave_gd / tu_osd / tu_f32.hip = one kernel
+// Part of libldpc_hip.so: included by every translation unit (bp_hip.hip = the C ABI; tu_stream / tu_serial / tu_onchip / tu_onchip_f32 / tu_onchip_rp / tu_onchip_mem / tu_onchip_relay / tu_onchip_wave_relay / tu_onchip_gd / tu_onchip_wave_gd / tu_onchip_wave_f32 / tu_osd / tu_f32.hip = one kernel
 // family each with its host side).  What one unit calls in another is declared at the end of this header.
 #pragma once
 
@@ -153,7 +153,7 @@ struct DeviceBuf {  // grow-only device allocation, freed with its owner (on the
 // creation, from the environment variables LDPC_HIP_<NAME>, changed afterwards only through ldpc_hip_bp_set_debug_switch -- no
 // getenv on the decode path, and nothing a test can change under a live handle by accident.
 static const char *const k_switch_names[] = {"PS_TEAM", "EXPLICIT_INIT", "OSD_UNBLOCKED", "OSD_PLANES",
-                                             "PS_TEAM_WAVES", "EDGE_STATIC_PCT", "EDGE_CHUNK", "NO_HOST_PIPELINE", "NO_DIRECT_LLR", "HOST_CHUNK_ROWS", "TIME_SMALL_CALLS", "REL_LDS", "HOST_PIPE_TIMING", "REL_LEVELS", "REL_PROF", "REL_SCRATCH_IN_L", "SER_RING", "SER_WAVES", "SER_LANE_MAX", "SER_LANE_THREADS", "SER_WAVES2", "RESIDENT", "SER_NO_REMAINDER", "SER_ROUND_TILES", "VAR_RING", "VAR_RING_UNITS", "SPREAD_NODES", "SER_VAR", "SER_VAR_UNITS", "REL_EXT", "OSD_COLLECT_AFTER", "EDGE_CLAMP", "OSD_NO_FLAT", "F32_NT", "F32_GRID_ROWS", "F32_ONCHIP", "F32_REPACK_MIN_TILES", "EDGE_RP", "SPREAD_NT", "REPACK_MIN_TILES", "DEM_GRID"};
+                                             "PS_TEAM_WAVES", "EDGE_STATIC_PCT", "EDGE_CHUNK", "NO_HOST_PIPELINE", "NO_DIRECT_LLR", "HOST_CHUNK_ROWS", "TIME_SMALL_CALLS", "REL_LDS", "HOST_PIPE_TIMING", "REL_LEVELS", "REL_PROF", "REL_SCRATCH_IN_L", "SER_RING", "SER_WAVES", "SER_LANE_MAX", "SER_LANE_THREADS", "SER_WAVES2", "RESIDENT", "SER_NO_REMAINDER", "SER_ROUND_TILES", "VAR_RING", "VAR_RING_UNITS", "SPREAD_NODES", "SER_VAR", "SER_VAR_UNITS", "REL_EXT", "OSD_COLLECT_AFTER", "EDGE_CLAMP", "OSD_NO_FLAT", "F32_NT", "F32_GRID_ROWS", "F32_ONCHIP", "F32_REPACK_MIN_TILES", "EDGE_RP", "SPREAD_NT", "REPACK_MIN_TILES", "DEM_GRID", "F32_WAVE_LLR"};
 constexpr int k_n_switches = (int)(sizeof(k_switch_names) / sizeof(k_switch_names[0]));
 
 struct ldpc_hip_bp {
@@ -173,6 +173,8 @@ struct ldpc_hip_bp {
     int32_t math_mode = LDPC_HIP_MATH_LIBM_EXACT;
     int32_t msg_dtype = LDPC_HIP_MSG_F64;  // ldpc_hip_bp_set_message_dtype: LDPC_HIP_MSG_F32 routes decode_device to decode_f32 (tu_f32.hip)
     DeviceBuf f32_llr0;      // ... [n] the priors rounded to FP32
+    bool f32_lane_node = false;  // ldpc_hip_bp_set_f32_lane_node: float32 decodes of codes beyond both lane = edge ladders go to bp_wave_f32_kernel (opt-in; a handle setting like small_mode, read only by float32 decodes)
+    DeviceBuf w_prior_f32;   // bp_wave_f32_kernel: [np + 2] the padded priors as floats (before every launch; released when the route is switched off)
     bool regular = false;   // every row has the same weight and every column has the same weight
     int32_t ring_depth = 2; // LDS-DMA ring slots per wavefront for regular matrices (0 = register variant)
     int32_t small_mode = -1; // on-chip kernels for small codes: -1 auto, 0 never, 1 whenever one fits, 2 the slot kernel only
@@ -649,8 +651,9 @@ int soft_info_device(ldpc_hip_bp *h, const double *soft, int64_t batch, double c
                      int32_t *iters, uint8_t *conv, double *soft_out);
 // tu_f32.hip: the float32 message mode (min-sum, parallel schedule)
 int decode_f32(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv);
-// tu_onchip.hip: the float32 mode's on-chip route (bp_edge_f32_kernel, bp_edge8_f32_kernel, instantiated in tu_onchip_f32.hip) for the codes
-// plan_edge / plan_edge8 take; *took = false: neither does (decode_f32 then runs its per-pass kernels)
+// tu_onchip.hip: the float32 mode's on-chip routes (plan_f32_route) -- bp_edge_f32_kernel, bp_edge8_f32_kernel (instantiated in tu_onchip_f32.hip) for the
+// codes plan_edge / plan_edge8 take, with f32_lane_node bp_wave_f32_kernel (tu_onchip_wave_f32.hip) for those plan_wave_f32 takes; *took = false: none
+// does (decode_f32 then runs its per-pass kernels)
 int decode_onchip_f32(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv, bool *took);
 // bp_hip.hip (host_decode_abi.h): the body of ldpc_hip_bp_decode_b8 on device pointers -- unpack, decode, zero-shot shortcut, observables / packed
 // decodings -- queued on h->stream without waiting (ldpc_hip_bp_simulate_b8 runs it per chunk)

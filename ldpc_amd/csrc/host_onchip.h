@@ -1,4 +1,4 @@
-// host_onchip.h -- host side of the on-chip kernels: plans (LDS / occupancy), tables and launches of bp_small / bp_wave / bp_wave_ps / bp_edge / bp_wave_relay / bp_wave_gd
+// host_onchip.h -- host side of the on-chip kernels: plans (LDS / occupancy), tables and launches of bp_small / bp_wave / bp_wave_ps / bp_edge / bp_wave_relay / bp_wave_gd / bp_wave_f32
 // Part of libldpc_hip.so: included by bp_hip.hip (one translation unit), in the order given there.
 #pragma once
 
@@ -85,7 +85,7 @@ struct WavePlan {
 };
 
 // The rungs (rows <=, columns <=) of the lane = node and lane = entry kernels, ascending: a code takes the first that holds it.  The first four are
-// bp_wave_ps_kernel's too (pick_wave_ps, which goes on with rungs of its own); all six are bp_wave_kernel's, bp_wave_relay_kernel's and bp_wave_gd_kernel's.
+// bp_wave_ps_kernel's too (pick_wave_ps, which goes on with rungs of its own); all six are bp_wave_kernel's, bp_wave_relay_kernel's, bp_wave_gd_kernel's and bp_wave_f32_kernel's.
 #define LDPC_WAVE_LADDER4(X) X(4, 2) X(4, 4) X(6, 3) X(8, 4)
 #define LDPC_WAVE_LADDER(X) LDPC_WAVE_LADDER4(X) X(8, 8) X(16, 8)
 
@@ -134,6 +134,14 @@ static void wave_solo_groups(WavePlan &p, size_t lds, int cap) {
     if (p.groups_per_cu < 1) p.groups_per_cu = 1;
 }
 
+// The LDS copy of the log-ratios is a convenience (the store of every iteration stays on chip); where it costs a resident wavefront and few are
+// resident, every bit pass stores them straight to HBM instead.  copy / lean: a syndrome's private bytes with and without the copy.
+static bool wave_llr_direct_rule(size_t lds, size_t shared, size_t copy, size_t lean) {
+    const size_t w_copy = shared + copy > lds ? 0 : (lds - shared) / copy;
+    const size_t w_lean = shared + lean > lds ? 0 : (lds - shared) / lean;
+    return w_copy < 4 && w_lean > w_copy;
+}
+
 static WavePlan plan_wave(const ldpc_hip_bp *h, bool forced, bool want_llr, int64_t batch) {
     WavePlan p;
     if (h->m <= 0 || h->n <= 0 || h->nnz <= 0 || h->max_row_deg > 16 || h->max_col_deg > 8) return p;
@@ -146,12 +154,8 @@ static WavePlan plan_wave(const ldpc_hip_bp *h, bool forced, bool want_llr, int6
     // small codes fit several such workgroups
     const size_t lds = 160u * 1024u - 64u;  // (the kernels' few bytes of static LDS come on top of the dynamic part)
     if (want_llr) {
-        // the LDS copy of the log-ratios is a convenience (the store of every iteration stays on chip); where it costs a
-        // resident wavefront and few are resident, every bit pass stores them straight to HBM instead
         const size_t lean = wave_lds_private(p.mp, p.np, p.dr, false);
-        const size_t w_copy = p.shared + p.per_wave > lds ? 0 : (lds - p.shared) / p.per_wave;
-        const size_t w_lean = p.shared + lean > lds ? 0 : (lds - p.shared) / lean;
-        if (w_copy < 4 && w_lean > w_copy) { p.per_wave = lean; p.llr_direct = true; }
+        if (wave_llr_direct_rule(lds, p.shared, p.per_wave, lean)) { p.per_wave = lean; p.llr_direct = true; }
     }
     if (p.shared + p.per_wave > lds) return p;
     size_t w = (lds - p.shared) / p.per_wave;
@@ -309,8 +313,8 @@ static int ensure_wave_ps_tables(ldpc_hip_bp *h, const WavePsPlan &p) {
     return LDPC_HIP_OK;
 }
 
-// ---- what the launches of the lane = node and lane = entry kernels share (bp_wave_kernel, bp_wave_ps_kernel, bp_wave_relay_kernel, bp_wave_gd_kernel) ----
-// PLAN: WavePlan or WavePsPlan (team, waves, groups_per_cu, shared, per_wave, np); ARGS: WaveArgs or WavePsArgs, where their field names agree.
+// ---- what the launches of the lane = node and lane = entry kernels share (bp_wave_kernel, bp_wave_ps_kernel, bp_wave_relay_kernel, bp_wave_gd_kernel, bp_wave_f32_kernel) ----
+// PLAN: WavePlan or WavePsPlan (team, waves, groups_per_cu, shared, per_wave, np); ARGS: WaveArgs, WavePsArgs or WaveF32Args, where their field names agree.
 
 // a team per syndrome and no more syndromes than resident teams -- e.g. ONE decode(): static assignment, no work counter to reset
 template <class PLAN>
@@ -340,6 +344,12 @@ static void wave_table_fields(const ldpc_hip_bp *h, const WavePlan &p, WaveArgs 
     a.mp = p.mp;
     a.ms_scaling_factor = h->ms_scaling_factor;
     a.rdeg = (const uint8_t *)h->w_rdeg.p; a.cdeg = (const uint8_t *)h->w_cdeg.p;
+    a.col = (const uint16_t *)h->w_col.p; a.apos = (const uint16_t *)h->w_apos.p;
+}
+static void wave_table_fields(const ldpc_hip_bp *h, const WavePlan &p, WaveF32Args &a) {
+    a.mp = p.mp;
+    a.ms_scaling_factor = h->ms_scaling_factor;
+    a.rdeg = (const uint8_t *)h->w_rdeg.p;
     a.col = (const uint16_t *)h->w_col.p; a.apos = (const uint16_t *)h->w_apos.p;
 }
 static void wave_table_fields(const ldpc_hip_bp *h, const WavePsPlan &, WavePsArgs &a) {
@@ -759,44 +769,71 @@ static int decode_edge_relay(ldpc_hip_bp *h, const EdgePlan &p, const DecodeIo &
 }
 
 // ---- Relay-BP and memory min-sum on the lane = node kernel (bp_wave_relay_kernel.h; instantiated in tu_onchip_wave_relay.hip): the codes beyond both lane = edge ladders ----
-// plan_wave's shared rules (the ladder, wave_pad, wave_padding_dominates, wave_team_rule and what follows it) with the posterior copy forced into LDS (it
-// IS the memory), min-sum only, the priors always read from the padded device array, and the wavefronts capped by what the instantiation was compiled for
-// (wave_ms_waves).  waves == 0: not applicable.  One planner for this kernel and for bp_wave_gd_kernel (plan_wave_gd): the size of a syndrome's private
-// region (`lds_private`) and the bytes left free for the kernel's static LDS (`lds_static`) are all that differ between the two.
-// (It stays a planner of its own beside plan_wave: the two share the rules above, but plan_wave chooses its kernel, llr_direct and prior_global, and has
+// plan_wave's shared rules (the ladder, wave_pad, wave_padding_dominates, wave_team_rule and what follows it), min-sum only, the priors always read from
+// the padded device array, and the wavefronts capped by what the instantiation was compiled for.  waves == 0: not applicable.  One planner for this
+// kernel, for bp_wave_gd_kernel (plan_wave_gd) and for bp_wave_f32_kernel (plan_wave_f32): what differs between them is said in a WaveLdsKernel --
+// the LDS sizes, the wavefronts its instantiations are compiled for, the wavefronts per compute
+// unit its registers allow -- and, where the kernel has the two forms of bp_wave_kernel's log-ratios, the size without the LDS copy.
+// (It stays a planner of its own beside plan_wave: the two share the rules above, but plan_wave chooses its kernel and prior_global, and has
 // other caps and another refusal -- merged, every second line would ask which of the two it serves.)
-static WavePlan plan_wave_lds(const ldpc_hip_bp *h, bool forced, int64_t batch, size_t (*lds_private)(int, int, int), size_t lds_static) {
+struct WaveLdsKernel {
+    size_t (*lds_shared)(int mp, int np, int dr, int dc);
+    size_t (*lds_private)(int mp, int np, int dr);       // a syndrome's private region (with the posteriors in LDS where the kernel keeps them there)
+    size_t (*lds_private_lean)(int mp, int np, int dr);  // ... without the copy of the posteriors: the llr_direct form; nullptr: the kernel has none
+    int (*waves)(int dr, int dc, bool team);             // wave_ms_waves / wave_f32_waves
+    int solo_cap;                                        // wavefronts per compute unit, one syndrome each
+};
+// llr_form (kernels with a lean form only): -1 wave_llr_direct_rule decides, 0 the LDS copy, 1 llr_direct.  lds_static: the bytes left free for the
+// kernel's static LDS -- WAVE_RELAY_LDS_STATIC / WAVE_GD_LDS_STATIC / WAVE_F32_LDS_STATIC, which each kernel asserts it keeps to.
+static WavePlan plan_wave_lds(const ldpc_hip_bp *h, bool forced, int64_t batch, const WaveLdsKernel &k, int llr_form, size_t lds_static) {
     WavePlan p;
     if (h->bp_method != LDPC_HIP_MINIMUM_SUM || h->m <= 0 || h->n <= 0 || h->nnz <= 0 || h->max_row_deg > 16 || h->max_col_deg > 8) return p;
 #define LDPC_RUNG(R, C) if (!p.dr && h->max_row_deg <= R && h->max_col_deg <= C) { p.dr = R; p.dc = C; }
     LDPC_WAVE_LADDER(LDPC_RUNG)
 #undef LDPC_RUNG
     if (!wave_pad(h, p) || (!forced && wave_padding_dominates(h, p))) return p;
-    p.shared = wave_relay_lds_shared(p.mp, p.np, p.dr, p.dc);
-    p.per_wave = lds_private(p.mp, p.np, p.dr);
+    p.shared = k.lds_shared(p.mp, p.np, p.dr, p.dc);
+    p.per_wave = k.lds_private(p.mp, p.np, p.dr);
     p.prior_global = true;
-    const size_t lds = 160u * 1024u - lds_static;  // (the kernel's static LDS comes on top of the dynamic part: WAVE_RELAY_LDS_STATIC / WAVE_GD_LDS_STATIC, which each kernel asserts it keeps to)
+    const size_t lds = 160u * 1024u - lds_static;  // (the kernel's static LDS comes on top of the dynamic part)
+    if (k.lds_private_lean) {
+        const size_t lean = k.lds_private_lean(p.mp, p.np, p.dr);
+        if (llr_form < 0 ? wave_llr_direct_rule(lds, p.shared, p.per_wave, lean) : llr_form != 0) { p.per_wave = lean; p.llr_direct = true; }
+    }
     if (p.shared + p.per_wave > lds) return p;
     size_t w = (lds - p.shared) / p.per_wave;
-    if (w > (size_t)wave_ms_waves(p.dr, p.dc, false)) w = (size_t)wave_ms_waves(p.dr, p.dc, false);
+    if (w > (size_t)k.waves(p.dr, p.dc, false)) w = (size_t)k.waves(p.dr, p.dc, false);
     const int u = wave_ms_nodes_per_lane(p.dr, 1);  // (the row part, as plan_wave)
     if (wave_team_rule(h, p, w, u, batch)) {
         p.team = true;
-        p.waves = wave_team_width(p, u, wave_ms_waves(p.dr, p.dc, true));
+        p.waves = wave_team_width(p, u, k.waves(p.dr, p.dc, true));
         wave_team_groups(p, lds);
         return p;
     }
     if (!forced && w < 2) return p;
     p.waves = (int)w;
-    wave_solo_groups(p, lds, 16);  // (the kernel's 87 .. 150 VGPRs: 16 wavefronts per compute unit, 12 where compiled for 12)
+    wave_solo_groups(p, lds, k.solo_cap);
     return p;
 }
+// (solo_cap 16: the kernels' 87 .. 150 VGPRs allow 16 wavefronts per compute unit, 12 where compiled for 12)
 static WavePlan plan_wave_relay(const ldpc_hip_bp *h, bool forced, int64_t batch) {
-    return plan_wave_lds(h, forced, batch, [](int mp, int np, int dr) { return wave_relay_lds_private(mp, np, dr); }, WAVE_RELAY_LDS_STATIC);
+    static const WaveLdsKernel k = {wave_relay_lds_shared, [](int mp, int np, int dr) { return wave_relay_lds_private(mp, np, dr); }, nullptr, wave_ms_waves, 16};
+    return plan_wave_lds(h, forced, batch, k, -1, WAVE_RELAY_LDS_STATIC);
 }
 // Guided decimation on bp_wave_gd_kernel (bp_wave_gd_kernel.h): the shared tables are the relay kernel's, the private region carries the two masks
 static WavePlan plan_wave_gd(const ldpc_hip_bp *h, bool forced, int64_t batch) {
-    return plan_wave_lds(h, forced, batch, [](int mp, int np, int dr) { return wave_gd_lds_private(mp, np, dr); }, WAVE_GD_LDS_STATIC);
+    static const WaveLdsKernel k = {wave_relay_lds_shared, [](int mp, int np, int dr) { return wave_gd_lds_private(mp, np, dr); }, nullptr, wave_ms_waves, 16};
+    return plan_wave_lds(h, forced, batch, k, -1, WAVE_GD_LDS_STATIC);
+}
+// The float32 message mode on bp_wave_f32_kernel (bp_wave_f32_kernel.h): plan_wave's choice between the LDS copy of the log-ratios and llr_direct, with
+// the FP32 sizes (debug switch F32_WAVE_LLR: 0 the copy, 1 direct, unset the rule); without log-ratios the lean region is all there is.
+// (solo_cap 20: the instantiations' <= 96 VGPRs allow five wavefronts per SIMD)
+static WavePlan plan_wave_f32(const ldpc_hip_bp *h, bool forced, bool want_llr, int64_t batch) {
+    static const auto copy = [](int mp, int np, int dr) { return wave_f32_lds_private(mp, np, dr, true); };
+    static const auto lean = [](int mp, int np, int dr) { return wave_f32_lds_private(mp, np, dr, false); };
+    static const WaveLdsKernel with_llr = {wave_f32_lds_shared, copy, lean, wave_f32_waves, 20};
+    static const WaveLdsKernel without = {wave_f32_lds_shared, lean, nullptr, wave_f32_waves, 20};
+    return plan_wave_lds(h, forced, batch, want_llr ? with_llr : without, h->sw("F32_WAVE_LLR"), WAVE_F32_LDS_STATIC);
 }
 
 // a and gamma of every leg as the kernel reads them: [legs][2][np], beyond n a = 1.0 and gamma = 0 (the padding columns form the finite prior 1.0)
@@ -962,17 +999,64 @@ int decode_onchip_gd(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t
                 "the lane = node route and a per-pass route are not built yet", (long long)batch);
 }
 
-// The float32 message mode's on-chip planner, called by decode_f32 (host_f32.h) after its refusals: decode_onchip's small-mode rule for the lane =
-// edge families, onchip_bound and plan_edge_family.  *took = false: neither family takes the code -- decode_f32 goes on with its per-pass kernels (in
-// float32 nothing ever goes to bp_wave_kernel, bp_small_kernel or any FP64 kernel).
+// ---- the float32 message mode on the lane = node kernel (bp_wave_f32_kernel.h; instantiated in tu_onchip_wave_f32.hip): the codes beyond both lane = edge ladders, opt-in ----
+// As decode_wave_gd: the shared position tables, the work counters without an OSD hook (bposd_device lists the unsolved rows itself), and the padded
+// priors -- here floats, in w_prior_f32, written before every launch (the priors may have changed): a buffer of this route alone, so a handle that
+// changes its message dtype never reads one type's priors as the other's.
+static int decode_wave_f32(ldpc_hip_bp *h, const WavePlan &p, const DecodeIo &io) {
+    const WaveF32Kernel kern = wave_f32_kernel(p.dr, p.dc, p.team);
+    if (!kern) return fail(LDPC_HIP_ERR_UNSUPPORTED, "float32 messages: no lane = node kernel was built for rows of %d, columns of %d", p.dr, p.dc);
+    int rc;
+    if ((rc = ensure_wave_tables(h, p)) || (rc = wave_counters(h, wave_static_teams(p, io.batch)))) return rc;
+    if ((rc = h->w_prior_f32.ensure(sizeof(float) * (size_t)(p.np + 2)))) return rc;
+    const WaveF32PriorKernel pad = wave_f32_prior_kernel();
+    LDPC_LAUNCH(pad, dim3((unsigned)((p.np + 2 + 255) / 256)), dim3(256), 0, h->stream, (const double *)h->d_llr0, h->n, p.np, (float *)h->w_prior_f32.p);
+    HIPCHK(hipGetLastError());
+    WaveF32Args a = {};
+    a.prior_g = (const float *)h->w_prior_f32.p;
+    a.llr_direct = p.llr_direct ? 1 : 0;
+    return launch_wave(h, p, kern, a, a, io);
+}
+
+// Which route a float32 decode of `batch` syndromes takes -- one decision for decode_onchip_f32 and ldpc_hip_bp_f32_route: 0 the per-pass kernels
+// (host_f32.h), 1 bp_edge, 2 bp_edge8 (bp_edge_f32_kernel.h), 3 / 4 bp_wave_f32 with one wavefront / a team per syndrome.
+// Per-pass whatever the code: small_mode 0 (never an on-chip kernel) and 2 (the slot kernel, which float32 has none of), the switch F32_ONCHIP 0, and
+// any switch that names the per-pass kernels (F32_NT, F32_GRID_ROWS, SPREAD_NODES: who sets one wants those kernels, on whatever code).  Modes -1, 1
+// and 6 ask the lane = edge families.  That is all with f32_lane_node off (in float32 nothing then goes beyond the lane = edge kernels).  With it on
+// (ldpc_hip_bp_set_f32_lane_node) the order is plan_relay_route's: mode 6 stops after the lane = edge families, modes -1, 1 and 3 take
+// plan_wave_f32's own choice between one wavefront and a team (1 and 3 forced, as plan_wave's `forced`), 4 and 5 force either.  No float32 decode
+// ever goes to bp_wave_kernel, bp_small_kernel or any FP64 kernel.
+static OnchipRoute plan_f32_route(const ldpc_hip_bp *h, int64_t batch, bool want_llr) {
+    OnchipRoute r;
+    if (h->small_mode == 0 || h->small_mode == 2 || h->sw("F32_ONCHIP") == 0 || h->sw("F32_NT") >= 0 || h->sw("F32_GRID_ROWS") > 0 || h->sw("SPREAD_NODES") > 0) return r;
+    if (!onchip_bound(h, batch)) return r;
+    if (h->small_mode == -1 || h->small_mode == 1 || h->small_mode == 6) {
+        r.ep = plan_edge_family(h);
+        r.route = r.ep.family;
+        if (r.route) return r;
+    }
+    if (!h->f32_lane_node || h->small_mode == 6) return r;
+    r.wp = plan_wave_f32(h, h->small_mode != -1, want_llr, batch);
+    if (r.wp.waves) r.route = r.wp.team ? 4 : 3;
+    return r;
+}
+
+int ldpc_hip_bp_f32_route(const ldpc_hip_bp *h, int64_t batch, int32_t want_llr, int32_t *route) {
+    if (!h || !route) return fail(LDPC_HIP_ERR_INVALID, "null argument");
+    if (batch < 0) return fail(LDPC_HIP_ERR_INVALID, "negative batch");
+    *route = plan_f32_route(h, batch, want_llr != 0).route;
+    return LDPC_HIP_OK;
+}
+
+// The float32 message mode's on-chip routes, called by decode_f32 (host_f32.h) after its refusals: plan_f32_route.  *took = false: no on-chip kernel
+// takes the batch -- decode_f32 goes on with its per-pass kernels.
 int decode_onchip_f32(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv, bool *took) {
-    *took = false;
-    if (!(h->small_mode == -1 || h->small_mode == 1 || h->small_mode == 6)) return LDPC_HIP_OK;
-    if (!onchip_bound(h, batch)) return LDPC_HIP_OK;
-    const EdgePlan ep = plan_edge_family(h);
-    if (!ep.family) return LDPC_HIP_OK;
-    *took = true;
-    return decode_edge_f32(h, ep, {synd, batch, decoding, llr, iters, conv});
+    const DecodeIo io = {synd, batch, decoding, llr, iters, conv};
+    const OnchipRoute r = plan_f32_route(h, batch, llr != nullptr);
+    *took = r.route != 0;
+    if (r.route == 1 || r.route == 2) return decode_edge_f32(h, r.ep, io);
+    if (r.route >= 3) return decode_wave_f32(h, r.wp, io);
+    return LDPC_HIP_OK;
 }
 
 // Which on-chip kernel (if any) takes this batch: called by decode_device (host_stream.h) before it falls back to the streamed tiles.

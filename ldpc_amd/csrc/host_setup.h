@@ -312,6 +312,24 @@ int ldpc_hip_bp_get_message_dtype(const ldpc_hip_bp *h) {
     return h->msg_dtype;
 }
 
+int ldpc_hip_bp_set_f32_lane_node(ldpc_hip_bp *h, int32_t on) {
+    if (!h) return fail(LDPC_HIP_ERR_INVALID, "null handle");
+    if (on != 0 && on != 1) return fail(LDPC_HIP_ERR_INVALID, "float32 messages: the lane = node switch is %d: it must be 0 or 1", (int)on);
+    if (!on && h->w_prior_f32.p) {  // off: its padded priors go (a decode still queued reads them)
+        HIPCHK(hipSetDevice(h->device));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        h->w_prior_f32.release();
+    }
+    h->f32_lane_node = on != 0;
+    return LDPC_HIP_OK;
+}
+
+int ldpc_hip_bp_get_f32_lane_node(const ldpc_hip_bp *h, int32_t *on) {
+    if (!h || !on) return fail(LDPC_HIP_ERR_INVALID, "null argument");
+    *on = h->f32_lane_node ? 1 : 0;
+    return LDPC_HIP_OK;
+}
+
 int ldpc_hip_bp_set_memory(ldpc_hip_bp *h, const double *gamma) {
     if (!h) return fail(LDPC_HIP_ERR_INVALID, "null handle");
     HIPCHK(hipSetDevice(h->device));

@@ -165,6 +165,29 @@ class HipBpEngine:
     def message_dtype(self) -> str:
         return ("float64", "float32")[int(self._lib.ldpc_hip_bp_get_message_dtype(self._h))]
 
+    def set_f32_lane_node(self, on):
+        """Opt in to (or out of) the lane = node route of the float32 message mode (``ldpc_hip_bp_set_f32_lane_node``; off by default): a
+        code neither lane = edge family takes -- rows of at most 16, columns of at most 8 entries, a syndrome's state within LDS -- is
+        decoded on chip by ``bp_wave_f32_kernel`` instead of the per-pass kernels; the bits are the same.  A setting of the engine, read
+        only by float32 decodes."""
+        _lib.check(self._lib.ldpc_hip_bp_set_f32_lane_node(self._h, 1 if on else 0))
+
+    @property
+    def f32_lane_node(self) -> bool:
+        on = C.c_int32(0)
+        _lib.check(self._lib.ldpc_hip_bp_get_f32_lane_node(self._h, C.byref(on)))
+        return bool(on.value)
+
+    F32_ROUTES = ("per_pass", "bp_edge", "bp_edge8", "bp_wave", "bp_wave_team")
+
+    def f32_route(self, batch=1, want_llr=True) -> str:
+        """Which kernels a float32 decode of ``batch`` syndromes takes on this engine as it is set now, whatever its current message dtype
+        (``ldpc_hip_bp_f32_route``; nothing is launched): ``"per_pass"``, ``"bp_edge"``, ``"bp_edge8"``, and with ``f32_lane_node`` also
+        ``"bp_wave"`` / ``"bp_wave_team"`` (the lane = node kernel with one wavefront / a team per syndrome)."""
+        route = C.c_int32(-1)
+        _lib.check(self._lib.ldpc_hip_bp_f32_route(self._h, int(batch), 1 if want_llr else 0, C.byref(route)))
+        return self.F32_ROUTES[int(route.value)]
+
     def set_memory(self, gamma):
         """Memory min-sum BP (``ldpc_hip_bp_set_memory``): ``gamma`` = one memory strength per bit, each finite and in ``[-1, 1)`` -- every
         iteration's bit pass then takes ``(1 - gamma) * prior + gamma * (the bit's previous posterior)`` for the prior -- or ``None``: off.

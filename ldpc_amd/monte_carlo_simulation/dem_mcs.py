@@ -51,7 +51,9 @@ class MonteCarloDemSimulation:
 
     The errors are drawn with the model's probabilities exactly; the decoder's priors are the same values clipped to
     ``[1e-9, 1 - 1e-9]``, so a mechanism at p = 0 or p = 1 keeps a finite log-ratio.  ``message_dtype="float32"`` decodes with FP32
-    messages (minimum-sum only: ``bp_method="ps"`` is then refused at ``run()``, as everywhere in the library).  ``memory_strength``
+    messages (minimum-sum only: ``bp_method="ps"`` is then refused at ``run()``, as everywhere in the library); a model beyond the lane =
+    edge kernels -- most are -- then takes the per-pass kernels unless ``float32_lane_node=True`` keeps it on chip
+    (``ldpc_hip_bp_set_f32_lane_node``: rows of at most 16, columns of at most 8 entries, a shot's state within LDS; same bits).  ``memory_strength``
     (``None``, a float, or one strength per mechanism in ``[-1, 1)``): memory min-sum BP, as ``BpDecoder.memory_strength``; minimum-sum with
     float64 messages only, and not together with a ``window_decoder``.  ``relay`` (a dict of ``ldpc_amd.relay_decoder.relay_schedule``
     keywords -- ``gamma0``, ``pre_iter``, ``num_sets``, ``set_max_iter``, ``gamma_dist_interval``, ``stop_nconv``, ``strengths``, ``seed``):
@@ -67,7 +69,8 @@ class MonteCarloDemSimulation:
 
     def __init__(self, model, *, target_run_count, batch_size: int = 65536, seed: int = 0, max_iter: int = 0, bp_method="ms",
                  ms_scaling_factor: float = 0.625, osd_method="osd0", osd_order: int = 0, message_dtype="float64", window_decoder=None,
-                 device: int = -1, memory_strength=None, relay=None, decimation=None, decimation_lane_node: bool = False) -> None:
+                 device: int = -1, memory_strength=None, relay=None, decimation=None, decimation_lane_node: bool = False,
+                 float32_lane_node: bool = False) -> None:
         from ldpc_amd.bp_decoder._bp_decoder import _bp_method_code
         from ldpc_amd.noise_models.dem import check_dem_probabilities
         from ldpc_amd.sinter_decoders.sinter_bposd_decoder import _osd_code
@@ -151,6 +154,9 @@ class MonteCarloDemSimulation:
         if not isinstance(decimation_lane_node, bool):
             raise ValueError("Invalid decimation_lane_node provided. It must be a bool.")
         self.decimation_lane_node = decimation_lane_node
+        if not isinstance(float32_lane_node, bool):
+            raise ValueError("Invalid float32_lane_node provided. It must be a bool.")
+        self.float32_lane_node = float32_lane_node
         if not isinstance(device, int) or isinstance(device, bool):
             raise ValueError("Invalid device provided.")
         self.device = device
@@ -176,6 +182,7 @@ class MonteCarloDemSimulation:
                               self.ms_scaling_factor, device=self.device)
             eng.set_osd(self._osd_code, 0 if self._osd_code == 1 else self.osd_order)
             eng.set_message_dtype(self.message_dtype)
+            eng.set_f32_lane_node(self.float32_lane_node)
             eng.set_memory(self.memory_strength)  # (what memory min-sum cannot do -- product-sum, float32 -- is refused at run(), by the library)
             if self.relay is not None:
                 eng.set_relay(*self.relay)  # (likewise)

@@ -7,12 +7,17 @@
     python tools/bench_f32.py --speed --configs small     # the small codes the on-chip kernels take (each at its own batch sizes)
     python tools/bench_f32.py --speed --repack 0          # ... with the two-pass decode off (set_repack; default -1: the previous decode's histogram decides)
     python tools/bench_f32.py --agreement-two-pass        # float32 two-pass against float32 with set_repack(0): rows that differ, log-ratio bits included
+    python tools/bench_f32.py --speed --configs node --modes float32_lane_node,float64   # the codes beyond the lane = edge kernels, float32 on the lane = node kernel
 
 Configurations: (3,6)-regular n = 10 000, min-sum 50 iterations, at p = 0.05 and 0.09; the irregular n = 10 000 code of
 ``bench.py --full`` (speed only); BB144 min-sum 50 + OSD-0 (agreement only).  ``--configs small`` (speed only): the codes whose messages
 stay on chip in both modes -- BB144 min-sum 50 at p = 0.05 (B = 65 536 and 262 144; bp_edge8, DC 3), the rotated surface code d = 21 min-sum
 30 at p = 0.05 (B = 262 144; bp_edge) and the hypergraph product of hamming_code(3) with itself min-sum 30 at p = 0.05 (B = 262 144;
 bp_edge8, DC 4); every line names the BP kernels its decode launched (``bp_kernels``, from the launch log), so the route is on record.
+``--configs node`` (speed, and the rows that differ between the modes of one call): the codes beyond the lane = edge ladders, which FP64
+decodes with bp_wave_kernel -- the hypergraph products [[400,16]] and [[1600,64]] of tools/bench_relay_wave.py at p = 0.02 min-sum 30, BB288
+at p = 0.05 min-sum 30, and the BB144 x 12 rounds detector error model of tools/bench_dem.py (864 x 2520) at p = 0.003 min-sum 30 + OSD-0, at
+``--batch`` rows; modes ``float32`` (the switch off: per-pass), ``float32_lane_node`` (ldpc_hip_bp_set_f32_lane_node on) and ``float64``.
 Syndromes are generated on the device; everything stays in HBM.  One JSON line per figure.  Reads nothing but this
 repository.
 """
@@ -102,6 +107,74 @@ def speed_small(modes, reps, warmup, tag, tree_name=None):
                                       min_syndromes_per_s=round(min(rates)), max_syndromes_per_s=round(max(rates)),
                                       kernel_ms=[round(x, 3) for x in kms], converged=int(out[3].sum()),
                                       mean_iterations=round(float(out[2].double().mean()), 3))), flush=True)
+        eng.close()
+
+
+def _node_configs():
+    """(name, h, priors, p, osd): the codes of --configs node; the detector error model comes with its own priors and is decoded with OSD-0."""
+    from ldpc_amd import codes
+    sys.path.insert(0, os.path.join(_TREE, "tests"))
+    from window_util import phenomenological_matrices
+    hgp = lambda n: codes.hypergraph_product_hx(codes.regular_ldpc_code(n, 3, 4, seed=5))  # noqa: E731
+    bb288 = codes.bivariate_bicycle_hx(12, 12, (("x", 3), ("y", 2), ("y", 7)), (("y", 3), ("x", 1), ("x", 2)))
+    check, _, pri = phenomenological_matrices(codes.bivariate_bicycle_hx(), 12, 0.003, 0.003, logical=tuple(range(12)))
+    return [("hgp400_ms30_p020", hgp(16), None, 0.02, False), ("hgp1600_ms30_p020", hgp(32), None, 0.02, False), ("bb288_ms30_p050", bb288, None, 0.05, False),
+            ("bb144x12_dem_ms30_osd0_p003", check, np.asarray(pri, np.float64), 0.003, True)]
+
+
+def speed_node(batch, modes, reps, warmup, tag, tree_name=None):
+    """The codes beyond the lane = edge ladders: `warmup` untimed decodes, then `reps` timed ones, per mode in the order given; every line names
+    the BP kernels its decode launched and, where the tree has it, the float32 route.  Then, per code, the rows whose decisions or flags differ
+    between the first mode and every other one of this call."""
+    import torch
+    from ldpc_amd.engine import HipBpEngine, launch_log
+    for name, h, pri, p, osd in _node_configs():
+        h = h.tocsr()
+        h.eliminate_zeros()
+        h.sort_indices()
+        m, n = h.shape
+        eng = HipBpEngine(h.indptr, h.indices, n, np.full(n, p) if pri is None else np.clip(pri, 1e-9, 1 - 1e-9), 30, 1, 0.625)
+        if osd:
+            eng.set_osd(1, 0)
+            eng.set_sampler(pri)
+            synd = eng.unpack_b8(eng.sample_b8(12345, 0, batch, device="cuda")[0], m).contiguous()
+        else:
+            synd = eng.gen_bsc_syndromes(12345, p, 0, batch, device="cuda")
+        kept = {}
+        for mode in modes:
+            eng.set_message_dtype("float64" if mode == "float64" else "float32")
+            if hasattr(eng, "set_f32_lane_node"):  # (a checkout from before the switch: float32 is its per-pass route)
+                eng.set_f32_lane_node(mode == "float32_lane_node")
+            elif mode == "float32_lane_node":
+                continue
+            route = eng.f32_route(batch, False) if mode != "float64" and hasattr(eng, "f32_route") else None
+            out, rates, kms, kernels = None, [], [], None
+            for r in range(reps + warmup):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                if r == 0:
+                    with launch_log() as log:
+                        out = eng.decode_batch(synd, want_llr=False, out=out, osd=osd)
+                        torch.cuda.synchronize()
+                    kernels = {k: v for k, v in sorted(log.items()) if k.startswith("bp_")}
+                else:
+                    out = eng.decode_batch(synd, want_llr=False, out=out, osd=osd)
+                torch.cuda.synchronize()
+                if r >= warmup:
+                    rates.append(batch / (time.perf_counter() - t0))
+                    kms.append(eng.last_kernel_ms())
+            kept.setdefault(mode, (out[0].clone(), out[3].clone()))
+            print(json.dumps(dict(kind="speed_node", config=name, shape=[m, n], mode=mode, f32_route=route, tree=tree_name or os.path.relpath(_TREE), tag=tag, batch=batch,
+                                  osd0=osd, bp_kernels=kernels, syndromes_per_s=[round(x) for x in rates], median_syndromes_per_s=round(float(np.median(rates))),
+                                  min_syndromes_per_s=round(min(rates)), max_syndromes_per_s=round(max(rates)), kernel_ms=[round(x, 3) for x in kms],
+                                  converged=int(out[3].sum()), mean_iterations=round(float(out[2].double().mean()), 3))), flush=True)
+        first = next(iter(kept), None)
+        for mode, (dec, cv) in kept.items():
+            if mode != first:
+                d, c = (dec != kept[first][0]).any(dim=1), cv != kept[first][1]
+                print(json.dumps(dict(kind="agreement_node", config=name, batch=batch, modes=[first, mode], tree=tree_name or os.path.relpath(_TREE), tag=tag, osd0=osd,
+                                      rows_decisions_differ=int(d.sum()), rows_converge_differ=int(c.sum()), rows_either_differ=int((d | c).sum()))), flush=True)
+        del kept
         eng.close()
 
 
@@ -225,7 +298,8 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--modes", default="float64,float32")
     ap.add_argument("--tree", default=None, help="another built checkout to take ldpc_amd from (default: this one)")
-    ap.add_argument("--configs", default="large", choices=["large", "small"], help="--speed: the n = 10 000 codes, or the small codes of the on-chip kernels")
+    ap.add_argument("--configs", default="large", choices=["large", "small", "node"],
+                    help="--speed: the n = 10 000 codes, the small codes of the lane = edge kernels, or the codes beyond them that the lane = node kernels take")
     ap.add_argument("--warmup", type=int, default=3, help="--configs small: untimed decodes before the timed ones")
     ap.add_argument("--tag", default="", help="--speed: copied into every line (which leg of a comparison this is)")
     ap.add_argument("--tree-name", default=None, help="--speed: what the lines call the tree (default: its path)")
@@ -239,6 +313,8 @@ def main():
         agreement_two_pass(a.batch, a.repack)
     if a.speed and a.configs == "small":
         speed_small(a.modes.split(","), a.reps, a.warmup, a.tag, a.tree_name)
+    elif a.speed and a.configs == "node":
+        speed_node(a.batch, a.modes.split(","), a.reps, a.warmup, a.tag, a.tree_name)
     elif a.speed:
         speed(a.batch, a.modes.split(","), a.reps, a.repack, a.tag, a.tree_name, tuple(a.only.split(",")))
 
