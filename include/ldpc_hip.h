@@ -444,9 +444,18 @@ int ldpc_hip_bp_set_handoff(ldpc_hip_bp *h, int32_t threshold_tiles);
  * 6 = those variants where they apply, else as -1.  The on-chip kernels take batches below 2^30 syndromes (larger ones
  * are streamed).  Results are identical.
  * Row priors (ldpc_hip_*_decode_batch_priors): mode 0 = the per-pass kernels; modes -1, 1, 6 with min-sum on a code of the lane = edge
- * variants = their row-prior forms (bp_edge_rp_kernel, bp_edge8_rp_kernel); any other code an on-chip kernel would take, and mode 2
- * always = the slot variant, the only other on-chip kernel that reads a prior per syndrome. */
+ * variants = their row-prior forms (bp_edge_rp_kernel, bp_edge8_rp_kernel); modes 3, 4, 5 with min-sum on a code the lane = node variant
+ * takes (rows <= 16, columns <= 8, a syndrome's state within LDS) = its row-prior form (bp_wave_rp_kernel: 3 its own choice between one
+ * wavefront and a team per syndrome, 4 / 5 force either) -- modes -1, 1, 6 take it for such a code beyond the lane = edge variants too
+ * (the debug switch "WAVE_RP" 0 switches that off); any other code an on-chip kernel would take, and mode 2 always = the
+ * slot variant, which reads a prior per syndrome too, if one slot fits 150 KiB of LDS, else the per-pass kernels.  All routes give the same bits.
+ *   ldpc_hip_bp_row_prior_route(h, batch, want_llr, &route): which kernels a row-prior decode of `batch` syndromes takes on this handle as it is
+ *       set now, whether or not priors are staged -- 0 the per-pass kernels, 1 bp_edge, 2 bp_edge8, 3 bp_wave with one wavefront per syndrome,
+ *       4 bp_wave with a team per syndrome, 5 the slot kernel.  Launches nothing.  LDPC_HIP_ERR_INVALID: NULL argument or negative batch;
+ *       LDPC_HIP_ERR_UNSUPPORTED, with the reason, where a row-prior decode would be refused (a serial schedule, float32 messages, memory,
+ *       Relay-BP, guided decimation). */
 int ldpc_hip_bp_set_small_code_kernel(ldpc_hip_bp *h, int32_t mode);
+int ldpc_hip_bp_row_prior_route(const ldpc_hip_bp *h, int64_t batch, int32_t want_llr, int32_t *route);
 /* Measurement / test switches: kernel-shape choices that never change a result (profiles/README.md lists them: "PS_TEAM",
  * "OSD_UNBLOCKED", "OSD_PLANES", "EDGE_STATIC_PCT", "EDGE_CHUNK", ...; for schedule = serial_relative: "REL_LDS" 0 = the
  * per-lane kernel with the state in HBM, 16 / 64 = lanes per syndrome of the on-chip kernel; "REL_LEVELS" 0 = sweep bit by bit instead of

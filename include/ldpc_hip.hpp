@@ -237,6 +237,12 @@ public:
         int32_t route = -1;
         return h_ && ldpc_hip_bp_decimation_route(h_, batch, &route) == LDPC_HIP_OK ? route : -1;
     }
+    // Which kernels a row-prior decode of `batch` syndromes takes (ldpc_hip_bp_row_prior_route): 0 per-pass, 1 bp_edge, 2 bp_edge8, 3 / 4 bp_wave with
+    // one wavefront / a team per syndrome, 5 the slot kernel; -1: such a decode is refused (ldpc_hip_last_error says why), or several GPUs
+    int32_t row_prior_route(int64_t batch, bool want_llr = true) const {
+        int32_t route = -1;
+        return h_ && ldpc_hip_bp_row_prior_route(h_, batch, want_llr ? 1 : 0, &route) == LDPC_HIP_OK ? route : -1;
+    }
 
     ldpc_hip_bp *handle() { return h_; }
     ldpc_hip_bp_multi *multi_handle() { return mh_; }  // null unless constructed with device_ids

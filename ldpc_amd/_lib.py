@@ -31,6 +31,7 @@ SYMBOLS = (
     "ldpc_hip_bp_set_decimation", "ldpc_hip_bp_get_decimation", "ldpc_hip_bp_decimation_route",
     "ldpc_hip_bp_set_decimation_lane_node", "ldpc_hip_bp_get_decimation_lane_node",
     "ldpc_hip_bp_set_f32_lane_node", "ldpc_hip_bp_get_f32_lane_node", "ldpc_hip_bp_f32_route",
+    "ldpc_hip_bp_row_prior_route",
 )
 
 
@@ -155,6 +156,8 @@ def load():
         lib.ldpc_hip_bp_set_f32_lane_node.argtypes = [vp, i32]
         lib.ldpc_hip_bp_get_f32_lane_node.argtypes = [vp, vp]
         lib.ldpc_hip_bp_f32_route.argtypes = [vp, i64, i32, vp]
+    if not os.environ.get("LDPC_HIP_LIB") or hasattr(lib, "ldpc_hip_bp_row_prior_route"):
+        lib.ldpc_hip_bp_row_prior_route.argtypes = [vp, i64, i32, vp]
     lib.ldpc_hip_bp_set_small_code_kernel.argtypes = [vp, i32]
     lib.ldpc_hip_bp_set_debug_switch.argtypes = [vp, C.c_char_p, i32]
     lib.ldpc_hip_bp_set_handoff.argtypes = [vp, i32]

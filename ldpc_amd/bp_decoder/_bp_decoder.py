@@ -467,6 +467,23 @@ class BpDecoderBase:
             raise NotImplementedError("float32_route with device_ids=[...]: float32 messages are decoded on one GPU only.")
         return self._get_engine().f32_route(getattr(self, "_last_batch", 1))
 
+    @property
+    def row_prior_route(self) -> str:
+        """Which kernels a ``decode_batch(..., channel_probs=P)`` takes on this decoder as it is set now, for a batch of the size last decoded
+        (1 before any): ``HipBpEngine.row_prior_route`` -- ``"per_pass"``, ``"bp_edge"``, ``"bp_edge8"``, ``"bp_wave"`` / ``"bp_wave_team"``
+        (the lane = node kernel with one wavefront / a team per syndrome) or ``"bp_small"`` (the slot kernel).  The routes give the same bits
+        and differ by an order of magnitude in speed.  Where such a decode is refused -- a serial schedule, ``message_dtype='float32'``,
+        ``memory_strength``, ``relay``, ``decimation``, ``device_ids=[...]`` -- its ``NotImplementedError`` is raised instead."""
+        self._require_modes()  # (what any decode of this decoder is refused for speaks first, as in decode_batch)
+        self._require_modes("channel_probs: per-row channel probabilities are decoded {only}")
+        if self._schedule != PARALLEL:
+            raise NotImplementedError(f"channel_probs with schedule='{self.schedule}': the serial schedules decode with the decoder's own "
+                                      "channel probabilities only; per-row probabilities need schedule='parallel'.")
+        if self._device_ids is not None:
+            raise NotImplementedError("row_prior_route with device_ids=[...]: the rows of channel_probs are not sharded over several GPUs; "
+                                      "decode on one GPU.")
+        return self._get_engine().row_prior_route(getattr(self, "_last_batch", 1))
+
     # ---- memory min-sum BP (additive; not a constructor keyword either) ----------------------------------------
     @property
     def memory_strength(self):

@@ -45,10 +45,11 @@
 //   bp_edge_f32_kernel.h bp_edge_f32_kernel, bp_edge8_f32_kernel   float32 message mode on the lane = edge families: messages in registers (tu_onchip_f32.hip)
 //   bp_wave_f32_kernel.h bp_wave_f32_kernel                        float32 message mode beyond the lane = edge families, opt-in: lane = node, messages in LDS (tu_onchip_wave_f32.hip)
 //   bp_edge_rp_kernel.h  bp_edge_rp_kernel, bp_edge8_rp_kernel     row priors on the lane = edge families: every syndrome its own priors (tu_onchip_rp.hip)
+//   bp_wave_rp_kernel.h  bp_wave_rp_kernel                         row priors beyond the lane = edge families, min-sum: lane = node, every syndrome its own priors, messages in LDS (tu_onchip_wave_rp.hip)
 //   bp_edge_mem_kernel.h bp_edge_mem_kernel, bp_edge8_mem_kernel   memory min-sum on the lane = edge families: per-bit memory strengths (tu_onchip_mem.hip)
 //   bp_edge_relay_kernel.h bp_edge_relay_kernel, bp_edge8_relay_kernel   Relay-BP on the lane = edge families: chained memory legs in one launch (tu_onchip_relay.hip)
 //   bp_wave_relay_kernel.h bp_wave_relay_kernel             Relay-BP and memory min-sum beyond the lane = edge families: lane = node, messages and memory in LDS (tu_onchip_wave_relay.hip)
-//   bp_wave_ms_body.h    (a textual fragment)                       one min-sum iteration on the lane = node layout, the do-while body of bp_wave_relay_kernel and bp_wave_gd_kernel
+//   bp_wave_ms_body.h    (a textual fragment)                       one min-sum iteration on the lane = node layout, the do-while body of bp_wave_relay_kernel, bp_wave_gd_kernel and bp_wave_rp_kernel
 //   bp_edge_gd_kernel.h  bp_edge_gd_kernel, bp_edge8_gd_kernel     BP with guided decimation on the lane = edge families: all rounds in one launch (tu_onchip_gd.hip)
 //   bp_edge_check4.h, bp_edge_check8.h, bp_edge_bit4.h, bp_edge_bit4_mem.h, bp_edge_bit8.h, bp_edge_synd.h, bp_edge_out_rows.h, bp_edge_out_status.h,
 //   bp_edge_relay_take.h (textual fragments)                        the passes of the lane = edge kernels, each written once and included by the kernels above (bp_edge_kernel.h lists them)

@@ -89,6 +89,15 @@ static int row_priors_refusal(const ldpc_hip_bp *h) {
     return decode_gate(h, "per-row channel probabilities are", false);
 }
 
+// Which kernels such a decode takes: the refusal such a decode would get, else plan_row_prior_route's answer (host_onchip.h) -- nothing is launched
+int ldpc_hip_bp_row_prior_route(const ldpc_hip_bp *h, int64_t batch, int32_t want_llr, int32_t *route) {
+    if (!h || !route) return fail(LDPC_HIP_ERR_INVALID, "null argument");
+    if (batch < 0) return fail(LDPC_HIP_ERR_INVALID, "negative batch");
+    { const int refused = row_priors_refusal(h); if (refused) return refused; }
+    *route = row_prior_route(h, batch, want_llr != 0);
+    return LDPC_HIP_OK;
+}
+
 int ldpc_hip_bp_decode_batch_priors(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr,
                                     int32_t *iters, uint8_t *conv, const double *channel_probs) {
     if (h && batch > 0 && !channel_probs) return fail(LDPC_HIP_ERR_INVALID, "channel_probs must not be NULL");

@@ -153,7 +153,7 @@ struct DeviceBuf {  // grow-only device allocation, freed with its owner (on the
 // creation, from the environment variables LDPC_HIP_<NAME>, changed afterwards only through ldpc_hip_bp_set_debug_switch -- no
 // getenv on the decode path, and nothing a test can change under a live handle by accident.
 static const char *const k_switch_names[] = {"PS_TEAM", "EXPLICIT_INIT", "OSD_UNBLOCKED", "OSD_PLANES",
-                                             "PS_TEAM_WAVES", "EDGE_STATIC_PCT", "EDGE_CHUNK", "NO_HOST_PIPELINE", "NO_DIRECT_LLR", "HOST_CHUNK_ROWS", "TIME_SMALL_CALLS", "REL_LDS", "HOST_PIPE_TIMING", "REL_LEVELS", "REL_PROF", "REL_SCRATCH_IN_L", "SER_RING", "SER_WAVES", "SER_LANE_MAX", "SER_LANE_THREADS", "SER_WAVES2", "RESIDENT", "SER_NO_REMAINDER", "SER_ROUND_TILES", "VAR_RING", "VAR_RING_UNITS", "SPREAD_NODES", "SER_VAR", "SER_VAR_UNITS", "REL_EXT", "OSD_COLLECT_AFTER", "EDGE_CLAMP", "OSD_NO_FLAT", "F32_NT", "F32_GRID_ROWS", "F32_ONCHIP", "F32_REPACK_MIN_TILES", "EDGE_RP", "SPREAD_NT", "REPACK_MIN_TILES", "DEM_GRID", "F32_WAVE_LLR"};
+                                             "PS_TEAM_WAVES", "EDGE_STATIC_PCT", "EDGE_CHUNK", "NO_HOST_PIPELINE", "NO_DIRECT_LLR", "HOST_CHUNK_ROWS", "TIME_SMALL_CALLS", "REL_LDS", "HOST_PIPE_TIMING", "REL_LEVELS", "REL_PROF", "REL_SCRATCH_IN_L", "SER_RING", "SER_WAVES", "SER_LANE_MAX", "SER_LANE_THREADS", "SER_WAVES2", "RESIDENT", "SER_NO_REMAINDER", "SER_ROUND_TILES", "VAR_RING", "VAR_RING_UNITS", "SPREAD_NODES", "SER_VAR", "SER_VAR_UNITS", "REL_EXT", "OSD_COLLECT_AFTER", "EDGE_CLAMP", "OSD_NO_FLAT", "F32_NT", "F32_GRID_ROWS", "F32_ONCHIP", "F32_REPACK_MIN_TILES", "EDGE_RP", "SPREAD_NT", "REPACK_MIN_TILES", "DEM_GRID", "F32_WAVE_LLR", "WAVE_RP"};
 constexpr int k_n_switches = (int)(sizeof(k_switch_names) / sizeof(k_switch_names[0]));
 
 struct ldpc_hip_bp {
@@ -324,7 +324,7 @@ struct ldpc_hip_bp {
     // Row priors (ldpc_hip_*_decode_batch_priors): the call's [batch][n] channel probabilities on the device while it runs, nullptr
     // otherwise -- decode_device, the streamed decode (host_stream.h: rp) and decode_onchip look here, nobody else; the handle's own channel_probs / d_llr0 are not touched.
     const double *row_probs = nullptr;
-    DeviceBuf rowp_llr;  // their log-ratios: in tile layout [tiles of a chunk][n][64] (io_kernels.h: row_priors_kernel), or row-major [batch][n] for the lane = edge kernels (row_priors_rowmajor_kernel)
+    DeviceBuf rowp_llr;  // their log-ratios: in tile layout [tiles of a chunk][n][64] (io_kernels.h: row_priors_kernel), or row-major [batch][n] for the lane = edge kernels (row_priors_rowmajor_kernel), or padded rows [batch][np + 2] for the lane = node kernel (wave_rp_prior_kernel, host_onchip.h)
     DeviceBuf st_probs;  // staging for a host pointer
     // Which of memory min-sum, Relay-BP and guided decimation is on -- at most one: the three setters switch it and refuse a second (mode_host.h: mode_exclusion)
     Variant variant = Variant::Plain;
@@ -413,6 +413,9 @@ static int upload_relay(ldpc_hip_bp *h) {
 // gd_lane_node 3 / 4 bp_wave_gd with one wavefront / a team per syndrome.
 // It looks at the matrix, the BP method, the small-code kernel mode and gd_lane_node only, and launches nothing.
 int gd_route(const ldpc_hip_bp *h, int64_t batch);
+// tu_onchip.hip (host_onchip.h): which kernels a row-prior decode of `batch` syndromes takes on the handle as it is set now -- plan_row_prior_route's
+// answer, the one decode_onchip acts on: 0 per-pass, 1 bp_edge, 2 bp_edge8, 3 / 4 bp_wave_rp with one wavefront / a team per syndrome, 5 the slot kernel
+int row_prior_route(const ldpc_hip_bp *h, int64_t batch, bool want_llr);
 
 // THE gate of every decode entry point, before anything is staged or launched: what the handle is set up for that its modes -- float32 messages,
 // and whichever of memory min-sum, Relay-BP and guided decimation is on -- cannot do (the rules and their texts: mode_host.h).  `what`: the call's own

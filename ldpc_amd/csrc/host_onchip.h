@@ -1,4 +1,4 @@
-// host_onchip.h -- host side of the on-chip kernels: plans (LDS / occupancy), tables and launches of bp_small / bp_wave / bp_wave_ps / bp_edge / bp_wave_relay / bp_wave_gd / bp_wave_f32
+// host_onchip.h -- host side of the on-chip kernels: plans (LDS / occupancy), tables and launches of bp_small / bp_wave / bp_wave_ps / bp_edge / bp_wave_relay / bp_wave_gd / bp_wave_f32 / bp_wave_rp
 // Part of libldpc_hip.so: included by bp_hip.hip (one translation unit), in the order given there.
 #pragma once
 
@@ -85,7 +85,7 @@ struct WavePlan {
 };
 
 // The rungs (rows <=, columns <=) of the lane = node and lane = entry kernels, ascending: a code takes the first that holds it.  The first four are
-// bp_wave_ps_kernel's too (pick_wave_ps, which goes on with rungs of its own); all six are bp_wave_kernel's, bp_wave_relay_kernel's, bp_wave_gd_kernel's and bp_wave_f32_kernel's.
+// bp_wave_ps_kernel's too (pick_wave_ps, which goes on with rungs of its own); all six are bp_wave_kernel's, bp_wave_relay_kernel's, bp_wave_gd_kernel's, bp_wave_f32_kernel's and bp_wave_rp_kernel's.
 #define LDPC_WAVE_LADDER4(X) X(4, 2) X(4, 4) X(6, 3) X(8, 4)
 #define LDPC_WAVE_LADDER(X) LDPC_WAVE_LADDER4(X) X(8, 8) X(16, 8)
 
@@ -313,7 +313,7 @@ static int ensure_wave_ps_tables(ldpc_hip_bp *h, const WavePsPlan &p) {
     return LDPC_HIP_OK;
 }
 
-// ---- what the launches of the lane = node and lane = entry kernels share (bp_wave_kernel, bp_wave_ps_kernel, bp_wave_relay_kernel, bp_wave_gd_kernel, bp_wave_f32_kernel) ----
+// ---- what the launches of the lane = node and lane = entry kernels share (bp_wave_kernel, bp_wave_ps_kernel, bp_wave_relay_kernel, bp_wave_gd_kernel, bp_wave_f32_kernel, bp_wave_rp_kernel) ----
 // PLAN: WavePlan or WavePsPlan (team, waves, groups_per_cu, shared, per_wave, np); ARGS: WaveArgs, WavePsArgs or WaveF32Args, where their field names agree.
 
 // a team per syndrome and no more syndromes than resident teams -- e.g. ONE decode(): static assignment, no work counter to reset
@@ -771,7 +771,7 @@ static int decode_edge_relay(ldpc_hip_bp *h, const EdgePlan &p, const DecodeIo &
 // ---- Relay-BP and memory min-sum on the lane = node kernel (bp_wave_relay_kernel.h; instantiated in tu_onchip_wave_relay.hip): the codes beyond both lane = edge ladders ----
 // plan_wave's shared rules (the ladder, wave_pad, wave_padding_dominates, wave_team_rule and what follows it), min-sum only, the priors always read from
 // the padded device array, and the wavefronts capped by what the instantiation was compiled for.  waves == 0: not applicable.  One planner for this
-// kernel, for bp_wave_gd_kernel (plan_wave_gd) and for bp_wave_f32_kernel (plan_wave_f32): what differs between them is said in a WaveLdsKernel --
+// kernel, for bp_wave_gd_kernel (plan_wave_gd), for bp_wave_f32_kernel (plan_wave_f32) and for bp_wave_rp_kernel (plan_wave_rp): what differs between them is said in a WaveLdsKernel --
 // the LDS sizes, the wavefronts its instantiations are compiled for, the wavefronts per compute
 // unit its registers allow -- and, where the kernel has the two forms of bp_wave_kernel's log-ratios, the size without the LDS copy.
 // (It stays a planner of its own beside plan_wave: the two share the rules above, but plan_wave chooses its kernel and prior_global, and has
@@ -784,7 +784,7 @@ struct WaveLdsKernel {
     int solo_cap;                                        // wavefronts per compute unit, one syndrome each
 };
 // llr_form (kernels with a lean form only): -1 wave_llr_direct_rule decides, 0 the LDS copy, 1 llr_direct.  lds_static: the bytes left free for the
-// kernel's static LDS -- WAVE_RELAY_LDS_STATIC / WAVE_GD_LDS_STATIC / WAVE_F32_LDS_STATIC, which each kernel asserts it keeps to.
+// kernel's static LDS -- WAVE_RELAY_LDS_STATIC / WAVE_GD_LDS_STATIC / WAVE_F32_LDS_STATIC / WAVE_RP_LDS_STATIC, which each kernel asserts it keeps to.
 static WavePlan plan_wave_lds(const ldpc_hip_bp *h, bool forced, int64_t batch, const WaveLdsKernel &k, int llr_form, size_t lds_static) {
     WavePlan p;
     if (h->bp_method != LDPC_HIP_MINIMUM_SUM || h->m <= 0 || h->n <= 0 || h->nnz <= 0 || h->max_row_deg > 16 || h->max_col_deg > 8) return p;
@@ -1059,10 +1059,106 @@ int decode_onchip_f32(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_
     return LDPC_HIP_OK;
 }
 
+// ---- row priors on the lane = node kernel (bp_wave_rp_kernel.h; instantiated in tu_onchip_wave_rp.hip): min-sum on the codes beyond both lane = edge ladders ----
+// The plan is plan_wave_lds's with this kernel's sizes: the relay kernel's shared tables, bp_wave_kernel's private region with the posterior copy (the
+// kernel has no llr_direct form).  (solo_cap 16: the instantiations' 76 .. 137 VGPRs allow 16 wavefronts per compute unit, 12 where compiled for 12)
+static WavePlan plan_wave_rp(const ldpc_hip_bp *h, bool forced, int64_t batch) {
+    static const WaveLdsKernel k = {wave_rp_lds_shared, [](int mp, int np, int dr) { return wave_rp_lds_private(mp, np, dr); }, nullptr, wave_ms_waves, 16};
+    return plan_wave_lds(h, forced, batch, k, -1, WAVE_RP_LDS_STATIC);
+}
+
+// h->row_probs [batch][n] -> out [batch][np + 2], every row padded as wave_prior_pad_kernel pads the shared priors: the log-ratio of column j < n by the
+// IEEE division and the bit-exact log twin of row_priors_rowmajor_kernel (io_kernels.h), 1.0 for the columns n .. np - 1, DBL_MAX at np, 1.0 at np + 1.
+// A thread reads probs only where j < n: row b's padding never looks at row b + 1 or past the array's end.
+__global__ void __launch_bounds__(256) wave_rp_prior_kernel(const double *__restrict__ probs, int64_t batch, int n, int np, double *__restrict__ out) {
+    __shared__ __attribute__((aligned(16))) double log_tab[256];
+    log_tab[threadIdx.x] = ldpc_math::k_log_tab[threadIdx.x];
+    __syncthreads();
+    const int64_t stride = np + 2, items = batch * stride;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < items; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t b = t / stride;
+        const int j = (int)(t - b * stride);
+        double v = j == np ? DBL_MAX : 1.0;
+        if (j < n) {
+            const double p = probs[b * (int64_t)n + j];
+            v = ldpc_math::log_libm((1.0 - p) / p, log_tab);
+        }
+        out[t] = v;
+    }
+}
+
+// The padded layout, not the unpadded one: the kernel then indexes a syndrome's row exactly as bp_wave_kernel indexes prior_g --
+// phantom entries and padding columns need no select in the bit pass -- for (np + 2) / n of the bytes.  The table lives in rowp_llr, the row-prior
+// decodes' grow-only buffer, whole batch; the handle's own priors (d_llr0, w_prior) are neither read nor written.
+static int decode_wave_rp(ldpc_hip_bp *h, const WavePlan &p, const DecodeIo &io) {
+    const WaveRpKernel kern = wave_rp_kernel(p.dr, p.dc, p.team);
+    if (!kern) return fail(LDPC_HIP_ERR_UNSUPPORTED, "row priors: no lane = node kernel was built for rows of %d, columns of %d", p.dr, p.dc);
+    int rc;
+    WaveRpArgs ra = {};
+    if ((rc = ensure_wave_tables(h, p)) || (rc = wave_counters(h, wave_static_teams(p, io.batch)))) return rc;  // (no OSD hook: bposd_device arms none for row priors)
+    const size_t items = (size_t)io.batch * (size_t)(p.np + 2);
+    if ((rc = h->rowp_llr.ensure(sizeof(double) * items))) return rc;
+    LDPC_LAUNCH(wave_rp_prior_kernel, flat_grid(items), dim3(256), 0, h->stream, h->row_probs, io.batch, h->n, p.np, (double *)h->rowp_llr.p);
+    HIPCHK(hipGetLastError());
+    ra.rowp = (const double *)h->rowp_llr.p;
+    return launch_wave(h, p, kern, ra, ra.w, io);
+}
+
+// Row priors on the lane = node kernel under the default modes (-1, 1, 6)?  Debug switch WAVE_RP: 0 off, 1 on, unset: the default below -- the route, by
+// the rule fixed before it was measured: on one MI355X in one job, B = 65 536, min-sum 30, it beat the better of the parent's two
+// row-prior runs 4.71x on HGP [[400,16]] (44.7 against 9.50 M syndromes/s, the slot kernel), 11.9x on the [[1600,64]] hypergraph product (9.77 against
+// 0.823 M/s, per-pass) and 4.73x on BB144 x 12 rounds (14.0 against 2.97 M/s, per-pass), run-to-run spreads <= 3.4 % (profiles/row_priors_wave.jsonl).
+// Modes 3, 4 and 5 take the kernel whatever this says.
+static constexpr bool k_wave_rp_default = true;
+static bool wave_rp_route(const ldpc_hip_bp *h) {
+    if (h->small_mode >= 3 && h->small_mode <= 5) return true;
+    const int s = h->sw("WAVE_RP");
+    return s >= 0 ? s != 0 : k_wave_rp_default;
+}
+
+// Which route a row-prior decode of `batch` syndromes takes -- one decision for decode_onchip and ldpc_hip_bp_row_prior_route: 0 the per-pass
+// kernels, 1 bp_edge_rp, 2 bp_edge8_rp, 3 / 4 bp_wave_rp with one wavefront / a team per syndrome, 5 the slot kernel (bp_small_kernel<., ., RP>).
+// The order is decode_onchip's own, and `took` means what it means there -- an on-chip kernel takes the PLAIN decode of this code:
+//   1. min-sum on a code plan_edge or plan_edge8 takes (modes -1, 1, 6): their row-prior forms where edge_rp_route says so;
+//   2. min-sum on a code no earlier branch took -- neither bp_wave_ps (product-sum) nor a lane = edge family -- and plan_wave_rp takes (any mode
+//      but 0 and 2): bp_wave_rp_kernel where wave_rp_route says so; a code an earlier branch took stays where it went before this route;
+//   3. the slot kernel, with as many slots (<= 4) as fit the budget: 150 KiB where the mode forces it or another on-chip kernel takes the code's
+//      plain decode, 39.5 KiB otherwise;
+//   4. the per-pass kernels, if not even one slot fits -- and for everything under mode 0.
+struct RowPriorRoute { int route = 0; EdgePlan ep; WavePlan wp; int slots = 0; };
+static RowPriorRoute plan_row_prior_route(const ldpc_hip_bp *h, int64_t batch, bool want_llr) {
+    RowPriorRoute r;
+    const int mode = h->small_mode;
+    if (!(mode != 0 && onchip_bound(h, batch))) return r;
+    bool took = false;
+    if (mode < 2 || mode == 6) took = plan_wave_ps(h, mode == 1, want_llr, batch).waves != 0;
+    if (!took && (mode == -1 || mode == 1 || mode == 6)) {
+        r.ep = plan_edge_family(h);
+        if (r.ep.family) {
+            took = true;
+            if (edge_rp_route(h)) { r.route = r.ep.family; return r; }
+        }
+    }
+    if (!took && mode != 2) {
+        const bool forced = mode == 1 || (mode >= 3 && mode != 6);
+        if (h->bp_method == LDPC_HIP_MINIMUM_SUM && wave_rp_route(h)) {
+            r.wp = plan_wave_rp(h, forced, batch);
+            if (r.wp.waves) { r.route = r.wp.team ? 4 : 3; return r; }
+        }
+        took = plan_wave(h, forced, want_llr, batch).waves != 0;
+    }
+    const size_t budget = (mode == 1 || mode == 2 || took) ? 150u * 1024u : 39u * 1024u + 512u;
+    for (int sl = 4; sl >= 1 && !r.slots; --sl)
+        if (small_lds_bytes(h, sl, true) <= budget) r.slots = sl;
+    if (r.slots) r.route = 5;
+    return r;
+}
+
+int row_prior_route(const ldpc_hip_bp *h, int64_t batch, bool want_llr) { return plan_row_prior_route(h, batch, want_llr).route; }
+
 // Which on-chip kernel (if any) takes this batch: called by decode_device (host_stream.h) before it falls back to the streamed tiles.
-// Row priors (h->row_probs): min-sum on a code that plan_edge or plan_edge8 takes (modes -1, 1, 6) runs on their row-prior forms (bp_edge_rp_kernel,
-// bp_edge8_rp_kernel) where edge_rp_route says so; any other code that one of these kernels takes goes to the SLOT kernel, which reads every syndrome's
-// own priors too (bp_small_kernel<., ., RP>) -- with as many slots as fit -- and to the per-pass kernels (took = false) if not even one slot fits.
+// Row priors (h->row_probs): plan_row_prior_route above says which kernels decode them -- the row-prior forms of the lane = edge families, of the
+// lane = node kernel, the SLOT kernel, which reads every syndrome's own priors too (bp_small_kernel<., ., RP>), or the per-pass kernels (took = false).
 int decode_onchip(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *decoding, double *llr, int32_t *iters, uint8_t *conv, bool *took) {
     *took = false;
     const DecodeIo io = {synd, batch, decoding, llr, iters, conv};
@@ -1078,32 +1174,34 @@ int decode_onchip(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
         if (r.route >= 3) return decode_wave_relay(h, r.wp, (const double *)h->mem_ag.p, 1, nullptr, 1, io);
         return LDPC_HIP_OK;
     }
+    if (rp) {  // every syndrome its own priors: one decision, the one ldpc_hip_bp_row_prior_route reports
+        const RowPriorRoute r = plan_row_prior_route(h, batch, llr != nullptr);
+        *took = r.route != 0;
+        if (r.route == 1 || r.route == 2) return decode_edge_rp(h, r.ep, io);
+        if (r.route == 3 || r.route == 4) return decode_wave_rp(h, r.wp, io);
+        if (r.route == 5) return decode_small(h, synd, batch, decoding, llr, iters, conv, r.slots);
+        return LDPC_HIP_OK;
+    }
     if (h->small_mode != 0 && onchip_bound(h, batch)) {
         // small code: keep the messages on chip.  Bounded degrees: one wavefront per syndrome (bp_wave_kernel).
         // Otherwise the slot kernel -- auto: the most resident syndromes (<= 4) per workgroup that still leave
         // four workgroups per CU (<= 39.5 KiB each); forced: whatever fits in 150 KiB
         if (h->small_mode < 2 || h->small_mode == 6) {  // (mode 6: as -1 wherever the lane = edge variants do not apply) product-sum: one lane per entry keeps the lanes busy with transcendentals
             const WavePsPlan pp = plan_wave_ps(h, h->small_mode == 1, llr != nullptr, batch);
-            if (pp.waves) { *took = true; if (!rp) return decode_wave_ps(h, pp, io); }
+            if (pp.waves) { *took = true; return decode_wave_ps(h, pp, io); }
         }
-        if (!*took && (h->small_mode == -1 || h->small_mode == 1 || h->small_mode == 6)) {  // min-sum on the surface-code family: lane = edge
+        if (h->small_mode == -1 || h->small_mode == 1 || h->small_mode == 6) {  // min-sum on the surface-code family: lane = edge
             const EdgePlan ep = plan_edge_family(h);
-            if (ep.family) {
-                *took = true;
-                if (!rp) return decode_edge(h, ep, io);
-                if (edge_rp_route(h)) return decode_edge_rp(h, ep, io);
-            }
+            if (ep.family) { *took = true; return decode_edge(h, ep, io); }
         }
-        if (!*took && h->small_mode != 2) {
+        if (h->small_mode != 2) {
             const WavePlan wp = plan_wave(h, h->small_mode == 1 || (h->small_mode >= 3 && h->small_mode != 6), llr != nullptr, batch);
-            if (wp.waves) { *took = true; if (!rp) return decode_wave(h, wp, io); }
+            if (wp.waves) { *took = true; return decode_wave(h, wp, io); }
         }
         int slots = 0;
-        // (*took here: row priors, and another on-chip kernel would have taken the code -- whatever fits, as when the slot kernel is forced)
-        const size_t budget = (h->small_mode == 1 || h->small_mode == 2 || *took) ? 150u * 1024u : 39u * 1024u + 512u;
-        *took = false;
+        const size_t budget = (h->small_mode == 1 || h->small_mode == 2) ? 150u * 1024u : 39u * 1024u + 512u;
         for (int sl = 4; sl >= 1 && !slots; --sl)
-            if (small_lds_bytes(h, sl, rp) <= budget) slots = sl;
+            if (small_lds_bytes(h, sl) <= budget) slots = sl;
         if (slots) { *took = true; return decode_small(h, synd, batch, decoding, llr, iters, conv, slots); }
     }
     return LDPC_HIP_OK;

@@ -482,8 +482,9 @@ int decode_device(ldpc_hip_bp *h, const uint8_t *synd, int64_t batch, uint8_t *d
     const int64_t tiles_total = (batch + LDPC_WAVE - 1) / LDPC_WAVE;
     if (tiles_total == 0) return LDPC_HIP_OK;
     h->timed_prev = h->timed_prev_mid = false;  // (what a two-pass decode before this one left)
-    // Row priors (ldpc_hip_*_decode_batch_priors): every row is decoded with its own channel probabilities, h->row_probs [batch][n].  Two kernel
-    // families read them: the slot kernel (decode_onchip sends there whatever an on-chip kernel would take) and the per-pass kernels (StreamPlan::rp).
+    // Row priors (ldpc_hip_*_decode_batch_priors): every row is decoded with its own channel probabilities, h->row_probs [batch][n].  decode_onchip
+    // sends them to the kernels plan_row_prior_route names (host_onchip.h: the row-prior forms of the lane = edge and lane = node kernels, the slot kernel);
+    // what it leaves goes to the per-pass kernels (StreamPlan::rp).
     // (the entry points have said so already, before staging anything: nothing wrong is ever decoded from here either)
     { const int refused = decode_gate(h, h->row_probs ? "per-row channel probabilities are" : nullptr, false); if (refused) return refused; }
     if (h->variant == Variant::Decimation) return decode_onchip_gd(h, synd, batch, decoding, llr, iters, conv);  // guided decimation: the lane = edge kernels or a refusal, never another family

@@ -13,6 +13,7 @@
 #include "bp_wave_relay_kernel.h"  // (likewise: tu_onchip_wave_relay.hip's)
 #include "bp_edge_gd_kernel.h"  // (likewise: the guided-decimation instantiations are tu_onchip_gd.hip's)
 #include "bp_wave_gd_kernel.h"  // (likewise: tu_onchip_wave_gd.hip's)
+#include "bp_wave_rp_kernel.h"  // (likewise: the row-prior lane = node instantiations are tu_onchip_wave_rp.hip's)
 #include "bp_wave_f32_kernel.h"  // (likewise: the FP32 lane = node instantiations are tu_onchip_wave_f32.hip's)
 #include "io_kernels.h"
 

@@ -188,6 +188,21 @@ class HipBpEngine:
         _lib.check(self._lib.ldpc_hip_bp_f32_route(self._h, int(batch), 1 if want_llr else 0, C.byref(route)))
         return self.F32_ROUTES[int(route.value)]
 
+    ROW_PRIOR_ROUTES = ("per_pass", "bp_edge", "bp_edge8", "bp_wave", "bp_wave_team", "bp_small")
+
+    def row_prior_route(self, batch=1, want_llr=True) -> str:
+        """Which kernels a ``decode_batch(..., channel_probs=P)`` of ``batch`` syndromes takes on this engine as it is set now
+        (``ldpc_hip_bp_row_prior_route``; nothing is launched, no priors need be staged): ``"per_pass"`` (four launches an iteration, the
+        messages in HBM), ``"bp_edge"`` / ``"bp_edge8"`` (the lane = edge kernels' row-prior forms), ``"bp_wave"`` / ``"bp_wave_team"`` (the
+        lane = node kernel's, with one wavefront / a team per syndrome) or ``"bp_small"`` (the slot kernel).  ``NotImplementedError``, with
+        the library's reason, where such a decode is refused (a serial schedule, float32 messages, memory, Relay-BP, guided decimation)."""
+        route = C.c_int32(-1)
+        rc = int(self._lib.ldpc_hip_bp_row_prior_route(self._h, int(batch), 1 if want_llr else 0, C.byref(route)))
+        if rc == -4:  # LDPC_HIP_ERR_UNSUPPORTED: the refusal of the decode itself
+            raise NotImplementedError(self._lib.ldpc_hip_last_error().decode("utf-8", "replace"))
+        _lib.check(rc)
+        return self.ROW_PRIOR_ROUTES[int(route.value)]
+
     def set_memory(self, gamma):
         """Memory min-sum BP (``ldpc_hip_bp_set_memory``): ``gamma`` = one memory strength per bit, each finite and in ``[-1, 1)`` -- every
         iteration's bit pass then takes ``(1 - gamma) * prior + gamma * (the bit's previous posterior)`` for the prior -- or ``None``: off.
